@@ -11,6 +11,7 @@ The headline loop carries no per-kernel instrumentation; a second, instrumented 
 `kernel_ms_per_step`; `warp` is the flow-warp leg (splat / grid_sample GB/s); `train` the training step.
 
     python bench.py --gpus 1 --steps 10 --warmup 2
+    python bench.py --gpus 1 --steps 10 --warmup 2 --dump-outputs bench_outputs     (+ the last timed step's outputs as .npy)
     python bench.py --gpus N ...            (starts its own N ranks as a child `python -m torch.distributed.run`)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 """
@@ -264,6 +265,35 @@ def warp_cpu_baseline(sample, B, H, W):
             "sample": f"1 of {B} samples at {H}x{W}"}
 
 
+DUMP_BUDGET_BYTES = 60 * 10 ** 6     # data of all dumped arrays together (the .npy headers add 128 B each): under 64 MB
+DUMP_SEED = 0
+
+
+def dump_outputs(outputs, out_dir):
+    """`--dump-outputs`: the arrays the last timed step returned to its caller, as <out_dir>/<name>.npy in float32.  An array is
+    written whole while all of them fit DUMP_BUDGET_BYTES; otherwise each gets an equal share of the budget as a fixed sample:
+    flat indices drawn without replacement from numpy's Generator seeded with DUMP_SEED, sorted, so two runs (or two builds)
+    with the same arguments write the same elements.  Returns the record of what was written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {n: t.detach().float().cpu().numpy() for n, t in outputs.items()}
+    whole = sum(a.nbytes for a in arrays.values()) <= DUMP_BUDGET_BYTES
+    per_array = DUMP_BUDGET_BYTES // 4 // len(arrays)
+    rec = {"dir": os.path.abspath(out_dir), "step": "last timed step", "dtype": "float32", "files": {}}
+    for n, a in arrays.items():
+        r = {"shape": list(a.shape)}
+        if whole or a.size <= per_array:
+            out = np.ascontiguousarray(a)
+            r["sample"] = None
+        else:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, per_array, replace=False))
+            out = a.reshape(-1)[idx]
+            r["sample"] = f"{per_array} of {a.size} elements: flat indices np.random.default_rng({DUMP_SEED}).choice({a.size}, {per_array}, replace=False), sorted"
+        np.save(os.path.join(out_dir, n + ".npy"), out)
+        rec["files"][n + ".npy"] = r
+    return rec
+
+
 def self_launch(args):
     """`python bench.py --gpus N` without a launcher: start the N ranks as a CHILD process (python -m torch.distributed.run, one rank
     per GPU) and exit with its code.  Runs before anything touches the GPU in this process (the reference gets its ranks from
@@ -296,7 +326,12 @@ def main():
     ap.add_argument("--grad-bucket-dtype", choices=["fp32", "bf16"], default="fp32", help="all-reduce bucket dtype of the training leg (N > 1)")
     ap.add_argument("--with-train", action="store_true", help="(accepted for compatibility: the training leg runs for every N)")
     ap.add_argument("--train-timeout", type=float, default=300.0, help="watchdog of the training leg, seconds")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned (the next sample `img` and `x_start`) as DIR/<name>.npy, "
+                         "float32, at most 64 MB in all (a fixed seeded sample of larger outputs); rank 0 only")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(self_launch(args))           # the parent never initialises the GPU
@@ -327,26 +362,36 @@ def main():
 
     def step(img, t):
         # noise=None: p_sample draws randn_like(x) itself, inside the step, as the reference does (DD:687)
-        out, _, _ = diff.p_sample(img, t, None, external_cond=cond)
-        return out
+        # (the next sample, x_start): what p_sample hands its caller (its third output is None without additional_tgt)
+        out, x_start, _ = diff.p_sample(img, t, None, external_cond=cond)
+        return out, x_start
 
     def sync():
         torch.cuda.synchronize()
         parallel.barrier(dev)
 
     T = 999
+
+    def t_of(k):
+        """timestep of the k-th step of the chain: T, T-1, ..., 0, then again from T (any number of steps stays in the schedule)"""
+        return (T - k) % (T + 1)
+
     with torch.no_grad():
         for i in range(args.warmup):
-            img = step(img, T - i)
+            img, _ = step(img, t_of(i))
         # ---- headline loop: un-instrumented (no per-kernel events), exactly `steps` steps between two barrier + synchronize pairs
         unet.set_profiling(False)
         sync()
         t0 = time.perf_counter()
         for i in range(args.steps):
-            img = step(img, T - args.warmup - i)
+            img, x_start = step(img, t_of(args.warmup + i))
         sync()
         elapsed = time.perf_counter() - t0
         assert torch.isfinite(img).all(), "non-finite samples"
+        dumped = None
+        if args.dump_outputs and rank == 0:
+            dumped = dump_outputs({"img": img, "x_start": x_start}, args.dump_outputs)
+        del x_start
         # ---- instrumented loop (feeds `roofline` and `kernel_ms_per_step` only): HIP events around every launch, on the launch stream
         prof, prof_steps, prof_elapsed = {}, max(1, min(args.profile_steps, args.steps)), None
         if not args.no_profile:
@@ -355,7 +400,7 @@ def main():
             torch.cuda.synchronize()
             t1 = time.perf_counter()
             for i in range(prof_steps):
-                img = step(img, max(T - args.warmup - args.steps - i, 1))
+                img, _ = step(img, max(T - args.warmup - args.steps - i, 1))
             torch.cuda.synchronize()
             prof_elapsed = time.perf_counter() - t1
             prof = unet.profile()
@@ -389,6 +434,8 @@ def main():
             line["warp"] = warp
         if prof:
             line.update(roofline_objects(prof, prof_steps, prof_elapsed, B, H, W))
+        if dumped is not None:
+            line["dump_outputs"] = dumped
 
     import threading
     emitted, lock = threading.Event(), threading.Lock()

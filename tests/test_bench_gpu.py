@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -38,6 +39,24 @@ def test_bench_line_carries_roofline_warp_and_train():
         assert d["warp"][k]["ms"] > 0 and 0 < d["warp"][k]["frac_of_hbm_peak"] < 1
     assert d["warp"]["shape"] == [2, 64, 96]
     assert d["train"]["value"] > 0 and "augmentation" in d["train"]["includes"]
+
+
+def test_bench_dump_outputs_repeat_run_to_run(tmp_path):
+    """--dump-outputs writes the last timed step's two outputs in float32; the same arguments give the same arrays"""
+    extra = ["--no-profile", "--no-warp", "--train-steps", "0"]
+    recs = [_run(extra + ["--dump-outputs", str(tmp_path / d)])["dump_outputs"] for d in ("a", "b")]
+    assert recs[0]["files"] == recs[1]["files"]
+    for n in ("img", "x_start"):
+        assert recs[0]["files"][f"{n}.npy"] == {"shape": [2, 2, 64, 96], "sample": None}
+        a, b = np.load(tmp_path / "a" / f"{n}.npy"), np.load(tmp_path / "b" / f"{n}.npy")
+        assert a.dtype == np.float32 and a.shape == (2, 2, 64, 96) and np.isfinite(a).all()
+        assert np.array_equal(a, b)
+
+
+def test_bench_steps_sets_the_timed_steps_past_one_chain():
+    """--steps is the number of timed steps even beyond the T = 1000 steps of one chain (the timestep wraps to T)"""
+    d = _run(["--batch", "1", "--height", "32", "--width", "64", "--steps", "1100", "--no-profile", "--no-warp", "--train-steps", "0"])
+    assert d["steps"] == 1100 and d["value"] > 0
 
 
 def test_bench_gpus_2_starts_its_own_ranks():
