@@ -165,17 +165,23 @@ def linear_attention(P, pre, x, eps, q):
     return q(out + x)
 
 
-def attention(P, pre, x, eps, q):
-    """Residual(PreNorm(DD:246-268 Attention)); pre = 'mid_attn'."""
+def attention(P, pre, x, eps, q, query_chunk=4096):
+    """Residual(PreNorm(DD:246-268 Attention)); pre = 'mid_attn'.
+
+    The queries go through in chunks of ``query_chunk``: each row's softmax is the same, but the (b, heads, n, n) score matrix
+    is never held whole (17 GB at 1080p, n = 32 400).  Up to ``query_chunk`` tokens this is a single chunk."""
     b, c, h, w = x.shape
     n = h * w
     xn = q(layer_norm_c(x, P[f"{pre}.fn.norm.g"], eps(f"{pre}.fn.norm", x)))
     qkv = q(F.conv2d(xn, q(P[f"{pre}.fn.fn.to_qkv.weight"])))
     qq, kk, vv = [t.reshape(b, HEADS, DIM_HEAD, n) for t in qkv.chunk(3, dim=1)]
     qq = qq * (DIM_HEAD ** -0.5)                                                   # DD:261
-    sim = torch.einsum("bhdi,bhdj->bhij", qq, kk)                                  # DD:263
-    attn = sim.softmax(dim=-1)
-    out = torch.einsum("bhij,bhdj->bhid", attn, vv)                                # DD:265
+    outs = []
+    for i0 in range(0, n, query_chunk):
+        sim = torch.einsum("bhdi,bhdj->bhij", qq[..., i0:i0 + query_chunk], kk)    # DD:263
+        attn = sim.softmax(dim=-1)
+        outs.append(torch.einsum("bhij,bhdj->bhid", attn, vv))                     # DD:265
+    out = outs[0] if len(outs) == 1 else torch.cat(outs, dim=2)
     out = q(out.permute(0, 1, 3, 2).reshape(b, HEADS * DIM_HEAD, h, w))            # DD:267
     out = F.conv2d(out, q(P[f"{pre}.fn.fn.to_out.weight"]), P[f"{pre}.fn.fn.to_out.bias"])
     return q(out + x)
