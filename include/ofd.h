@@ -154,13 +154,16 @@ typedef struct ofd_unet ofd_unet;
 
 typedef struct {
     int dim;            /* 64 (must be a multiple of 64) */
-    int channels;       /* UNet input channels = x channels + cond channels (5 or 9) */
-    int out_dim;        /* 2 */
+    int channels;       /* UNet input channels = x channels + cond channels (1..48: 5 / 6 / 9 pixel space, 3 / 19 autoencoder, 18 / 33 / 35 latent) */
+    int out_dim;        /* 1..16 (2 for the diffusion UNet) */
     int eps_mode;       /* 0: eps 1e-5 everywhere (reference precision 32);
                            1: per-site eps the reference uses under bf16 autocast (DD:107,122) */
     int no_time;        /* 0: Unet(time_in=True) (the diffusion UNet).  1: Unet(time_in=False) (DD:306-324, FD:110 with
                            is_diffusion=False; flow_learner.py:93-98): no time MLP, ResnetBlocks without scale/shift
                            (DD:192-195), the `t` argument of the forward calls is ignored and may be NULL */
+    int n_levels;       /* resolution levels: 0 or 4 = dim_mults (1,2,4,8) (the diffusion UNet; 0 keeps configs written before this
+                           field existed meaning 4), 3 = dim_mults (1,2,4) (the reference's Autoencoder, flow_pred.py:17-35; requires
+                           no_time = 1; inference only: the training calls return OFD_ERR_ARG).  channels 1..48, out_dim 1..16. */
 } ofd_unet_config;
 
 int ofd_unet_create(const ofd_unet_config* cfg, ofd_unet** out);
@@ -209,6 +212,13 @@ int ofd_unet_read_tap(ofd_unet* u, const char* name, float* dst, size_t numel, v
  * the final 1x1 conv (DD:361) then rides on the tile of its producer (out_dim 2, H*W a multiple of 128) and "final_res_block" is
  * not a tap.  The two forms sum the 64 products of a pixel in different orders (equal to fp32 rounding). */
 int ofd_unet_set_debug_taps(ofd_unet* u, int enabled);
+/* elementwise glue of the reference's Autoencoder (flow_pred.py:38-58) folded into the inference forward (the training calls return
+ * OFD_ERR_ARG while any of it is on):
+ *   x_affine / cond_affine = 1: the input staging feeds 2 v - 1 instead of v for the x / cond planes (encoder 2x-1; decoder cat(l, 2x-1));
+ *   out_mode 0: plain output; 1: clamp(clamp(v, -1, 1) / out_div, -1, 1) (encode, and FD:145-148 with out_div = latent_max);
+ *   2: (clamp(v, -1, 1) + 1) / 2 (decode).  Applied by the final 1x1 conv's kernel on its fp32 result (out_mode != 0 runs the unfused
+ *   final conv).  Changing it drops captured graphs. */
+int ofd_unet_set_glue(ofd_unet* u, int x_affine, int cond_affine, int out_mode, float out_div);
 /* deterministic backward (default: the environment variable OFD_DETERMINISTIC, else off).  The backward accumulates parameter
  * gradients from many workgroups with float atomics, whose order -- and so the last bits of the sums -- changes from run to run
  * (torch's cuDNN weight gradients behave the same way in the reference).  Enabled, every such accumulation goes through a 64-bit
@@ -298,6 +308,8 @@ int ofd_conv_upsample_phase_weight_prep(const float* w_oihw, void* w_out, int Co
 int ofd_conv_dgrad_weight_prep(const void* w_fwd, void* w_t, int Cout, int Cin, int ksize, void* stream);
 int ofd_conv_wgrad(const ofd_conv_args* fwd, const void* dy, float* dw_acc, void* stream);
 int ofd_conv7_wgrad(const void* x16, const void* dy, float* dw_acc, int B, int H, int W, void* stream);
+/* the same for an input packed to `channels` = 8, 16, 32 or 48 (pixel stride); dw_acc is [49][channels][64] */
+int ofd_conv7_wgrad_c(const void* x, const void* dy, float* dw_acc, int B, int H, int W, int channels, void* stream);
 int ofd_conv_wgrad_finish(const float* dw_acc, const float* w_oihw, float* dst_oihw, int Cout, int Cin, int Cin_pad,
                           int ksize, float ws_eps, int unshuffle, int accumulate, void* stream);
 int ofd_grad_scatter(const void* D, int Ctot, int ch_off, void* dst, int C, int B, int H, int W, int mode,
@@ -321,6 +333,9 @@ int ofd_gn_silu_backward(const void* g, const void* h, const float* a, const flo
 int ofd_affine_silu(const void* h, const float* a, const float* s, void* out, int B, int H, int W, int C, void* stream);
 int ofd_layernorm_c_backward(const void* x, const float* g, const void* dy, void* dx, float* dg, size_t npix, int C,
                              float eps, int accumulate, void* stream);
+/* DD:361 forward: x NHWC bf16 (C channels) -> out NCHW fp32 (out_dim <= 16), with the glue epilogue of ofd_unet_set_glue (out_mode, out_div) */
+int ofd_final_conv(const void* x, const float* w, const float* b, float* out, int B, int H, int W, int C, int out_dim, int out_mode,
+                   float out_div, void* stream);
 int ofd_final_conv_backward(const void* x, const float* w, const float* dy, void* dx, float* dw, float* db,
                             int B, int H, int W, int C, int out_dim, void* stream);
 

@@ -19,7 +19,8 @@ class OfdError(RuntimeError):
 
 
 class UnetConfig(ctypes.Structure):
-    _fields_ = [("dim", c_int), ("channels", c_int), ("out_dim", c_int), ("eps_mode", c_int), ("no_time", c_int)]
+    # n_levels: 0 / 4 = dim_mults (1,2,4,8), 3 = (1,2,4); a config built from the first five fields alone keeps 0 = four levels
+    _fields_ = [("dim", c_int), ("channels", c_int), ("out_dim", c_int), ("eps_mode", c_int), ("no_time", c_int), ("n_levels", c_int)]
 
 
 class ConvSrc(ctypes.Structure):
@@ -84,6 +85,7 @@ SIGNATURES = {
     "ofd_unet_set_split_streams": (c_int, [c_void_p, c_int, c_int]),
     "ofd_unet_read_tap": (c_int, [c_void_p, c_char_p, c_void_p, c_size_t, c_void_p]),
     "ofd_unet_set_debug_taps": (c_int, [c_void_p, c_int]),
+    "ofd_unet_set_glue": (c_int, [c_void_p, c_int, c_int, c_int, c_float]),
     "ofd_unet_set_profiling": (c_int, [c_void_p, c_int]),
     "ofd_unet_set_deterministic": (c_int, [c_void_p, c_int]),
     "ofd_unet_deterministic_misses": (ctypes.c_long, [c_void_p]),
@@ -100,6 +102,7 @@ SIGNATURES = {
     "ofd_conv_dgrad_weight_prep": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "ofd_conv_wgrad": (c_int, [ctypes.POINTER(ConvArgs), c_void_p, c_void_p, c_void_p]),
     "ofd_conv7_wgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "ofd_conv7_wgrad_c": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ofd_conv_wgrad_finish": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_float, c_int, c_int, c_void_p]),
     "ofd_grad_scatter": (c_int, [c_void_p, c_int, c_int, c_void_p] + [c_int] * 8 + [c_void_p]),
     "ofd_channel_sum": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
@@ -108,6 +111,7 @@ SIGNATURES = {
     "ofd_affine_silu": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p]),
     "ofd_layernorm_c_backward": (c_int, [c_void_p] * 5 + [c_size_t, c_int, c_float, c_int, c_void_p]),
     "ofd_final_conv_backward": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p]),
+    "ofd_final_conv": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_float, c_void_p]),
     "ofd_la_workspace_floats": (c_size_t, [c_int, c_int]),
     "ofd_la_bwd_workspace_floats": (c_size_t, [c_int, c_int]),
     "ofd_linear_attention_core": (c_int, [c_void_p] * 5 + [c_int, c_int, c_void_p]),

@@ -24,10 +24,12 @@ __device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
     return make_uint4(pack2(f[0], f[1]), pack2(f[2], f[3]), pack2(f[4], f[5]), pack2(f[6], f[7]));
 }
 
-// ---- DD:368: cat(x, cond) -> NHWC bf16 padded to CP = 8 or 16 channels (input of the 7x7 init_conv) --------
+// ---- DD:368: cat(x, cond) -> NHWC bf16 padded to CP = 8, 16, 32 or 48 channels (input of the 7x7 init_conv) --------
+// ax / ac = 1: the x / cond planes enter as 2 v - 1 (the Autoencoder's input glue, flow_pred.py:51,57; 2 v is exact, so this is torch's
+// fp32 `2 * v - 1.0` rounded once)
 template <int CP>
 __global__ void __launch_bounds__(256) pack_input_kernel(const float* __restrict__ x, int Cx, const float* __restrict__ cond, int Cc,
-                                                         bf16_t* __restrict__ out, int B, size_t plane) {
+                                                         bf16_t* __restrict__ out, int B, size_t plane, int ax, int ac) {
     const size_t total = (size_t)B * plane;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const size_t n = i / plane, pix = i % plane;
@@ -35,8 +37,8 @@ __global__ void __launch_bounds__(256) pack_input_kernel(const float* __restrict
 #pragma unroll
         for (int c = 0; c < CP; ++c) {
             float t = 0.0f;
-            if (c < Cx) t = x[(n * Cx + c) * plane + pix];
-            else if (c < Cx + Cc) t = cond[(n * Cc + (c - Cx)) * plane + pix];
+            if (c < Cx) { t = x[(n * Cx + c) * plane + pix]; if (ax) t = 2.0f * t - 1.0f; }
+            else if (c < Cx + Cc) { t = cond[(n * Cc + (c - Cx)) * plane + pix]; if (ac) t = 2.0f * t - 1.0f; }
             v[c] = t;
         }
         uint4* o = (uint4*)(out + i * CP);
@@ -391,12 +393,24 @@ __global__ void __launch_bounds__(256) flash_attn_d32_kernel(const bf16_t* __res
 
 // ---- DD:361,417: final 1x1 conv (fp32 weights) -> NCHW fp32 -------------------------------------
 // C/8 lanes cooperate on one pixel (16 B each, so a wave reads whole 128-B lines); shuffle-reduce.
+// out_mode: the Autoencoder's output glue on the fp32 result v (flow_pred.py:50-58, FD:145-148), NaN propagating like torch.clamp
+__device__ __forceinline__ float clamp1(float v) { return v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v); }
+__device__ __forceinline__ float out_glue(float v, int mode, float div) {
+    if (mode == 1) return clamp1(clamp1(v) / div);          // encode: clamp(enc, -1, 1) (/ latent_max, clamp again)
+    if (mode == 2) return (clamp1(v) + 1.0f) / 2.0f;        // decode
+    return v;
+}
+
+// OD = 4 (the diffusion UNet, out_dim <= 4) or 16 (the Autoencoder's encoder, 16 latents): lane `sub` of a pixel's group writes the outputs
+// sub, sub + C/8, ...
+template <int OD>
 __global__ void __launch_bounds__(256) final_conv_kernel(const bf16_t* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
-                                                         float* __restrict__ out, int C, int out_dim, size_t plane, size_t total) {
+                                                         float* __restrict__ out, int C, int out_dim, size_t plane, size_t total, int out_mode,
+                                                         float out_div) {
     const int lpp = C / 8, lane = threadIdx.x & 63, sub = lane % lpp, slot = lane / lpp, ppw = 64 / lpp;
-    float wv[4][8];
+    float wv[OD][8];
 #pragma unroll
-    for (int o = 0; o < 4; ++o)
+    for (int o = 0; o < OD; ++o)
 #pragma unroll
         for (int j = 0; j < 8; ++j) wv[o][j] = (o < out_dim) ? w[o * C + sub * 8 + j] : 0.0f;
     const size_t wave_global = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((size_t)gridDim.x * blockDim.x) >> 6;
@@ -404,21 +418,28 @@ __global__ void __launch_bounds__(256) final_conv_kernel(const bf16_t* __restric
         const size_t i = min(p0 + slot, total - 1);
         float f[8];
         unpack8(*(const uint4*)(x + i * C + sub * 8), f);
-        float acc[4];
+        float acc[OD];
 #pragma unroll
-        for (int o = 0; o < 4; ++o) {
+        for (int o = 0; o < OD; ++o) {
             acc[o] = 0.0f;
 #pragma unroll
             for (int j = 0; j < 8; ++j) acc[o] += f[j] * wv[o][j];
             for (int k = 1; k < lpp; k <<= 1) acc[o] += __shfl_xor(acc[o], k, 64);
         }
-        if (sub < out_dim && p0 + slot < total) {
+        if (OD == 4) {
+            if (sub < out_dim && p0 + slot < total) {
+                const size_t n = i / plane, pix = i % plane;
+                float r = acc[0];
+                if (sub == 1) r = acc[1];
+                if (sub == 2) r = acc[2];
+                if (sub == 3) r = acc[3];
+                out[(n * out_dim + sub) * plane + pix] = out_glue(r + bias[sub], out_mode, out_div);
+            }
+        } else if (p0 + slot < total) {
             const size_t n = i / plane, pix = i % plane;
-            float r = acc[0];
-            if (sub == 1) r = acc[1];
-            if (sub == 2) r = acc[2];
-            if (sub == 3) r = acc[3];
-            out[(n * out_dim + sub) * plane + pix] = r + bias[sub];
+#pragma unroll
+            for (int o = 0; o < OD; ++o)
+                if (o < out_dim && o % lpp == sub) out[(n * out_dim + o) * plane + pix] = out_glue(acc[o] + bias[o], out_mode, out_div);
         }
     }
 }
@@ -454,10 +475,14 @@ static inline int sgrid(size_t total, int block = 256, int cap = 4096) {
 }
 
 // ------------------------------------------------------------------------------------ launchers
-int k_pack_input(const float* x, int Cx, const float* cond, int Cc, bf16_t* out, int B, int H, int W, hipStream_t s, int cpad) {
-    OFD_CHECK_ARG((cpad == 8 || cpad == 16) && Cx + Cc <= cpad && Cx > 0, "pack_input: %d+%d channels into %d", Cx, Cc, cpad);
-    if (cpad == 8) pack_input_kernel<8><<<sgrid((size_t)B * H * W), 256, 0, s>>>(x, Cx, cond, Cc, out, B, (size_t)H * W);
-    else pack_input_kernel<16><<<sgrid((size_t)B * H * W), 256, 0, s>>>(x, Cx, cond, Cc, out, B, (size_t)H * W);
+int k_pack_input(const float* x, int Cx, const float* cond, int Cc, bf16_t* out, int B, int H, int W, hipStream_t s, int cpad, int ax, int ac) {
+    OFD_CHECK_ARG((cpad == 8 || cpad == 16 || cpad == 32 || cpad == 48) && Cx + Cc <= cpad && Cx > 0, "pack_input: %d+%d channels into %d", Cx, Cc, cpad);
+    const int g = sgrid((size_t)B * H * W);
+    const size_t plane = (size_t)H * W;
+    if (cpad == 8) pack_input_kernel<8><<<g, 256, 0, s>>>(x, Cx, cond, Cc, out, B, plane, ax, ac);
+    else if (cpad == 16) pack_input_kernel<16><<<g, 256, 0, s>>>(x, Cx, cond, Cc, out, B, plane, ax, ac);
+    else if (cpad == 32) pack_input_kernel<32><<<g, 256, 0, s>>>(x, Cx, cond, Cc, out, B, plane, ax, ac);
+    else pack_input_kernel<48><<<g, 256, 0, s>>>(x, Cx, cond, Cc, out, B, plane, ax, ac);
     OFD_LAUNCH_CHECK();
     return OFD_OK;
 }
@@ -502,10 +527,14 @@ int k_flash_attention(const bf16_t* qkv, bf16_t* out, int B, int n, hipStream_t 
     OFD_LAUNCH_CHECK();
     return OFD_OK;
 }
-int k_final_conv(const bf16_t* x, const float* w, const float* bias, float* out, int B, int H, int W, int C, int out_dim, hipStream_t s) {
-    OFD_CHECK_ARG(out_dim >= 1 && out_dim <= 4 && C % 8 == 0, "final_conv: out_dim=%d C=%d", out_dim, C);
+int k_final_conv(const bf16_t* x, const float* w, const float* bias, float* out, int B, int H, int W, int C, int out_dim, hipStream_t s, int out_mode,
+                 float out_div) {
+    OFD_CHECK_ARG(out_dim >= 1 && out_dim <= 16 && C % 8 == 0, "final_conv: out_dim=%d C=%d", out_dim, C);
     OFD_CHECK_ARG(C == 64 || C == 128 || C == 256 || C == 512, "final_conv: C=%d unsupported", C);
-    final_conv_kernel<<<sgrid(((size_t)B * H * W + (512 / C) - 1) / (512 / C) * 64), 256, 0, s>>>(x, w, bias, out, C, out_dim, (size_t)H * W, (size_t)B * H * W);
+    OFD_CHECK_ARG(out_mode >= 0 && out_mode <= 2 && out_div > 0.0f, "final_conv: out_mode=%d out_div=%g", out_mode, (double)out_div);
+    const int g = sgrid(((size_t)B * H * W + (512 / C) - 1) / (512 / C) * 64);
+    if (out_dim <= 4) final_conv_kernel<4><<<g, 256, 0, s>>>(x, w, bias, out, C, out_dim, (size_t)H * W, (size_t)B * H * W, out_mode, out_div);
+    else final_conv_kernel<16><<<g, 256, 0, s>>>(x, w, bias, out, C, out_dim, (size_t)H * W, (size_t)B * H * W, out_mode, out_div);
     OFD_LAUNCH_CHECK();
     return OFD_OK;
 }

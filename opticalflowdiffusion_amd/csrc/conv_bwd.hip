@@ -767,9 +767,11 @@ __global__ void __launch_bounds__(512, 1) conv_wgrad3_db_kernel(const WgradParam
 // CH = 8 (r04: the input packed to 8 channels, what the forward conv reads): 16 B per pixel, a 32-row A operand carries FOUR taps (kx .. kx + 3) x 8
 // channels -- 2 MFMAs per kernel row and pixel block instead of 4, 4 accumulator tiles per wave; the accumulator keeps its [tap][16][64] layout
 // (channels 8 .. 15 stay zero).
+// Wider inputs (17..48 channels, packed to XS = 32 or 48: the latent UNet's init conv) run the CH = 16 form once per 16-channel chunk: x16 then
+// points at the chunk's first channel, XS is the pixel stride of the packed input and dw the chunk's rows of a [tap][XS][64] accumulator.
 template <int CH>
 __global__ void __launch_bounds__(512) conv7_wgrad_kernel(const bf16_t* __restrict__ x16, const bf16_t* __restrict__ dy, float* __restrict__ dw,
-                                                          int B, int H, int W, int tiles_x, int tiles_y, float* __restrict__ dbias) {
+                                                          int B, int H, int W, int tiles_x, int tiles_y, float* __restrict__ dbias, int XS) {
     constexpr int XW = 40, XPIX = 14 * XW;                // 38 columns needed (+1 for the phantom tap kx = 7)
     constexpr int PB = CH * 2, UPP = PB / 16, TPF = 64 / PB, NK = 8 / TPF;      // bytes and 16-byte units per pixel; taps per A fragment; fragments per kernel row
     __shared__ __attribute__((aligned(16))) unsigned char xs[XPIX * PB];
@@ -802,7 +804,7 @@ __global__ void __launch_bounds__(512) conv7_wgrad_kernel(const bf16_t* __restri
             const int p = i / UPP, u = i % UPP, ty = p / XW, tx = p - ty * XW;
             const int iy = oy0 + ty - 3, ix = ox0 + tx - 3;
             const bool ok = iy >= 0 && iy < H && ix >= 0 && ix < W;
-            xr[k] = *(const u32x4*)(x16 + (((size_t)b * H + min(max(iy, 0), H - 1)) * W + min(max(ix, 0), W - 1)) * CH + u * 8);
+            xr[k] = *(const u32x4*)(x16 + (((size_t)b * H + min(max(iy, 0), H - 1)) * W + min(max(ix, 0), W - 1)) * XS + u * 8);
             okm |= (ok ? 1u : 0u) << k;
         }
 #pragma unroll
@@ -861,7 +863,7 @@ __global__ void __launch_bounds__(512) conv7_wgrad_kernel(const bf16_t* __restri
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int m = (r & 3) + 8 * (r >> 2) + 4 * half, kx = TPF * k + m / CH, ci = m % CH;
-                if (kx < 7) gacc_add(dw + ((size_t)(ky * 7 + kx) * 16 + ci) * 64 + nt * 32 + l31, acc[a][k][r]);
+                if (kx < 7) gacc_add(dw + ((size_t)(ky * 7 + kx) * (CH == 8 ? 16 : XS) + ci) * 64 + nt * 32 + l31, acc[a][k][r]);
             }
     }
 }
@@ -1173,13 +1175,15 @@ int k_conv_wgrad(const ofd_conv_args* a, const bf16_t* dy, float* dw, hipStream_
 
 int k_conv7_wgrad(const bf16_t* x16, const bf16_t* dy, float* dw, int B, int H, int W, hipStream_t s, float* dbias, int channels) {
     const int tx = cdiv(W, 32), ty = cdiv(H, 8);
-    OFD_CHECK_ARG(channels == 16 || channels == 8, "conv7_wgrad: input packed to %d channels", channels);
+    OFD_CHECK_ARG(channels == 8 || channels == 16 || channels == 32 || channels == 48, "conv7_wgrad: input packed to %d channels", channels);
     static const int grid_env = getenv("OFD_CONV7_WGRAD_GRID") ? atoi(getenv("OFD_CONV7_WGRAD_GRID")) : 0;
     int grid = tx * ty * B;
     const int cap = grid_env > 0 ? grid_env : (channels == 8 ? 512 : 768);       // (the 8-channel form: two workgroups per CU at 128 registers, all resident: 0.45 ms at 512, 0.47 at 768, 0.58 at 1024)
     if (grid > cap) grid = cap;
-    if (channels == 8) conv7_wgrad_kernel<8><<<grid, 512, 0, s>>>(x16, dy, dw, B, H, W, tx, ty, dbias);
-    else conv7_wgrad_kernel<16><<<grid, 512, 0, s>>>(x16, dy, dw, B, H, W, tx, ty, dbias);
+    if (channels == 8) conv7_wgrad_kernel<8><<<grid, 512, 0, s>>>(x16, dy, dw, B, H, W, tx, ty, dbias, 8);
+    else
+        for (int c0 = 0; c0 < channels; c0 += 16)       // (32 / 48: one launch per 16-channel chunk, the bias sums ride on the first)
+            conv7_wgrad_kernel<16><<<grid, 512, 0, s>>>(x16 + c0, dy, dw + (size_t)c0 * 64, B, H, W, tx, ty, c0 ? nullptr : dbias, channels);
     OFD_LAUNCH_CHECK();
     return OFD_OK;
 }
@@ -1237,6 +1241,10 @@ extern "C" int ofd_conv_wgrad(const ofd_conv_args* fwd, const void* dy, float* d
 extern "C" int ofd_conv7_wgrad(const void* x16, const void* dy, float* dw_acc, int B, int H, int W, void* stream) {
     OFD_CHECK_ARG(x16 && dy && dw_acc, "conv7_wgrad: null argument");
     return k_conv7_wgrad((const bf16_t*)x16, (const bf16_t*)dy, dw_acc, B, H, W, (hipStream_t)stream, nullptr, 16);
+}
+extern "C" int ofd_conv7_wgrad_c(const void* x, const void* dy, float* dw_acc, int B, int H, int W, int channels, void* stream) {
+    OFD_CHECK_ARG(x && dy && dw_acc, "conv7_wgrad_c: null argument");
+    return k_conv7_wgrad((const bf16_t*)x, (const bf16_t*)dy, dw_acc, B, H, W, (hipStream_t)stream, nullptr, channels);
 }
 extern "C" int ofd_conv_wgrad_finish(const float* dw_acc, const float* w_oihw, float* dst_oihw, int Cout, int Cin, int Cin_pad, int ksize,
                                      float ws_eps, int unshuffle, int accumulate, void* stream) {

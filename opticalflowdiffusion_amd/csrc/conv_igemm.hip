@@ -114,7 +114,7 @@ __device__ __forceinline__ void conv_load_w(U4Arr<Cfg<KS, BN>::WPT>& wr, const b
         if (C::SC8 * BN % NTHREADS != 0) u = min(u, C::SC8 * BN - 1);
         const int r = u / BN, n = u % BN;
         size_t row;
-        if (KS == 7) row = (size_t)(st * 7 + r / 2) * 2 + (r & 1);
+        if (KS == 7) row = (size_t)(st * 7 + r / 2) * cin8 + kc * 2 + (r & 1);     // [tap][Cin_pad / 8]: chunk kc = channel octets 2 kc, 2 kc + 1
         else if (KS == 8) row = (size_t)st * 8 + r;
         else row = (size_t)st * cin8 + kc * 8 + r;
         wr.v[i] = *(const u32x4*)(weight + (row * Cout + n0 + n) * 8);   // (diagnostic bit 2 handled by the caller)
@@ -1185,8 +1185,9 @@ int conv_forward_impl(const ofd_conv_args* a, hipStream_t s, int cout0, int pool
         P.total_chunks += d.chunks;
     }
     P.Cin_total = cin;
-    OFD_CHECK_ARG(a->ksize != 7 || (P.total_chunks == 1 && a->Cout == 64 && !a->in_scale && !a->src[0].upsample && !a->src[0].unshuffle),
-                  "conv: 7x7 supports one 8- or 16-channel source, Cout=64");
+    OFD_CHECK_ARG(a->ksize != 7 || (a->n_src == 1 && (k7p || P.total_chunks <= 3) && a->Cout == 64 && !a->in_scale && !a->src[0].upsample &&
+                                    !a->src[0].unshuffle),
+                  "conv: 7x7 supports one source of 8 channels or 1..3 16-channel chunks (up to 48), Cout=64");
     P.weight = (const bf16_t*)a->weight; P.bias = a->bias; P.in_scale = a->in_scale; P.in_shift = a->in_shift;
     P.residual = (const bf16_t*)a->residual; P.res_act = (const bf16_t*)a->res_act; P.res_scale = a->res_scale; P.res_shift = a->res_shift;
     P.out = (bf16_t*)a->out; P.gn_partial = a->gn_partial;

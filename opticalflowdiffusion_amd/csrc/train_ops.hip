@@ -558,6 +558,11 @@ extern "C" int ofd_final_conv_backward(const void* x, const float* w, const floa
 }
 
 // forward building blocks of the executor, exported for callers that compose their own blocks (SURVEY 8b export set)
+extern "C" int ofd_final_conv(const void* x, const float* w, const float* b, float* out, int B, int H, int W, int C, int out_dim, int out_mode,
+                              float out_div, void* stream) {
+    OFD_CHECK_ARG(x && w && b && out, "final_conv: null argument");
+    return k_final_conv((const bf16_t*)x, w, b, out, B, H, W, C, out_dim, (hipStream_t)stream, out_mode, out_div);
+}
 extern "C" int ofd_layernorm_c(const void* x, const float* g, const void* residual, void* out, size_t npix, int C, float eps, void* stream) {
     OFD_CHECK_ARG(x && g && out, "layernorm_c: null argument");
     return k_layernorm_c((const bf16_t*)x, g, (const bf16_t*)residual, (bf16_t*)out, npix, C, eps, (hipStream_t)stream);

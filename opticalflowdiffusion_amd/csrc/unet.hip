@@ -34,7 +34,8 @@ static void add_param(ofd_unet* u, const std::string& name, std::vector<int> sha
 static void add_conv(ofd_unet* u, const std::string& prefix, int co, int ci, int k, bool bias, float ws_eps, int unshuffle = 0) {
     add_param(u, prefix + ".weight", {co, ci, k, k});
     if (bias) add_param(u, prefix + ".bias", {co});
-    ConvDesc c{prefix + ".weight", co, ci, (k == 7) ? 16 : ci, k, ws_eps, unshuffle, u->n_wbuf};
+    // 7x7: K padded to whole 16-channel chunks of the generic kernel (conv_igemm.hip Cfg<7, 64>: 16, 32 or 48)
+    ConvDesc c{prefix + ".weight", co, ci, (k == 7) ? (ci + 15) / 16 * 16 : ci, k, ws_eps, unshuffle, u->n_wbuf};
     u->n_wbuf += (size_t)k * k * c.Cin_pad * co;
     if (k == 7 && ci <= 8) {
         c.pack8_off = (long)u->n_wbuf;
@@ -74,32 +75,34 @@ static void add_linattn(ofd_unet* u, const std::string& name, int c) {
 }
 
 static void build_registry(ofd_unet* u) {
-    const int dim = u->cfg.dim;
-    u->dims = {dim, dim, dim * 2, dim * 4, dim * 8};
+    const int dim = u->cfg.dim, L = u->L;
+    u->dims = {dim, dim, dim * 2, dim * 4};                 // [dim] + dim * dim_mults, dim_mults = (1, 2, 4) or (1, 2, 4, 8)
+    if (L == 4) u->dims.push_back(dim * 8);
     const int tdim = dim * 4;
     add_conv(u, "init_conv", dim, u->cfg.channels, 7, true, -1.0f);
+    u->cin_pad = u->convs.back().Cin_pad;
     if (!u->cfg.no_time) {
         add_param(u, "time_mlp.1.weight", {tdim, dim});
         add_param(u, "time_mlp.1.bias", {tdim});
         add_param(u, "time_mlp.3.weight", {tdim, tdim});
         add_param(u, "time_mlp.3.bias", {tdim});
     }
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < L; ++i) {
         const int ci = u->dims[i], co = u->dims[i + 1];
         const std::string p = "downs." + std::to_string(i);
         add_resblock(u, p + ".0", ci, ci);
         add_resblock(u, p + ".1", ci, ci);
         add_linattn(u, p + ".2", ci);
-        if (i < 3) add_conv(u, p + ".3.1", co, ci * 4, 1, true, -1.0f, 1);
+        if (i < L - 1) add_conv(u, p + ".3.1", co, ci * 4, 1, true, -1.0f, 1);
         else add_conv(u, p + ".3", co, ci, 3, true, -1.0f);
     }
-    for (int i = 0; i < 4; ++i) {
-        const int ci = u->dims[3 - i], co = u->dims[4 - i];
+    for (int i = 0; i < L; ++i) {
+        const int ci = u->dims[L - 1 - i], co = u->dims[L - i];
         const std::string p = "ups." + std::to_string(i);
         add_resblock(u, p + ".0", co + ci, co);
         add_resblock(u, p + ".1", co + ci, co);
         add_linattn(u, p + ".2", co);
-        if (i < 3) {
+        if (i < L - 1) {
             add_conv(u, p + ".3.1", ci, co, 3, true, -1.0f);
             ConvDesc& d = u->convs.back();              // Upsample(x2) + 3x3 also as four 2x2 phase kernels (forward)
             d.phase_off = (long)u->n_wbuf;
@@ -107,7 +110,7 @@ static void build_registry(ofd_unet* u) {
         }
         else add_conv(u, p + ".3", ci, co, 3, true, -1.0f);
     }
-    const int mid = u->dims[4];
+    const int mid = u->dims[L];
     add_resblock(u, "mid_block1", mid, mid);
     add_conv(u, "mid_attn.fn.fn.to_qkv", 384, mid, 1, false, -1.0f);
     add_conv(u, "mid_attn.fn.fn.to_out", mid, 128, 1, true, -1.0f);
@@ -380,10 +383,11 @@ int run_forward(Ctx& c, const float* x, int Cx, const float* cond, int Cc, const
     // r04: the 16-channel copy and its pack pass are gone).
     static const bool no_pack8 = getenv("OFD_NO_CONV7_PACK8") && atoi(getenv("OFD_NO_CONV7_PACK8"));
     const bool pack8 = !no_pack8 && u->convs[u->cindex.at("init_conv")].pack8_off >= 0;
-    const int cpad = pack8 ? 8 : 16;
+    const int cpad = pack8 ? 8 : u->cin_pad;
+    const int L = u->L;
     Tensor xin = c.keep(cpad, H, W);
     c.begin(PC_MISC, 0, 0);
-    RUN(k_pack_input(x, Cx, cond, cond ? Cc : 0, xin.p, B, H, W, c.s, cpad));
+    RUN(k_pack_input(x, Cx, cond, cond ? Cc : 0, xin.p, B, H, W, c.s, cpad, c.train ? 0 : u->glue_x, c.train ? 0 : u->glue_cond));
     if (!u->cfg.no_time) {
         RUN(k_time_mlp(t, u->P("time_mlp.1.weight"), u->P("time_mlp.1.bias"), u->P("time_mlp.3.weight"), u->P("time_mlp.3.bias"), temb, temb_silu, B, dim, c.s));
         RUN(k_block_mlp(temb_silu, u->d_mlp, (int)u->resblocks.size(), c.ss, B, dim * 4, u->ss_stride, c.s));
@@ -397,7 +401,7 @@ int run_forward(Ctx& c, const float* x, int Cx, const float* cond, int Cc, const
 
     Tensor xcur = r;
     std::vector<Tensor> hs;
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < L; ++i) {
         const std::string p = "downs." + std::to_string(i);
         c.reset_scratch();
         xcur = resblock(c, p + ".0", {xcur}, u->dims[i]);
@@ -410,7 +414,7 @@ int run_forward(Ctx& c, const float* x, int Cx, const float* cond, int Cc, const
         xcur = linattn(c, p + ".2", x1);
         hs.push_back(xcur);
         u->taps[p + ".2"] = xcur;
-        if (i < 3) {
+        if (i < L - 1) {
             Tensor d = c.keep(u->dims[i + 1], xcur.H / 2, xcur.W / 2);
             std::vector<SrcSpec> srcs;
             for (int sub = 0; sub < 4; ++sub) { SrcSpec s; s.t = xcur; s.unshuffle = 1; s.p1 = sub >> 1; s.p2 = sub & 1; srcs.push_back(s); }
@@ -425,17 +429,17 @@ int run_forward(Ctx& c, const float* x, int Cx, const float* cond, int Cc, const
         u->taps[p + ".3"] = xcur;
     }
     c.reset_scratch();
-    xcur = resblock(c, "mid_block1", {xcur}, u->dims[4]);
+    xcur = resblock(c, "mid_block1", {xcur}, u->dims[L]);
     u->taps["mid_block1"] = xcur;
     c.reset_scratch();
     xcur = midattn(c, xcur);
     u->taps["mid_attn"] = xcur;
     c.reset_scratch();
-    xcur = resblock(c, "mid_block2", {xcur}, u->dims[4]);
+    xcur = resblock(c, "mid_block2", {xcur}, u->dims[L]);
     u->taps["mid_block2"] = xcur;
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < L; ++i) {
         const std::string p = "ups." + std::to_string(i);
-        const int co = u->dims[4 - i], ci = u->dims[3 - i];
+        const int co = u->dims[L - i], ci = u->dims[L - 1 - i];
         c.reset_scratch();
         Tensor h = hs.back(); hs.pop_back();
         xcur = resblock(c, p + ".0", {xcur, h}, co);
@@ -447,7 +451,7 @@ int run_forward(Ctx& c, const float* x, int Cx, const float* cond, int Cc, const
         c.reset_scratch();
         xcur = linattn(c, p + ".2", xcur);
         u->taps[p + ".2"] = xcur;
-        if (i < 3) {
+        if (i < L - 1) {
             Tensor d = c.keep(ci, xcur.H * 2, xcur.W * 2);
             SrcSpec s; s.t = xcur; s.upsample = 1;
             upsample_conv(c, p + ".3.1", s, d);
@@ -466,7 +470,8 @@ int run_forward(Ctx& c, const float* x, int Cx, const float* cond, int Cc, const
     // shape is not the streaming kernel's (out_dim 2, whole 128-pixel tiles)
     static const bool no_fc = (getenv("OFD_NO_FC_FUSE") && atoi(getenv("OFD_NO_FC_FUSE"))) || (getenv("OFD_CONV1_WP") && atoi(getenv("OFD_CONV1_WP")) == 0) ||
                               (getenv("OFD_CONV_DBG") && atoi(getenv("OFD_CONV_DBG")));
-    const bool fuse_fc = !c.train && !u->debug_taps && !no_fc && u->cfg.out_dim == 2 && dim == 64 && ((long)H * W) % 128 == 0;
+    const int glue = c.train ? 0 : u->glue_out;
+    const bool fuse_fc = !c.train && !u->debug_taps && !no_fc && !glue && u->cfg.out_dim == 2 && dim == 64 && ((long)H * W) % 128 == 0;
     if (fuse_fc) {
         const FcFuse fc{u->P("final_conv.weight"), u->P("final_conv.bias"), out};
         if (c.rc == OFD_OK && !c.dry) {
@@ -478,7 +483,7 @@ int run_forward(Ctx& c, const float* x, int Cx, const float* cond, int Cc, const
         xcur = resblock(c, "final_res_block", {xcur, r}, dim);
         u->taps["final_res_block"] = xcur;
         c.begin(PC_MISC, 2.0 * B * H * W * dim * u->cfg.out_dim, (double)B * H * W * (dim * 2 + u->cfg.out_dim * 4));
-        RUN(k_final_conv(xcur.p, u->P("final_conv.weight"), u->P("final_conv.bias"), out, B, H, W, dim, u->cfg.out_dim, c.s));
+        RUN(k_final_conv(xcur.p, u->P("final_conv.weight"), u->P("final_conv.bias"), out, B, H, W, dim, u->cfg.out_dim, c.s, glue, u->glue_div));
         c.end();
     }
     if (c.train) {
@@ -491,18 +496,19 @@ int run_forward(Ctx& c, const float* x, int Cx, const float* cond, int Cc, const
 size_t persist_bytes(const ofd_unet* u, int B, int H, int W) {
     // every kept tensor of the forward: r, 3 per down level, 1 resample per level, mid (3), 3+1 per up level, final
     auto T = [&](int C, int h, int w) { return ((size_t)B * h * w * C * 2 + 255) / 256 * 256; };
-    size_t n = T(16, H, W) + T(u->dims[0], H, W);
+    const int L = u->L;
+    size_t n = T(u->cin_pad, H, W) + T(u->dims[0], H, W);
     int h = H, w = W;
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < L; ++i) {
         n += 3 * T(u->dims[i], h, w);
-        if (i < 3) { h /= 2; w /= 2; }
+        if (i < L - 1) { h /= 2; w /= 2; }
         n += T(u->dims[i + 1], h, w);
     }
-    n += 3 * T(u->dims[4], h, w);
-    for (int i = 0; i < 4; ++i) {
-        const int co = u->dims[4 - i], ci = u->dims[3 - i];
+    n += 3 * T(u->dims[L], h, w);
+    for (int i = 0; i < L; ++i) {
+        const int co = u->dims[L - i], ci = u->dims[L - 1 - i];
         n += 3 * T(co, h, w);
-        if (i < 3) { h *= 2; w *= 2; }
+        if (i < L - 1) { h *= 2; w *= 2; }
         n += T(ci, h, w);
     }
     n += T(u->dims[0], H, W);
@@ -516,8 +522,8 @@ size_t scratch_bytes(const ofd_unet* u, int B, int H, int W) {
     const int C = u->dims[0];
     size_t act = px * 2 * (size_t)(3 * C + C + 384 + 128 + C);
     // mid level widest: 512 ch at 1/64 of the pixels is far smaller; small buffers:
-    size_t small = 4 * ofd_conv_gn_partial_count(B, H, W, u->dims[4]) * 4 + (size_t)B * 4 * ((size_t)(la_fwd_parts(B, H * W) > 256 ? la_fwd_parts(B, H * W) : 256) * 1088 + 1024) * 4 +
-                   16 * (size_t)B * u->dims[4] * 4 + 64 * 1024;
+    size_t small = 4 * ofd_conv_gn_partial_count(B, H, W, u->dims[u->L]) * 4 + (size_t)B * 4 * ((size_t)(la_fwd_parts(B, H * W) > 256 ? la_fwd_parts(B, H * W) : 256) * 1088 + 1024) * 4 +
+                   16 * (size_t)B * u->dims[u->L] * 4 + 64 * 1024;
     return act + small + 64 * 256;
 }
 
@@ -564,12 +570,16 @@ extern "C" int ofd_unet_bind_param_buffer(ofd_unet* u, float* dev_params, size_t
 extern "C" int ofd_unet_create(const ofd_unet_config* cfg, ofd_unet** out) {
     OFD_CHECK_ARG(cfg && out, "unet_create: null argument");
     OFD_CHECK_ARG(cfg->dim == 64, "unet_create: dim=%d unsupported (the FlowDiffuser UNet is Unet(64), flow_diffuser.py:106)", cfg->dim);
-    OFD_CHECK_ARG(cfg->channels >= 1 && cfg->channels <= 16, "unet_create: channels=%d (1..16)", cfg->channels);
-    OFD_CHECK_ARG(cfg->out_dim >= 1 && cfg->out_dim <= 4, "unet_create: out_dim=%d (1..4)", cfg->out_dim);
+    OFD_CHECK_ARG(cfg->channels >= 1 && cfg->channels <= 48, "unet_create: channels=%d (1..48)", cfg->channels);
+    OFD_CHECK_ARG(cfg->out_dim >= 1 && cfg->out_dim <= 16, "unet_create: out_dim=%d (1..16)", cfg->out_dim);
+    OFD_CHECK_ARG(cfg->n_levels == 0 || cfg->n_levels == 3 || cfg->n_levels == 4, "unet_create: n_levels=%d (0 or 4: dim_mults (1,2,4,8); 3: (1,2,4))",
+                  cfg->n_levels);
+    OFD_CHECK_ARG(cfg->n_levels != 3 || cfg->no_time == 1, "unet_create: the three-level UNet (the Autoencoder's) takes no time input (no_time=1)");
     OFD_CHECK_ARG(cfg->eps_mode == 0 || cfg->eps_mode == 1, "unet_create: eps_mode=%d", cfg->eps_mode);
     OFD_CHECK_ARG(cfg->no_time == 0 || cfg->no_time == 1, "unet_create: no_time=%d", cfg->no_time);
     ofd_unet* u = new ofd_unet();
     u->cfg = *cfg;
+    u->L = cfg->n_levels == 3 ? 3 : 4;
     { const char* e = getenv("OFD_DETERMINISTIC"); u->deterministic = e && atoi(e) != 0; }      // default of ofd_unet_set_deterministic
     build_registry(u);
     if (hipMalloc(&u->d_params, u->n_param_floats * sizeof(float)) != hipSuccess ||
@@ -727,7 +737,9 @@ extern "C" int ofd_unet_set_graph(ofd_unet* u, int enabled) {
 extern "C" int ofd_unet_forward(ofd_unet* u, const float* x, int Cx, const float* cond, int Cc, const int64_t* t, float* out,
                                 int B, int H, int W, void* workspace, size_t workspace_bytes, void* stream) {
     OFD_CHECK_ARG(u && x && (t || u->cfg.no_time) && out && workspace, "unet_forward: null argument");
-    OFD_CHECK_ARG(B > 0 && H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0, "unet_forward: H=%d W=%d must be positive multiples of 8 (three 2x down-samplings, DD:95-99)", H, W);
+    const int mult = 1 << (u->L - 1);
+    OFD_CHECK_ARG(B > 0 && H > 0 && W > 0 && H % mult == 0 && W % mult == 0, "unet_forward: H=%d W=%d must be positive multiples of %d (%d 2x down-samplings, DD:95-99)",
+                  H, W, mult, u->L - 1);
     OFD_CHECK_ARG(Cx + (cond ? Cc : 0) == u->cfg.channels, "unet_forward: %d + %d input channels, UNet has %d", Cx, cond ? Cc : 0, u->cfg.channels);
     if (!u->prepared) { set_error("unet_forward: call ofd_unet_prepare after setting parameters"); return OFD_ERR_STATE; }
     if (workspace_bytes < ofd_unet_workspace_bytes(u, B, H, W)) {
@@ -859,6 +871,16 @@ extern "C" int ofd_unet_set_split_streams(ofd_unet* u, int enabled, int offset_b
 extern "C" int ofd_unet_set_debug_taps(ofd_unet* u, int enabled) {
     OFD_CHECK_ARG(u, "unet_set_debug_taps: null handle");
     u->debug_taps = enabled != 0;
+    return OFD_OK;
+}
+
+extern "C" int ofd_unet_set_glue(ofd_unet* u, int x_affine, int cond_affine, int out_mode, float out_div) {
+    OFD_CHECK_ARG(u, "unet_set_glue: null handle");
+    OFD_CHECK_ARG((x_affine == 0 || x_affine == 1) && (cond_affine == 0 || cond_affine == 1), "unet_set_glue: affine flags are 0 or 1");
+    OFD_CHECK_ARG(out_mode >= 0 && out_mode <= 2, "unet_set_glue: out_mode=%d (0..2)", out_mode);
+    OFD_CHECK_ARG(out_div > 0.0f, "unet_set_glue: out_div=%g must be positive", (double)out_div);
+    u->glue_x = x_affine; u->glue_cond = cond_affine; u->glue_out = out_mode; u->glue_div = out_div;
+    drop_graphs(u);                  // the captured launches carry the old values
     return OFD_OK;
 }
 

@@ -86,7 +86,12 @@ using namespace ofd;
 
 struct ofd_unet {
     ofd_unet_config cfg;
-    std::vector<int> dims;        // [dim, dim*1, dim*2, dim*4, dim*8]
+    int L = 4;                    // resolution levels (cfg.n_levels, 0 -> 4)
+    std::vector<int> dims;        // [dim, dim*1, dim*2, dim*4(, dim*8)]: L + 1 entries
+    int cin_pad = 16;             // channels of the staged input / the 7x7 init conv's K (16, 32 or 48; 8 with the tap-pair packing)
+    // ofd_unet_set_glue: the Autoencoder's elementwise glue, folded into the input staging and the final conv (inference only)
+    int glue_x = 0, glue_cond = 0, glue_out = 0;
+    float glue_div = 1.0f;
     std::vector<Param> params;
     std::map<std::string, int> pindex;
     std::vector<ConvDesc> convs;

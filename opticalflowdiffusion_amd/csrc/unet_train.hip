@@ -490,7 +490,7 @@ static int plan(ofd_unet* u, int B, int H, int W, TrainLayout& L) {
 }  // namespace ofd
 
 extern "C" size_t ofd_unet_train_workspace_bytes(ofd_unet* u, int B, int H, int W) {
-    if (!u || B <= 0 || H <= 0 || W <= 0 || H % 8 || W % 8) return 0;
+    if (!u || u->L != 4 || B <= 0 || H <= 0 || W <= 0 || H % 8 || W % 8) return 0;
     TrainLayout L;
     if (plan(u, B, H, W, L) != OFD_OK) return 0;
     return L.small_b + 2 * L.persist_b + L.scratch_b + 4096;
@@ -579,6 +579,10 @@ static int prepare_train(ofd_unet* u, hipStream_t s) {
 extern "C" int ofd_unet_train_forward(ofd_unet* u, const float* x, int Cx, const float* cond, int Cc, const int64_t* t, float* out, int B, int H,
                                       int W, void* workspace, size_t workspace_bytes, void* stream) {
     OFD_CHECK_ARG(u && x && (t || u->cfg.no_time) && out && workspace, "unet_train_forward: null argument");
+    OFD_CHECK_ARG(u->L == 4, "unet_train_forward: the three-level UNet (the Autoencoder's, dim_mults=(1,2,4)) is inference-only: it stays frozen "
+                  "in FlowDiffuser, and training it belongs to the reference's FlowPred");
+    OFD_CHECK_ARG(!u->glue_x && !u->glue_cond && !u->glue_out, "unet_train_forward: the Autoencoder glue (ofd_unet_set_glue) is inference-only");
+    OFD_CHECK_ARG(u->cfg.out_dim <= 4, "unet_train_forward: out_dim=%d: training takes out_dim <= 4", u->cfg.out_dim);
     OFD_CHECK_ARG(B > 0 && H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0, "unet_train_forward: H=%d W=%d must be positive multiples of 8", H, W);
     OFD_CHECK_ARG(Cx + (cond ? Cc : 0) == u->cfg.channels, "unet_train_forward: %d + %d input channels, UNet has %d", Cx, cond ? Cc : 0, u->cfg.channels);
     OFD_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "unet_train_forward: workspace must be 256-byte aligned");
@@ -610,6 +614,7 @@ extern "C" int ofd_unet_train_forward(ofd_unet* u, const float* x, int Cx, const
 
 extern "C" int ofd_unet_backward(ofd_unet* u, const float* dout, ofd_grad_ready_fn on_ready, void* user, void* stream) {
     OFD_CHECK_ARG(u && dout, "unet_backward: null argument");
+    OFD_CHECK_ARG(u->L == 4, "unet_backward: the three-level UNet (dim_mults=(1,2,4)) is inference-only");
     if (!u->ts.valid) { set_error("unet_backward: no training forward to differentiate (call ofd_unet_train_forward first)"); return OFD_ERR_STATE; }
     if (!u->d_grads) { set_error("unet_backward: bind a gradient buffer first (ofd_unet_bind_grad_buffer)"); return OFD_ERR_STATE; }
     const int B = u->ts.B;

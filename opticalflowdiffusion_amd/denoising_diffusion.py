@@ -39,10 +39,10 @@ class _Node(nn.Module):
     """Parameter container that reproduces the reference's module tree in state-dict keys."""
 
 
-def _registry(dim, channels, out_dim, eps_mode, no_time=0):
+def _registry(dim, channels, out_dim, eps_mode, no_time=0, n_levels=4):
     """(handle, [(name, shape)]) from the C library, which owns the layer table."""
     lib = L.lib()
-    cfg = L.UnetConfig(dim, channels, out_dim, eps_mode, no_time)
+    cfg = L.UnetConfig(dim, channels, out_dim, eps_mode, no_time, n_levels)
     h = ctypes.c_void_p()
     L.check(lib.ofd_unet_create(ctypes.byref(cfg), ctypes.byref(h)))
     names = []
@@ -72,15 +72,21 @@ class _UnetTrain(torch.autograd.Function):
 
 class Unet(nn.Module):
     """DD:272-417.  Supported: dim=64, dim_mults=(1,2,4,8), no self-conditioning -- the UNet FlowDiffuser instantiates
-    (FD:106-111), with time_in=True (diffusion) or time_in=False (is_diffusion=False, and FlowLearner's regression UNet)."""
+    (FD:106-111), with time_in=True (diffusion) or time_in=False (is_diffusion=False, and FlowLearner's regression UNet) --
+    and dim_mults=(1,2,4) with time_in=False, the two UNets of the reference's Autoencoder (flow_pred.py:21-34), for
+    inference only.  channels 1..48, out_dim 1..16."""
 
     def __init__(self, dim, init_dim=None, out_dim=None, dim_mults=(1, 2, 4, 8), channels=3, self_condition=False,
                  resnet_block_groups=8, learned_variance=False, learned_sinusoidal_cond=False,
                  random_fourier_features=False, learned_sinusoidal_dim=16, time_in=True, precision="bf16"):
         super().__init__()
-        if (dim != 64 or tuple(dim_mults) != (1, 2, 4, 8) or self_condition or learned_variance or learned_sinusoidal_cond
+        levels = {(1, 2, 4, 8): 4, (1, 2, 4): 3}.get(tuple(dim_mults))
+        if (dim != 64 or levels is None or (levels == 3 and time_in) or self_condition or learned_variance or learned_sinusoidal_cond
                 or random_fourier_features or resnet_block_groups != 8 or init_dim not in (None, dim)):
-            raise NotImplementedError("the HIP engine implements the FlowDiffuser UNet: Unet(64, channels=, out_dim=, time_in=)")
+            raise NotImplementedError("the HIP engine implements the FlowDiffuser UNet: Unet(64, channels=, out_dim=, time_in=), and the "
+                                      "Autoencoder's Unet(64, dim_mults=(1, 2, 4), time_in=False, channels=, out_dim=)")
+        self.dim_mults = tuple(dim_mults)
+        self.n_levels = levels
         self.channels = channels
         self.self_condition = False
         self.time_in = bool(time_in)
@@ -89,7 +95,7 @@ class Unet(nn.Module):
         self.dim = dim
         # eps_mode 1: per-site eps of the reference under bf16 autocast (DD:107,122); 0: fp32 rule
         self.eps_mode = 1 if precision == "bf16" else 0
-        self._handle, reg = _registry(dim, channels, self.out_dim, self.eps_mode, 0 if self.time_in else 1)
+        self._handle, reg = _registry(dim, channels, self.out_dim, self.eps_mode, 0 if self.time_in else 1, levels)
         self._names = [n for n, _ in reg]
         gen = torch.Generator().manual_seed(torch.initial_seed() % (2 ** 31))
         fan_in = 1
@@ -192,6 +198,9 @@ class Unet(nn.Module):
         x = L.f32c(x)
         cond = L.f32c(external_cond) if external_cond is not None else None
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            if self.n_levels == 3:
+                raise L.OfdError("Unet(dim_mults=(1, 2, 4)) is inference-only on the HIP engine (the Autoencoder stays frozen): call it under "
+                                 "torch.no_grad() or with requires_grad_(False) parameters")
             return _UnetTrain.apply(self, x, cond, time.to(torch.int64).contiguous() if self.time_in else None,
                                     *[self._param(n) for n in self._names])
         B, Cx, H, W = x.shape
@@ -282,6 +291,11 @@ class Unet(nn.Module):
         """materialise every named intermediate of the inference forward for `read_tap` (off: `final_res_block`'s output is never written,
         the final 1x1 conv rides on its producer's tile)"""
         L.check(L.lib().ofd_unet_set_debug_taps(self._handle, int(enabled)))
+
+    def set_glue(self, x_affine=False, cond_affine=False, out_mode=0, out_div=1.0):
+        """the Autoencoder's elementwise glue inside the forward (inference only): x / cond planes enter as 2 v - 1, and the output is
+        clamp(clamp(v, -1, 1) / out_div, -1, 1) (out_mode 1) or (clamp(v, -1, 1) + 1) / 2 (out_mode 2)"""
+        L.check(L.lib().ofd_unet_set_glue(self._handle, int(bool(x_affine)), int(bool(cond_affine)), int(out_mode), float(out_div)))
 
     def set_graph(self, enabled=True):
         """replay the inference forward as one hipGraph per (shape, stream) instead of ~250 launches (launch-bound

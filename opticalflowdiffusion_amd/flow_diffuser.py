@@ -6,8 +6,10 @@ The reference class is a `pl.LightningModule`; Lightning, Hydra and W&B are opti
 with the hooks `experiments/exp_base.py` drives (`log_dict`, `configure_optimizers`,
 `training_step`, `validation_step`).  `cfg` may be a DictConfig, a dict or any attribute object
 with the keys of configurations/algorithm/flow_diffuser.yaml (+ optional `image_size: [H, W]`,
-`sampling_timesteps`, `precision`).
+`sampling_timesteps`, `precision`, `ae_checkpoint`).
 """
+import os
+
 import torch
 
 from .denoising_diffusion import Unet, ConditionalDiffusion
@@ -106,9 +108,18 @@ class UnetWithWarp(torch.nn.Module):
         return torch.cat((out, flow), dim=1)
 
 
+def ae_checkpoint_path(cfg):
+    """where latent mode loads the autoencoder from: the optional cfg key `ae_checkpoint`, else the reference's local path
+    outputs/loaded_checkpoints/diffusion_control/<ae>/model.ckpt relative to the working directory (FD:84-85)"""
+    p = cfg.ae_checkpoint if "ae_checkpoint" in cfg else None
+    return p if p else os.path.join("outputs", "loaded_checkpoints", "diffusion_control", str(cfg.ae), "model.ckpt")
+
+
 class FlowDiffuser(_Base):
-    """FD:65-388 (latent=False): `training_step` is differentiable through the HIP training executor
-    (`ofd_unet_train_forward` / `ofd_unet_backward` behind `denoising_diffusion._UnetTrain`)."""
+    """FD:65-388: `training_step` is differentiable through the HIP training executor
+    (`ofd_unet_train_forward` / `ofd_unet_backward` behind `denoising_diffusion._UnetTrain`).  latent=True runs the diffusion
+    on the latents of the reference's frozen `Autoencoder` (flow_pred.py), loaded from a local Lightning checkpoint
+    (`ae_checkpoint_path`); nothing is downloaded."""
 
     def __init__(self, cfg):
         super().__init__()
@@ -119,9 +130,19 @@ class FlowDiffuser(_Base):
         self.is_diffusion = cfg.is_diffusion
         self.latent = cfg.latent
         self.target = cfg.target
-        if self.latent:
-            raise NotImplementedError("latent=True needs the reference's W&B autoencoder checkpoint (FD:84-90): network fetch")
-        self.dim = 3
+        if self.latent:                                                     # FD:81-95, without the download
+            path = ae_checkpoint_path(cfg)
+            if not os.path.exists(path):                                    # checked before any engine call
+                raise FileNotFoundError(f"latent=True: no autoencoder checkpoint at '{path}' (train one with the reference's FlowPred, or "
+                                        f"set cfg.ae_checkpoint; nothing is downloaded)")
+            from .flow_pred import Autoencoder
+            self.ae = Autoencoder(cfg)
+            state_dict = torch.load(path, map_location="cpu", weights_only=False)["state_dict"]
+            state_dict = {k.replace("ae.", ""): v for k, v in state_dict.items() if k.startswith("ae.")}
+            self.ae.load_state_dict(state_dict)
+            for p in self.ae.parameters():
+                p.requires_grad = False
+        self.dim = cfg.latent_dim if self.latent else 3
         if self.target == "target":                                         # FD:98-104
             unet_dims = self.dim + 1
         elif self.target == "joint":
@@ -137,9 +158,11 @@ class FlowDiffuser(_Base):
         if not self.is_diffusion:                                           # FD:128-129: plain regression cond -> flow
             self.model = self._model
             return
-        self.model = ConditionalDiffusion(                                  # FD:118-127
+        # FD:118-127.  The diffused tensor has the target's real channel count: flow 2, target `dim`, joint `dim + 2` (the reference passes
+        # latent_dim for every latent target, FD:122, which feeds its UNet the wrong count for joint / flow: INTEGRATION.md)
+        self.model = ConditionalDiffusion(
             self._model, cfg.image_size, objective="pred_x0",
-            channels=2 + 1 * int(cfg.target == "target") + 3 * int(cfg.target == "joint"),
+            channels={"target": self.dim, "joint": self.dim + 2}.get(cfg.target, 2),
             auto_normalize=False, noise_space="image" if cfg.noiser == "image" else "flow",
             timesteps=cfg.timesteps, sampling_timesteps=cfg.sampling_timesteps, min_snr_loss_weight=True)
         if "trajectory_stride" in cfg:                                      # optional key, default = every frame as the reference
@@ -166,8 +189,13 @@ class FlowDiffuser(_Base):
                 batch = self.augmentor(batch)
         img, tgt, flow = batch
         flow = torch.clamp(flow / self.flow_max, -1.0, 1.0)
-        img = 2 * img - 1.0
-        tgt = 2 * tgt - 1.0
+        if self.latent:                                                     # FD:143-148: clamp(clamp(enc, -1, 1) / latent_max, -1, 1)
+            with torch.no_grad():
+                img = self.ae._enc(img, float(self.latent_max))
+                tgt = self.ae._enc(tgt, float(self.latent_max))
+        else:
+            img = 2 * img - 1.0
+            tgt = 2 * tgt - 1.0
         ret = []
         if self.target == "target":
             ret.append(warp(img, None, flow * self.flow_max, mode="forward"))
@@ -279,8 +307,8 @@ class FlowDiffuser(_Base):
                 p_flows = p_flows[:, -1] * self.flow_max
             else:
                 p_flows = p_flows * self.flow_max if not warped_target else p_flows
-            # samples / tgt live in [-1, 1] / [0, 1] exactly as in the reference's comparison (FD:255)
-            mse = torch.nn.functional.mse_loss(torch.nan_to_num(samples), tgt)
+            # samples / tgt live in [-1, 1] / [0, 1] exactly as in the reference's comparison (FD:255; latent: against ae.encode(tgt))
+            mse = torch.nn.functional.mse_loss(torch.nan_to_num(samples), tgt if not self.latent else self.ae.encode(tgt))
             scalars = {
                 "val/loss": loss, "val/mse": mse,
                 "val/cond_min": torch.min(cond), "val/cond_max": torch.max(cond), "val/cond_mean": torch.mean(cond),
@@ -311,16 +339,27 @@ class FlowDiffuser(_Base):
             self._log_image("original", chunk(img))
             self._log_image("target", chunk(tgt))
             self._log_image("diffusion_tgt", chunk((tgt_[:, :self.dim] + 1.0) * 0.5) if tgt_.shape[1] >= self.dim else chunk(tgt))
-            self._log_image("original_warped", chunk(warp(img, None, flow, mode="forward")))
+            if not self.latent:
+                self._log_image("original_warped", chunk(warp(img, None, flow, mode="forward")))
             self._log_image("gt_flow", chunk(gt_flow))
             self._log_image("target_p", chunk(sample_flow))
             self._log_image("concat", chunk(torch.cat((gt_flow, sample_flow), dim=3)))
             self._log_image("difference", chunk(diff_flow))
-            self._log_image("samples", chunk(samples))
+            if self.latent:                                                  # FD:304-311: the samples decoded back to images
+                dec = self.ae.decode(samples * self.latent_max, img)
+                self._log_image("samples", chunk(dec))
+                self._log_image("compare", chunk(torch.cat((img, dec), dim=-1)))
+                self._log_image("dec_gt", chunk(self.ae(img, flow)))
+            else:
+                self._log_image("samples", chunk(samples))
 
             if self.is_diffusion and warped_target:                          # FD:317-338: strips of every 50th step
-                strip = torch.cat(torch.chunk(mid_samples, mid_samples.shape[1], dim=1), dim=-1)[:, 0]
-                strip = torch.clamp(torch.nan_to_num(strip), -1.0, 1.0)
+                if self.latent:                                              # FD:316-320: every strip frame decoded
+                    strip = torch.cat([self.ae.decode(m[:, 0] * self.latent_max, img)
+                                       for m in torch.chunk(mid_samples, mid_samples.shape[1], dim=1)], dim=-1)
+                else:
+                    strip = torch.cat(torch.chunk(mid_samples, mid_samples.shape[1], dim=1), dim=-1)[:, 0]
+                    strip = torch.clamp(torch.nan_to_num(strip), -1.0, 1.0)
                 if self.target == "target":
                     fstrip = torch.cat([flow_to_image(m) / 255.0 for m in mid_flows], dim=-1)
                 else:

@@ -185,9 +185,11 @@ def attach_grad_sync(flow_diffuser_or_unet, bucket_bytes=32 << 20, group=None, b
     """data-parallel training: average the UNet's gradients across ranks inside every backward."""
     from .denoising_diffusion import Unet
     root = flow_diffuser_or_unet
-    unets = [m for m in root.modules() if isinstance(m, Unet)] if isinstance(root, torch.nn.Module) else []
+    # the trainable ones: FlowDiffuser(latent=True) also holds the frozen Autoencoder's two UNets, which take no part in the all-reduce
+    unets = ([m for m in root.modules() if isinstance(m, Unet) and any(p.requires_grad for p in m.parameters())]
+             if isinstance(root, torch.nn.Module) else [])
     if len(unets) != 1:        # FlowDiffuser.unet, FlowLearner.unet.model (inside UnetWithWarp), or a bare Unet
-        raise ValueError(f"attach_grad_sync: expected exactly one engine Unet under the module, found {len(unets)}")
+        raise ValueError(f"attach_grad_sync: expected exactly one trainable engine Unet under the module, found {len(unets)}")
     unets[0].grad_sync = BucketedAllReduce(bucket_bytes, group, bucket_dtype)
     return unets[0].grad_sync
 
