@@ -163,7 +163,7 @@ typedef struct {
                            (DD:192-195), the `t` argument of the forward calls is ignored and may be NULL */
     int n_levels;       /* resolution levels: 0 or 4 = dim_mults (1,2,4,8) (the diffusion UNet; 0 keeps configs written before this
                            field existed meaning 4), 3 = dim_mults (1,2,4) (the reference's Autoencoder, flow_pred.py:17-35; requires
-                           no_time = 1; inference only: the training calls return OFD_ERR_ARG).  channels 1..48, out_dim 1..16. */
+                           no_time = 1; trains like the four-level UNet).  channels 1..48, out_dim 1..16. */
 } ofd_unet_config;
 
 int ofd_unet_create(const ofd_unet_config* cfg, ofd_unet** out);
@@ -212,8 +212,8 @@ int ofd_unet_read_tap(ofd_unet* u, const char* name, float* dst, size_t numel, v
  * the final 1x1 conv (DD:361) then rides on the tile of its producer (out_dim 2, H*W a multiple of 128) and "final_res_block" is
  * not a tap.  The two forms sum the 64 products of a pixel in different orders (equal to fp32 rounding). */
 int ofd_unet_set_debug_taps(ofd_unet* u, int enabled);
-/* elementwise glue of the reference's Autoencoder (flow_pred.py:38-58) folded into the inference forward (the training calls return
- * OFD_ERR_ARG while any of it is on):
+/* elementwise glue of the reference's Autoencoder (flow_pred.py:38-58) folded into the forward, inference and training (the backward
+ * differentiates the clamps as torch.clamp does: gradient where -1 <= v <= 1, v recomputed by the final conv's backward kernel):
  *   x_affine / cond_affine = 1: the input staging feeds 2 v - 1 instead of v for the x / cond planes (encoder 2x-1; decoder cat(l, 2x-1));
  *   out_mode 0: plain output; 1: clamp(clamp(v, -1, 1) / out_div, -1, 1) (encode, and FD:145-148 with out_div = latent_max);
  *   2: (clamp(v, -1, 1) + 1) / 2 (decode).  Applied by the final 1x1 conv's kernel on its fp32 result (out_mode != 0 runs the unfused
@@ -310,6 +310,10 @@ int ofd_conv_wgrad(const ofd_conv_args* fwd, const void* dy, float* dw_acc, void
 int ofd_conv7_wgrad(const void* x16, const void* dy, float* dw_acc, int B, int H, int W, void* stream);
 /* the same for an input packed to `channels` = 8, 16, 32 or 48 (pixel stride); dw_acc is [49][channels][64] */
 int ofd_conv7_wgrad_c(const void* x, const void* dy, float* dw_acc, int B, int H, int W, int channels, void* stream);
+/* data gradient of the 7x7 init conv w.r.t. its first cx <= 16 input channels: dy NHWC bf16 [B][H][W][64], w_t the tap-flipped transposed
+ * weights of ofd_conv_dgrad_weight_prep (Cin = cin_pad = 16, 32 or 48) -> dx NCHW fp32 [B][cx][H][W] = scale * conv_transpose(dy)
+ * (written, not added; deterministic: a gather, no atomics) */
+int ofd_conv7_dgrad(const void* dy, const void* w_t, int cin_pad, float* dx, int cx, int B, int H, int W, float scale, void* stream);
 int ofd_conv_wgrad_finish(const float* dw_acc, const float* w_oihw, float* dst_oihw, int Cout, int Cin, int Cin_pad,
                           int ksize, float ws_eps, int unshuffle, int accumulate, void* stream);
 int ofd_grad_scatter(const void* D, int Ctot, int ch_off, void* dst, int C, int B, int H, int W, int mode,
@@ -338,6 +342,11 @@ int ofd_final_conv(const void* x, const float* w, const float* b, float* out, in
                    float out_div, void* stream);
 int ofd_final_conv_backward(const void* x, const float* w, const float* dy, void* dx, float* dw, float* db,
                             int B, int H, int W, int C, int out_dim, void* stream);
+/* the same through the forward's output glue (ofd_final_conv's out_mode / out_div): dy is dL/d(glue output); the clamps are
+ * differentiated as torch.clamp (gradient where -1 <= v <= 1, inclusive), v recomputed from x, w and b with the forward's arithmetic.
+ * out_dim <= 4 (C = 64 or 128) or <= 16 (C = 64). */
+int ofd_final_conv_backward_glue(const void* x, const float* w, const float* b, const float* dy, void* dx, float* dw, float* db,
+                                 int B, int H, int W, int C, int out_dim, int out_mode, float out_div, void* stream);
 
 /* --------------------------------------------------- attention cores, forward + backward -------
  * qkv / dqkv: [B][n][384] bf16 (q | k | v, 4 heads x 32); out / dout: [B][n][128] bf16.
@@ -372,6 +381,9 @@ int ofd_unet_bind_grad_buffer(ofd_unet* u, float* dev_grads, size_t floats);
 int ofd_unet_train_forward(ofd_unet* u, const float* x, int Cx, const float* cond, int Cc, const int64_t* t,
                            float* out, int B, int H, int W, void* workspace, size_t workspace_bytes, void* stream);
 int ofd_unet_backward(ofd_unet* u, const float* dout, ofd_grad_ready_fn on_ready, void* user, void* stream);
+/* ofd_unet_backward plus dL/dx of the first Cdx (<= 16) input channels, written to dx [B][Cdx][H][W] fp32: the data gradient of the 7x7
+ * init conv (times 2 when the x glue of ofd_unet_set_glue stages 2 x - 1) */
+int ofd_unet_backward_dx(ofd_unet* u, const float* dout, float* dx, int Cdx, ofd_grad_ready_fn on_ready, void* user, void* stream);
 
 /* --------------------------------------------------- forward building blocks of the UNet executor ----
  * ofd_layernorm_c (DD:116-125): out = LN_channels(x) * g (+ residual), NHWC bf16, npix rows of C channels.

@@ -5,3 +5,4 @@ from .softsplat import softsplat  # noqa: F401
 from .denoising_diffusion import Unet, ConditionalDiffusion  # noqa: F401,E402
 from .flow_diffuser import FlowDiffuser, UnetWithWarp  # noqa: F401,E402
 from .flow_learner import FlowLearner  # noqa: F401,E402
+from .flow_pred import FlowPred, Autoencoder  # noqa: F401,E402

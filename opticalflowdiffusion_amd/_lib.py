@@ -111,6 +111,8 @@ SIGNATURES = {
     "ofd_affine_silu": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p]),
     "ofd_layernorm_c_backward": (c_int, [c_void_p] * 5 + [c_size_t, c_int, c_float, c_int, c_void_p]),
     "ofd_final_conv_backward": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p]),
+    "ofd_final_conv_backward_glue": (c_int, [c_void_p] * 7 + [c_int] * 6 + [c_float, c_void_p]),
+    "ofd_conv7_dgrad": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "ofd_final_conv": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_float, c_void_p]),
     "ofd_la_workspace_floats": (c_size_t, [c_int, c_int]),
     "ofd_la_bwd_workspace_floats": (c_size_t, [c_int, c_int]),
@@ -124,6 +126,7 @@ SIGNATURES = {
     "ofd_unet_bind_grad_buffer": (c_int, [c_void_p, c_void_p, c_size_t]),
     "ofd_unet_train_forward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "ofd_unet_backward": (c_int, [c_void_p, c_void_p, GRAD_READY, c_void_p, c_void_p]),
+    "ofd_unet_backward_dx": (c_int, [c_void_p, c_void_p, c_void_p, c_int, GRAD_READY, c_void_p, c_void_p]),
     "ofd_nan_mse_grad": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ofd_layernorm_c": (c_int, [c_void_p] * 4 + [c_size_t, c_int, c_float, c_void_p]),
     "ofd_time_mlp": (c_int, [c_void_p] * 7 + [c_int, c_int, c_void_p]),

@@ -72,7 +72,10 @@ int k_gn_silu_backward(const bf16_t* g, const bf16_t* h, const float* a, const f
 int k_layernorm_c_bwd(const bf16_t* x, const float* gw, const bf16_t* dy, bf16_t* dx, float* dg, size_t npix, int C, float eps, int accumulate,
                       hipStream_t st, const bf16_t* extra = nullptr);
 int k_final_conv_bwd(const bf16_t* x, const float* w, const float* dy, bf16_t* dx, float* dw, float* db, int B, int H, int W, int C, int out_dim,
-                     hipStream_t st);
+                     hipStream_t st, const float* bias = nullptr, int out_mode = 0, float out_div = 1.0f);
+// data gradient of the 7x7 init conv w.r.t. its first cx <= 16 input channels (conv7_dgrad.hip): dY NHWC bf16 (64 channels), wt the tap-flipped
+// transposed bf16 weights (k_wt_transpose layout, cin_pad input channels) -> dx NCHW fp32 [B][cx][H][W] = scale * conv^T(dY)
+int k_conv7_dgrad(const bf16_t* dy, const bf16_t* wt, int cin_pad, float* dx, int cx, int B, int H, int W, float scale, hipStream_t s);
 int k_block_mlp_bwd(const float* dss, const float* temb_silu, const float* weight, int n_out, int offset, float* dweight, float* dbias, float* dts,
                     int B, int tdim, int ss_stride, hipStream_t st);
 int k_time_mlp_bwd(const int64_t* t, const float* temb, const float* dts, const float* w1, const float* b1, const float* w2, float* dw1, float* db1,

@@ -247,17 +247,35 @@ __global__ void __launch_bounds__(256) layernorm_c_bwd_kernel(const bf16_t* __re
 
 // ---- final 1x1 conv backward (DD:361,417): y[o] = sum_c w[o,c] x[c] + b[o], y NCHW fp32, x NHWC bf16 -----
 // dx[c] = sum_o w[o,c] dy[o] ; dw[o,c] += sum_p dy[o] x[c] ; db[o] += sum_p dy[o]
-__global__ void __launch_bounds__(256) final_conv_bwd_kernel(const bf16_t* __restrict__ x, const float* __restrict__ w, const float* __restrict__ dy,
-                                                             bf16_t* __restrict__ dx, float* __restrict__ dw, float* __restrict__ db, int C, int out_dim,
-                                                             size_t plane, size_t total) {
-    extern __shared__ float sm[];          // [4 waves][out_dim*C + 4]: dw row and db of each wave, added in wave order (no LDS float atomics)
-    const int rowf = out_dim * C + 4;
+// OD = 4 (out_dim <= 4, C = 64 or 128) or 16 (the Autoencoder's encoder: 5..16 outputs, C = 64).
+// out_mode != 0: the forward's output glue (blocks.hip out_glue) is differentiated as torch.clamp is: dy passes where -1 <= v <= 1
+// (inclusive; NaN: no), times 1 / div (mode 1, both clamps) or 1 / 2 (mode 2).  v is recomputed here with the forward kernel's own
+// arithmetic (same lane layout, same per-lane product order, same butterfly), so the mask is the forward's.
+__device__ __forceinline__ float t_clamp1(float v) { return v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v); }
+__device__ __forceinline__ float glue_grad(float d, float v, int mode, float div) {
+    if (mode == 1) {
+        const float u = t_clamp1(v) / div;
+        return (v >= -1.0f && v <= 1.0f && u >= -1.0f && u <= 1.0f) ? d / div : 0.0f;
+    }
+    if (mode == 2) return (v >= -1.0f && v <= 1.0f) ? d * 0.5f : 0.0f;
+    return d;
+}
+
+template <int OD>
+__global__ void __launch_bounds__(256) final_conv_bwd_kernel(const bf16_t* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                                             const float* __restrict__ dy, bf16_t* __restrict__ dx, float* __restrict__ dw,
+                                                             float* __restrict__ db, int C, int out_dim, size_t plane, size_t total, int out_mode,
+                                                             float out_div) {
+    extern __shared__ float sm[];          // [4 waves][out_dim*C + OD]: dw row and db of each wave, added in wave order (no LDS float atomics)
+    const int rowf = out_dim * C + OD;
     const int lpp = C / 8, lane = threadIdx.x & 63, sub = lane % lpp, slot = lane / lpp, ppw = 64 / lpp;
-    float wv[4][8], dwl[4][8], dbl[4] = {0, 0, 0, 0};
+    float wv[OD][8], dwl[OD][8], dbl[OD];
 #pragma unroll
-    for (int o = 0; o < 4; ++o)
+    for (int o = 0; o < OD; ++o) {
+        dbl[o] = 0.0f;
 #pragma unroll
         for (int j = 0; j < 8; ++j) { wv[o][j] = (o < out_dim) ? w[o * C + sub * 8 + j] : 0.0f; dwl[o][j] = 0.0f; }
+    }
     const size_t wave_global = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((size_t)gridDim.x * blockDim.x) >> 6;
     for (size_t p0 = wave_global * ppw; p0 < total; p0 += nwaves * ppw) {
         const size_t i = min(p0 + slot, total - 1);
@@ -265,10 +283,22 @@ __global__ void __launch_bounds__(256) final_conv_bwd_kernel(const bf16_t* __res
         const size_t n = i / plane, pix = i % plane;
         float f[8], dxv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         t_unpack8(*(const uint4*)(x + i * C + sub * 8), f);
+        float v[OD];
+        if (out_mode) {
+            // the forward's v (blocks.hip final_conv_kernel): per-lane products in channel order, then the xor butterfly
 #pragma unroll
-        for (int o = 0; o < 4; ++o) {
+            for (int o = 0; o < OD; ++o) {
+                v[o] = 0.0f;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[o] += f[j] * wv[o][j];
+                for (int k = 1; k < lpp; k <<= 1) v[o] += __shfl_xor(v[o], k, 64);
+            }
+        }
+#pragma unroll
+        for (int o = 0; o < OD; ++o) {
             if (o < out_dim) {
-                const float d = ok ? dy[(n * out_dim + o) * plane + pix] : 0.0f;
+                float d = ok ? dy[(n * out_dim + o) * plane + pix] : 0.0f;
+                if (out_mode) d = glue_grad(d, v[o] + bias[o], out_mode, out_div);
                 if (sub == 0) dbl[o] += d;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) { dxv[j] += wv[o][j] * d; dwl[o][j] += d * f[j]; }
@@ -278,7 +308,7 @@ __global__ void __launch_bounds__(256) final_conv_bwd_kernel(const bf16_t* __res
     }
     float* const row = sm + (threadIdx.x >> 6) * rowf;
 #pragma unroll
-    for (int o = 0; o < 4; ++o)
+    for (int o = 0; o < OD; ++o)
         if (o < out_dim) {
             // lanes sub, sub + lpp, ... hold partial sums of the same 8 channels (db: the lanes with sub == 0): butterfly over the pixel slots
 #pragma unroll
@@ -478,11 +508,18 @@ int k_layernorm_c_bwd(const bf16_t* x, const float* gw, const bf16_t* dy, bf16_t
 }
 
 int k_final_conv_bwd(const bf16_t* x, const float* w, const float* dy, bf16_t* dx, float* dw, float* db, int B, int H, int W, int C, int out_dim,
-                     hipStream_t st) {
-    OFD_CHECK_ARG(out_dim >= 1 && out_dim <= 4 && (C == 64 || C == 128), "final_conv_bwd: out_dim=%d C=%d", out_dim, C);
+                     hipStream_t st, const float* bias, int out_mode, float out_div) {
+    OFD_CHECK_ARG(out_dim >= 1 && out_dim <= 16 && (C == 64 || (C == 128 && out_dim <= 4)), "final_conv_bwd: out_dim=%d C=%d", out_dim, C);
+    OFD_CHECK_ARG(out_mode >= 0 && out_mode <= 2 && out_div > 0.0f && (out_mode == 0 || bias), "final_conv_bwd: out_mode=%d out_div=%g (glue needs the bias)",
+                  out_mode, (double)out_div);
     const size_t total = (size_t)B * H * W;
-    final_conv_bwd_kernel<<<tgrid((total + (512 / C) - 1) / (512 / C) * 64, 1024), 256, 4 * (out_dim * C + 4) * sizeof(float), st>>>(
-        x, w, dy, dx, dw, db, C, out_dim, (size_t)H * W, total);
+    const int od = out_dim <= 4 ? 4 : 16;
+    const size_t lds = 4 * (out_dim * C + od) * sizeof(float);
+    const int grid = tgrid((total + (512 / C) - 1) / (512 / C) * 64, 1024);
+    if (od == 4)
+        final_conv_bwd_kernel<4><<<grid, 256, lds, st>>>(x, w, bias, dy, dx, dw, db, C, out_dim, (size_t)H * W, total, out_mode, out_div);
+    else
+        final_conv_bwd_kernel<16><<<grid, 256, lds, st>>>(x, w, bias, dy, dx, dw, db, C, out_dim, (size_t)H * W, total, out_mode, out_div);
     OFD_LAUNCH_CHECK();
     return OFD_OK;
 }
@@ -555,6 +592,11 @@ extern "C" int ofd_final_conv_backward(const void* x, const float* w, const floa
                                        int out_dim, void* stream) {
     OFD_CHECK_ARG(x && w && dy && dx && dw && db, "final_conv_backward: null argument");
     return k_final_conv_bwd((const bf16_t*)x, w, dy, (bf16_t*)dx, dw, db, B, H, W, C, out_dim, (hipStream_t)stream);
+}
+extern "C" int ofd_final_conv_backward_glue(const void* x, const float* w, const float* b, const float* dy, void* dx, float* dw, float* db, int B,
+                                            int H, int W, int C, int out_dim, int out_mode, float out_div, void* stream) {
+    OFD_CHECK_ARG(x && w && b && dy && dx && dw && db, "final_conv_backward_glue: null argument");
+    return k_final_conv_bwd((const bf16_t*)x, w, dy, (bf16_t*)dx, dw, db, B, H, W, C, out_dim, (hipStream_t)stream, b, out_mode, out_div);
 }
 
 // forward building blocks of the executor, exported for callers that compose their own blocks (SURVEY 8b export set)

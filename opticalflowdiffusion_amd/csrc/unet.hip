@@ -387,7 +387,7 @@ int run_forward(Ctx& c, const float* x, int Cx, const float* cond, int Cc, const
     const int L = u->L;
     Tensor xin = c.keep(cpad, H, W);
     c.begin(PC_MISC, 0, 0);
-    RUN(k_pack_input(x, Cx, cond, cond ? Cc : 0, xin.p, B, H, W, c.s, cpad, c.train ? 0 : u->glue_x, c.train ? 0 : u->glue_cond));
+    RUN(k_pack_input(x, Cx, cond, cond ? Cc : 0, xin.p, B, H, W, c.s, cpad, u->glue_x, u->glue_cond));
     if (!u->cfg.no_time) {
         RUN(k_time_mlp(t, u->P("time_mlp.1.weight"), u->P("time_mlp.1.bias"), u->P("time_mlp.3.weight"), u->P("time_mlp.3.bias"), temb, temb_silu, B, dim, c.s));
         RUN(k_block_mlp(temb_silu, u->d_mlp, (int)u->resblocks.size(), c.ss, B, dim * 4, u->ss_stride, c.s));
@@ -470,7 +470,7 @@ int run_forward(Ctx& c, const float* x, int Cx, const float* cond, int Cc, const
     // shape is not the streaming kernel's (out_dim 2, whole 128-pixel tiles)
     static const bool no_fc = (getenv("OFD_NO_FC_FUSE") && atoi(getenv("OFD_NO_FC_FUSE"))) || (getenv("OFD_CONV1_WP") && atoi(getenv("OFD_CONV1_WP")) == 0) ||
                               (getenv("OFD_CONV_DBG") && atoi(getenv("OFD_CONV_DBG")));
-    const int glue = c.train ? 0 : u->glue_out;
+    const int glue = u->glue_out;             // (training: the backward differentiates the clamps, unet_train.hip)
     const bool fuse_fc = !c.train && !u->debug_taps && !no_fc && !glue && u->cfg.out_dim == 2 && dim == 64 && ((long)H * W) % 128 == 0;
     if (fuse_fc) {
         const FcFuse fc{u->P("final_conv.weight"), u->P("final_conv.bias"), out};
@@ -944,6 +944,7 @@ const char* prof_class_name(int cls) {
         names[PC_LABWD] = "linear_attention_backward";
         names[PC_FLASHBWD] = "flash_attention_backward";
         names[PC_CONVUP] = std::string(phase_wp ? "conv_up2_phases_wp_kernel" : "conv_igemm_kernel<2,BN>") + " [Upsample x2 + 3x3 as four 2x2 phase convs]";
+        names[PC_DGRAD7] = "conv7_dgrad_kernel [7x7 init conv data gradient]";
         built = true;
     }
     return (cls >= 0 && cls < PC_COUNT) ? names[cls].c_str() : "";

@@ -37,7 +37,7 @@ struct Tensor {
     bf16_t* g = nullptr;     // gradient buffer (training forward only)
 };
 
-enum ProfClass { PC_CONV3 = 0, PC_CONV3_64, PC_CONV3_PP, PC_CONV1, PC_CONV7, PC_GN, PC_RESOUT, PC_LN, PC_LINATTN, PC_FLASH, PC_MISC, PC_WGRAD3, PC_WGRAD1, PC_DGRAD3, PC_DGRAD1, PC_GNBWD, PC_LABWD, PC_FLASHBWD, PC_CONVUP, PC_COUNT };
+enum ProfClass { PC_CONV3 = 0, PC_CONV3_64, PC_CONV3_PP, PC_CONV1, PC_CONV7, PC_GN, PC_RESOUT, PC_LN, PC_LINATTN, PC_FLASH, PC_MISC, PC_WGRAD3, PC_WGRAD1, PC_DGRAD3, PC_DGRAD1, PC_GNBWD, PC_LABWD, PC_FLASHBWD, PC_CONVUP, PC_DGRAD7, PC_COUNT };
 // class = the group of layers the executor asked for.  The NAME of a class is the kernel that serves it under the library's current switches
 // (prof_class_name, unet.hip): `<kernel family> [<layer group>]` -- classes served by the same kernel share the text before " [", which is
 // what bench.py groups by when it picks the dominant kernel.

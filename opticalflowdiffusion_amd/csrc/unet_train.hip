@@ -383,7 +383,9 @@ static TrainLayout small_layout(const ofd_unet* u, int B) {
     return L;
 }
 
-static int run_backward(Ctx& c, const float* dout, const TrainLayout& L, float* fsmall, ofd_grad_ready_fn cb, void* user) {
+// dx (may be null): dL/dx of the first cdx input channels, fp32 NCHW (the 7x7 init conv's data gradient, conv7_dgrad.hip)
+static int run_backward(Ctx& c, const float* dout, const TrainLayout& L, float* fsmall, ofd_grad_ready_fn cb, void* user, float* dx = nullptr,
+                        int cdx = 0) {
     ofd_unet* u = c.u;
     Bwd b{c, {}};
     const int B = c.B, H = u->ts.H, W = u->ts.W, dim = u->cfg.dim;
@@ -409,9 +411,9 @@ static int run_backward(Ctx& c, const float* dout, const TrainLayout& L, float* 
         if (det) RUN(det_begin(c, dts, (size_t)B * dim * 4));
         if (c.rc != OFD_OK) return c.rc;
     }
-    c.begin(PC_MISC, 0, 0, "final_conv bwd");
+    c.begin(PC_MISC, 0, (double)B * H * W * (dim * 4 + u->cfg.out_dim * 4), "final_conv bwd");
     RUN(k_final_conv_bwd(u->ts.xf.p, u->P("final_conv.weight"), dout, u->ts.xf.g, u->G("final_conv.weight"), u->G("final_conv.bias"), B, H, W, dim,
-                         u->cfg.out_dim, c.s));
+                         u->cfg.out_dim, c.s, u->P("final_conv.bias"), u->glue_out, u->glue_div));
     c.end();
     b.mark(u->ts.xf);
     notify("final_conv");
@@ -434,6 +436,13 @@ static int run_backward(Ctx& c, const float* dout, const TrainLayout& L, float* 
                 Tensor D = conv_backward(b, r.name, r.srcs, r.out.g, r.out.H, r.out.W, !first, nullptr, false, direct || up1);
                 const bool landed = direct || (up1 && D.p == r.srcs[0].t.g);
                 if (!first && !landed && c.rc == OFD_OK) scatter_to_sources(b, D, r.srcs);
+                if (first && dx) {
+                    // the input's gradient: x entered the staging as 2 x - 1 when the glue says so (d/dx = 2)
+                    const ConvDesc& d = u->convs[u->cindex.at("init_conv")];
+                    c.begin(PC_DGRAD7, 2.0 * B * H * W * 16.0 * 64 * 49, (double)B * H * W * (64 * 2 + cdx * 4), "init_conv dgrad (7x7)");
+                    RUN(k_conv7_dgrad(r.out.g, u->d_wtbuf + d.w_off, d.Cin_pad, dx, cdx, B, H, W, u->glue_x ? 2.0f : 1.0f, c.s));
+                    c.end();
+                }
             }
         }
         notify(r.name);
@@ -490,7 +499,7 @@ static int plan(ofd_unet* u, int B, int H, int W, TrainLayout& L) {
 }  // namespace ofd
 
 extern "C" size_t ofd_unet_train_workspace_bytes(ofd_unet* u, int B, int H, int W) {
-    if (!u || u->L != 4 || B <= 0 || H <= 0 || W <= 0 || H % 8 || W % 8) return 0;
+    if (!u || B <= 0 || H <= 0 || W <= 0 || H % 8 || W % 8) return 0;
     TrainLayout L;
     if (plan(u, B, H, W, L) != OFD_OK) return 0;
     return L.small_b + 2 * L.persist_b + L.scratch_b + 4096;
@@ -552,11 +561,10 @@ static int prepare_train(ofd_unet* u, hipStream_t s) {
     if (!u->d_wtbuf) OFD_HIP(hipMalloc(&u->d_wtbuf, u->n_wbuf * sizeof(bf16_t)));
     if (!u->d_wacc) OFD_HIP(hipMalloc(&u->d_wacc, u->n_wbuf * sizeof(float)));
     if (!u->wt_prepared) {
-        if (!u->d_tr) {                                       // one launch for all convs: blocks in proportion to the weight count
+        if (!u->d_tr) {                                       // one launch for all convs (the 7x7 too: ofd_unet_backward_dx): blocks in proportion to the weight count
             std::vector<ofd_weight_prep_desc> h;
             int blocks = 0;
             for (auto& cd : u->convs) {
-                if (cd.ksize == 7) continue;                  // first layer: no data gradient
                 ofd_weight_prep_desc d{(const float*)(u->d_wbuf + cd.w_off), u->d_wtbuf + cd.w_off, cd.Cout, cd.Cin, cd.Cin_pad, cd.ksize, -1.0f, 0, blocks};
                 h.push_back(d);
                 const size_t total = (size_t)cd.ksize * cd.ksize * cd.Cin_pad * cd.Cout;
@@ -579,10 +587,6 @@ static int prepare_train(ofd_unet* u, hipStream_t s) {
 extern "C" int ofd_unet_train_forward(ofd_unet* u, const float* x, int Cx, const float* cond, int Cc, const int64_t* t, float* out, int B, int H,
                                       int W, void* workspace, size_t workspace_bytes, void* stream) {
     OFD_CHECK_ARG(u && x && (t || u->cfg.no_time) && out && workspace, "unet_train_forward: null argument");
-    OFD_CHECK_ARG(u->L == 4, "unet_train_forward: the three-level UNet (the Autoencoder's, dim_mults=(1,2,4)) is inference-only: it stays frozen "
-                  "in FlowDiffuser, and training it belongs to the reference's FlowPred");
-    OFD_CHECK_ARG(!u->glue_x && !u->glue_cond && !u->glue_out, "unet_train_forward: the Autoencoder glue (ofd_unet_set_glue) is inference-only");
-    OFD_CHECK_ARG(u->cfg.out_dim <= 4, "unet_train_forward: out_dim=%d: training takes out_dim <= 4", u->cfg.out_dim);
     OFD_CHECK_ARG(B > 0 && H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0, "unet_train_forward: H=%d W=%d must be positive multiples of 8", H, W);
     OFD_CHECK_ARG(Cx + (cond ? Cc : 0) == u->cfg.channels, "unet_train_forward: %d + %d input channels, UNet has %d", Cx, cond ? Cc : 0, u->cfg.channels);
     OFD_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "unet_train_forward: workspace must be 256-byte aligned");
@@ -612,9 +616,7 @@ extern "C" int ofd_unet_train_forward(ofd_unet* u, const float* x, int Cx, const
     return OFD_OK;
 }
 
-extern "C" int ofd_unet_backward(ofd_unet* u, const float* dout, ofd_grad_ready_fn on_ready, void* user, void* stream) {
-    OFD_CHECK_ARG(u && dout, "unet_backward: null argument");
-    OFD_CHECK_ARG(u->L == 4, "unet_backward: the three-level UNet (dim_mults=(1,2,4)) is inference-only");
+static int backward(ofd_unet* u, const float* dout, ofd_grad_ready_fn on_ready, void* user, void* stream, float* dx, int cdx) {
     if (!u->ts.valid) { set_error("unet_backward: no training forward to differentiate (call ofd_unet_train_forward first)"); return OFD_ERR_STATE; }
     if (!u->d_grads) { set_error("unet_backward: bind a gradient buffer first (ofd_unet_bind_grad_buffer)"); return OFD_ERR_STATE; }
     const int B = u->ts.B;
@@ -629,7 +631,19 @@ extern "C" int ofd_unet_backward(ofd_unet* u, const float* dout, ofd_grad_ready_
     c.persist = w + L.small_b; c.persist_cap = L.persist_b; c.persist_used = u->ts.persist_used;
     c.grad_offset = L.persist_b;
     c.scratch = c.persist + 2 * L.persist_b; c.scratch_cap = u->ts.workspace_bytes - (size_t)(c.scratch - w);
-    rc = run_backward(c, dout, L, fsmall, on_ready, user);
+    rc = run_backward(c, dout, L, fsmall, on_ready, user, dx, cdx);
     u->ts.valid = false;                      // the tape is consumed (activations' scratch was reused)
     return rc;
+}
+
+extern "C" int ofd_unet_backward(ofd_unet* u, const float* dout, ofd_grad_ready_fn on_ready, void* user, void* stream) {
+    OFD_CHECK_ARG(u && dout, "unet_backward: null argument");
+    return backward(u, dout, on_ready, user, stream, nullptr, 0);
+}
+
+extern "C" int ofd_unet_backward_dx(ofd_unet* u, const float* dout, float* dx, int Cdx, ofd_grad_ready_fn on_ready, void* user, void* stream) {
+    OFD_CHECK_ARG(u && dout && dx, "unet_backward_dx: null argument");
+    OFD_CHECK_ARG(Cdx >= 1 && Cdx <= 16 && Cdx <= u->cfg.channels, "unet_backward_dx: Cdx=%d (1..16, at most the UNet's %d input channels)", Cdx,
+                  u->cfg.channels);
+    return backward(u, dout, on_ready, user, stream, dx, Cdx);
 }

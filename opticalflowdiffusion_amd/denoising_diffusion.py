@@ -62,19 +62,22 @@ class _UnetTrain(torch.autograd.Function):
     def forward(ctx, unet, x, cond, t, *params):
         ctx.unet = unet
         ctx.ticket = unet._train_forward(x, cond, t)
+        ctx.cx = x.shape[1]
         return unet._train_out
 
     @staticmethod
     def backward(ctx, gout):
-        grads = ctx.unet._backward(ctx.ticket, gout)
-        return (None, None, None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[4:]))
+        want_dx = ctx.needs_input_grad[1]
+        grads, dx = ctx.unet._backward(ctx.ticket, gout, ctx.cx if want_dx else 0)
+        return (None, dx, None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[4:]))
 
 
 class Unet(nn.Module):
     """DD:272-417.  Supported: dim=64, dim_mults=(1,2,4,8), no self-conditioning -- the UNet FlowDiffuser instantiates
     (FD:106-111), with time_in=True (diffusion) or time_in=False (is_diffusion=False, and FlowLearner's regression UNet) --
-    and dim_mults=(1,2,4) with time_in=False, the two UNets of the reference's Autoencoder (flow_pred.py:21-34), for
-    inference only.  channels 1..48, out_dim 1..16."""
+    and dim_mults=(1,2,4) with time_in=False, the two UNets of the reference's Autoencoder (flow_pred.py:21-34), which train only
+    after `set_trainable(True)` (FlowPred).  channels 1..48, out_dim 1..16.  On the training path the gradient w.r.t. `x` is produced
+    when x has at most 16 channels (the decoder's latent input); never w.r.t. `external_cond`."""
 
     def __init__(self, dim, init_dim=None, out_dim=None, dim_mults=(1, 2, 4, 8), channels=3, self_condition=False,
                  resnet_block_groups=8, learned_variance=False, learned_sinusoidal_cond=False,
@@ -113,6 +116,11 @@ class Unet(nn.Module):
         self._gflat = None
         self._ticket = 0
         self.grad_sync = None          # parallel.BucketedAllReduce for data-parallel training (or None)
+        self._trainable = levels == 4  # the three-level UNet trains after set_trainable(True)
+
+    def set_trainable(self, enabled=True):
+        """opt the three-level UNet (the Autoencoder's) into the training path; the four-level UNet always trains"""
+        self._trainable = bool(enabled) or self.n_levels == 4
 
     # -- parameter tree ----------------------------------------------------------------------
     def _add(self, name, param):
@@ -193,14 +201,17 @@ class Unet(nn.Module):
         if not self.time_in and time is not None:
             raise ValueError("this Unet does not take time arg")                           # DD:382-383
         L.require_gpu(x, external_cond, time)
-        if x.requires_grad or (external_cond is not None and external_cond.requires_grad):
-            raise L.OfdError("Unet.forward: gradients w.r.t. the inputs are not produced (the training step never needs them)")
+        training = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        if external_cond is not None and external_cond.requires_grad:
+            raise L.OfdError("Unet.forward: the gradient w.r.t. external_cond is not produced")
+        if x.requires_grad and torch.is_grad_enabled() and not (training and self._trainable and x.shape[1] <= 16):
+            raise L.OfdError("Unet.forward: the gradient w.r.t. x is produced on the training path only, for at most 16 channels of x")
         x = L.f32c(x)
         cond = L.f32c(external_cond) if external_cond is not None else None
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            if self.n_levels == 3:
+        if training:
+            if not self._trainable:
                 raise L.OfdError("Unet(dim_mults=(1, 2, 4)) is inference-only on the HIP engine (the Autoencoder stays frozen): call it under "
-                                 "torch.no_grad() or with requires_grad_(False) parameters")
+                                 "torch.no_grad() or with requires_grad_(False) parameters, or opt in with set_trainable(True) (FlowPred)")
             return _UnetTrain.apply(self, x, cond, time.to(torch.int64).contiguous() if self.time_in else None,
                                     *[self._param(n) for n in self._names])
         B, Cx, H, W = x.shape
@@ -245,7 +256,8 @@ class Unet(nn.Module):
         self._ticket += 1
         return self._ticket
 
-    def _backward(self, ticket, gout):
+    def _backward(self, ticket, gout, cdx=0):
+        """parameter gradients (views of one copy of the flat buffer) and, for cdx > 0, dL/dx of x's first cdx channels (else None)"""
         if ticket != self._ticket:
             raise L.OfdError("Unet backward: the tape belongs to an older forward (one training forward per backward; "
                              "retain_graph / double backward are not supported)")
@@ -264,7 +276,13 @@ class Unet(nn.Module):
         cb = L.GRAD_READY(ready)
         if sync is not None:
             sync.begin(flat)
-        L.check(lib.ofd_unet_backward(self._handle, L.ptr(gout), cb, None, L.stream()))
+        dx = None
+        if cdx:
+            B, _, H, W = gout.shape
+            dx = torch.empty(B, cdx, H, W, dtype=torch.float32, device=gout.device)
+            L.check(lib.ofd_unet_backward_dx(self._handle, L.ptr(gout), L.ptr(dx), cdx, cb, None, L.stream()))
+        else:
+            L.check(lib.ofd_unet_backward(self._handle, L.ptr(gout), cb, None, L.stream()))
         if err:
             raise err[0]
         if sync is not None:
@@ -279,7 +297,7 @@ class Unet(nn.Module):
             p = self._param(name)
             off = self._goffsets[i]
             grads.append(snap[off:off + p.numel()].view(p.shape))
-        return grads
+        return grads, dx
 
     def read_tap(self, name, shape):
         """named intermediate of the last forward as NCHW fp32 (parity tests)."""
@@ -293,7 +311,7 @@ class Unet(nn.Module):
         L.check(L.lib().ofd_unet_set_debug_taps(self._handle, int(enabled)))
 
     def set_glue(self, x_affine=False, cond_affine=False, out_mode=0, out_div=1.0):
-        """the Autoencoder's elementwise glue inside the forward (inference only): x / cond planes enter as 2 v - 1, and the output is
+        """the Autoencoder's elementwise glue inside the forward (inference and training): x / cond planes enter as 2 v - 1, and the output is
         clamp(clamp(v, -1, 1) / out_div, -1, 1) (out_mode 1) or (clamp(v, -1, 1) + 1) / 2 (out_mode 2)"""
         L.check(L.lib().ofd_unet_set_glue(self._handle, int(bool(x_affine)), int(bool(cond_affine)), int(out_mode), float(out_div)))
 

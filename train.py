@@ -21,7 +21,8 @@ import time
 import torch
 import yaml
 
-from opticalflowdiffusion_amd import FlowDiffuser, FlowLearner, parallel
+from opticalflowdiffusion_amd import FlowDiffuser, FlowLearner, FlowPred, parallel
+from opticalflowdiffusion_amd.flow_pred import parse_image_size
 from opticalflowdiffusion_amd.data import SintelPairs, SyntheticFlowPairs
 
 DEFAULTS = {
@@ -38,7 +39,11 @@ DEFAULTS = {
 # configurations/algorithm/flow_learner.yaml; selected with --set algorithm.name=flow_learner (experiments/exp_99.py:22-28)
 FLOW_LEARNER = {"name": "flow_learner", "image_size": [128, 128], "flow_max": 20, "latent": False, "zero_init": True, "c2f": False, "lr": 8e-5,
                 "weight_decay": 1e-6, "sparsity_weight": 0.0, "occlusion_mask": True, "train_aug": True}
-ALGORITHMS = {"flow_diffuser": FlowDiffuser, "flow_learner": FlowLearner}
+# configurations/algorithm/flow_pred.yaml (the Autoencoder of latent mode; experiments/exp_99.py:24): --set algorithm.name=flow_pred.
+# image_size "W,H" as the reference writes it; nan_holes: see FlowPred
+FLOW_PRED = {"name": "flow_pred", "image_size": "128,128", "lr": 4e-5, "weight_decay": 1e-6, "latent_dim": 16, "ae_frac": 0.1, "nan_holes": False}
+ALGORITHMS = {"flow_diffuser": FlowDiffuser, "flow_learner": FlowLearner, "flow_pred": FlowPred}
+ALGORITHM_DEFAULTS = {"flow_learner": FLOW_LEARNER, "flow_pred": FLOW_PRED}
 
 
 def deep_update(d, u):
@@ -97,8 +102,8 @@ def main(argv=None):
     if a.config_dir:
         from opticalflowdiffusion_amd.compat import compose
         composed = compose(a.config_dir, a.overrides).to_container()
-        if composed.get("algorithm", {}).get("name") == "flow_learner":
-            cfg["algorithm"] = dict(FLOW_LEARNER)
+        if composed.get("algorithm", {}).get("name") in ALGORITHM_DEFAULTS:
+            cfg["algorithm"] = dict(ALGORITHM_DEFAULTS[composed["algorithm"]["name"]])
         deep_update(cfg, composed)
         size = cfg["algorithm"].get("image_size")
         if isinstance(size, str):                          # dataset/sintel.yaml writes "512,256" (W,H)
@@ -106,15 +111,16 @@ def main(argv=None):
             cfg["algorithm"]["image_size"] = [h, w]
     if a.config:
         deep_update(cfg, yaml.safe_load(open(a.config)) or {})
-    if any(kv.replace(" ", "") == "algorithm.name=flow_learner" for kv in a.set):
-        cfg["algorithm"] = dict(FLOW_LEARNER)
+    for name, dflt in ALGORITHM_DEFAULTS.items():
+        if any(kv.replace(" ", "") == f"algorithm.name={name}" for kv in a.set):
+            cfg["algorithm"] = dict(dflt)
     for kv in a.set:
         k, v = kv.split("=", 1)
         set_path(cfg, k, v)
     alg, tr = cfg["algorithm"], cfg["experiment"]["training"]
     alg.setdefault("precision", "bf16" if str(tr.get("precision", "bf16")).startswith(("bf16", "16")) else "fp32")
     alg.setdefault("clip", float(tr.get("clipping") or 0.0))          # gradient_clip_val folded into the fused Adam
-    H, W = alg["image_size"] if isinstance(alg["image_size"], (list, tuple)) else (alg["image_size"],) * 2
+    H, W = parse_image_size(alg["image_size"])             # "W,H" strings (flow_pred.yaml) as the reference reads them
 
     rank, local_rank, world = parallel.env_rank_world()
     dev = torch.device("cuda", local_rank)
@@ -133,7 +139,7 @@ def main(argv=None):
     step, epoch = (load_checkpoint(a.resume, fd, opt) if a.resume else (0, 0))
 
     B = int(tr["data"]["batch_size"])
-    ds = SyntheticFlowPairs(cfg["dataset"].get("length", 1 << 20), H, W, flow_max=float(alg["flow_max"]), seed=cfg["dataset"].get("seed", 0))
+    ds = SyntheticFlowPairs(cfg["dataset"].get("length", 1 << 20), H, W, flow_max=float(alg.get("flow_max", 20)), seed=cfg["dataset"].get("seed", 0))
     if cfg["dataset"].get("name") == "sintel":        # --set dataset.name=sintel dataset.root=/path/to/MPI_Sintel
         files = SintelPairs(cfg["dataset"]["root"], render=cfg["dataset"].get("render", "clean"), image_size=(H, W))
 
