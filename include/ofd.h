@@ -15,9 +15,11 @@
  *   warp.py:121-156   warp_forward_flow (NaN handling + holes)          -> ofd_warp_prep / ofd_warp_holes
  *   warp.py:95-119    warp_backward_flow (2x F.grid_sample + mask)      -> ofd_grid_warp_fwd, ofd_grid_warp_bwd
  *   denoising_diffusion.py:363-417    Unet.forward                      -> ofd_unet_forward
- *   denoising_diffusion.py:666-698    p_mean_variance + p_sample update -> ofd_ddpm_update
- *   denoising_diffusion.py:750-767    ddim_sample update                -> ofd_ddim_update
+ *   denoising_diffusion.py:666-698    p_mean_variance + p_sample update -> ofd_ddpm_update(_obj)
+ *   denoising_diffusion.py:750-767    ddim_sample update                -> ofd_ddim_update(_obj)
  *   denoising_diffusion.py:806-812    q_sample                          -> ofd_q_sample
+ *   denoising_diffusion.py:844-879,985-993  p_losses noise / target     -> ofd_diffusion_prep
+ *   denoising_diffusion.py:73-77      (un)normalize                     -> ofd_range_map
  *   warp.py:260-271 + denoising_diffusion.py:908,973  nan_mse + nanmean -> ofd_nan_mse_sum
  */
 #ifndef OFD_H
@@ -124,6 +126,31 @@ int ofd_ddim_update(const float* x_t, const float* model_out, const float* noise
                     const float* sqrt_recip_ac, const float* sqrt_recipm1_ac,
                     const float* sqrt_alpha_next, const float* c, const float* sigma, int last,
                     float* out, float* x_start, int B, size_t n_per_sample, void* stream);
+/* The objective-aware forms (DD:589-611, 634-664).  objective: OFD_PRED_X0, OFD_PRED_NOISE or OFD_PRED_V.  x_start before the
+ * clamp is model_out (pred_x0), xa*x_t - xb*model_out with (xa, xb) = (sqrt_recip_ac, sqrt_recipm1_ac) for pred_noise and
+ * (sqrt_ac, sqrt_1mac) for pred_v; xa / xb may be NULL for pred_x0.  The DDPM step clamps it (DD:670-671); the DDIM step clamps it
+ * and re-derives eps from the clamped value for every objective (clip_x_start, rederive_pred_noise, DD:645-662).  Each product is
+ * rounded on its own (no FMA contraction), as torch computes it.  ofd_q_sample / ofd_ddpm_update / ofd_ddim_update are the
+ * OFD_PRED_X0 instantiations. */
+#define OFD_PRED_X0 0
+#define OFD_PRED_NOISE 1
+#define OFD_PRED_V 2
+int ofd_ddpm_update_obj(int objective, const float* x_t, const float* model_out, const float* noise,
+                        const float* coef1, const float* coef2, const float* sigma, const float* xa, const float* xb,
+                        float* out, float* x_start, int B, size_t n_per_sample, void* stream);
+int ofd_ddim_update_obj(int objective, const float* x_t, const float* model_out, const float* noise,
+                        const float* sqrt_recip_ac, const float* sqrt_recipm1_ac, const float* xa, const float* xb,
+                        const float* sqrt_alpha_next, const float* c, const float* sigma, int last,
+                        float* out, float* x_start, int B, size_t n_per_sample, void* stream);
+/* Training prep, one launch (DD:844-848, 806-812, 874-879, 985-993), x0 / noise / outputs (B,C,hw):
+ *   x0n = normalize ? 2*x0 - 1 : x0;  nz = noise + offset_strength*offset[b,c] (offset (B,C), or NULL: no offset noise);
+ *   x_t = sqrt_ac*x0n + sqrt_1mac*nz;  target = nz (pred_noise), x0n (pred_x0), sqrt_ac*nz - sqrt_1mac*x0n (pred_v).
+ * target and x_norm (x0n) are written when non-NULL; noise is never modified. */
+int ofd_diffusion_prep(int objective, const float* x0, const float* noise, const float* offset, float offset_strength,
+                       const float* sqrt_ac, const float* sqrt_1mac, int normalize, float* x_t, float* target, float* x_norm,
+                       int B, int C, size_t hw, void* stream);
+/* DD:73-77 over n floats: mode 0 -> 2*in - 1 (normalize), mode 1 -> (in + 1)*0.5 (unnormalize); in == out allowed. */
+int ofd_range_map(const float* in, float* out, size_t n, int mode, void* stream);
 /* sum and count over positions where neither pred nor target is NaN of (pred-target)^2.
  * result (device): ofd_nan_mse_result_doubles() doubles -- [0] sum, [1] count, the rest scratch (per-workgroup partial sums, added
  * in a fixed order: the same inputs give the same sum bit for bit). */

@@ -1,29 +1,16 @@
 // Diffusion elementwise steps (denoising_diffusion.py:589-623, 666-698, 750-767, 806-812) and the
 // NaN-masked squared-error reduction (warp.py:260-271 + torch.nanmean, DD:908,973).
 // HBM-bound streaming kernels: float4 accesses, per-sample scalar coefficients.
+#include <type_traits>
+
 #include "common.h"
 
 namespace ofd {
 
 __device__ __forceinline__ float clamp1(float v) { return fminf(fmaxf(v, -1.0f), 1.0f); }
 
-// n4 = n_per_sample / 4 (host checks divisibility, else the scalar tail kernel is used)
-template <int VEC>
-__global__ void __launch_bounds__(256) q_sample_kernel(const float* __restrict__ x0, const float* __restrict__ noise,
-                                                       const float* __restrict__ a, const float* __restrict__ b,
-                                                       float* __restrict__ out, size_t n_per_sample) {
-    const int s = blockIdx.y;
-    const float ca = a[s], cb = b[s];
-    const size_t base = (size_t)s * n_per_sample, nv = n_per_sample / VEC;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (size_t)gridDim.x * blockDim.x) {
-        if (VEC == 4) {
-            const float4 u = ((const float4*)(x0 + base))[i], v = ((const float4*)(noise + base))[i];
-            ((float4*)(out + base))[i] = make_float4(ca * u.x + cb * v.x, ca * u.y + cb * v.y, ca * u.z + cb * v.z, ca * u.w + cb * v.w);
-        } else {
-            out[base + i] = ca * x0[base + i] + cb * noise[base + i];
-        }
-    }
-}
+// The objective of a reverse step / training prep (DD:589-611, 634-664, 874-879): what the network predicts.
+enum Objective { PRED_X0 = OFD_PRED_X0, PRED_NOISE = OFD_PRED_NOISE, PRED_V = OFD_PRED_V };
 
 // one element group of VEC consecutive floats: a single dwordx4 access per operand when VEC == 4 (scalar dword accesses at a 16-byte lane
 // stride run these kernels at ~2.3 TB/s; a lane-contiguous float4 form streams)
@@ -39,13 +26,56 @@ template <int VEC> __device__ __forceinline__ void ew_store(float* p, const EwVe
     else p[0] = r.v[0];
 }
 
-template <int VEC>
+// x_start from the model output before any clamp: pred_x0 -> mo; pred_noise -> sr x - srm1 eps (DD:589-593); pred_v -> sqrt_ac x - sqrt_1mac v
+// (DD:607-611).  ka / kb are (sr, srm1) or (sqrt_ac, sqrt_1mac); the two products are rounded separately (-ffp-contract=off), as torch does.
+template <int OBJ> __device__ __forceinline__ float start_from_output(float mo, float xt, float ka, float kb) {
+    if constexpr (OBJ == PRED_X0) return mo;
+    else return ka * xt - kb * mo;
+}
+
+// Training prep (DD:844-848, 806-812, 874-879, 985-993), one launch: x0n = normalize ? 2 x0 - 1 : x0; nz' = noise + strength * offset[b, c];
+// x_t = sqrt_ac x0n + sqrt_1mac nz'; target = nz' (pred_noise), x0n (pred_x0), sqrt_ac nz' - sqrt_1mac x0n (pred_v).  x_norm / target may be
+// null (not written); offset null = no offset noise.  hw = elements per channel plane (VEC == 4 needs hw % 4 == 0 when offset is given).
+template <int OBJ, int VEC>
+__global__ void __launch_bounds__(256) diffusion_prep_kernel(const float* __restrict__ x0, const float* __restrict__ noise,
+                                                             const float* __restrict__ offset, float strength, int C, size_t hw,
+                                                             const float* __restrict__ a, const float* __restrict__ b, int normalize,
+                                                             float* __restrict__ out, float* __restrict__ target, float* __restrict__ x_norm,
+                                                             size_t n_per_sample) {
+    const int s = blockIdx.y;
+    const float ca = a[s], cb = b[s];
+    const size_t base = (size_t)s * n_per_sample, nv = n_per_sample / VEC;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t e = base + i * VEC;
+        EwVec<VEC> u = ew_load<VEC>(x0 + e), v = ew_load<VEC>(noise + e), r, tg;
+        const float off = offset ? strength * offset[(size_t)s * C + (i * VEC) / hw] : 0.0f;     // DD:848: the (b, c) offset, rounded once
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+            if (normalize) u.v[j] = u.v[j] * 2.0f - 1.0f;                  // DD:73-74
+            if (offset) v.v[j] = v.v[j] + off;
+            r.v[j] = ca * u.v[j] + cb * v.v[j];                            // DD:806-812
+            if constexpr (OBJ == PRED_V) tg.v[j] = ca * v.v[j] - cb * u.v[j];   // DD:601-605
+            else if constexpr (OBJ == PRED_NOISE) tg.v[j] = v.v[j];
+            else tg.v[j] = u.v[j];
+        }
+        ew_store<VEC>(out + e, r);
+        if (target) ew_store<VEC>(target + e, tg);
+        if (x_norm) ew_store<VEC>(x_norm + e, u);
+    }
+}
+
+// DDPM step (DD:666-698): x_start from the output, clamped in p_mean_variance (DD:670-671), posterior mean, noise.  xa / xb: the
+// start_from_output coefficients (unused for pred_x0).
+template <int OBJ, int VEC>
 __global__ void __launch_bounds__(256) ddpm_update_kernel(const float* __restrict__ x_t, const float* __restrict__ mo,
                                                           const float* __restrict__ noise, const float* __restrict__ c1,
                                                           const float* __restrict__ c2, const float* __restrict__ sg,
+                                                          const float* __restrict__ xa, const float* __restrict__ xb,
                                                           float* __restrict__ out, float* __restrict__ x_start, size_t n_per_sample) {
     const int s = blockIdx.y;
     const float k1 = c1[s], k2 = c2[s], ks = (noise && sg) ? sg[s] : 0.0f;
+    float ka = 0.0f, kb = 0.0f;
+    if constexpr (OBJ != PRED_X0) { ka = xa[s]; kb = xb[s]; }
     const size_t base = (size_t)s * n_per_sample, nv = n_per_sample / VEC;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (size_t)gridDim.x * blockDim.x) {
         const size_t e = base + i * VEC;
@@ -54,7 +84,7 @@ __global__ void __launch_bounds__(256) ddpm_update_kernel(const float* __restric
         if (ks != 0.0f) nz = ew_load<VEC>(noise + e);
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
-            const float x0 = clamp1(m.v[j]);                             // DD:670-671
+            const float x0 = clamp1(start_from_output<OBJ>(m.v[j], xt.v[j], ka, kb));   // DD:670-671
             float v = k1 * x0 + k2 * xt.v[j];                            // DD:615-618
             if (ks != 0.0f) v = v + ks * nz.v[j];                        // DD:688
             r.v[j] = v;
@@ -65,25 +95,30 @@ __global__ void __launch_bounds__(256) ddpm_update_kernel(const float* __restric
     }
 }
 
-template <int VEC>
+// DDIM step (DD:731-774) with clip_x_start = rederive_pred_noise = True (DD:747): x_start clamped, eps re-derived from it for every
+// objective (DD:645-662), then x_start sqrt(an) + c eps + sigma z; the last step returns x_start.
+template <int OBJ, int VEC>
 __global__ void __launch_bounds__(256) ddim_update_kernel(const float* __restrict__ x_t, const float* __restrict__ mo,
                                                           const float* __restrict__ noise, const float* __restrict__ sr,
-                                                          const float* __restrict__ srm1, const float* __restrict__ san,
+                                                          const float* __restrict__ srm1, const float* __restrict__ xa,
+                                                          const float* __restrict__ xb, const float* __restrict__ san,
                                                           const float* __restrict__ cc, const float* __restrict__ sg, int last,
                                                           float* __restrict__ out, float* __restrict__ x_start, size_t n_per_sample) {
     const int s = blockIdx.y;
     const float k_sr = sr[s], k_srm1 = srm1[s];
     const float k_an = last ? 0.0f : san[s], k_c = last ? 0.0f : cc[s], k_s = (last || !noise || !sg) ? 0.0f : sg[s];
+    float ka = 0.0f, kb = 0.0f;
+    if constexpr (OBJ != PRED_X0) { ka = xa[s]; kb = xb[s]; }
     const size_t base = (size_t)s * n_per_sample, nv = n_per_sample / VEC;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (size_t)gridDim.x * blockDim.x) {
         const size_t e = base + i * VEC;
         const EwVec<VEC> m = ew_load<VEC>(mo + e);
         EwVec<VEC> xt, nz, r, xs;
-        if (!last) xt = ew_load<VEC>(x_t + e);
+        if (!last || OBJ != PRED_X0) xt = ew_load<VEC>(x_t + e);
         if (k_s != 0.0f) nz = ew_load<VEC>(noise + e);
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
-            const float x0 = clamp1(m.v[j]);                             // clip_x_start (DD:655)
+            const float x0 = clamp1(start_from_output<OBJ>(m.v[j], xt.v[j], ka, kb));   // clip_x_start (DD:655)
             float v = x0;
             if (!last) {
                 const float eps = (k_sr * xt.v[j] - x0) / k_srm1;        // DD:595-599
@@ -95,6 +130,17 @@ __global__ void __launch_bounds__(256) ddim_update_kernel(const float* __restric
         }
         ew_store<VEC>(out + e, r);
         if (x_start) ew_store<VEC>(x_start + e, xs);
+    }
+}
+
+// DD:73-77 on a whole tensor: mode 0 -> 2 v - 1, mode 1 -> (v + 1) * 0.5
+template <int VEC>
+__global__ void __launch_bounds__(256) range_map_kernel(const float* __restrict__ in, float* __restrict__ out, size_t nv, int mode) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (size_t)gridDim.x * blockDim.x) {
+        EwVec<VEC> u = ew_load<VEC>(in + i * VEC);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) u.v[j] = mode == 0 ? u.v[j] * 2.0f - 1.0f : (u.v[j] + 1.0f) * 0.5f;
+        ew_store<VEC>(out + i * VEC, u);
     }
 }
 
@@ -161,24 +207,82 @@ using namespace ofd;
 
 #define OFD_EW_ARGS_OK(B, n) OFD_CHECK_ARG((B) > 0 && (B) <= 65535 && (n) > 0, "bad B=%d n_per_sample=%zu", (B), (size_t)(n))
 
+#define OFD_OBJ_OK(o) OFD_CHECK_ARG((o) == PRED_X0 || (o) == PRED_NOISE || (o) == PRED_V, "bad objective %d", (o))
+
+// f(std::integral_constant<int, OBJ>{}) for the runtime objective: one kernel instantiation per objective
+template <typename F> static void obj_dispatch(int obj, F&& f) {
+    if (obj == PRED_NOISE) f(std::integral_constant<int, PRED_NOISE>{});
+    else if (obj == PRED_V) f(std::integral_constant<int, PRED_V>{});
+    else f(std::integral_constant<int, PRED_X0>{});
+}
+
+extern "C" int ofd_diffusion_prep(int objective, const float* x0, const float* noise, const float* offset, float offset_strength,
+                                  const float* sqrt_ac, const float* sqrt_1mac, int normalize, float* x_t, float* target, float* x_norm,
+                                  int B, int C, size_t hw, void* stream) {
+    OFD_OBJ_OK(objective);
+    OFD_CHECK_ARG(C > 0 && hw > 0, "diffusion_prep: bad C=%d hw=%zu", C, hw);
+    const size_t n = (size_t)C * hw;
+    OFD_EW_ARGS_OK(B, n);
+    OFD_CHECK_ARG(x0 && noise && sqrt_ac && sqrt_1mac && x_t, "diffusion_prep: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    const bool v4 = n % 4 == 0 && (!offset || hw % 4 == 0);
+    obj_dispatch(objective, [&](auto o) {
+        constexpr int OBJ = decltype(o)::value;
+        if (v4) diffusion_prep_kernel<OBJ, 4><<<ew_grid(B, n / 4), 256, 0, s>>>(x0, noise, offset, offset_strength, C, hw, sqrt_ac, sqrt_1mac,
+                                                                               normalize, x_t, target, x_norm, n);
+        else diffusion_prep_kernel<OBJ, 1><<<ew_grid(B, n), 256, 0, s>>>(x0, noise, offset, offset_strength, C, hw, sqrt_ac, sqrt_1mac,
+                                                                        normalize, x_t, target, x_norm, n);
+    });
+    OFD_LAUNCH_CHECK();
+    return OFD_OK;
+}
+
 extern "C" int ofd_q_sample(const float* x0, const float* noise, const float* sqrt_ac, const float* sqrt_1mac, float* out,
                             int B, size_t n, void* stream) {
     OFD_EW_ARGS_OK(B, n);
-    OFD_CHECK_ARG(x0 && noise && sqrt_ac && sqrt_1mac && out, "q_sample: null pointer");
+    return ofd_diffusion_prep(PRED_X0, x0, noise, nullptr, 0.0f, sqrt_ac, sqrt_1mac, 0, out, nullptr, nullptr, B, 1, n, stream);
+}
+
+extern "C" int ofd_ddpm_update_obj(int objective, const float* x_t, const float* model_out, const float* noise, const float* coef1,
+                                   const float* coef2, const float* sigma, const float* xa, const float* xb, float* out, float* x_start,
+                                   int B, size_t n, void* stream) {
+    OFD_OBJ_OK(objective);
+    OFD_EW_ARGS_OK(B, n);
+    OFD_CHECK_ARG(x_t && model_out && coef1 && coef2 && out, "ddpm_update: null pointer");
+    OFD_CHECK_ARG(objective == PRED_X0 || (xa && xb), "ddpm_update: missing x_start coefficients");
     hipStream_t s = (hipStream_t)stream;
-    if (n % 4 == 0) q_sample_kernel<4><<<ew_grid(B, n / 4), 256, 0, s>>>(x0, noise, sqrt_ac, sqrt_1mac, out, n);
-    else q_sample_kernel<1><<<ew_grid(B, n), 256, 0, s>>>(x0, noise, sqrt_ac, sqrt_1mac, out, n);
+    obj_dispatch(objective, [&](auto o) {
+        constexpr int OBJ = decltype(o)::value;
+        if (n % 4 == 0) ddpm_update_kernel<OBJ, 4><<<ew_grid(B, n / 4), 256, 0, s>>>(x_t, model_out, noise, coef1, coef2, sigma, xa, xb, out, x_start, n);
+        else ddpm_update_kernel<OBJ, 1><<<ew_grid(B, n), 256, 0, s>>>(x_t, model_out, noise, coef1, coef2, sigma, xa, xb, out, x_start, n);
+    });
     OFD_LAUNCH_CHECK();
     return OFD_OK;
 }
 
 extern "C" int ofd_ddpm_update(const float* x_t, const float* model_out, const float* noise, const float* coef1,
                                const float* coef2, const float* sigma, float* out, float* x_start, int B, size_t n, void* stream) {
+    return ofd_ddpm_update_obj(PRED_X0, x_t, model_out, noise, coef1, coef2, sigma, nullptr, nullptr, out, x_start, B, n, stream);
+}
+
+extern "C" int ofd_ddim_update_obj(int objective, const float* x_t, const float* model_out, const float* noise, const float* sqrt_recip_ac,
+                                   const float* sqrt_recipm1_ac, const float* xa, const float* xb, const float* sqrt_alpha_next,
+                                   const float* c, const float* sigma, int last, float* out, float* x_start, int B, size_t n, void* stream) {
+    OFD_OBJ_OK(objective);
     OFD_EW_ARGS_OK(B, n);
-    OFD_CHECK_ARG(x_t && model_out && coef1 && coef2 && out, "ddpm_update: null pointer");
+    OFD_CHECK_ARG(x_t && model_out && sqrt_recip_ac && sqrt_recipm1_ac && out, "ddim_update: null pointer");
+    OFD_CHECK_ARG(last || (sqrt_alpha_next && c), "ddim_update: missing coefficients");
+    OFD_CHECK_ARG(objective == PRED_X0 || (xa && xb), "ddim_update: missing x_start coefficients");
     hipStream_t s = (hipStream_t)stream;
-    if (n % 4 == 0) ddpm_update_kernel<4><<<ew_grid(B, n / 4), 256, 0, s>>>(x_t, model_out, noise, coef1, coef2, sigma, out, x_start, n);
-    else ddpm_update_kernel<1><<<ew_grid(B, n), 256, 0, s>>>(x_t, model_out, noise, coef1, coef2, sigma, out, x_start, n);
+    obj_dispatch(objective, [&](auto o) {
+        constexpr int OBJ = decltype(o)::value;
+        if (n % 4 == 0)
+            ddim_update_kernel<OBJ, 4><<<ew_grid(B, n / 4), 256, 0, s>>>(x_t, model_out, noise, sqrt_recip_ac, sqrt_recipm1_ac, xa, xb,
+                                                                        sqrt_alpha_next, c, sigma, last, out, x_start, n);
+        else
+            ddim_update_kernel<OBJ, 1><<<ew_grid(B, n), 256, 0, s>>>(x_t, model_out, noise, sqrt_recip_ac, sqrt_recipm1_ac, xa, xb,
+                                                                    sqrt_alpha_next, c, sigma, last, out, x_start, n);
+    });
     OFD_LAUNCH_CHECK();
     return OFD_OK;
 }
@@ -186,14 +290,19 @@ extern "C" int ofd_ddpm_update(const float* x_t, const float* model_out, const f
 extern "C" int ofd_ddim_update(const float* x_t, const float* model_out, const float* noise, const float* sqrt_recip_ac,
                                const float* sqrt_recipm1_ac, const float* sqrt_alpha_next, const float* c, const float* sigma,
                                int last, float* out, float* x_start, int B, size_t n, void* stream) {
-    OFD_EW_ARGS_OK(B, n);
-    OFD_CHECK_ARG(x_t && model_out && sqrt_recip_ac && sqrt_recipm1_ac && out, "ddim_update: null pointer");
-    OFD_CHECK_ARG(last || (sqrt_alpha_next && c), "ddim_update: missing coefficients");
+    return ofd_ddim_update_obj(PRED_X0, x_t, model_out, noise, sqrt_recip_ac, sqrt_recipm1_ac, nullptr, nullptr, sqrt_alpha_next, c, sigma,
+                               last, out, x_start, B, n, stream);
+}
+
+extern "C" int ofd_range_map(const float* in, float* out, size_t n, int mode, void* stream) {
+    OFD_CHECK_ARG(in && out && n > 0 && (mode == 0 || mode == 1), "range_map: bad argument");
     hipStream_t s = (hipStream_t)stream;
-    if (n % 4 == 0)
-        ddim_update_kernel<4><<<ew_grid(B, n / 4), 256, 0, s>>>(x_t, model_out, noise, sqrt_recip_ac, sqrt_recipm1_ac, sqrt_alpha_next, c, sigma, last, out, x_start, n);
-    else
-        ddim_update_kernel<1><<<ew_grid(B, n), 256, 0, s>>>(x_t, model_out, noise, sqrt_recip_ac, sqrt_recipm1_ac, sqrt_alpha_next, c, sigma, last, out, x_start, n);
+    const bool v4 = n % 4 == 0 && ((uintptr_t)in % 16) == 0 && ((uintptr_t)out % 16) == 0;
+    const size_t nv = v4 ? n / 4 : n;
+    size_t b = (nv + 255) / 256;
+    if (b > 2048) b = 2048;
+    if (v4) range_map_kernel<4><<<(unsigned)b, 256, 0, s>>>(in, out, nv, mode);
+    else range_map_kernel<1><<<(unsigned)b, 256, 0, s>>>(in, out, nv, mode);
     OFD_LAUNCH_CHECK();
     return OFD_OK;
 }

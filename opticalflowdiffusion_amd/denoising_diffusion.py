@@ -4,9 +4,9 @@
 `Unet(dim, channels=, out_dim=, time_in=True)` owns fp32 `nn.Parameter`s under the reference's
 state-dict names (DD:272-361), so reference checkpoints load with `load_state_dict`.  Its
 forward is ONE C call (`ofd_unet_forward`) that runs the hand-written HIP kernels; there is no
-PyTorch fallback.  `ConditionalDiffusion` restates DD:463-993 for the configuration FlowDiffuser
-builds (FD:118-127) with the elementwise steps fused into single HIP kernels, generalised to
-non-square `image_size=(H, W)` and with a working DDIM path.
+PyTorch fallback.  `ConditionalDiffusion` restates DD:463-993 for the three objectives (pred_noise, pred_x0,
+pred_v), auto-normalisation and offset noise, with the elementwise steps fused into single HIP
+kernels, generalised to non-square `image_size=(H, W)` and with a working DDIM path.
 """
 import ctypes
 import math
@@ -33,6 +33,28 @@ def default(val, d):
 
 def identity(t, *args, **kwargs):
     return t
+
+
+OBJECTIVES = {"pred_x0": 0, "pred_noise": 1, "pred_v": 2}     # OFD_PRED_X0 / OFD_PRED_NOISE / OFD_PRED_V (include/ofd.h)
+
+
+def _range_map(x, mode):
+    """DD:73-77 as one HIP launch into a new tensor: mode 0 = 2 x - 1, mode 1 = (x + 1) * 0.5"""
+    L.require_gpu(x)
+    x = L.f32c(x)
+    out = torch.empty_like(x)
+    L.check(L.lib().ofd_range_map(L.ptr(x), L.ptr(out), x.numel(), mode, L.stream()))
+    return out
+
+
+def normalize_to_neg_one_to_one(img):
+    """DD:73-74"""
+    return _range_map(img, 0)
+
+
+def unnormalize_to_zero_to_one(t):
+    """DD:76-77"""
+    return _range_map(t, 1)
 
 
 class _Node(nn.Module):
@@ -388,7 +410,8 @@ def cosine_beta_schedule(timesteps, s=0.008):
 
 
 class ConditionalDiffusion(nn.Module):
-    """DD:463-993 for objective='pred_x0', noise_space='image' (what FlowDiffuser builds)."""
+    """DD:463-993 for noise_space='image' and every objective (pred_noise, pred_x0, pred_v), with auto_normalize and offset noise.
+    Deviations from the reference are listed in INTEGRATION.md."""
 
     def __init__(self, model, image_size, timesteps=1000, sampling_timesteps=None, objective="pred_v",
                  beta_schedule="sigmoid", schedule_fn_kwargs=dict(), ddim_sampling_eta=0.0, auto_normalize=True,
@@ -399,9 +422,18 @@ class ConditionalDiffusion(nn.Module):
         # eta == 0 multiplies it by zero (DD:763); the engine skips that draw, so a SEEDED eta == 0 run consumes a different RNG
         # stream.  True restores the draw (same stream positions as the reference) for seeded comparisons.
         self.ddim_draw_unused_noise = bool(ddim_draw_unused_noise)
-        if objective != "pred_x0" or noise_space != "image" or auto_normalize or offset_noise_strength != 0.0:
-            raise NotImplementedError("HIP path: objective='pred_x0', noise_space='image', auto_normalize=False (FD:118-127); "
-                                      "noise_space='flow' is broken in the reference itself (warp.py:181-182)")
+        assert objective in OBJECTIVES, "objective must be either pred_noise (predict noise) or pred_x0 (predict image start) or pred_v " \
+            "(predict v [v-parameterization as defined in appendix D of progressive distillation paper, used in imagen-video successfully])"
+        if noise_space != "image":
+            raise NotImplementedError("HIP path: noise_space='image'; noise_space='flow' is broken in the reference itself (warp.py:181-182)")
+        if getattr(model, "self_condition", False):
+            raise NotImplementedError("self_condition is not supported by the HIP engine's Unet")
+        if objective != "pred_x0" and getattr(model, "out_dim", None) != channels:
+            # pred_noise / pred_v read the network output as eps / v of exactly the diffused channels: x_start = a x_t - b out, one
+            # element of out per element of x_t, in one fused launch per step.  A model that does not declare that width (`out_dim`,
+            # as the engine's Unet does) cannot be checked before its first call, so it is refused here rather than mis-read later.
+            raise NotImplementedError(f"objective={objective!r} needs a model whose out_dim equals channels={channels} (the engine's Unet); "
+                                      f"got out_dim={getattr(model, 'out_dim', None)!r}")
         self.model = model
         self.channels = channels
         self.self_condition = False
@@ -448,9 +480,15 @@ class ConditionalDiffusion(nn.Module):
         clipped = snr.clone()
         if min_snr_loss_weight:
             clipped.clamp_(max=min_snr_gamma)
-        reg("loss_weight", clipped)                        # pred_x0 (DD:575-576)
-        self.normalize = identity
-        self.unnormalize = identity
+        if objective == "pred_noise":                                              # DD:573-578, float64 as the reference
+            reg("loss_weight", clipped / snr)
+        elif objective == "pred_x0":
+            reg("loss_weight", clipped)
+        else:
+            reg("loss_weight", clipped / (snr + 1))
+        self.auto_normalize = bool(auto_normalize)
+        self.normalize = normalize_to_neg_one_to_one if auto_normalize else identity       # DD:582-583 (HIP launches)
+        self.unnormalize = unnormalize_to_zero_to_one if auto_normalize else identity
 
     @property
     def device(self):
@@ -466,21 +504,61 @@ class ConditionalDiffusion(nn.Module):
         return self.model(x, external_cond if self.conditioned else None, t, x_self_cond,
                           additional_out=additional_tgt is not None)
 
+    @property
+    def _obj(self):
+        return OBJECTIVES[self.objective]
+
+    def predict_start_from_noise(self, x_t, t, noise):
+        """DD:589-593"""
+        return extract(self.sqrt_recip_alphas_cumprod, t, x_t.shape) * x_t - extract(self.sqrt_recipm1_alphas_cumprod, t, x_t.shape) * noise
+
     def predict_noise_from_start(self, x_t, t, x0):
         return (extract(self.sqrt_recip_alphas_cumprod, t, x_t.shape) * x_t - x0) / \
             extract(self.sqrt_recipm1_alphas_cumprod, t, x_t.shape)
 
+    def predict_v(self, x_start, t, noise):
+        """DD:601-605"""
+        return extract(self.sqrt_alphas_cumprod, t, x_start.shape) * noise - extract(self.sqrt_one_minus_alphas_cumprod, t, x_start.shape) * x_start
+
+    def predict_start_from_v(self, x_t, t, v):
+        """DD:607-611"""
+        return extract(self.sqrt_alphas_cumprod, t, x_t.shape) * x_t - extract(self.sqrt_one_minus_alphas_cumprod, t, x_t.shape) * v
+
+    def q_posterior(self, x_start, x_t, t):
+        """DD:613-623 (noise_space='image')"""
+        mean = extract(self.posterior_mean_coef1, t, x_t.shape) * x_start + extract(self.posterior_mean_coef2, t, x_t.shape) * x_t
+        return mean, extract(self.posterior_variance, t, x_t.shape), extract(self.posterior_log_variance_clipped, t, x_t.shape)
+
     def model_predictions(self, x, t, x_self_cond=None, clip_x_start=False, rederive_pred_noise=False,
                           external_cond=None, additional_tgt=None):
-        """DD:634-664 (pred_x0 branch)."""
+        """DD:634-664, every objective.  The sampling loops do not call this: their steps are fused HIP kernels."""
         out = self.model_with_condition(x, t, x_self_cond, external_cond=external_cond, additional_tgt=additional_tgt)
         additional_out = None
         if additional_tgt is not None:
             additional_out = out[:, -1 * additional_tgt.shape[1]:]
             out = out[:, :-1 * additional_tgt.shape[1]]
-        x_start = torch.clamp(out, min=-1.0, max=1.0) if clip_x_start else out
-        pred_noise = self.predict_noise_from_start(x, t, x_start)
+        maybe_clip = (lambda v: torch.clamp(v, min=-1.0, max=1.0)) if clip_x_start else identity
+        if self.objective == "pred_noise":
+            pred_noise = out
+            x_start = maybe_clip(self.predict_start_from_noise(x, t, pred_noise))
+            if clip_x_start and rederive_pred_noise:
+                pred_noise = self.predict_noise_from_start(x, t, x_start)
+        elif self.objective == "pred_x0":
+            x_start = maybe_clip(out)
+            pred_noise = self.predict_noise_from_start(x, t, x_start)
+        else:
+            x_start = maybe_clip(self.predict_start_from_v(x, t, out))
+            pred_noise = self.predict_noise_from_start(x, t, x_start)
         return ModelPrediction(pred_noise, x_start, additional_out)
+
+    def p_mean_variance(self, x, t, x_self_cond=None, clip_denoised=True, external_cond=None, additional_tgt=None):
+        """DD:666-674"""
+        preds = self.model_predictions(x, t, x_self_cond, external_cond=external_cond, additional_tgt=additional_tgt)
+        x_start = preds.pred_x_start
+        if clip_denoised:
+            x_start.clamp_(-1.0, 1.0)
+        mean, var, logvar = self.q_posterior(x_start=x_start, x_t=x, t=t)
+        return mean, var, logvar, x_start, preds.additional_out
 
     def q_sample(self, x_start, t, noise=None):
         """DD:806-812 as one fused HIP kernel."""
@@ -503,18 +581,32 @@ class ConditionalDiffusion(nn.Module):
         additional_out = None
         if additional_tgt is not None:
             additional_out = out[:, -1 * additional_tgt.shape[1]:]
-            out = L.f32c(out[:, :-1 * additional_tgt.shape[1]])
+            out = out[:, :-1 * additional_tgt.shape[1]]
         x = L.f32c(x)
+        out = self._same_shape(L.f32c(out), x)
         c1, c2, sigma = tab["c1"][t], tab["c2"][t], tab["sigma"][t]
         if t > 0:
-            noise = default(noise, lambda: torch.randn_like(x))
+            noise = self._same_shape(L.f32c(default(noise, lambda: torch.randn_like(x))), x)
         else:
             noise = None                                                               # DD:687
         pred = torch.empty_like(x)
         x_start = torch.empty_like(x)
-        L.check(L.lib().ofd_ddpm_update(L.ptr(x), L.ptr(out), L.ptr(noise), L.ptr(c1), L.ptr(c2), L.ptr(sigma),
-                                        L.ptr(pred), L.ptr(x_start), b, x[0].numel(), L.stream()))
+        L.check(L.lib().ofd_ddpm_update_obj(self._obj, L.ptr(x), L.ptr(out), L.ptr(noise), L.ptr(c1), L.ptr(c2), L.ptr(sigma),
+                                            *self._xab(tab, t), L.ptr(pred), L.ptr(x_start), b, x[0].numel(), L.stream()))
         return pred, x_start, additional_out
+
+    @staticmethod
+    def _same_shape(out, x):
+        """the fused steps read model_out with x's per-sample size: a different shape would be read out of step (or out of bounds)"""
+        if tuple(out.shape) != tuple(x.shape):
+            raise L.OfdError(f"model output {tuple(out.shape)} does not match the diffused tensor {tuple(x.shape)}")
+        return out
+
+    def _xab(self, tab, t):
+        """the x_start coefficient rows of the objective at step t (include/ofd.h: xa, xb); none for pred_x0"""
+        if self.objective == "pred_x0":
+            return None, None
+        return L.ptr(tab["xa"][t]), L.ptr(tab["xb"][t])
 
     def _sampling_tables(self, batch, device):
         """per-(T, batch) views of everything a reverse step reads that does not depend on the data: timestep tensors and the
@@ -522,15 +614,21 @@ class ConditionalDiffusion(nn.Module):
         # the key carries the identity AND version of every schedule buffer a row is derived from: load_state_dict of another
         # schedule, a dtype / device move or an in-place edit of a buffer rebuilds the tables instead of serving stale rows
         srcs = (self.posterior_mean_coef1, self.posterior_mean_coef2, self.posterior_log_variance_clipped,
-                self.sqrt_recip_alphas_cumprod, self.sqrt_recipm1_alphas_cumprod)
-        key = (batch, str(device)) + tuple((b.data_ptr(), b._version, b.dtype) for b in srcs)
+                self.sqrt_recip_alphas_cumprod, self.sqrt_recipm1_alphas_cumprod, self.sqrt_alphas_cumprod,
+                self.sqrt_one_minus_alphas_cumprod)
+        key = (batch, str(device), self.objective) + tuple((b.data_ptr(), b._version, b.dtype) for b in srcs)
         if getattr(self, "_samp_tab", None) is None or self._samp_tab[0] != key:
             T = self.num_timesteps
             rep = lambda v: v.to(device=device, dtype=torch.float32).reshape(T, 1).repeat(1, batch).contiguous()
             sigma = (0.5 * self.posterior_log_variance_clipped).exp()
-            self._samp_tab = (key, dict(t=torch.arange(T, device=device, dtype=torch.long).reshape(T, 1).repeat(1, batch).contiguous(),
-                                        c1=rep(self.posterior_mean_coef1), c2=rep(self.posterior_mean_coef2), sigma=rep(sigma),
-                                        sr=rep(self.sqrt_recip_alphas_cumprod), srm1=rep(self.sqrt_recipm1_alphas_cumprod)))
+            tab = dict(t=torch.arange(T, device=device, dtype=torch.long).reshape(T, 1).repeat(1, batch).contiguous(),
+                       c1=rep(self.posterior_mean_coef1), c2=rep(self.posterior_mean_coef2), sigma=rep(sigma),
+                       sr=rep(self.sqrt_recip_alphas_cumprod), srm1=rep(self.sqrt_recipm1_alphas_cumprod))
+            if self.objective == "pred_noise":                                        # x_start = sr x - srm1 eps (DD:589-593)
+                tab.update(xa=tab["sr"], xb=tab["srm1"])
+            elif self.objective == "pred_v":                                          # x_start = sqrt_ac x - sqrt_1mac v (DD:607-611)
+                tab.update(xa=rep(self.sqrt_alphas_cumprod), xb=rep(self.sqrt_one_minus_alphas_cumprod))
+            self._samp_tab = (key, tab)
         return self._samp_tab[1]
 
     @torch.no_grad()
@@ -547,25 +645,26 @@ class ConditionalDiffusion(nn.Module):
                 if return_all_timesteps:
                     imgs.append(img)
                 additionals.append(additional_out)
-            return (img if not return_all_timesteps else torch.stack(imgs, dim=1)), additionals
+            return self.unnormalize(img if not return_all_timesteps else torch.stack(imgs, dim=1)), additionals
         imgs = [img]
         stride = self.trajectory_stride
         tab = self._sampling_tables(shape[0], img.device)
         b, n = shape[0], img[0].numel()
         pong = [torch.empty_like(img), torch.empty_like(img)]
         noise, x_start = torch.empty_like(img), torch.empty_like(img)
-        lib = L.lib()
+        lib, obj = L.lib(), self._obj
         for i, t in enumerate(reversed(range(0, self.num_timesteps))):
-            out = L.f32c(self.model_with_condition(img, tab["t"][t], None, external_cond=external_cond))
+            out = self._same_shape(L.f32c(self.model_with_condition(img, tab["t"][t], None, external_cond=external_cond)), img)
             if t > 0:
                 noise.normal_()                                                       # DD:687: z = 0 at t = 0
             nxt = pong[i & 1]
-            L.check(lib.ofd_ddpm_update(L.ptr(img), L.ptr(out), L.ptr(noise) if t > 0 else None, L.ptr(tab["c1"][t]), L.ptr(tab["c2"][t]),
-                                        L.ptr(tab["sigma"][t]), L.ptr(nxt), L.ptr(x_start), b, n, L.stream()))
+            L.check(lib.ofd_ddpm_update_obj(obj, L.ptr(img), L.ptr(out), L.ptr(noise) if t > 0 else None, L.ptr(tab["c1"][t]),
+                                            L.ptr(tab["c2"][t]), L.ptr(tab["sigma"][t]), *self._xab(tab, t), L.ptr(nxt), L.ptr(x_start), b, n,
+                                            L.stream()))
             img = nxt
             if return_all_timesteps and (stride is None or (i + 1) % stride == 0 or t == 0):
                 imgs.append(img.clone())
-        return img if not return_all_timesteps else torch.stack(imgs, dim=1)
+        return self.unnormalize(img if not return_all_timesteps else torch.stack(imgs, dim=1))             # DD:725-726
 
     # -- DDIM --------------------------------------------------------------------------------
     @torch.no_grad()
@@ -592,24 +691,28 @@ class ConditionalDiffusion(nn.Module):
         coef = torch.stack((alpha_next.sqrt(), c, sigma), dim=1).to(torch.float32).reshape(len(time_pairs), 3, 1).repeat(1, 1, batch).contiguous()
         pong = [torch.empty_like(img), torch.empty_like(img)]
         noise = torch.empty_like(img) if (eta > 0 or self.ddim_draw_unused_noise) else None
-        lib = L.lib()
+        lib, obj = L.lib(), self._obj
         for i, (time, time_next) in enumerate(time_pairs):
-            out = L.f32c(self.model_with_condition(img, tab["t"][time], None, external_cond=external_cond))
+            out = self._same_shape(L.f32c(self.model_with_condition(img, tab["t"][time], None, external_cond=external_cond)), img)
             last = time_next < 0
             if noise is not None and not last:
                 noise.normal_()                                                          # DD:763 (eta == 0: only with ddim_draw_unused_noise)
             nxt = pong[i & 1]
-            L.check(lib.ofd_ddim_update(L.ptr(img), L.ptr(out), L.ptr(noise) if not last else None, L.ptr(tab["sr"][time]), L.ptr(tab["srm1"][time]),
-                                        None if last else L.ptr(coef[i, 0]), None if last else L.ptr(coef[i, 1]), None if last else L.ptr(coef[i, 2]),
-                                        int(last), L.ptr(nxt), None, batch, n, L.stream()))
+            L.check(lib.ofd_ddim_update_obj(obj, L.ptr(img), L.ptr(out), L.ptr(noise) if not last else None, L.ptr(tab["sr"][time]),
+                                            L.ptr(tab["srm1"][time]), *self._xab(tab, time), None if last else L.ptr(coef[i, 0]),
+                                            None if last else L.ptr(coef[i, 1]), None if last else L.ptr(coef[i, 2]), int(last), L.ptr(nxt), None,
+                                            batch, n, L.stream()))
             img = nxt
             if return_all_timesteps and (stride is None or (i + 1) % stride == 0 or last):
                 imgs.append(img.clone())
-        return img if not return_all_timesteps else torch.stack(imgs, dim=1)
+        return self.unnormalize(img if not return_all_timesteps else torch.stack(imgs, dim=1))             # DD:772-773
 
     @torch.no_grad()
     def sample(self, batch_size=16, return_all_timesteps=False, external_cond=None, additional_tgt=None):
-        """DD:776-784, with image_size allowed to be (H, W)."""
+        """DD:776-784, with image_size allowed to be (H, W).  external_cond is normalised once per call (DD:778-779); the loops
+        unnormalise what they return."""
+        if external_cond is not None:
+            external_cond = self.normalize(external_cond)
         H, W = self._hw()
         fn = self.p_sample_loop if not self.is_ddim_sampling else self.ddim_sample
         assert external_cond is None or external_cond.shape[0] == batch_size
@@ -617,11 +720,59 @@ class ConditionalDiffusion(nn.Module):
                   external_cond=external_cond, additional_tgt=additional_tgt)
 
     # -- training loss -----------------------------------------------------------------------
+    @torch.no_grad()
+    def interpolate(self, x1, x2, t=None, lam=0.5, external_cond=None):
+        """DD:787-804: both images noised to step t (own noise draws), mixed (1 - lam) x1 + lam x2 in the q_sample kernel, then t
+        DDPM steps.  As in the reference, external_cond is used as given and the result is not unnormalised."""
+        b = x1.shape[0]
+        t = default(t, self.num_timesteps - 1)
+        assert x1.shape == x2.shape
+        t_batched = torch.full((b,), t, device=x1.device)
+        xt1, xt2 = map(lambda x: self.q_sample(x, t=t_batched), (x1, x2))
+        img = torch.empty_like(xt1)
+        wa = torch.full((b,), 1 - lam, dtype=torch.float32, device=x1.device)
+        wb = torch.full((b,), lam, dtype=torch.float32, device=x1.device)
+        L.check(L.lib().ofd_q_sample(L.ptr(xt1), L.ptr(xt2), L.ptr(wa), L.ptr(wb), L.ptr(img), b, xt1[0].numel(), L.stream()))
+        for i in reversed(range(0, t)):
+            img, _, _ = self.p_sample(img, i, None, external_cond=external_cond)
+        return img
+
+    def _prep(self, x_start, t, noise, offset_noise_strength, normalize):
+        """the training prep launch (ofd_diffusion_prep): (x_t, target, x_start as the loss sees it).  The offset noise is drawn
+        after `noise`, as DD:840-847 draws it; the caller's `noise` is not modified (the reference adds the offset in place, DD:848)."""
+        strength = float(default(offset_noise_strength, self.offset_noise_strength))
+        offset = torch.randn(x_start.shape[:2], device=x_start.device) if strength > 0.0 else None
+        x0, nz = L.f32c(x_start), L.f32c(noise)
+        self._same_shape(nz, x0)
+        B, C = x0.shape[:2]
+        if tuple(t.shape) != (B,):
+            raise L.OfdError(f"t must hold one timestep per sample: got {tuple(t.shape)} for a batch of {B}")
+        x_t = torch.empty_like(x0)
+        xn = torch.empty_like(x0) if normalize else None
+        if self.objective == "pred_noise":
+            target = torch.empty_like(x0) if offset is not None else None
+        elif self.objective == "pred_v":
+            target = torch.empty_like(x0)
+        else:
+            target = None
+        a, b = self.sqrt_alphas_cumprod[t].contiguous(), self.sqrt_one_minus_alphas_cumprod[t].contiguous()
+        L.check(L.lib().ofd_diffusion_prep(self._obj, L.ptr(x0), L.ptr(nz), L.ptr(offset), strength, L.ptr(a), L.ptr(b), int(normalize),
+                                           L.ptr(x_t), L.ptr(target), L.ptr(xn), B, C, x0[0, 0].numel(), L.stream()))
+        x0 = xn if normalize else x_start
+        if target is None:
+            target = nz if self.objective == "pred_noise" else x0
+        return x_t, target, x0
+
     def p_losses(self, x_start, t, noise=None, offset_noise_strength=None, external_cond=None, additional_tgt=None,
                  additional_weight=None, model_out_override=None):
         """DD:823-891."""
+        return self._p_losses(x_start, t, noise, offset_noise_strength, external_cond, additional_tgt, additional_weight, model_out_override)
+
+    def _p_losses(self, x_start, t, noise=None, offset_noise_strength=None, external_cond=None, additional_tgt=None,
+                  additional_weight=None, model_out_override=None, normalize=False):
+        """p_losses on x_start; normalize=True: x_start is still in [0, 1] and the prep launch maps it (forward(), DD:988)"""
         noise = default(noise, lambda: torch.randn_like(x_start))
-        x = self.q_sample(x_start=x_start, t=t, noise=noise)
+        x, target, x_start = self._prep(x_start, t, noise, offset_noise_strength, normalize)
         if model_out_override is None:
             model_out_full = self.model_with_condition(x, t, None, external_cond=external_cond, additional_tgt=additional_tgt)
             model_out = model_out_full
@@ -629,7 +780,6 @@ class ConditionalDiffusion(nn.Module):
                 model_out = model_out_full[:, :-1 * additional_tgt.shape[1]]
         else:
             model_out, _ = model_out_override
-        target = x_start                                                               # pred_x0 (DD:876-877)
         if additional_tgt is not None:                                                 # target='target' (DD:884-885)
             additional_out = model_out_full[:, -1 * additional_tgt.shape[1]:] if model_out_override is None else model_out_override[1]
             return self._loss(model_out, target, t, additional_tgt, external_cond, additional_out, additional_weight)
@@ -663,9 +813,11 @@ class ConditionalDiffusion(nn.Module):
         return num / den.float()
 
     def forward(self, img, external_cond=None, *args, **kwargs):
-        """DD:985-993."""
+        """DD:985-993.  img is normalised inside the prep launch, external_cond by one range_map launch (auto_normalize)."""
         b, c, h, w = img.shape
         H, W = self._hw()
         assert h == H and w == W, f"height and width of image must be {(H, W)}"
         t = torch.randint(0, self.num_timesteps, (b,), device=img.device).long()
-        return self.p_losses(img, t, external_cond=external_cond, *args, **kwargs)
+        if external_cond is not None:
+            external_cond = self.normalize(external_cond)
+        return self._p_losses(img, t, *args, external_cond=external_cond, normalize=self.auto_normalize, **kwargs)

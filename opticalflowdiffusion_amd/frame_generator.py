@@ -1,0 +1,101 @@
+"""`FrameGenerator` (algorithms/diffusion_animation/diffusion_animation.py:14-125, "DA") on the HIP engine.
+
+A conditional DDPM over video frames: the four-level `Unet(64, channels=3 + 3 + 2, out_dim=3)` predicts the noise
+(`ConditionalDiffusion(..., objective="pred_noise")` with the reference's defaults: sigmoid schedule, T = 1000,
+auto_normalize=True) of the next frame, conditioned on the last frame and the flow between them.  Attribute names are the
+reference's (`_model`, `diffusion_model` holding the same UNet), so its checkpoint keys load unchanged.
+"""
+import torch
+
+from .compat.shims.utils.image_prediction.logging import log_photos
+from .compat.shims.utils.video_prediction.visualization import log_video
+from .denoising_diffusion import ConditionalDiffusion, Unet
+from .flow_diffuser import FlowDiffuser, _Base, _Cfg
+from .flow_pred import parse_image_size
+
+
+class _FrameCfg(_Cfg):
+    """configurations/algorithm/frame_generator.yaml, plus `clip` (the trainer's gradient_clip_val, folded into FusedAdam),
+    `precision`, `timesteps` and `sampling_timesteps` (DDIM when fewer than `timesteps`)"""
+
+    _DEFAULTS = dict(name="frame_generator", image_size=64, lr=7e-5, weight_decay=2e-4, clip=0.0, precision="bf16", timesteps=1000,
+                     sampling_timesteps=None)
+
+
+class FrameGenerator(_Base):
+    """DA:14-125.  `training_step` returns the loss (the trainer runs backward and the optimiser step, as for FlowDiffuser);
+    `on_before_optimizer_step` logs the reference's grad_norm / gpr statistics (DA:62, 103-125).  `validation_step` implements the
+    evident intent of DA:64-100 (which raises at `batch.size[1]`): first-frame loss and samples, then `rollout`."""
+
+    def __init__(self, cfg):
+        super().__init__()
+        cfg = cfg if isinstance(cfg, _FrameCfg) else _FrameCfg(cfg)
+        self.automatic_optimization = False
+        self.cfg = cfg
+        h, w = parse_image_size(cfg.image_size)
+        self.image_size = h if h == w else (h, w)
+        self._model = Unet(64, channels=3 + 3 + 2, out_dim=3, precision=cfg.precision)              # DA:25-29
+        self.diffusion_model = ConditionalDiffusion(self._model, self.image_size, objective="pred_noise",   # DA:30-34
+                                                    timesteps=int(cfg.timesteps), sampling_timesteps=cfg.sampling_timesteps)
+
+    def configure_optimizers(self):                                                                  # DA:36-41
+        """Adam(lr, weight_decay) as the reference, as the HIP multi-tensor step (optim.FusedAdam)"""
+        from .optim import FusedAdam
+        self.optimizers = FusedAdam(self.diffusion_model.parameters(), lr=self.cfg.lr, weight_decay=self.cfg.weight_decay,
+                                    max_grad_norm=float(self.cfg.clip or 0.0))
+        return self.optimizers
+
+    @staticmethod
+    def split(batch):
+        """(target, cond): the reference's (B, 8, H, W) tensor cat(target, last_frame, flow) (DA:43-44), or the trainer's
+        (img, tgt, flow) tuple as target = tgt, cond = cat(img, flow)"""
+        if isinstance(batch, (tuple, list)):
+            img, tgt, flow = batch
+            return tgt, torch.cat((img, flow), dim=1)
+        return batch[:, :3], batch[:, 3:]
+
+    def training_step(self, batch, batch_idx):                                                       # DA:43-62
+        target, cond = self.split(batch)
+        loss = self.diffusion_model(target, cond)
+        self.log_dict({"train/loss": loss})
+        return loss
+
+    def on_before_optimizer_step(self, optimizer):
+        """DA:62: the gradient statistics, once the gradients exist"""
+        self.log_grad_norm_stat()
+
+    log_grad_norm_stat = FlowDiffuser.log_grad_norm_stat                                             # DA:103-125 == FD:367-388
+
+    @torch.no_grad()
+    def sample(self, cond):
+        """one sampling chain per sample of cond (B, 5, H, W) in [0, 1]; returns (B, 3, H, W) in [0, 1]"""
+        return self.diffusion_model.sample(batch_size=cond.shape[0], external_cond=cond)
+
+    @torch.no_grad()
+    def rollout(self, batch):
+        """DA:84-100: batch (B, V, 8, H, W); frame k is sampled with cond = batch[:, k, 3:], whose last-frame channels are replaced
+        by frame k-1's sample for k >= 1.  Returns (V, B, 3, H, W)."""
+        samples = []
+        for k in range(batch.shape[1]):
+            cond = batch[:, k, 3:].clone()
+            if k != 0:
+                cond[:, :3] = samples[-1][:, :3]                                                     # DA:90-91
+            samples.append(self.sample(cond))
+        return torch.stack(samples, dim=0)
+
+    def validation_step(self, batch, batch_idx):                                                     # DA:64-100
+        batch_ = batch[:, 0]
+        target, cond = self.split(batch_)
+        last_frames, flows = cond[:, :3], cond[:, 3:]
+        with torch.no_grad():
+            loss = self.diffusion_model(target, cond)
+            samples = self.sample(cond)
+            self.log_dict({"val/loss": loss})
+            for photos, key in zip((samples, target, last_frames, flows), ("samples", "targets", "last_frames", "flows")):
+                log_photos((photos,), self, keyword=f"val/{key}")
+            frames = self.rollout(batch)
+            logger = getattr(self, "logger", None)
+            log_video(frames, batch[:, :, :3].transpose(0, 1), step=getattr(self, "global_step", 0), namespace="val", context_frames=1,
+                      logger=getattr(logger, "experiment", None))
+        self.last_rollout = frames
+        return loss

@@ -21,7 +21,7 @@ import time
 import torch
 import yaml
 
-from opticalflowdiffusion_amd import FlowDiffuser, FlowLearner, FlowPred, parallel
+from opticalflowdiffusion_amd import FlowDiffuser, FlowLearner, FlowPred, FrameGenerator, parallel
 from opticalflowdiffusion_amd.flow_pred import parse_image_size
 from opticalflowdiffusion_amd.data import SintelPairs, SyntheticFlowPairs
 
@@ -42,8 +42,11 @@ FLOW_LEARNER = {"name": "flow_learner", "image_size": [128, 128], "flow_max": 20
 # configurations/algorithm/flow_pred.yaml (the Autoencoder of latent mode; experiments/exp_99.py:24): --set algorithm.name=flow_pred.
 # image_size "W,H" as the reference writes it; nan_holes: see FlowPred
 FLOW_PRED = {"name": "flow_pred", "image_size": "128,128", "lr": 4e-5, "weight_decay": 1e-6, "latent_dim": 16, "ae_frac": 0.1, "nan_holes": False}
-ALGORITHMS = {"flow_diffuser": FlowDiffuser, "flow_learner": FlowLearner, "flow_pred": FlowPred}
-ALGORITHM_DEFAULTS = {"flow_learner": FLOW_LEARNER, "flow_pred": FLOW_PRED}
+# configurations/algorithm/frame_generator.yaml (experiments/exp_control.py:22): --set algorithm.name=frame_generator.  The synthetic
+# (img, tgt, flow) batches feed it as target = tgt, cond = cat(img, flow) (FrameGenerator.split)
+FRAME_GENERATOR = {"name": "frame_generator", "image_size": 64, "lr": 7e-5, "weight_decay": 2e-4}
+ALGORITHMS = {"flow_diffuser": FlowDiffuser, "flow_learner": FlowLearner, "flow_pred": FlowPred, "frame_generator": FrameGenerator}
+ALGORITHM_DEFAULTS = {"flow_learner": FLOW_LEARNER, "flow_pred": FLOW_PRED, "frame_generator": FRAME_GENERATOR}
 
 
 def deep_update(d, u):
@@ -161,6 +164,9 @@ def main(argv=None):
             with hold:
                 loss = step_module.training_step(batch, step)
                 (loss / accum).backward()
+        hook = getattr(fd, "on_before_optimizer_step", None)        # Lightning's hook (FrameGenerator logs its gradient statistics there)
+        if hook is not None:
+            hook(opt)
         opt.step()
         step += 1
         if rank == 0 and (step % a.log_every == 0 or step == a.steps):
