@@ -21,6 +21,8 @@
  *   denoising_diffusion.py:844-879,985-993  p_losses noise / target     -> ofd_diffusion_prep
  *   denoising_diffusion.py:73-77      (un)normalize                     -> ofd_range_map
  *   warp.py:260-271 + denoising_diffusion.py:908,973  nan_mse + nanmean -> ofd_nan_mse_sum
+ *   diffusion_animation.py:159-175    FlowCompleter._sparse_from_dense  -> ofd_sparse_flow_sample
+ *   diffusion_animation.py:10-11,177-183  weighted_mse_loss (flow norm) -> ofd_completer_loss(_grad)
  */
 #ifndef OFD_H
 #define OFD_H
@@ -443,6 +445,31 @@ int ofd_augment_table(const float* uniforms, float* params, int B, void* stream)
  * deviation across the batch} (device); ws: ofd_batch_stats_ws_doubles() doubles of device scratch (partial sums, added in a fixed order). */
 size_t ofd_batch_stats_ws_doubles(void);
 int ofd_batch_stats(const float* x, int B, size_t n_per_sample, double* ws, float* out4, void* stream);
+
+/* FlowCompleter (algorithms/diffusion_animation/diffusion_animation.py:127-246): sparse-flow sampling, its loss and the null-embedding
+ * gradient, with no host sync and no float atomics (every output is the same bits for the same inputs).
+ *
+ * ofd_sparse_flow_sample: dense (B,2,H,W) fp32, u (B,H*W) uniforms in [0,1), k (B,) int32 picks per frame (clamped to [1,8]), null_emb (2,)
+ * device.  m = sqrtf(fx*fx + fy*fy), s = batch mean of m (fixed-order sum), w = m + s (1 everywhere when s = 0); frame b keeps the k_b
+ * largest keys logf(u) / w, equal keys to the lower index (Efraimidis-Spirakis weighted sampling without replacement).  Writes sparse
+ * (B,2,H,W) = null_emb[c] except dense at the picks, picks (B,8) int32 flat indices padded with -1, amax (B,) = max of m per frame.
+ * ws: ofd_sparse_flow_ws_bytes(B, H, W) bytes of device scratch, 8-byte aligned.  Four launches. */
+size_t ofd_sparse_flow_ws_bytes(int B, int H, int W);
+int ofd_sparse_flow_sample(const float* dense, const float* u, const int* k, const float* null_emb, float* sparse, int* picks, float* amax,
+                           int B, int H, int W, void* ws, size_t ws_bytes, void* stream);
+/* loss = mean over (b,h,w) of (lmbd + m / amax_b) * ||out - dense||_2 over the two channels (lmbd where amax_b = 0), out / dense (B,2,H,W);
+ * result: ofd_completer_loss_result_doubles() doubles of device scratch, [0] the fixed-order sum; loss: one device float */
+size_t ofd_completer_loss_result_doubles(void);
+int ofd_completer_loss(const float* out, const float* dense, const float* amax, float lmbd, int B, int H, int W, double* result, float* loss,
+                       void* stream);
+/* dout = gout[0] * (lmbd + m / amax_b) * (out - dense) / ||out - dense|| / (B*H*W), 0 where the norm is 0 */
+int ofd_completer_loss_grad(const float* out, const float* dense, const float* amax, const float* gout, float lmbd, int B, int H, int W,
+                            float* dout, void* stream);
+/* dnull[c] = sum of dx[b,c,h,w] over the pixels that are not picks of their frame (fixed order); ws: ofd_null_grad_ws_doubles() doubles */
+size_t ofd_null_grad_ws_doubles(void);
+int ofd_null_embedding_grad(const float* dx, const int* picks, int B, int H, int W, double* ws, float* dnull, void* stream);
+/* out = sparse with every NaN of channel c replaced by null_emb[c] (FlowCompleter.complete) */
+int ofd_sparse_flow_fill(const float* sparse, const float* null_emb, float* out, int B, int H, int W, void* stream);
 
 #ifdef __cplusplus
 }

@@ -7,3 +7,4 @@ from .flow_diffuser import FlowDiffuser, UnetWithWarp  # noqa: F401,E402
 from .flow_learner import FlowLearner  # noqa: F401,E402
 from .flow_pred import FlowPred, Autoencoder  # noqa: F401,E402
 from .frame_generator import FrameGenerator  # noqa: F401,E402
+from .flow_completer import FlowCompleter  # noqa: F401,E402

@@ -137,6 +137,14 @@ SIGNATURES = {
     "ofd_gn_finalize": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ofd_conv_upsample_phase_weight_prep": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "ofd_conv_weight_prep": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_float, c_int, c_void_p]),
+    "ofd_sparse_flow_ws_bytes": (c_size_t, [c_int] * 3),
+    "ofd_sparse_flow_sample": (c_int, [c_void_p] * 7 + [c_int] * 3 + [c_void_p, c_size_t, c_void_p]),
+    "ofd_completer_loss_result_doubles": (c_size_t, []),
+    "ofd_completer_loss": (c_int, [c_void_p] * 3 + [c_float] + [c_int] * 3 + [c_void_p] * 3),
+    "ofd_completer_loss_grad": (c_int, [c_void_p] * 4 + [c_float] + [c_int] * 3 + [c_void_p] * 2),
+    "ofd_null_grad_ws_doubles": (c_size_t, []),
+    "ofd_null_embedding_grad": (c_int, [c_void_p] * 2 + [c_int] * 3 + [c_void_p] * 3),
+    "ofd_sparse_flow_fill": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p]),
 }
 
 _lib = None

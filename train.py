@@ -21,7 +21,7 @@ import time
 import torch
 import yaml
 
-from opticalflowdiffusion_amd import FlowDiffuser, FlowLearner, FlowPred, FrameGenerator, parallel
+from opticalflowdiffusion_amd import FlowCompleter, FlowDiffuser, FlowLearner, FlowPred, FrameGenerator, parallel
 from opticalflowdiffusion_amd.flow_pred import parse_image_size
 from opticalflowdiffusion_amd.data import SintelPairs, SyntheticFlowPairs
 
@@ -45,8 +45,13 @@ FLOW_PRED = {"name": "flow_pred", "image_size": "128,128", "lr": 4e-5, "weight_d
 # configurations/algorithm/frame_generator.yaml (experiments/exp_control.py:22): --set algorithm.name=frame_generator.  The synthetic
 # (img, tgt, flow) batches feed it as target = tgt, cond = cat(img, flow) (FrameGenerator.split)
 FRAME_GENERATOR = {"name": "frame_generator", "image_size": 64, "lr": 7e-5, "weight_decay": 2e-4}
-ALGORITHMS = {"flow_diffuser": FlowDiffuser, "flow_learner": FlowLearner, "flow_pred": FlowPred, "frame_generator": FrameGenerator}
-ALGORITHM_DEFAULTS = {"flow_learner": FLOW_LEARNER, "flow_pred": FLOW_PRED, "frame_generator": FRAME_GENERATOR}
+# configurations/algorithm/flow_completer.yaml (experiments/exp_control.py:23): --set algorithm.name=flow_completer.  The synthetic
+# (img, tgt, flow) batches feed it as frame = img, dense flow = flow (FlowCompleter.split)
+FLOW_COMPLETER = {"name": "flow_completer", "image_size": 64, "lr": 4.5e-6, "weight_decay": 2e-4}
+ALGORITHMS = {"flow_diffuser": FlowDiffuser, "flow_learner": FlowLearner, "flow_pred": FlowPred, "frame_generator": FrameGenerator,
+              "flow_completer": FlowCompleter}
+ALGORITHM_DEFAULTS = {"flow_learner": FLOW_LEARNER, "flow_pred": FLOW_PRED, "frame_generator": FRAME_GENERATOR,
+                      "flow_completer": FLOW_COMPLETER}
 
 
 def deep_update(d, u):
