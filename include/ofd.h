@@ -17,6 +17,7 @@
  *   denoising_diffusion.py:363-417    Unet.forward                      -> ofd_unet_forward
  *   denoising_diffusion.py:666-698    p_mean_variance + p_sample update -> ofd_ddpm_update(_obj)
  *   denoising_diffusion.py:750-767    ddim_sample update                -> ofd_ddim_update(_obj)
+ *   (not in the reference)            DPM-Solver++ multistep update     -> ofd_dpmpp_update
  *   denoising_diffusion.py:806-812    q_sample                          -> ofd_q_sample
  *   denoising_diffusion.py:844-879,985-993  p_losses noise / target     -> ofd_diffusion_prep
  *   denoising_diffusion.py:73-77      (un)normalize                     -> ofd_range_map
@@ -144,6 +145,20 @@ int ofd_ddim_update_obj(int objective, const float* x_t, const float* model_out,
                         const float* sqrt_recip_ac, const float* sqrt_recipm1_ac, const float* xa, const float* xb,
                         const float* sqrt_alpha_next, const float* c, const float* sigma, int last,
                         float* out, float* x_start, int B, size_t n_per_sample, void* stream);
+/* DPM-Solver++ multistep step (Lu et al., "DPM-Solver++: Fast Solver for Guided Sampling of Diffusion Probabilistic Models", 2022,
+ * data prediction; an addition, not the reference's sampler).  With alpha = sqrt(ac), sigma = sqrt(1 - ac), lambda = log(alpha/sigma),
+ * h = lambda_next - lambda_cur and D_k the clamped x_start predictions of this (k = 0) and the previous k steps:
+ *   order 1: x_next = (sigma_next/sigma_cur) x_t - alpha_next*expm1(-h)*D0                    (= DDIM with eta = 0)
+ *   order 2 (2M, paper Alg. 2): ... - alpha_next*expm1(-h)*(D0 + (D0 - D1)/(2r)),  r = h_prev/h
+ *   order 3 (3M): ... + alpha_next*(expm1(-h)/h + 1)*D1' - alpha_next*((expm1(-h) + h)/h^2 - 1/2)*D2'  with the divided differences
+ *            D1' = d0 + r0/(r0 + r1)*(d0 - d1), D2' = (d0 - d1)/(r0 + r1), d0 = (D0 - D1)/r0, d1 = (D1 - D2)/r1.
+ * The host folds each into per-sample rows: out = cx*x_t + w0*D0 + w1*d_prev1 + w2*d_prev2 (order 1 reads no history, order 2
+ * d_prev1 and w1, order 3 also d_prev2 and w2; each product rounded once, added in that order).  D0 = clamp(x_start, -1, 1) with
+ * x_start formed as in ofd_ddim_update_obj (xa / xb as there, NULL for OFD_PRED_X0).  last != 0 writes D0 to out (the final
+ * evaluation; no coefficient or history is read).  D0 is also written to d_out when non-NULL.  out == x_t is allowed. */
+int ofd_dpmpp_update(int objective, int order, const float* x_t, const float* model_out, const float* xa, const float* xb,
+                     const float* d_prev1, const float* d_prev2, const float* cx, const float* w0, const float* w1,
+                     const float* w2, int last, float* out, float* d_out, int B, size_t n_per_sample, void* stream);
 /* Training prep, one launch (DD:844-848, 806-812, 874-879, 985-993), x0 / noise / outputs (B,C,hw):
  *   x0n = normalize ? 2*x0 - 1 : x0;  nz = noise + offset_strength*offset[b,c] (offset (B,C), or NULL: no offset noise);
  *   x_t = sqrt_ac*x0n + sqrt_1mac*nz;  target = nz (pred_noise), x0n (pred_x0), sqrt_ac*nz - sqrt_1mac*x0n (pred_v).

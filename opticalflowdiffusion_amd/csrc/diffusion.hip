@@ -1,4 +1,4 @@
-// Diffusion elementwise steps (denoising_diffusion.py:589-623, 666-698, 750-767, 806-812) and the
+// Diffusion elementwise steps (denoising_diffusion.py:589-623, 666-698, 750-767, 806-812), the DPM-Solver++ multistep step, and the
 // NaN-masked squared-error reduction (warp.py:260-271 + torch.nanmean, DD:908,973).
 // HBM-bound streaming kernels: float4 accesses, per-sample scalar coefficients.
 #include <type_traits>
@@ -130,6 +130,49 @@ __global__ void __launch_bounds__(256) ddim_update_kernel(const float* __restric
         }
         ew_store<VEC>(out + e, r);
         if (x_start) ew_store<VEC>(x_start + e, xs);
+    }
+}
+
+// DPM-Solver++ multistep step (Lu et al. 2022, data prediction; not in the reference): D0 = clamp(x_start) formed exactly as the DDIM
+// step forms it, then x_next = cx x_t + w0 D0 + w1 D1 + w2 D2 with D1 / D2 the clamped predictions of the previous one / two steps and the
+// per-sample coefficient rows folded on the host (ConditionalDiffusion._dpmpp_tables); last returns D0.  D0 is also written to d_out (the
+// caller's history slot).  x_t and out may alias (in place): each element is read before it is written, by the same thread, so neither
+// pointer is __restrict__.  ORDER 1 / 2 / 3 reads 0 / 1 / 2 history tensors: 16 / 20 / 24 B per element.
+template <int OBJ, int ORDER, int VEC>
+__global__ void __launch_bounds__(256) dpmpp_update_kernel(const float* x_t, const float* __restrict__ mo, const float* __restrict__ xa,
+                                                           const float* __restrict__ xb, const float* __restrict__ d1,
+                                                           const float* __restrict__ d2, const float* __restrict__ cx,
+                                                           const float* __restrict__ w0, const float* __restrict__ w1,
+                                                           const float* __restrict__ w2, int last, float* out, float* __restrict__ d_out,
+                                                           size_t n_per_sample) {
+    const int s = blockIdx.y;
+    const float k_x = last ? 0.0f : cx[s], k_0 = last ? 0.0f : w0[s];
+    const float k_1 = (ORDER >= 2 && !last) ? w1[s] : 0.0f, k_2 = (ORDER >= 3 && !last) ? w2[s] : 0.0f;
+    float ka = 0.0f, kb = 0.0f;
+    if constexpr (OBJ != PRED_X0) { ka = xa[s]; kb = xb[s]; }
+    const size_t base = (size_t)s * n_per_sample, nv = n_per_sample / VEC;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t e = base + i * VEC;
+        const EwVec<VEC> m = ew_load<VEC>(mo + e);
+        EwVec<VEC> xt, p1, p2, r, xs;
+        if (!last || OBJ != PRED_X0) xt = ew_load<VEC>(x_t + e);
+        if constexpr (ORDER >= 2) { if (!last) p1 = ew_load<VEC>(d1 + e); }
+        if constexpr (ORDER >= 3) { if (!last) p2 = ew_load<VEC>(d2 + e); }
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+            const float x0 = clamp1(start_from_output<OBJ>(m.v[j], xt.v[j], ka, kb));   // as ddim_update_kernel
+            float v = x0;
+            if (!last) {
+                v = k_x * xt.v[j];                                       // each product rounded once, added in this order
+                v = v + k_0 * x0;
+                if constexpr (ORDER >= 2) v = v + k_1 * p1.v[j];
+                if constexpr (ORDER >= 3) v = v + k_2 * p2.v[j];
+            }
+            r.v[j] = v;
+            xs.v[j] = x0;
+        }
+        ew_store<VEC>(out + e, r);
+        if (d_out) ew_store<VEC>(d_out + e, xs);
     }
 }
 
@@ -292,6 +335,38 @@ extern "C" int ofd_ddim_update(const float* x_t, const float* model_out, const f
                                int last, float* out, float* x_start, int B, size_t n, void* stream) {
     return ofd_ddim_update_obj(PRED_X0, x_t, model_out, noise, sqrt_recip_ac, sqrt_recipm1_ac, nullptr, nullptr, sqrt_alpha_next, c, sigma,
                                last, out, x_start, B, n, stream);
+}
+
+extern "C" int ofd_dpmpp_update(int objective, int order, const float* x_t, const float* model_out, const float* xa, const float* xb,
+                                const float* d_prev1, const float* d_prev2, const float* cx, const float* w0, const float* w1,
+                                const float* w2, int last, float* out, float* d_out, int B, size_t n, void* stream) {
+    OFD_OBJ_OK(objective);
+    OFD_EW_ARGS_OK(B, n);
+    OFD_CHECK_ARG(order >= 1 && order <= 3, "dpmpp_update: bad order %d", order);
+    OFD_CHECK_ARG(x_t && model_out && out, "dpmpp_update: null pointer");
+    OFD_CHECK_ARG(objective == PRED_X0 || (xa && xb), "dpmpp_update: missing x_start coefficients");
+    OFD_CHECK_ARG(last || (cx && w0), "dpmpp_update: missing coefficients");
+    OFD_CHECK_ARG(last || order < 2 || (d_prev1 && w1), "dpmpp_update: order %d needs d_prev1 and w1", order);
+    OFD_CHECK_ARG(last || order < 3 || (d_prev2 && w2), "dpmpp_update: order 3 needs d_prev2 and w2");
+    const int ord = last ? 1 : order;                                  // the final evaluation reads no history
+    hipStream_t s = (hipStream_t)stream;
+    obj_dispatch(objective, [&](auto o) {
+        constexpr int OBJ = decltype(o)::value;
+        auto go = [&](auto oc) {
+            constexpr int ORD = decltype(oc)::value;
+            if (n % 4 == 0)
+                dpmpp_update_kernel<OBJ, ORD, 4><<<ew_grid(B, n / 4), 256, 0, s>>>(x_t, model_out, xa, xb, d_prev1, d_prev2, cx, w0, w1, w2,
+                                                                                  last, out, d_out, n);
+            else
+                dpmpp_update_kernel<OBJ, ORD, 1><<<ew_grid(B, n), 256, 0, s>>>(x_t, model_out, xa, xb, d_prev1, d_prev2, cx, w0, w1, w2,
+                                                                              last, out, d_out, n);
+        };
+        if (ord == 3) go(std::integral_constant<int, 3>{});
+        else if (ord == 2) go(std::integral_constant<int, 2>{});
+        else go(std::integral_constant<int, 1>{});
+    });
+    OFD_LAUNCH_CHECK();
+    return OFD_OK;
 }
 
 extern "C" int ofd_range_map(const float* in, float* out, size_t n, int mode, void* stream) {

@@ -38,6 +38,65 @@ def identity(t, *args, **kwargs):
 OBJECTIVES = {"pred_x0": 0, "pred_noise": 1, "pred_v": 2}     # OFD_PRED_X0 / OFD_PRED_NOISE / OFD_PRED_V (include/ofd.h)
 
 
+SAMPLERS = (None, "ddim", "dpmpp")      # None: the reference's rule (DDPM when sampling_timesteps == timesteps, else DDIM)
+SAMPLER_SPACINGS = ("logsnr", "ddim")
+
+
+def _half_logsnr(ac):
+    """lambda = log(alpha / sigma) of float64 alphas_cumprod"""
+    return 0.5 * (torch.log(ac) - torch.log1p(-ac))
+
+
+def dpmpp_grid(alphas_cumprod, steps, spacing="logsnr"):
+    """The integer timesteps of the DPM-Solver++ model calls, T - 1 first (not in the reference).  "logsnr": `steps` points uniform in
+    lambda from t = T - 1 to t = 0, each snapped to the step of nearest lambda, duplicates removed.  "ddim": the DDIM grid of ddim_sample
+    (linspace(-1, T - 1, steps + 1) truncated) without its final -1, whose call is the final evaluation, as DDIM's last jump is."""
+    ac = alphas_cumprod.detach().to("cpu", torch.float64)
+    T = ac.shape[0]
+    if spacing == "logsnr":
+        lam = _half_logsnr(ac)
+        want = torch.linspace(float(lam[T - 1]), float(lam[0]), steps, dtype=torch.float64) if steps > 1 else lam[T - 1:]
+        ts = (lam.reshape(1, T) - want.reshape(-1, 1)).abs().argmin(dim=1).tolist()
+    elif spacing == "ddim":
+        ts = list(reversed(torch.linspace(-1, T - 1, steps=steps + 1).int().tolist()))[:-1]
+    else:
+        raise ValueError(f"unknown sampler_spacing {spacing!r}: expected one of {SAMPLER_SPACINGS}")
+    grid = []
+    for t in ts:
+        if not grid or t != grid[-1]:
+            grid.append(int(t))
+    return grid
+
+
+def dpmpp_coefficients(alphas_cumprod, grid, order):
+    """float64 (len(grid), 4) rows (cx, w0, w1, w2) of the DPM-Solver++ multistep updates along `grid` (include/ofd.h,
+    ofd_dpmpp_update), and the order of each of the len(grid) - 1 steps.  Step i runs at order min(order, i + 1) (the warm-up: only
+    i earlier predictions exist) and the step into the final point at most at order 2; the last row (the final evaluation) is zero."""
+    ac = alphas_cumprod.detach().to("cpu", torch.float64)[torch.tensor(grid, dtype=torch.long)]
+    alpha, sigma, lam = ac.sqrt(), (1.0 - ac).sqrt(), _half_logsnr(ac)
+    S = len(grid)
+    coef = torch.zeros(S, 4, dtype=torch.float64)
+    orders = []
+    for i in range(S - 1):
+        o = min(order, i + 1, 2 if i == S - 2 else 3)
+        h = float(lam[i + 1] - lam[i])
+        em, an = math.expm1(-h), float(alpha[i + 1])
+        w = [-an * em, 0.0, 0.0]                                        # order 1: DDIM with eta = 0
+        if o == 2:                                                      # 2M: D0 + (D0 - D1) / (2 r)
+            r = float(lam[i] - lam[i - 1]) / h
+            w = [-an * em * (1.0 + 0.5 / r), an * em * 0.5 / r, 0.0]
+        elif o == 3:                                                    # 3M: the divided differences of (D0, D1, D2) folded into w
+            r0, r1 = float(lam[i] - lam[i - 1]) / h, float(lam[i - 1] - lam[i - 2]) / h
+            d0 = torch.tensor([1.0 / r0, -1.0 / r0, 0.0], dtype=torch.float64)
+            d1 = torch.tensor([0.0, 1.0 / r1, -1.0 / r1], dtype=torch.float64)
+            D1 = d0 + (r0 / (r0 + r1)) * (d0 - d1)
+            D2 = (d0 - d1) / (r0 + r1)
+            w = (torch.tensor(w, dtype=torch.float64) + an * (em / h + 1.0) * D1 - an * ((em + h) / (h * h) - 0.5) * D2).tolist()
+        coef[i] = torch.tensor([float(sigma[i + 1] / sigma[i])] + list(w), dtype=torch.float64)
+        orders.append(o)
+    return coef, orders
+
+
 def _range_map(x, mode):
     """DD:73-77 as one HIP launch into a new tensor: mode 0 = 2 x - 1, mode 1 = (x + 1) * 0.5"""
     L.require_gpu(x)
@@ -416,8 +475,20 @@ class ConditionalDiffusion(nn.Module):
     def __init__(self, model, image_size, timesteps=1000, sampling_timesteps=None, objective="pred_v",
                  beta_schedule="sigmoid", schedule_fn_kwargs=dict(), ddim_sampling_eta=0.0, auto_normalize=True,
                  offset_noise_strength=0.0, min_snr_loss_weight=False, min_snr_gamma=5, conditioned=True,
-                 channels=3, noise_space="image", ddim_draw_unused_noise=False):
+                 channels=3, noise_space="image", ddim_draw_unused_noise=False, sampler=None, solver_order=2,
+                 sampler_spacing="logsnr"):
         super().__init__()
+        # sampler (not in the reference): None = the reference's rule (DDPM, or DDIM when sampling_timesteps < timesteps); "ddim" forces
+        # DDIM; "dpmpp" = DPM-Solver++ multistep of order solver_order over sampling_timesteps model calls on the sampler_spacing grid
+        if sampler not in SAMPLERS:
+            raise ValueError(f"unknown sampler {sampler!r}: expected one of {SAMPLERS}")
+        if solver_order not in (1, 2, 3):
+            raise ValueError(f"solver_order must be 1, 2 or 3, got {solver_order!r}")
+        if sampler_spacing not in SAMPLER_SPACINGS:
+            raise ValueError(f"unknown sampler_spacing {sampler_spacing!r}: expected one of {SAMPLER_SPACINGS}")
+        if sampler == "dpmpp" and (sampling_timesteps is None or not 1 <= int(sampling_timesteps) <= timesteps):
+            raise ValueError(f"sampler='dpmpp' needs sampling_timesteps in [1, timesteps={timesteps}], got {sampling_timesteps!r}")
+        self.sampler, self.solver_order, self.sampler_spacing = sampler, int(solver_order), sampler_spacing
         # ddim_draw_unused_noise (not in the reference): the reference's ddim_sample draws randn_like(img) every step even when
         # eta == 0 multiplies it by zero (DD:763); the engine skips that draw, so a SEEDED eta == 0 run consumes a different RNG
         # stream.  True restores the draw (same stream positions as the reference) for seeded comparisons.
@@ -456,7 +527,7 @@ class ConditionalDiffusion(nn.Module):
         # frames (1001 x 57.7 MB = 57.8 GB at B=16, 440x1024; the reference's logging only looks at samples[:, ::50], FD:246).
         # None = the reference's behaviour (every frame).
         self.trajectory_stride = None
-        self.is_ddim_sampling = self.sampling_timesteps < timesteps
+        self.is_ddim_sampling = self.sampling_timesteps < timesteps or sampler == "ddim"
         self.ddim_sampling_eta = ddim_sampling_eta
 
         def reg(name, val):
@@ -707,6 +778,57 @@ class ConditionalDiffusion(nn.Module):
                 imgs.append(img.clone())
         return self.unnormalize(img if not return_all_timesteps else torch.stack(imgs, dim=1))             # DD:772-773
 
+    # -- DPM-Solver++ (not in the reference) --------------------------------------------------
+    def _dpmpp_tables(self, batch, device):
+        """(grid, per-step orders, (S, 4, batch) fp32 rows cx / w0 / w1 / w2) for this sampler's settings, computed once in float64 from
+        alphas_cumprod and cached like _sampling_tables: a step reads rows, no allocation, gather or host sync"""
+        ac = self.alphas_cumprod
+        key = (batch, str(device), self.sampling_timesteps, self.solver_order, self.sampler_spacing, ac.data_ptr(), ac._version, ac.dtype)
+        if getattr(self, "_dpmpp_tab", None) is None or self._dpmpp_tab[0] != key:
+            grid = dpmpp_grid(ac, self.sampling_timesteps, self.sampler_spacing)
+            coef, orders = dpmpp_coefficients(ac, grid, self.solver_order)
+            rows = coef.to(torch.float32).reshape(len(grid), 4, 1).repeat(1, 1, batch).contiguous().to(device)
+            self._dpmpp_tab = (key, (grid, orders, rows))
+        return self._dpmpp_tab[1]
+
+    @torch.no_grad()
+    def dpmpp_sample(self, shape, return_all_timesteps=False, external_cond=None, additional_tgt=None, x_T=None):
+        """DPM-Solver++ multistep sampling (include/ofd.h, ofd_dpmpp_update): one UNet call per grid point, S - 1 solver steps and a
+        final evaluation that returns the clamped prediction.  Signature, x_T, trajectory_stride and the (B, S + 1, C, H, W)
+        trajectory are ddim_sample's.  With additional_tgt (FlowDiffuser's target='target') the model's extra output channels are
+        returned per step as p_sample_loop returns them: (images, [None, out_1, ..., out_S]).  A step is one UNet call and one fused
+        update launch; the predictions live in a three-slot ring rotated by pointer, the image in two ping-pong buffers."""
+        batch = shape[0]
+        img = torch.randn(shape, device=self.device) if x_T is None else L.f32c(x_T)
+        assert tuple(img.shape) == tuple(shape)
+        grid, orders, coef = self._dpmpp_tables(batch, img.device)
+        tab = self._sampling_tables(batch, img.device)
+        imgs, additionals = [img], [None]
+        n = img[0].numel()
+        stride = self.trajectory_stride
+        pong = [torch.empty_like(img), torch.empty_like(img)]
+        ring = [torch.empty_like(img) for _ in range(3)]
+        lib, obj = L.lib(), self._obj
+        for i, t in enumerate(grid):
+            out = self.model_with_condition(img, tab["t"][t], None, external_cond=external_cond, additional_tgt=additional_tgt)
+            if additional_tgt is not None:
+                additionals.append(out[:, -1 * additional_tgt.shape[1]:])
+                out = out[:, :-1 * additional_tgt.shape[1]]
+            out = self._same_shape(L.f32c(out), img)
+            last = i == len(grid) - 1
+            order = 1 if last else orders[i]
+            c = coef[i]
+            nxt = pong[i & 1]
+            L.check(lib.ofd_dpmpp_update(obj, order, L.ptr(img), L.ptr(out), *self._xab(tab, t),
+                                         L.ptr(ring[(i - 1) % 3]) if order >= 2 else None, L.ptr(ring[(i - 2) % 3]) if order >= 3 else None,
+                                         L.ptr(c[0]), L.ptr(c[1]), L.ptr(c[2]), L.ptr(c[3]), int(last), L.ptr(nxt),
+                                         None if last else L.ptr(ring[i % 3]), batch, n, L.stream()))
+            img = nxt
+            if return_all_timesteps and (stride is None or (i + 1) % stride == 0 or last):
+                imgs.append(img.clone())
+        res = self.unnormalize(img if not return_all_timesteps else torch.stack(imgs, dim=1))
+        return (res, additionals) if additional_tgt is not None else res
+
     @torch.no_grad()
     def sample(self, batch_size=16, return_all_timesteps=False, external_cond=None, additional_tgt=None):
         """DD:776-784, with image_size allowed to be (H, W).  external_cond is normalised once per call (DD:778-779); the loops
@@ -714,7 +836,10 @@ class ConditionalDiffusion(nn.Module):
         if external_cond is not None:
             external_cond = self.normalize(external_cond)
         H, W = self._hw()
-        fn = self.p_sample_loop if not self.is_ddim_sampling else self.ddim_sample
+        if self.sampler == "dpmpp":
+            fn = self.dpmpp_sample
+        else:
+            fn = self.p_sample_loop if not self.is_ddim_sampling else self.ddim_sample
         assert external_cond is None or external_cond.shape[0] == batch_size
         return fn((batch_size, self.channels, H, W), return_all_timesteps=return_all_timesteps,
                   external_cond=external_cond, additional_tgt=additional_tgt)

@@ -6,7 +6,8 @@ The reference class is a `pl.LightningModule`; Lightning, Hydra and W&B are opti
 with the hooks `experiments/exp_base.py` drives (`log_dict`, `configure_optimizers`,
 `training_step`, `validation_step`).  `cfg` may be a DictConfig, a dict or any attribute object
 with the keys of configurations/algorithm/flow_diffuser.yaml (+ optional `image_size: [H, W]`,
-`sampling_timesteps`, `precision`, `ae_checkpoint`).
+`sampling_timesteps`, `precision`, `ae_checkpoint`, and the sampler keys `sampler`, `solver_order`,
+`sampler_spacing` of ConditionalDiffusion, which are not in the reference).
 """
 import os
 
@@ -40,7 +41,7 @@ class _Cfg:
     _DEFAULTS = dict(name="flow_diffuser", image_size=128, latent_dim=16, flow_max=20, latent_max=2, lr=1e-5,
                      flow_weight=0.0, weight_decay=1e-6, is_diffusion=True, latent=False, timesteps=1000,
                      target="joint", ae="px8q8g0m", noiser="image", zero_init=True,
-                     sampling_timesteps=None, precision="bf16", augment=True)
+                     sampling_timesteps=None, precision="bf16", augment=True, sampler=None, solver_order=2, sampler_spacing="logsnr")
 
     def __init__(self, cfg):
         self._d = dict(self._DEFAULTS)
@@ -164,7 +165,8 @@ class FlowDiffuser(_Base):
             self._model, cfg.image_size, objective="pred_x0",
             channels={"target": self.dim, "joint": self.dim + 2}.get(cfg.target, 2),
             auto_normalize=False, noise_space="image" if cfg.noiser == "image" else "flow",
-            timesteps=cfg.timesteps, sampling_timesteps=cfg.sampling_timesteps, min_snr_loss_weight=True)
+            timesteps=cfg.timesteps, sampling_timesteps=cfg.sampling_timesteps, min_snr_loss_weight=True,
+            sampler=cfg.sampler, solver_order=int(cfg.solver_order), sampler_spacing=cfg.sampler_spacing)   # not in the reference
         if "trajectory_stride" in cfg:                                      # optional key, default = every frame as the reference
             self.model.trajectory_stride = cfg.trajectory_stride
 

@@ -16,10 +16,11 @@ from .flow_pred import parse_image_size
 
 class _FrameCfg(_Cfg):
     """configurations/algorithm/frame_generator.yaml, plus `clip` (the trainer's gradient_clip_val, folded into FusedAdam),
-    `precision`, `timesteps` and `sampling_timesteps` (DDIM when fewer than `timesteps`)"""
+    `precision`, `timesteps` and `sampling_timesteps` (DDIM when fewer than `timesteps`), and the sampler keys of ConditionalDiffusion
+    (`sampler`, `solver_order`, `sampler_spacing`; not in the reference)"""
 
     _DEFAULTS = dict(name="frame_generator", image_size=64, lr=7e-5, weight_decay=2e-4, clip=0.0, precision="bf16", timesteps=1000,
-                     sampling_timesteps=None)
+                     sampling_timesteps=None, sampler=None, solver_order=2, sampler_spacing="logsnr")
 
 
 class FrameGenerator(_Base):
@@ -36,7 +37,9 @@ class FrameGenerator(_Base):
         self.image_size = h if h == w else (h, w)
         self._model = Unet(64, channels=3 + 3 + 2, out_dim=3, precision=cfg.precision)              # DA:25-29
         self.diffusion_model = ConditionalDiffusion(self._model, self.image_size, objective="pred_noise",   # DA:30-34
-                                                    timesteps=int(cfg.timesteps), sampling_timesteps=cfg.sampling_timesteps)
+                                                    timesteps=int(cfg.timesteps), sampling_timesteps=cfg.sampling_timesteps,
+                                                    sampler=cfg.sampler, solver_order=int(cfg.solver_order),
+                                                    sampler_spacing=cfg.sampler_spacing)
 
     def configure_optimizers(self):                                                                  # DA:36-41
         """Adam(lr, weight_decay) as the reference, as the HIP multi-tensor step (optim.FusedAdam)"""
