@@ -466,10 +466,8 @@ __global__ void __launch_bounds__(256) nchw_to_nhwc_kernel(const float* __restri
 // uncapped, the blocks in flight form one moving window of a few MB and DRAM pages are streamed through once -- same-box A/B on
 // resblock_out: 1.77 ms (cap 4096) -> 1.43 ms per denoise step; GroupNorm backward 16.4 -> 15.2 ms per training step.  Kernels with a
 // per-thread preamble (final_conv, pack_input, the layout converters) lose (misc 0.46 -> 0.97 ms) and keep the cap.
-// OFD_GRID_CAP restores a cap on the uncapped ones for A/B runs.
 static inline int sgrid(size_t total, int block = 256, int cap = 4096) {
-    static const int env_cap = getenv("OFD_GRID_CAP") ? atoi(getenv("OFD_GRID_CAP")) : (1 << 22);
-    if (cap <= 0) cap = env_cap;
+    if (cap <= 0) cap = 1 << 22;
     size_t b = (total + block - 1) / block;
     return (int)(b < 1 ? 1 : (b > (size_t)cap ? cap : b));
 }

@@ -4,6 +4,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdint>
+#include <cstdlib>
 #include "../../include/ofd.h"
 
 namespace ofd {
@@ -30,6 +31,13 @@ void set_error(const char* fmt, ...);
 #define OFD_LAUNCH_CHECK() OFD_HIP(hipGetLastError())
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// Integer value of an environment switch, `dflt` when unset.  Read on every call: the tests flip the reference switches (OFD_CONV_PC,
+// OFD_GW_BAND, OFD_CONV1_NO_PL, OFD_CONV1_GRID, OFD_CONV7_PERSIST) inside one process to compare a fast kernel with its reference.
+static inline int env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
 
 typedef uint16_t bf16_t;   // raw bits
 

@@ -14,7 +14,7 @@
 //     fragment reads are inline-asm ds_read_b128 for the same reason (a visible LDS load waits for ALL outstanding LDS-DMA).  The
 //     waits are counted by hand: per tile and wave the VMEM issue order is [DMA(t+1)] ... [h2(t+1)] [stores(t)], the top-of-tile
 //     wait is vmcnt(#h2 + #stores), the wait before the epilogue vmcnt(#stores + #DMA).
-// Persistent: workgroup w walks tiles w, w + G, ... (P.interleave; all resident workgroups inside one moving window of memory).
+// Persistent: workgroup w walks tiles w, w + G, ... (all resident workgroups inside one moving window of memory).
 // Tiles are always full and stores never predicated (the hand-counted waits depend on it): when TILE does not divide H*W the LAST tile of
 // a sample starts at H*W - TILE and recomputes the pixels it shares with the tile before it (same inputs, same arithmetic, the same
 // bytes written twice; the host admits this only for same-size sources, an output that is none of the inputs, and never for the
@@ -76,7 +76,6 @@ struct Params {
     const float* fc_w;         // FC instantiation: the final 1x1 conv [2][Cout], its bias [2], its zeroed (B, 2, H, W) fp32 output
     const float* fc_b;
     float* fc_out;
-    int interleave;            // 1: workgroup w walks tiles w, w + G, ... (the resident workgroups sweep ONE moving window of memory); 0: a contiguous range each
     // 1-D grid of gx * nb workgroups (gx tile walkers x nb output-channel blocks), channel block fastest and the nb blocks of a walker on ONE
     // XCD (workgroup i runs on XCD i % 8): the walker's input tile comes from HBM once and from that XCD's L2 for the other blocks, and every
     // workgroup is resident from the start.  (The 2-D grid ran the channel blocks one after the other: 768 -> 512 at 55 x 128 read its
@@ -207,9 +206,9 @@ __global__ void __launch_bounds__(NTHREADS, CIN > 512 ? 1 : 2) conv1x1_wp_kernel
     // tile walk: interleaved (t = w, w + G, ...) keeps the ~500 resident workgroups inside one moving window of a few MB -- DRAM pages
     // are streamed through once; contiguous per-workgroup ranges spread them over the whole tensor (measured 20 % slower on the
     // same pattern in resblock_out).  The price: the sample index changes every plane / TILE / G tiles instead of once or twice.
-    const int t_step = P.interleave ? P.gx : 1;
-    int t = P.interleave ? wx : (int)(((long)wx * P.ntiles) / P.gx);
-    const int t_end = P.interleave ? P.ntiles : (int)(((long)(wx + 1) * P.ntiles) / P.gx);
+    const int t_step = P.gx;
+    int t = wx;
+    const int t_end = P.ntiles;
     if (t >= t_end) return;
     int b_cur = -1;
     float4 sc4[RA ? 4 : 1], sh4[RA ? 4 : 1];
@@ -375,11 +374,10 @@ static int launch(const Params& P, hipStream_t s) {
     const int per_cu = (LDS * 2 <= 160 * 1024) ? 2 : 1;
     const int nb = (P.Cout - P.cout0) / (32 * NSG * NCB);
     int gx = 256 * per_cu;
-    // several channel blocks: all of them resident at once, walkers in whole groups of 8 (one per XCD); OFD_CONV1_NB_ROUNDS=1: a full set of
-    // walkers per channel block as before (nb rounds of workgroups)
-    static const int nb_rounds = getenv("OFD_CONV1_NB_ROUNDS") ? atoi(getenv("OFD_CONV1_NB_ROUNDS")) : 0;
-    if (nb > 1 && !nb_rounds) gx = (gx / nb) / 8 * 8;
-    if (const char* e = getenv("OFD_CONV1_GRID")) gx = atoi(e) > 0 ? atoi(e) : gx;       // diagnostics / tests: long tile ranges on small inputs
+    // several channel blocks: all of them resident at once, walkers in whole groups of 8 (one per XCD)
+    if (nb > 1) gx = (gx / nb) / 8 * 8;
+    const int grid_env = env_int("OFD_CONV1_GRID", 0);     // (read per call) tests: long tile ranges on small inputs
+    if (grid_env > 0) gx = grid_env;
     if (gx > P.ntiles) gx = P.ntiles;
     if (nb > 1 && gx > 8) gx = gx / 8 * 8;
     Params Q = P;
@@ -406,8 +404,7 @@ int launch_conv1x1_wp(const ConvParams& C, hipStream_t s) {
     using namespace c1;
     if (C.in_scale || C.gn_partial) return 1;
     // plain residual(s) and / or a split output (the 1x1 data gradients of the training backward, the mid attention's to_out): the PL instantiations
-    const char* e_pl = getenv("OFD_CONV1_NO_PL");          // read per call (A/B switch): 1 = these go to the shared-slab kernel as before
-    const bool no_pl = e_pl && atoi(e_pl);
+    const bool no_pl = env_int("OFD_CONV1_NO_PL", 0);     // (read per call) 1: these go to the shared-slab kernel, the tests' reference
     const bool pl = (C.residual || C.residual2 || C.split > 0) && !C.res_act;
     if (!pl && (C.residual || C.residual2 || C.split || C.out2)) return 1;
     if (pl && (no_pl || C.fc_out || C.residual_b || C.pool2 || C.cout0 || (C.split > 0 && (!C.out2 || C.split % 32 != 0 || C.split >= C.Cout)))) return 1;
@@ -443,8 +440,6 @@ int launch_conv1x1_wp(const ConvParams& C, hipStream_t s) {
     P.fc_w = C.fc_w; P.fc_b = C.fc_b; P.fc_out = C.fc_out;
     if (C.fc_out && !(cin == 128 && C.Cout == 64 && ra)) return 1;
     P.B = C.B; P.H = C.H; P.W = C.W; P.Cout = C.Cout; P.ntiles = C.B * ((plane + tile - 1) / tile);
-    static const int order = getenv("OFD_CONV1_ORDER") ? atoi(getenv("OFD_CONV1_ORDER")) : 1;
-    P.interleave = order;
     const bool narrow = C.Cout == 64;
     P.cout0 = 0;
     if (pl) {

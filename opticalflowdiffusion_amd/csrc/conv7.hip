@@ -20,11 +20,6 @@
 #include "common.h"
 #include "conv_params.h"
 
-// diagnostic builds (tools/build_wp_variants.sh <tag> "-DOFD_C7_ABL=n" conv7.hip): bit 0 no MFMAs, bit 1 no output stores, bit 2 no input prefetch
-#ifndef OFD_C7_ABL
-#define OFD_C7_ABL 0
-#endif
-
 namespace ofd {
 namespace c7 {
 
@@ -122,7 +117,7 @@ __global__ void __launch_bounds__(NTHREADS, 2) conv7x7_c8_persist_kernel(const C
 
     for (int it = 0; it < n_iter; ++it) {
         const Tile nxt = tile_of((int)blockIdx.x + (it + 1) * (int)gridDim.x, ntiles, P.tiles_x, tpi);
-        if (it + 1 < n_iter && !(OFD_C7_ABL & 4)) load_x(xr, P, nxt, wave, lane);
+        if (it + 1 < n_iter) load_x(xr, P, nxt, wave, lane);
 
         f32x16 acc[2][2];
 #pragma unroll
@@ -150,7 +145,6 @@ __global__ void __launch_bounds__(NTHREADS, 2) conv7x7_c8_persist_kernel(const C
             const bf16x8 x0 = xkeep[ky & 1][ks], x1 = xn[cb];
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt) {
-                if (OFD_C7_ABL & 1) { asm volatile("" ::"v"(wf[cb][nt]), "v"(x0), "v"(x1)); continue; }
                 acc[nt][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[cb][nt], x0, acc[nt][0], 0, 0, 0);
                 acc[nt][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[cb][nt], x1, acc[nt][1], 0, 0, 0);
             }
@@ -181,8 +175,7 @@ __global__ void __launch_bounds__(NTHREADS, 2) conv7x7_c8_persist_kernel(const C
             for (int k = 0; k < 4; ++k) {
                 const int pl = (lane >> 3) + 8 * k, cu = lane & 7;
                 const uint4 v = *(const uint4*)(xw + pl * OPITCH + cu * 16);
-                if (OFD_C7_ABL & 2) asm volatile("" ::"v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w));
-                else if (oy < P.H && cur.ox0 + pl < P.W) *(uint4*)(orow + pl * 64 + cu * 8) = v;
+                if (oy < P.H && cur.ox0 + pl < P.W) *(uint4*)(orow + pl * 64 + cu * 8) = v;
             }
         }
 
@@ -197,8 +190,8 @@ __global__ void __launch_bounds__(NTHREADS, 2) conv7x7_c8_persist_kernel(const C
 // 1 = shape not served (the caller falls through to the generic kernel)
 int launch_conv7x7_c8_persist(const ConvParams& P, hipStream_t s) {
     using namespace c7;
-    const char* e = getenv("OFD_CONV7_PERSIST");          // read per call (an A/B switch, as OFD_CONV_PC): 0 = the generic kernel
-    if ((e && !atoi(e)) || P.dbg || P.Cout != 64 || P.n_src != 1 || P.Cin_total != 8 || P.src[0].mode != 0 || P.in_scale || P.residual || P.res_act ||
+    // OFD_CONV7_PERSIST=0 (read per call): the generic kernel, the tests' reference
+    if (!env_int("OFD_CONV7_PERSIST", 1) || P.Cout != 64 || P.n_src != 1 || P.Cin_total != 8 || P.src[0].mode != 0 || P.in_scale || P.residual || P.res_act ||
         P.gn_partial || P.split || P.residual_b || P.pool2)
         return 1;
     static bool attr_set = false;
@@ -212,9 +205,8 @@ int launch_conv7x7_c8_persist(const ConvParams& P, hipStream_t s) {
         n_cu = prop.multiProcessorCount;
         attr_set = true;
     }
-    static const int grid_env = getenv("OFD_CONV7_GRID") ? atoi(getenv("OFD_CONV7_GRID")) : 0;
     const int ntiles = P.tiles_x * P.tiles_y * P.B;
-    int grid = grid_env > 0 ? grid_env : 2 * (n_cu / 8 * 8);       // two workgroups per CU, a multiple of the 8 XCDs
+    int grid = 2 * (n_cu / 8 * 8);       // two workgroups per CU, a multiple of the 8 XCDs
     if (grid < 8) grid = 8;
     if (grid > ntiles) grid = ntiles;
     conv7x7_c8_persist_kernel<<<grid, NTHREADS, LDS_BYTES, s>>>(P);

@@ -69,8 +69,6 @@ struct WgradParams {
     // GroupNorm-affine + SiLU prologue): the weight gradient of a block's second conv reads h1 instead of a materialised act1
     const float* in_scale;
     const float* in_shift;
-    int no_dma;          // A/B switch (OFD_WGRAD_NO_DMA): 3x3 dY tiles through registers
-    int dbg;             // conv_wgrad3_db_kernel ablation bits (OFD_WGRAD_DBG; 0 in production): 1 no DMA after the first tile, 2 no fragment reads after the first row, 4 no MFMAs
     // 3x3 only: where output pixel (b, oy, ox) of the (H, W) grid lives in dY: pixel b * dy_bs + (oy * dy_s + dy_y0) * dy_w + ox * dy_s + dy_x0
     // (plain: dy_bs = H W, dy_w = W, dy_s = 1; one phase of an up-sample conv, see conv_wgrad3_kernel: the stride-2 samples of the 2H x 2W tensor)
     long dy_bs;
@@ -376,8 +374,7 @@ template <int CO, int WCO>
 static void launch_wgrad1_wide(const WgradParams& P, size_t npix, int ncib, hipStream_t s) {
     // workgroups over all ci blocks: two per CU; four for Cout = 64, whose 20 KB / 62-register workgroups are short of loads in flight at two
     // (full-resolution res_conv 128 -> 64: 0.76 / 0.61 / 0.66 ms at 512 / 1024 / 2048; 256 -> 128 at half resolution: 0.355 / 0.378 / 0.343)
-    static const int total_env = getenv("OFD_WGRAD1_WIDE_WGS") ? atoi(getenv("OFD_WGRAD1_WIDE_WGS")) : 0;
-    const int total = total_env > 0 ? total_env : (CO == 64 ? 1024 : 512);
+    const int total = CO == 64 ? 1024 : 512;
     int g = cdiv(total, ncib * (P.Cout / CO));
     const size_t nt = (npix + WQ_PX - 1) / WQ_PX;
     if ((size_t)g > nt) g = (int)nt;
@@ -685,7 +682,7 @@ __global__ void __launch_bounds__(512, 1) conv_wgrad3_db_kernel(const WgradParam
     }
     for (; t < ntiles; t += gridDim.x) {
         unsigned char* buf = smem + cur * BUF;
-        if (!(P.dbg & 8)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this wave's pieces of tile t have landed
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this wave's pieces of tile t have landed
         if (zm) {
 #pragma unroll
             for (int i = 0; i < 6; ++i)
@@ -704,7 +701,7 @@ __global__ void __launch_bounds__(512, 1) conv_wgrad3_db_kernel(const WgradParam
         // the next tile's DMA pieces are requested BETWEEN the MFMAs of rows 0..4 (two per row): their address arithmetic runs in the shadow of
         // this wave's own MFMAs instead of ahead of them (the two waves of a SIMD are in step: nobody else would feed the pipe meanwhile)
         const int tn = t + gridDim.x;
-        const bool has_next = tn < ntiles && !(P.dbg & 1);
+        const bool has_next = tn < ntiles;
         const Tile Tn = tile_of(has_next ? tn : t);
         unsigned char* nbuf = smem + (cur ^ 1) * BUF;
         zm = 0;
@@ -723,7 +720,7 @@ __global__ void __launch_bounds__(512, 1) conv_wgrad3_db_kernel(const WgradParam
             yw[2] = yw[1];
             yw[1] = yw[0];
             if constexpr (rr < 8) yw[0] = yn[c].get();
-            if (rr + 1 < 10 && !(P.dbg & 2)) {
+            if (rr + 1 < 10) {
                 tr_read<((rr + 1) * IWK) * 128>(xf[nx][0], xa[((rr + 1) * IWK) & 3]);
                 tr_read<((rr + 1) * IWK + 1) * 128>(xf[nx][1], xa[((rr + 1) * IWK + 1) & 3]);
                 tr_read<((rr + 1) * IWK + 2) * 128>(xf[nx][2], xa[((rr + 1) * IWK + 2) & 3]);
@@ -740,7 +737,7 @@ __global__ void __launch_bounds__(512, 1) conv_wgrad3_db_kernel(const WgradParam
                 const bf16x8 xv = xf[c][kx].get();
 #pragma unroll
                 for (int ky = 0; ky < 3; ++ky)
-                    if (rr - ky >= 0 && rr - ky < 8 && !(P.dbg & 4)) acc[ky][kx] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xv, yw[ky], acc[ky][kx], 0, 0, 0);   // rows = ci, cols = co
+                    if (rr - ky >= 0 && rr - ky < 8) acc[ky][kx] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xv, yw[ky], acc[ky][kx], 0, 0, 0);   // rows = ci, cols = co
             }
         });
         cur ^= 1;
@@ -1058,15 +1055,12 @@ int k_conv_wgrad(const ofd_conv_args* a, const bf16_t* dy, float* dw, hipStream_
     P.dy_bs = (long)a->H * a->W; P.dy_w = a->W; P.dy_s = 1; P.dy_y0 = 0; P.dy_x0 = 0;
     OFD_CHECK_ARG(!a->in_scale || (a->in_shift && a->ksize == 3), "conv_wgrad: the input prologue is a 3x3 feature");
     P.in_scale = a->in_scale; P.in_shift = a->in_shift;
-    { static const int nd = getenv("OFD_WGRAD_NO_DMA") ? atoi(getenv("OFD_WGRAD_NO_DMA")) : 0; P.no_dma = nd; }
-    P.dbg = getenv("OFD_WGRAD_DBG") ? atoi(getenv("OFD_WGRAD_DBG")) : 0;
     const int ntiles = P.tiles_x * P.tiles_y * P.B, combos = (cin / 64) * (a->Cout / 64);
     int gx = cdiv(1024, combos * a->ksize);     // ~4 workgroups per CU in total; each walks ntiles / gx pixel tiles
     if (gx < 1) gx = 1;
     if (gx > ntiles) gx = ntiles;
     OFD_CHECK_ARG(combos <= 65535, "conv_wgrad: too many channel blocks");
-    static const bool no_wq = getenv("OFD_NO_WGRAD_QKV") && atoi(getenv("OFD_NO_WGRAD_QKV"));
-    if (a->ksize == 1 && a->Cout == WQ_CO && a->n_src == 1 && P.src[0].mode == 0 && !dbias && !no_wq) {
+    if (a->ksize == 1 && a->Cout == WQ_CO && a->n_src == 1 && P.src[0].mode == 0 && !dbias) {
         const size_t npix = (size_t)a->B * a->H * a->W;
         const int ncib = cin / 64;
         int g = cdiv(512, ncib);                                 // two workgroups per CU
@@ -1076,8 +1070,7 @@ int k_conv_wgrad(const ofd_conv_args* a, const bf16_t* dy, float* dw, hipStream_
         OFD_LAUNCH_CHECK();
         return OFD_OK;
     }
-    static const bool no_wide = getenv("OFD_NO_WGRAD1_WIDE") && atoi(getenv("OFD_NO_WGRAD1_WIDE"));
-    if (a->ksize == 1 && !no_wide && !P.in_scale && (a->Cout == 64 || a->Cout == 128 || a->Cout == 192 || a->Cout == 256 || a->Cout == 512)) {
+    if (a->ksize == 1 && !P.in_scale && (a->Cout == 64 || a->Cout == 128 || a->Cout == 192 || a->Cout == 256 || a->Cout == 512)) {
         bool plain = true;
         for (int i = 0; i < a->n_src; ++i) plain = plain && P.src[i].mode == 0;
         if (plain) {
@@ -1097,13 +1090,10 @@ int k_conv_wgrad(const ofd_conv_args* a, const bf16_t* dy, float* dw, hipStream_
         if (!attr) {
             OFD_HIP(hipFuncSetAttribute((const void*)conv_wgrad3_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
             OFD_HIP(hipFuncSetAttribute((const void*)conv_wgrad3_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-            OFD_HIP(hipFuncSetAttribute((const void*)conv_wgrad3_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
             OFD_HIP(hipFuncSetAttribute((const void*)conv_wgrad3_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
             attr = true;
         }
-        static const bool no_phase = getenv("OFD_NO_WGRAD_PHASES") && atoi(getenv("OFD_NO_WGRAD_PHASES"));
-        static const int phase_min_combos = getenv("OFD_WGRAD_PHASE_MIN_COMBOS") ? atoi(getenv("OFD_WGRAD_PHASE_MIN_COMBOS")) : 4;
-        if (!no_phase && !P.no_dma && !P.in_scale && a->n_src == 1 && P.src[0].mode == 1 && a->H % 2 == 0 && a->W % 2 == 0 && combos >= phase_min_combos) {
+        if (!P.in_scale && a->n_src == 1 && P.src[0].mode == 1 && a->H % 2 == 0 && a->W % 2 == 0 && combos >= 4) {
             // up-sample conv: four phase passes on the low-resolution grid (see conv_wgrad3_kernel, PH).  The passes stage as many tiles as the
             // plain form (the low-resolution halo tile once per phase), so only the MFMA share of the time shrinks: 0.99 -> 0.85 ms (192 -> 128 at
             // 220 x 512), 0.955 -> 0.80 ms (256 -> 192 at 110 x 256), but 0.99 -> 1.07 ms for the two channel-block pairs of 128 -> 64 at full
@@ -1136,16 +1126,15 @@ int k_conv_wgrad(const ofd_conv_args* a, const bf16_t* dy, float* dw, hipStream_
             OFD_LAUNCH_CHECK();
             return OFD_OK;
         }
-        static const int db = getenv("OFD_WGRAD3_DB") ? atoi(getenv("OFD_WGRAD3_DB")) : 1;
         // (its per-sample element offsets are 32-bit UNSIGNED arithmetic: a plane of 2^32 elements or more keeps the kernel above)
         bool small_planes = (size_t)a->H * a->W * a->Cout < (1ull << 32);
         for (int i = 0; i < a->n_src; ++i) small_planes = small_planes && (size_t)P.src[i].SH * P.src[i].SW * P.src[i].src_channels < (1ull << 32);
-        if (db && !P.no_dma && !P.in_scale && small_planes) {
+        if (!P.in_scale && small_planes) {
             // double-buffered form: ONE 8-wave workgroup per CU (2 x 75 KB of LDS), each walking ntiles / gx tiles
             constexpr int LDS_DB = 2 * (43 * 1024 + 256 * 128);
             static bool attr_db = false;
             if (!attr_db) { OFD_HIP(hipFuncSetAttribute((const void*)conv_wgrad3_db_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DB)); attr_db = true; }
-            gx = 256 * db / combos;
+            gx = 256 / combos;
             if (gx < 1) gx = 1;
             if (gx > ntiles) gx = ntiles;
             conv_wgrad3_db_kernel<<<dim3(gx, combos), 512, LDS_DB, s>>>(P);
@@ -1155,14 +1144,9 @@ int k_conv_wgrad(const ofd_conv_args* a, const bf16_t* dy, float* dw, hipStream_
         gx = cdiv(512, combos);                  // two workgroups per CU fit (75.5 KB LDS each)
         if (gx < 1) gx = 1;
         if (gx > ntiles) gx = ntiles;
-        if (P.no_dma) {
-            if (P.in_scale) conv_wgrad3_kernel<true, false><<<dim3(gx, combos), 256, LDS, s>>>(P);
-            else conv_wgrad3_kernel<false, false><<<dim3(gx, combos), 256, LDS, s>>>(P);
-        } else {
-            // (the prologue instantiation is over its register budget either way: 13 spilled registers through registers, 20 with the DMA)
-            if (P.in_scale) conv_wgrad3_kernel<true, false><<<dim3(gx, combos), 256, LDS, s>>>(P);
-            else conv_wgrad3_kernel<false, true><<<dim3(gx, combos), 256, LDS, s>>>(P);
-        }
+        // (the prologue instantiation is over its register budget either way: 13 spilled registers through registers, 20 with the DMA)
+        if (P.in_scale) conv_wgrad3_kernel<true, false><<<dim3(gx, combos), 256, LDS, s>>>(P);
+        else conv_wgrad3_kernel<false, true><<<dim3(gx, combos), 256, LDS, s>>>(P);
     } else {
         constexpr int LDS = 8 * 32 * 128 + 256 * 128;
         static bool attr = false;
@@ -1176,9 +1160,8 @@ int k_conv_wgrad(const ofd_conv_args* a, const bf16_t* dy, float* dw, hipStream_
 int k_conv7_wgrad(const bf16_t* x16, const bf16_t* dy, float* dw, int B, int H, int W, hipStream_t s, float* dbias, int channels) {
     const int tx = cdiv(W, 32), ty = cdiv(H, 8);
     OFD_CHECK_ARG(channels == 8 || channels == 16 || channels == 32 || channels == 48, "conv7_wgrad: input packed to %d channels", channels);
-    static const int grid_env = getenv("OFD_CONV7_WGRAD_GRID") ? atoi(getenv("OFD_CONV7_WGRAD_GRID")) : 0;
     int grid = tx * ty * B;
-    const int cap = grid_env > 0 ? grid_env : (channels == 8 ? 512 : 768);       // (the 8-channel form: two workgroups per CU at 128 registers, all resident: 0.45 ms at 512, 0.47 at 768, 0.58 at 1024)
+    const int cap = channels == 8 ? 512 : 768;       // (the 8-channel form: two workgroups per CU at 128 registers, all resident: 0.45 ms at 512, 0.47 at 768, 0.58 at 1024)
     if (grid > cap) grid = cap;
     if (channels == 8) conv7_wgrad_kernel<8><<<grid, 512, 0, s>>>(x16, dy, dw, B, H, W, tx, ty, dbias, 8);
     else

@@ -205,7 +205,6 @@ __global__ void __launch_bounds__(NTHREADS, 2) conv_igemm_kernel(const ConvParam
     U4Arr<C::WPT> w1, w2;     // slabs g+1 and g+2
     const int cin8 = P.Cin_total / 8;
     const int total_slabs = P.total_chunks * C::STAGES;
-    const int dbg = P.dbg;
     conv_load_w<KS, BN>(w1, ph_weight, cin8, P.Cout, n0, 0, 0, tid);                                   // slab 0
     if (DEEP) conv_load_w<KS, BN>(w2, ph_weight, cin8, P.Cout, n0, 0, (total_slabs > 1) ? 1 : 0, tid);   // slab 1
 
@@ -237,7 +236,7 @@ __global__ void __launch_bounds__(NTHREADS, 2) conv_igemm_kernel(const ConvParam
             int sy = cy, sx = cx;
             if (s_mode == 1) { sy = cy >> 1; sx = cx >> 1; }
             else if (s_mode == 2) { sy = 2 * cy + s_p1; sx = 2 * cx + s_p2; }
-            xreg[i] = (dbg & 1) ? make_uint4(tid, i, 0, 0) : *(const uint4*)(s_base + ((size_t)sy * s_SW + sx) * s_ch);
+            xreg[i] = *(const uint4*)(s_base + ((size_t)sy * s_SW + sx) * s_ch);
         }
         float ps[8], pb[8];
         if (P.in_scale) {
@@ -296,22 +295,15 @@ __global__ void __launch_bounds__(NTHREADS, 2) conv_igemm_kernel(const ConvParam
 #pragma unroll
                 for (int nt = 0; nt < C::NTN; ++nt)
                     wf[nt] = *(const bf16x8*)(wbuf + ((ks * 2 + half) * BN + nt * 32 + l31) * 16);
-                if (!(dbg & 4)) {
-                    // the MFMA issue of this wave goes ahead of the other resident workgroup's staging / epilogue instructions on the
-                    // same SIMD (same-box A/B: <3,128> 12.41 -> 11.82 ms per denoise step, <3,64> 4.13 -> 3.90)
-                    if (!(dbg & 128)) __builtin_amdgcn_s_setprio(2);
+                // the MFMA issue of this wave goes ahead of the other resident workgroup's staging / epilogue instructions on the
+                // same SIMD (same-box A/B: <3,128> 12.41 -> 11.82 ms per denoise step, <3,64> 4.13 -> 3.90)
+                __builtin_amdgcn_s_setprio(2);
 #pragma unroll
-                    for (int nt = 0; nt < C::NTN; ++nt)
+                for (int nt = 0; nt < C::NTN; ++nt)
 #pragma unroll
-                        for (int pt = 0; pt < 2; ++pt)
-                            acc[nt][pt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[nt], xf[pt], acc[nt][pt], 0, 0, 0);
-                    if (!(dbg & 128)) __builtin_amdgcn_s_setprio(0);
-                } else {
-#pragma unroll
-                    for (int nt = 0; nt < C::NTN; ++nt) asm volatile("" ::"v"(wf[nt]));
-#pragma unroll
-                    for (int pt = 0; pt < 2; ++pt) asm volatile("" ::"v"(xf[pt]));
-                }
+                    for (int pt = 0; pt < 2; ++pt)
+                        acc[nt][pt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[nt], xf[pt], acc[nt][pt], 0, 0, 0);
+                __builtin_amdgcn_s_setprio(0);
             }
             // slab g+1 (loaded two stages ago) -> the other LDS buffer (last read in stage g-1, and
             // every wave is past this stage's barrier); then start the load of slab g+3
@@ -340,7 +332,7 @@ __global__ void __launch_bounds__(NTHREADS, 2) conv_igemm_kernel(const ConvParam
 #pragma unroll
     for (int pt = 0; pt < 2; ++pt) {
         const int oy = oy0 + wave * 2 + pt, ox = ox0 + l31;
-        const bool ok = oy < P.H && ox < P.W && !(dbg & 16);
+        const bool ok = oy < P.H && ox < P.W;
         const size_t pix = ((size_t)b * P.H + min(oy, P.H - 1)) * P.W + min(ox, P.W - 1);   // clamped: loads stay in bounds
         // KS == 2: this launch is one phase of an up-sampled 3x3 -> the output pixel is (2y + oy, 2x + ox) of a (2H, 2W) tensor
         const size_t opix = (KS == 2) ? ((size_t)b * (2 * P.H) + 2 * min(oy, P.H - 1) + ph_oy) * (2 * P.W) + 2 * min(ox, P.W - 1) + ph_ox : pix;
@@ -432,7 +424,7 @@ __global__ void __launch_bounds__(NTHREADS, 2) conv_igemm_kernel(const ConvParam
         for (int k = 0; k < UPR; ++k) {
             const int id = lane + k * 64, pl = id / UPR, cu = id % UPR;       // pl: 0..63 = (row pt, column x)
             const int oy = oy0 + wave * 2 + (pl >> 5), ox = ox0 + (pl & 31);
-            const bool ok = oy < P.H && ox < P.W && !(dbg & 16);
+            const bool ok = oy < P.H && ox < P.W;
             const size_t pix = ((size_t)b * P.H + min(oy, P.H - 1)) * P.W + min(ox, P.W - 1);
             const size_t opix = (KS == 2) ? ((size_t)b * (2 * P.H) + 2 * min(oy, P.H - 1) + ph_oy) * (2 * P.W) + 2 * min(ox, P.W - 1) + ph_ox : pix;
             const int c0 = n0 + cu * 8;
@@ -453,566 +445,6 @@ __global__ void __launch_bounds__(NTHREADS, 2) conv_igemm_kernel(const ConvParam
     }
 }
 
-// ================================================================================================
-// Persistent ping-pong variant for the full-resolution workhorse: 3x3, Cin = Cout = 64, one source.
-// The generic kernel above re-streams the 73.7 KB of weights for every 8x32 tile and runs its
-// phases (stage X, 9 weight slabs, epilogue) back to back, which leaves the MFMA pipe idle ~75 %
-// of the time at N = 64.  Here a workgroup of 8 waves stays resident (one per CU):
-//   * all 9 taps of weights live in LDS for the whole launch (loaded once);
-//   * the waves form two groups of 4 that work on neighbouring tiles in opposite phases: while
-//     group A issues the 144 MFMAs per wave of its tile, group B runs its epilogue (bias, bf16
-//     store, GroupNorm partials) and stages its next input tile (prologue affine+SiLU, LDS
-//     write) -- then they swap.  One workgroup barrier per phase;
-//   * the global loads of a group's NEXT input tile are issued at the start of its MFMA phase
-//     and consumed in the following staging phase, so their latency hides behind the MFMAs.
-// LDS: 73,728 B weights + 2 x 43,520 B input tiles = 160,768 B.
-constexpr int PP_THREADS = 512;
-// X tile in LDS is unit-major: [8 channel-octets][341 pixel slots][16 B].  Consecutive pixels of one
-// octet are consecutive 16-B slots (conflict-free ds_read_b128 with no swizzle), taps and k-steps are
-// immediate offsets from ONE base address per output row, and 341 (odd multiple of 4 banks off 32)
-// keeps the 8 octets of a pixel on distinct banks for the staging writes.
-constexpr int PP_US = 341 * 16;   // bytes per octet row
-constexpr int PP_XB = 8 * PP_US, PP_WB = 9 * 8 * 64 * 16, PP_LDS = PP_WB + 2 * PP_XB + 256;
-
-struct PPTile {
-    int b, oy0, ox0, t_in;
-    bool valid;
-};
-
-__device__ __forceinline__ PPTile pp_tile(int t, int ntiles, int tiles_x, int tpi) {
-    PPTile r;
-    r.valid = t < ntiles;
-    t = min(t, ntiles - 1);
-    r.b = t / tpi;
-    r.t_in = t - r.b * tpi;
-    r.oy0 = (r.t_in / tiles_x) * TH;
-    r.ox0 = (r.t_in % tiles_x) * TW;
-    return r;
-}
-
-struct PPX {
-    u32x4 v[11];
-    unsigned okmask;
-};
-
-// staging map: wave w of a group owns the 85 tile pixels [85 w, 85 w + 85) (8 pixels x 8 channel octets per instruction, 11
-// instructions; the surplus 3 re-write the last pixel).  Owning a CONTIGUOUS range is what lets the epilogue borrow exactly
-// the bytes this same wave overwrites next (pp_epilogue).
-constexpr int PP_PPW = 85;
-__device__ __forceinline__ int pp_pixel(int gt, int i) {
-    const int wv = gt >> 6, lane = gt & 63;
-    return wv * PP_PPW + min((lane >> 3) + i * 8, PP_PPW - 1);
-}
-
-__device__ __forceinline__ void pp_load_x(PPX& xr, const ConvParams& P, const PPTile& T, int gt) {
-    const int c8 = gt & 7;
-    const bf16_t* base = P.src[0].ptr + (size_t)T.b * P.H * P.W * P.src[0].src_channels + P.src[0].ch_offset + c8 * 8;
-    unsigned ok_all = 0;
-#pragma unroll
-    for (int i = 0; i < 11; ++i) {
-        const int p = pp_pixel(gt, i);
-        const int ty = p / 34, tx = p - ty * 34;
-        const int iy = T.oy0 - 1 + ty, ix = T.ox0 - 1 + tx;
-        const bool ok = iy >= 0 && iy < P.H && ix >= 0 && ix < P.W;
-        ok_all |= (ok ? 1u : 0u) << i;
-        const int cy = min(max(iy, 0), P.H - 1), cx = min(max(ix, 0), P.W - 1);
-        xr.v[i] = *(const u32x4*)(base + ((size_t)cy * P.W + cx) * P.src[0].src_channels);
-    }
-    xr.okmask = ok_all;
-}
-
-__device__ __forceinline__ void pp_write_x(const PPX& xr, const ConvParams& P, const PPTile& T, unsigned char* xbuf, int gt) {
-    const int c8 = gt & 7;
-    float ps[8], pb[8];
-    if (P.in_scale) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            ps[j] = P.in_scale[(size_t)T.b * 64 + c8 * 8 + j];
-            pb[j] = P.in_shift[(size_t)T.b * 64 + c8 * 8 + j];
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 11; ++i) {
-        const int p = pp_pixel(gt, i);
-        u32x4 v = xr.v[i];
-        if (P.in_scale) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float lo = silu_f(bf2f((bf16_t)(v[j] & 0xffffu)) * ps[2 * j] + pb[2 * j]);
-                const float hi = silu_f(bf2f((bf16_t)(v[j] >> 16)) * ps[2 * j + 1] + pb[2 * j + 1]);
-                v[j] = pack2(lo, hi);
-            }
-        }
-        const bool ok = (xr.okmask >> i) & 1u;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = ok ? v[j] : 0u;
-        *(u32x4*)(xbuf + c8 * PP_US + p * 16) = v;
-    }
-}
-
-__device__ __forceinline__ void pp_mfma(f32x16 (&acc)[2][2], const unsigned char* lds_w, const unsigned char* xbuf, int wv, int l31, int half,
-                                        bool prio) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int k = 0; k < 16; ++k) acc[i][j][k] = 0.0f;
-    // 36 k-steps (9 taps x 4); the operand fragments of step s+1 are read from LDS before the
-    // MFMAs of step s are issued (one wave per SIMD is in its MFMA phase: nobody else hides the
-    // ds_read latency)
-    const unsigned char* xrow = xbuf + half * PP_US + (wv * 2 * 34 + l31) * 16;   // every operand read = base + immediate
-    const unsigned char* wrow = lds_w + (half * 64 + l31) * 16;
-    bf16x8 xf[3][2], wf[3][2];
-    auto read_frags = [&](int step, bf16x8 (&x2)[2], bf16x8 (&w2)[2]) {
-        const int tap = step >> 2, ks = step & 3, ky = tap / 3, kx = tap % 3;
-#pragma unroll
-        for (int pt = 0; pt < 2; ++pt) x2[pt] = *(const bf16x8*)(xrow + ((pt + ky) * 34 + kx) * 16 + ks * 2 * PP_US);
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) w2[nt] = *(const bf16x8*)(wrow + ((tap * 8 + ks * 2) * 64 + nt * 32) * 16);
-    };
-    read_frags(0, xf[0], wf[0]);
-    read_frags(1, xf[1], wf[1]);
-    if (prio) __builtin_amdgcn_s_setprio(2);      // ahead of the other group's VALU phase on the same SIMD
-#pragma unroll
-    for (int step = 0; step < 36; ++step) {
-        if (step + 2 < 36) read_frags(step + 2, xf[(step + 2) % 3], wf[(step + 2) % 3]);
-        __builtin_amdgcn_sched_barrier(0);   // keep the reads two steps ahead of the MFMAs that consume them
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int pt = 0; pt < 2; ++pt)
-                acc[nt][pt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[step % 3][nt], xf[step % 3][pt], acc[nt][pt], 0, 0, 0);
-    }
-    if (prio) __builtin_amdgcn_s_setprio(0);
-}
-
-// Epilogue with 16-byte stores: a lane holds 4 consecutive channels (8 B) per register quad; one
-// v_permlane32_swap per dword between quads g and g+1 gives the lower half-wave 8 consecutive
-// channels of quad g and the upper half-wave those of quad g+1 -> half as many store instructions
-// (the 8-byte form is store-issue bound).
-__device__ __forceinline__ void pp_epilogue(const f32x16 (&acc)[2][2], const ConvParams& P, const PPTile& T, const float* s_bias, int wv, int lane,
-                                            unsigned char* xbuf) {
-    const int l31 = lane & 31, half = lane >> 5;
-    float stat[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) stat[i] = 0.0f;
-    // The stores go through LDS so that they leave fully coalesced (a lane-per-pixel store pattern writes at 2.9 TB/s, consecutive
-    // 16-byte units of a pixel row at 5.3+, tools/probe/store_pattern_probe.hip).  The group's input buffer is dead during its
-    // VALU phase, but there is no group-level barrier: every wave therefore borrows only the bytes IT stages next (its 85-pixel
-    // slice of each of the 8 octet rows, 1360 B each): region row r (144 B: 64 channels + pad) lives in octet row r / 9.
-    unsigned char* const reg0 = xbuf + wv * PP_PPW * 16;
-    auto region = [&](int r) { return reg0 + (r / 9) * PP_US + (r % 9) * 144; };
-#pragma unroll
-    for (int pt = 0; pt < 2; ++pt) {
-        const int oy = T.oy0 + wv * 2 + pt, ox = T.ox0 + l31;
-        const bool ok = oy < P.H && ox < P.W;
-        unsigned char* const rrow = region(pt * 32 + l31);
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) {
-            uint2 q[4];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const float4 bv = *(const float4*)(s_bias + nt * 32 + 8 * g + 4 * half);
-                q[g] = make_uint2(pack2(acc[nt][pt][4 * g] + bv.x, acc[nt][pt][4 * g + 1] + bv.y),
-                                  pack2(acc[nt][pt][4 * g + 2] + bv.z, acc[nt][pt][4 * g + 3] + bv.w));
-                if (P.gn_partial && ok) {
-                    const float q0 = bf2f((bf16_t)(q[g].x & 0xffffu)), q1 = bf2f((bf16_t)(q[g].x >> 16));
-                    const float q2 = bf2f((bf16_t)(q[g].y & 0xffffu)), q3 = bf2f((bf16_t)(q[g].y >> 16));
-                    stat[(nt * 4 + g) * 2] += (q0 + q1) + (q2 + q3);
-                    stat[(nt * 4 + g) * 2 + 1] += (q0 * q0 + q1 * q1) + (q2 * q2 + q3 * q3);
-                }
-            }
-#pragma unroll
-            for (int g = 0; g < 4; g += 2) {
-                const auto rx = __builtin_amdgcn_permlane32_swap(q[g].x, q[g + 1].x, false, false);
-                const auto ry = __builtin_amdgcn_permlane32_swap(q[g].y, q[g + 1].y, false, false);
-                *(uint4*)(rrow + (nt * 32 + 8 * g + 8 * half) * 2) = make_uint4(rx[0], ry[0], rx[1], ry[1]);
-            }
-        }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // this wave's own LDS writes
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {                              // 64 pixels x 8 units: 8 lanes per pixel row, 8 pixels per instruction
-        const int id = lane + k * 64, pl = id >> 3, cu = id & 7;
-        const int oy = T.oy0 + wv * 2 + (pl >> 5), ox = T.ox0 + (pl & 31);
-        const uint4 v = *(const uint4*)(region(pl) + cu * 16);
-        if (oy < P.H && ox < P.W) *(uint4*)(P.out + (((size_t)T.b * P.H + oy) * P.W + ox) * 64 + cu * 8) = v;
-    }
-    if (P.gn_partial) {
-        wave_reduce_multi<16>(stat);
-        if ((lane & 3) == 0) {
-            const int vi = lane >> 2;
-            P.gn_partial[gn_partial_index(T.b, P.tiles_x * P.tiles_y * 4, T.t_in * 4 + wv, 8, vi >> 1) + (vi & 1)] = stat[0];
-        }
-    }
-}
-
-// Phase barrier: only LDS traffic has to be complete (lgkmcnt).  __syncthreads() would also drain
-// vmcnt, i.e. wait for the epilogue's global stores and the in-flight prefetch of the next tile.
-__device__ __forceinline__ void pp_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-
-__global__ void __launch_bounds__(PP_THREADS, 1) conv3x3_c64_pingpong_kernel(const ConvParams P) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char* lds_w = smem;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, half = lane >> 5;
-    const int group = wave >> 2, wv = wave & 3, gt = tid & 255;
-    unsigned char* xbuf = smem + PP_WB + group * PP_XB;
-    const int tpi = P.tiles_x * P.tiles_y, ntiles = tpi * P.B;
-    const int npairs = (ntiles + 1) / 2;
-    const int n_iter = (npairs - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;   // pairs of this workgroup
-
-    // weights: resident for the whole launch
-#pragma unroll
-    for (int i = 0; i < PP_WB / 16 / PP_THREADS; ++i)
-        *(u32x4*)(lds_w + (tid + i * PP_THREADS) * 16) = *(const u32x4*)(P.weight + (size_t)(tid + i * PP_THREADS) * 8);
-
-    float* s_bias = (float*)(smem + PP_WB + 2 * PP_XB);
-    if (tid < 64) s_bias[tid] = P.bias ? P.bias[tid] : 0.0f;
-
-    auto my_tile = [&](int i) { return pp_tile(((int)blockIdx.x + i * (int)gridDim.x) * 2 + group, ntiles, P.tiles_x, tpi); };
-
-    PPX xr;
-    PPTile cur = my_tile(0), prev = cur;
-    pp_load_x(xr, P, cur, gt);
-    pp_write_x(xr, P, cur, xbuf, gt);
-    __syncthreads();
-
-    f32x16 acc[2][2];
-    for (int i = 0; i < n_iter; ++i) {
-        const PPTile nxt = my_tile(i + 1);        // (clamped to a valid tile past the end; never stored)
-        if (group == 0) {
-            if (!(P.dbg & 1)) pp_load_x(xr, P, nxt, gt);
-            if (!(P.dbg & 4)) pp_mfma(acc, lds_w, xbuf, wv, l31, half, !(P.dbg & 256));
-        } else if (i > 0) {
-            if (prev.valid && !(P.dbg & 16)) pp_epilogue(acc, P, prev, s_bias, wv, lane, xbuf);
-            if (!(P.dbg & 32)) pp_write_x(xr, P, cur, xbuf, gt);
-        }
-        pp_barrier();
-        if (group == 0) {
-            if (cur.valid && !(P.dbg & 16)) pp_epilogue(acc, P, cur, s_bias, wv, lane, xbuf);
-            if (!(P.dbg & 32)) pp_write_x(xr, P, nxt, xbuf, gt);
-        } else {
-            if (!(P.dbg & 1)) pp_load_x(xr, P, nxt, gt);
-            if (!(P.dbg & 4)) pp_mfma(acc, lds_w, xbuf, wv, l31, half, !(P.dbg & 256));
-        }
-        pp_barrier();
-        prev = cur;
-        cur = nxt;
-    }
-    if (group == 1 && n_iter > 0 && prev.valid) pp_epilogue(acc, P, prev, s_bias, wv, lane, xbuf);
-}
-
-// ================================================================================================
-// Warp-specialised persistent 3x3 kernel (all 3x3 layers except the 64->64 ping-pong case).
-// Workgroup = 8 waves, one per CU: waves 0-3 are CONSUMERS (ds_read + MFMA + epilogue only), waves
-// 4-7 are PRODUCERS (global loads, GroupNorm-affine+SiLU prologue, LDS writes).  A stage is one
-// kernel row (3 taps) of one K-chunk: 48 MFMAs per consumer wave between two workgroup barriers,
-// while the producers fill the other weight buffer (slab q+1, loaded two stages earlier into
-// registers) and, per chunk, the other input-tile buffer.  Raw s_barrier + lgkmcnt only, so the
-// producers' global loads stay in flight across barriers.  The workgroup walks many tiles
-// (persistent, grid = 256 / n-blocks), so the producers run ahead into the next tile while the
-// consumers are in their epilogue.
-//   BN = 64 : K-chunk 64 channels, input tile 43.6 KB x2, weight slab 24 KB x2  (135 KB LDS)
-//   BN = 128: K-chunk 32 channels, input tile 21.8 KB x2, weight slab 24 KB x2  ( 92 KB LDS)
-template <int BN>
-struct WsCfg {
-    static constexpr int CK = (BN == 64) ? 64 : 32;
-    static constexpr int NC = CK / 8;
-    static constexpr int IW = 34, NPIX = 340, US = 341 * 16;
-    static constexpr int XB = NC * US;
-    static constexpr int WROWS = 3 * NC;
-    static constexpr int WB = WROWS * BN * 16;
-    static constexpr int LDS = 2 * XB + 2 * WB;
-    static constexpr int XPT = (NPIX * NC + 255) / 256;
-    static constexpr int WPT = WROWS * BN / 256;
-    static constexpr int NTN = BN / 32;
-    static constexpr int KSTEPS = CK / 16;
-    static_assert(WROWS * BN % 256 == 0, "weight slab must divide over the producer threads");
-};
-
-template <int BN>
-struct WsX {
-    u32x4 v[WsCfg<BN>::XPT];
-    unsigned okmask;
-};
-
-// producer: global -> registers of K-chunk kc (CK-channel units over the concatenated sources)
-template <int BN>
-__device__ __forceinline__ void ws_load_x(WsX<BN>& xr, const ConvParams& P, const PPTile& T, int kc, int gt) {
-    using C = WsCfg<BN>;
-    constexpr int R = 64 / C::CK;          // chunks of this kernel per 64-channel chunk of the descriptors
-    int si = 0, first = 0;
-    while (si + 1 < P.n_src && kc >= first + P.src[si].chunks * R) {
-        first += P.src[si].chunks * R;
-        ++si;
-    }
-    const int kcl = kc - first;
-    const int s_ch = P.src[si].src_channels, s_SH = P.src[si].SH, s_SW = P.src[si].SW, s_mode = P.src[si].mode;
-    const int c8 = gt % C::NC;
-    const bf16_t* base = P.src[si].ptr + (size_t)T.b * s_SH * s_SW * s_ch + P.src[si].ch_offset + kcl * C::CK + c8 * 8;
-    unsigned ok_all = 0;
-#pragma unroll
-    for (int i = 0; i < C::XPT; ++i) {
-        const int p = min(gt / C::NC + i * (256 / C::NC), C::NPIX - 1);
-        const int ty = p / C::IW, tx = p - ty * C::IW;
-        const int iy = T.oy0 - 1 + ty, ix = T.ox0 - 1 + tx;
-        const bool ok = iy >= 0 && iy < P.H && ix >= 0 && ix < P.W;
-        ok_all |= (ok ? 1u : 0u) << i;
-        const int cy = min(max(iy, 0), P.H - 1), cx = min(max(ix, 0), P.W - 1);
-        int sy = cy, sx = cx;
-        if (s_mode == 1) { sy = cy >> 1; sx = cx >> 1; }
-        else if (s_mode == 2) { sy = 2 * cy + P.src[si].p1; sx = 2 * cx + P.src[si].p2; }
-        xr.v[i] = *(const u32x4*)(base + ((size_t)sy * s_SW + sx) * s_ch);
-    }
-    xr.okmask = ok_all;
-}
-
-template <int BN>
-__device__ __forceinline__ void ws_write_x(const WsX<BN>& xr, const ConvParams& P, const PPTile& T, int kc, unsigned char* xbuf, int gt) {
-    using C = WsCfg<BN>;
-    const int c8 = gt % C::NC;
-    float ps[8], pb[8];
-    if (P.in_scale) {
-        const int cg = kc * C::CK + c8 * 8;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            ps[j] = P.in_scale[(size_t)T.b * P.Cin_total + cg + j];
-            pb[j] = P.in_shift[(size_t)T.b * P.Cin_total + cg + j];
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < C::XPT; ++i) {
-        const int p = min(gt / C::NC + i * (256 / C::NC), C::NPIX - 1);
-        u32x4 v = xr.v[i];
-        if (P.in_scale) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float lo = silu_f(bf2f((bf16_t)(v[j] & 0xffffu)) * ps[2 * j] + pb[2 * j]);
-                const float hi = silu_f(bf2f((bf16_t)(v[j] >> 16)) * ps[2 * j + 1] + pb[2 * j + 1]);
-                v[j] = pack2(lo, hi);
-            }
-        }
-        const bool ok = (xr.okmask >> i) & 1u;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = ok ? v[j] : 0u;
-        *(u32x4*)(xbuf + c8 * C::US + p * 16) = v;
-    }
-}
-
-// weight slab of (chunk kc, kernel row ky): rows r = kx * NC + c8
-template <int BN>
-__device__ __forceinline__ void ws_load_w(U4Arr<WsCfg<BN>::WPT>& w, const ConvParams& P, int n0, int kc, int ky, int gt) {
-    using C = WsCfg<BN>;
-    const int cin8 = P.Cin_total / 8;
-#pragma unroll
-    for (int i = 0; i < C::WPT; ++i) {
-        const int u = gt + i * 256;
-        const int r = u / BN, n = u % BN;
-        const size_t row = (size_t)(ky * 3 + r / C::NC) * cin8 + kc * C::NC + r % C::NC;
-        w.v[i] = *(const u32x4*)(P.weight + (row * P.Cout + n0 + n) * 8);
-    }
-}
-template <int BN>
-__device__ __forceinline__ void ws_store_w(const U4Arr<WsCfg<BN>::WPT>& w, unsigned char* wbuf, int gt) {
-#pragma unroll
-    for (int i = 0; i < WsCfg<BN>::WPT; ++i) *(u32x4*)(wbuf + (gt + i * 256) * 16) = w.v[i];
-}
-
-// consumer: one stage = 3 taps x KSTEPS k-steps, operand reads one k-step ahead of the MFMAs
-template <int BN>
-__device__ __forceinline__ void ws_compute(f32x16 (&acc)[WsCfg<BN>::NTN][2], const unsigned char* wbuf, const unsigned char* xbuf, int ky,
-                                           int wv, int l31, int half) {
-    using C = WsCfg<BN>;
-    constexpr int NS = 3 * C::KSTEPS;
-    const unsigned char* xrow = xbuf + half * C::US + ((wv * 2 + ky) * C::IW + l31) * 16;
-    const unsigned char* wrow = wbuf + (half * BN + l31) * 16;
-    bf16x8 xf[2][2], wf[2][C::NTN];
-    auto read_frags = [&](int step, bf16x8 (&x2)[2], bf16x8 (&w2)[C::NTN]) {
-        const int kx = step / C::KSTEPS, ks = step % C::KSTEPS;
-#pragma unroll
-        for (int pt = 0; pt < 2; ++pt) x2[pt] = *(const bf16x8*)(xrow + (pt * C::IW + kx) * 16 + ks * 2 * C::US);
-#pragma unroll
-        for (int nt = 0; nt < C::NTN; ++nt) w2[nt] = *(const bf16x8*)(wrow + ((kx * C::NC + ks * 2) * BN + nt * 32) * 16);
-    };
-    read_frags(0, xf[0], wf[0]);
-#pragma unroll
-    for (int step = 0; step < NS; ++step) {
-        if (step + 1 < NS) read_frags(step + 1, xf[(step + 1) & 1], wf[(step + 1) & 1]);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int nt = 0; nt < C::NTN; ++nt)
-#pragma unroll
-            for (int pt = 0; pt < 2; ++pt)
-                acc[nt][pt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[step & 1][nt], xf[step & 1][pt], acc[nt][pt], 0, 0, 0);
-    }
-}
-
-// shared epilogue of a 4-wave x (2 rows x 32 px) x BN tile: bias, residual forms, bf16 16-byte
-// stores through v_permlane32_swap, per-wave GroupNorm partial sums
-template <int BN>
-__device__ __forceinline__ void conv_tile_epilogue(const f32x16 (&acc)[BN / 32][2], const ConvParams& P, const PPTile& T, int n0, int wv, int lane) {
-    constexpr int NTN = BN / 32, NV = (BN / 8) * 2;
-    const int l31 = lane & 31, half = lane >> 5;
-    float stat[NV];
-#pragma unroll
-    for (int i = 0; i < NV; ++i) stat[i] = 0.0f;
-#pragma unroll
-    for (int pt = 0; pt < 2; ++pt) {
-        const int oy = T.oy0 + wv * 2 + pt, ox = T.ox0 + l31;
-        const bool ok = oy < P.H && ox < P.W;
-        const size_t pix = ((size_t)T.b * P.H + min(oy, P.H - 1)) * P.W + min(ox, P.W - 1);
-#pragma unroll
-        for (int nt = 0; nt < NTN; ++nt) {
-            uint2 q[4];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int c = n0 + nt * 32 + 8 * g + 4 * half;
-                float v[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = acc[nt][pt][4 * g + j];
-                if (P.bias) {
-                    const float4 bv = *(const float4*)(P.bias + c);
-                    v[0] += bv.x; v[1] += bv.y; v[2] += bv.z; v[3] += bv.w;
-                }
-                if (P.res_act) {
-                    const uint2 r = *(const uint2*)(P.res_act + pix * P.Cout + c);
-                    const float4 sc = *(const float4*)(P.res_scale + (size_t)T.b * P.Cout + c);
-                    const float4 sh = *(const float4*)(P.res_shift + (size_t)T.b * P.Cout + c);
-                    v[0] += silu_f(bf2f((bf16_t)(r.x & 0xffffu)) * sc.x + sh.x);
-                    v[1] += silu_f(bf2f((bf16_t)(r.x >> 16)) * sc.y + sh.y);
-                    v[2] += silu_f(bf2f((bf16_t)(r.y & 0xffffu)) * sc.z + sh.z);
-                    v[3] += silu_f(bf2f((bf16_t)(r.y >> 16)) * sc.w + sh.w);
-                }
-                if (P.residual) {
-                    const uint2 r = *(const uint2*)(P.residual + pix * P.Cout + c);
-                    v[0] += bf2f((bf16_t)(r.x & 0xffffu));
-                    v[1] += bf2f((bf16_t)(r.x >> 16));
-                    v[2] += bf2f((bf16_t)(r.y & 0xffffu));
-                    v[3] += bf2f((bf16_t)(r.y >> 16));
-                }
-                q[g] = make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
-                if (P.gn_partial && ok) {
-                    const float q0 = bf2f((bf16_t)(q[g].x & 0xffffu)), q1 = bf2f((bf16_t)(q[g].x >> 16));
-                    const float q2 = bf2f((bf16_t)(q[g].y & 0xffffu)), q3 = bf2f((bf16_t)(q[g].y >> 16));
-                    stat[(nt * 4 + g) * 2] += (q0 + q1) + (q2 + q3);
-                    stat[(nt * 4 + g) * 2 + 1] += (q0 * q0 + q1 * q1) + (q2 * q2 + q3 * q3);
-                }
-            }
-#pragma unroll
-            for (int g = 0; g < 4; g += 2) {
-                const auto rx = __builtin_amdgcn_permlane32_swap(q[g].x, q[g + 1].x, false, false);
-                const auto ry = __builtin_amdgcn_permlane32_swap(q[g].y, q[g + 1].y, false, false);
-                if (ok) *(uint4*)(P.out + pix * P.Cout + n0 + nt * 32 + 8 * g + 8 * half) = make_uint4(rx[0], ry[0], rx[1], ry[1]);
-            }
-        }
-    }
-    if (P.gn_partial) {
-        wave_reduce_multi<NV>(stat);
-        constexpr int SH_ = (NV == 32) ? 1 : 2;
-        if ((lane & ((1 << SH_) - 1)) == 0) {
-            const int vi = lane >> SH_;
-            P.gn_partial[gn_partial_index(T.b, P.tiles_x * P.tiles_y * 4, T.t_in * 4 + wv, P.Cout / 8, n0 / 8 + (vi >> 1)) + (vi & 1)] = stat[0];
-        }
-    }
-}
-
-template <int BN>
-__global__ void __launch_bounds__(512, 1) conv3x3_ws_kernel(const ConvParams P) {
-    using C = WsCfg<BN>;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char* xb = smem;                  // [2][XB]
-    unsigned char* wb = smem + 2 * C::XB;      // [2][WB]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, half = lane >> 5;
-    const int role = wave >> 2, wv = wave & 3, gt = tid & 255;
-    const int tpi = P.tiles_x * P.tiles_y, ntiles = tpi * P.B;
-    const int n0 = blockIdx.y * BN;
-    const int n_my = (ntiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
-    const int nchunks = P.total_chunks * (64 / C::CK);
-    const int S = nchunks * 3, Q = n_my * S, CT = n_my * nchunks;     // steps per tile, total steps, total chunks
-    auto tile_at = [&](int i) { return pp_tile((int)blockIdx.x + i * (int)gridDim.x, ntiles, P.tiles_x, tpi); };
-
-    if (role == 1) {
-        // ------------------------------------------------------------------ producers
-        WsX<BN> xr;
-        U4Arr<C::WPT> w1, w2;
-        {
-            const PPTile T0 = tile_at(0);
-            ws_load_x<BN>(xr, P, T0, 0, gt);
-            ws_load_w<BN>(w1, P, n0, 0, 0, gt);
-            ws_write_x<BN>(xr, P, T0, 0, xb, gt);
-            ws_store_w<BN>(w1, wb, gt);
-            const int g1 = (Q > 1) ? 1 : 0, g2 = (Q > 2) ? 2 : 0;
-            ws_load_w<BN>(w1, P, n0, (g1 % S) / 3, g1 % 3, gt);
-            ws_load_w<BN>(w2, P, n0, (g2 % S) / 3, g2 % 3, gt);
-        }
-        pp_barrier();
-        int q = 0, c = 0;
-        for (int i = 0; i < n_my; ++i) {
-            for (int kc = 0; kc < nchunks; ++kc, ++c) {
-                const bool has_next = (c + 1 < CT);
-                const int cn = c + 1, in_ = cn / nchunks, kcn = cn - in_ * nchunks;   // next chunk: tile index, local chunk
-                const PPTile Tn = tile_at(has_next ? in_ : i);
-#pragma unroll
-                for (int ky = 0; ky < 3; ++ky, ++q) {
-                    if (q + 1 < Q) ws_store_w<BN>(w1, wb + ((q + 1) & 1) * C::WB, gt);   // slab q+1, loaded two stages ago
-                    w1 = w2;
-                    if (q + 3 < Q) {
-                        const int g = (q + 3) % S;
-                        ws_load_w<BN>(w2, P, n0, g / 3, g % 3, gt);
-                    }
-                    if (ky == 0 && has_next) ws_load_x<BN>(xr, P, Tn, kcn, gt);
-                    if (ky == 2 && has_next) ws_write_x<BN>(xr, P, Tn, kcn, xb + (cn & 1) * C::XB, gt);
-                    pp_barrier();
-                }
-            }
-        }
-    } else {
-        // ------------------------------------------------------------------ consumers
-        pp_barrier();
-        f32x16 acc[C::NTN][2];
-        int q = 0, c = 0;
-        for (int i = 0; i < n_my; ++i) {
-#pragma unroll
-            for (int a = 0; a < C::NTN; ++a)
-#pragma unroll
-                for (int b2 = 0; b2 < 2; ++b2)
-#pragma unroll
-                    for (int k = 0; k < 16; ++k) acc[a][b2][k] = 0.0f;
-            for (int kc = 0; kc < nchunks; ++kc, ++c) {
-                const unsigned char* xbuf = xb + (c & 1) * C::XB;
-#pragma unroll
-                for (int ky = 0; ky < 3; ++ky, ++q) {
-                    ws_compute<BN>(acc, wb + (q & 1) * C::WB, xbuf, ky, wv, l31, half);
-                    pp_barrier();
-                }
-            }
-            const PPTile T = tile_at(i);
-            if (T.valid) conv_tile_epilogue<BN>(acc, P, T, n0, wv, lane);
-        }
-    }
-}
-
-template <int BN>
-static int launch_conv_ws(const ConvParams& P, hipStream_t s) {
-    using C = WsCfg<BN>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        OFD_HIP(hipFuncSetAttribute((const void*)conv3x3_ws_kernel<BN>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS));
-        attr_set = true;
-    }
-    const int ntiles = P.tiles_x * P.tiles_y * P.B, nb = P.Cout / BN;
-    int gx = 256 / nb;
-    if (gx < 1) gx = 1;
-    if (gx > ntiles) gx = ntiles;
-    conv3x3_ws_kernel<BN><<<dim3(gx, nb), 512, C::LDS, s>>>(P);
-    OFD_LAUNCH_CHECK();
-    return OFD_OK;
-}
 
 // ---- weight preparation: OIHW fp32 -> [tap][Cin_pad/8][Cout][8] bf16 (+ weight standardisation)
 __device__ __forceinline__ void conv_weight_prep_body(const float* __restrict__ w, bf16_t* __restrict__ out, int Cout, int Cin, int Cin_pad,
@@ -1111,42 +543,32 @@ static int launch_conv(const ConvParams& P, hipStream_t s) {
     return OFD_OK;
 }
 
-int launch_conv3x3_c64_rw(const ConvParams& P, hipStream_t s);     // conv_rw.hip
 int launch_conv3x3_wp(const ConvParams& P, bool wide, hipStream_t s);   // conv_wp.hip
 int launch_conv1x1_wp(const ConvParams& P, hipStream_t s);              // conv1_wp.hip: 1 = shape not served
 int launch_conv_up2_phases_wp(const ConvParams& P, hipStream_t s);      // conv_wp.hip: 1 = shape not served
 int launch_conv7x7_c8_persist(const ConvParams& P, hipStream_t s);      // conv7.hip: 1 = shape not served
 
-static int conv_wp_bits() {
-    static int use_wp = -1;
-    if (use_wp < 0) { const char* e = getenv("OFD_CONV_WP"); use_wp = e ? atoi(e) : 7; }
-    return use_wp;
-}
 // the pooled epilogue exists in conv_wp.hip only: 3x3, even size, one output tensor, no fused GroupNorm statistics / activation residual
 bool conv_pool2_supported(const ofd_conv_args* a) {
-    static const bool off = getenv("OFD_NO_DGRAD_POOL") && atoi(getenv("OFD_NO_DGRAD_POOL"));
-    if (off || !a || a->ksize != 3 || a->H % 2 || a->W % 2 || a->split || a->gn_partial || a->res_act || a->Cout % 64) return false;
+    if (!a || a->ksize != 3 || a->H % 2 || a->W % 2 || a->split || a->gn_partial || a->res_act || a->Cout % 64) return false;
     int cin = 0;
     for (int i = 0; i < a->n_src; ++i) { if (a->src[i].unshuffle) return false; cin += a->src[i].channels; }
-    const bool c64 = a->Cout == 64 && cin == 64;
-    return !c64 && (conv_wp_bits() & 3) == 3;
+    return !(a->Cout == 64 && cin == 64);
 }
 
 // final 1x1 conv fused into the final res_conv (conv1_wp.hip, FC instantiation): 128 -> 64, fused h2 input, whole 128-pixel tiles, out_dim 2
 bool conv_fc_fuse_supported(const ofd_conv_args* a, int out_dim) {
-    static const bool off = (getenv("OFD_NO_FC_FUSE") && atoi(getenv("OFD_NO_FC_FUSE"))) || (getenv("OFD_CONV1_WP") && atoi(getenv("OFD_CONV1_WP")) == 0);
-    if (off || !a || out_dim != 2 || a->ksize != 1 || a->Cout != 64 || !a->res_act || a->residual || a->gn_partial || a->split || a->in_scale) return false;
+    if (!a || out_dim != 2 || a->ksize != 1 || a->Cout != 64 || !a->res_act || a->residual || a->gn_partial || a->split || a->in_scale) return false;
     int cin = 0;
     for (int i = 0; i < a->n_src; ++i) { if (a->src[i].upsample || a->src[i].unshuffle || a->src[i].channels % 64) return false; cin += a->src[i].channels; }
     return cin == 128 && ((long)a->H * a->W) % 128 == 0;
 }
 
 bool conv_residual_b_supported(const ofd_conv_args* a) {
-    static const bool off = getenv("OFD_NO_RESIDUAL_B") && atoi(getenv("OFD_NO_RESIDUAL_B"));
-    if (off || !a || a->ksize != 3 || a->split || a->Cout % 64) return false;
+    if (!a || a->ksize != 3 || a->split || a->Cout % 64) return false;
     for (int i = 0; i < a->n_src; ++i)
         if (a->src[i].unshuffle) return false;
-    return (conv_wp_bits() & 7) == 7 || ((conv_wp_bits() & 3) == 3 && a->residual);      // (with a residual the 64 -> 64 case is conv_wp's too)
+    return true;
 }
 
 int conv_forward_impl(const ofd_conv_args* a, hipStream_t s, int cout0, int pool2, const bf16_t* residual_b, const FcFuse* fc) {
@@ -1204,63 +626,29 @@ int conv_forward_impl(const ofd_conv_args* a, hipStream_t s, int cout0, int pool
     OFD_CHECK_ARG(!fc || conv_fc_fuse_supported(a, 2), "conv: the fused final conv serves the 128 -> 64 streaming 1x1 with a SiLU(GN(h2)) input only");
     OFD_CHECK_ARG(!residual_b || conv_residual_b_supported(a), "conv: a second residual is served by the conv_wp 3x3 kernels only");
     OFD_CHECK_ARG(!pool2 || conv_pool2_supported(a), "conv: the 2x2-pooled epilogue does not serve this configuration");
-    { static int dbg_env = -1; if (dbg_env < 0) { const char* e = getenv("OFD_CONV_DBG"); dbg_env = e ? atoi(e) : 0; } P.dbg = dbg_env; }
     // 128 output channels per workgroup unless that leaves CUs without work: small images (the reference's default 128 x 128 reaches
     // 16 x 16 at the coarsest level: 32 pixel tiles x 4 channel blocks for 256 CUs) take the 64-channel instantiation: twice the
     // workgroups
-    static const int small_grid = getenv("OFD_CONV_SMALL_GRID") ? atoi(getenv("OFD_CONV_SMALL_GRID")) : 256;
-    const bool wide = (a->Cout % 128 == 0) && (long)P.tiles_x * P.tiles_y * P.B * (a->Cout / 128) >= small_grid;
-    // wave-private-weights kernel (conv_wp.hip): OFD_CONV_WP bit 0 = the 128-channel-block layers, bit 1 = the 64-channel-block
-    // layers other than 64 -> 64, bit 2 = 64 -> 64 (instead of the ping-pong kernel)
-    static int use_wp = -1;
-    if (use_wp < 0) { const char* e = getenv("OFD_CONV_WP"); use_wp = e ? atoi(e) : 7; }
-    if (a->ksize == 3 && use_wp) {
+    const bool wide = (a->Cout % 128 == 0) && (long)P.tiles_x * P.tiles_y * P.B * (a->Cout / 128) >= 256;
+    if (a->ksize == 3) {
+        // wave-private-weights kernels (conv_wp.hip) for same-size and up-sampled sources; the shared-slab kernel for unshuffled ones
         bool modes_ok = true;
         for (int i = 0; i < a->n_src; ++i) modes_ok = modes_ok && P.src[i].mode != 2;
-        const bool c64 = a->Cout == 64 && P.Cin_total == 64 && a->n_src == 1 && P.src[0].mode == 0 && !a->residual && !a->res_act;
-        const int bit = wide ? 1 : (c64 ? 4 : 2);
-        if (modes_ok && (use_wp & bit)) return launch_conv3x3_wp(P, wide, s);
+        if (modes_ok) return launch_conv3x3_wp(P, wide, s);
+        return wide ? launch_conv<3, 128>(P, s) : launch_conv<3, 64>(P, s);
     }
-    static int no_pp = -1;
-    if (no_pp < 0) { const char* e = getenv("OFD_NO_PINGPONG"); no_pp = (e && atoi(e)) ? 1 : 0; }
-    static int use_rw = -1;
-    if (use_rw < 0) { const char* e = getenv("OFD_CONV_RW"); use_rw = e ? atoi(e) : 0; }      // register-window variant: opt-in (conv_rw.hip)
-    if (a->ksize == 3 && a->Cout == 64 && P.Cin_total == 64 && a->n_src == 1 && P.src[0].mode == 0 && !a->residual && !a->res_act && use_rw && !a->split)
-        return launch_conv3x3_c64_rw(P, s);
-    if (a->ksize == 3 && a->Cout == 64 && P.Cin_total == 64 && a->n_src == 1 && P.src[0].mode == 0 && !a->residual && !a->res_act && !no_pp) {
-        static bool attr_set = false;
-        if (!attr_set) {
-            OFD_HIP(hipFuncSetAttribute((const void*)conv3x3_c64_pingpong_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS));
-            attr_set = true;
-        }
-        const int ntiles = P.tiles_x * P.tiles_y * P.B, npairs = (ntiles + 1) / 2;
-        static int pp_grid = -1;
-        if (pp_grid < 0) { const char* e = getenv("OFD_PP_GRID"); pp_grid = e ? atoi(e) : 256; }
-        conv3x3_c64_pingpong_kernel<<<npairs < pp_grid ? npairs : pp_grid, PP_THREADS, PP_LDS, s>>>(P);
-        OFD_LAUNCH_CHECK();
-        return OFD_OK;
-    }
-    // warp-specialised variant: measured equal-to-slightly-slower than the generic kernel this round
-    // (DESIGN.md section 4), so it is opt-in for A/B runs: OFD_CONV_WS=1
-    static int use_ws = -1;
-    if (use_ws < 0) { const char* e = getenv("OFD_CONV_WS"); use_ws = (e && atoi(e)) ? 1 : 0; }
-    if (a->ksize == 3 && use_ws && !a->split) return wide ? launch_conv_ws<128>(P, s) : launch_conv_ws<64>(P, s);
-    if (a->ksize == 3) return wide ? launch_conv<3, 128>(P, s) : launch_conv<3, 64>(P, s);
-    // streaming 1x1 kernel (conv1_wp.hip) where it serves the shape: OFD_CONV1_WP=0 switches it off
-    static int use_c1 = -1;
-    if (use_c1 < 0) { const char* e = getenv("OFD_CONV1_WP"); use_c1 = e ? atoi(e) : 1; }
-    if (a->ksize == 1 && use_c1 && !P.dbg) {
+    if (a->ksize == 1) {                                 // streaming 1x1 kernel (conv1_wp.hip) where it serves the shape
         const int r = launch_conv1x1_wp(P, s);
         if (r != 1) return r;
     }
     OFD_CHECK_ARG(!P.fc_out, "conv: the fused final conv was requested for a shape the streaming 1x1 kernel does not serve");
     if (a->ksize == 1) return wide ? launch_conv<1, 128>(P, s) : launch_conv<1, 64>(P, s);
-    if (a->ksize == 2 && P.phase_all && !P.dbg) {        // the four phases as four wave pairs of one workgroup (conv_wp.hip): OFD_PHASE_WP=0 switches it off
+    if (a->ksize == 2 && P.phase_all) {                  // the four phases as four wave pairs of one workgroup (conv_wp.hip)
         const int r = launch_conv_up2_phases_wp(P, s);
         if (r != 1) return r;
     }
     if (a->ksize == 2) return wide ? launch_conv<2, 128>(P, s) : launch_conv<2, 64>(P, s);
-    if (k7p) {                                           // weights resident in LDS, a workgroup walks many tiles (conv7.hip): OFD_CONV7_PERSIST=0 switches it off
+    if (k7p) {                                           // weights resident in LDS, a workgroup walks many tiles (conv7.hip)
         const int r = launch_conv7x7_c8_persist(P, s);
         if (r != 1) return r;
     }

@@ -37,7 +37,7 @@ struct ConvParams {
     int phase_all;      // KS == 2: one launch computes the four phases; block j -> XCD j % 8, phase (j / 8) % 4, tile slot j / 32 (the phases of a
                         // tile run on one XCD at the same time: its input tile comes from that L2 three times out of four)
     int cout0;          // 1x1 streaming kernel: output channels below cout0 are not computed (training to_qkv with q recomputed downstream); 0 = all
-    int cy_fast;        // conv_wp: 1-D grid, the channel blocks of a pixel tile adjacent in dispatch order and on one XCD (A/B switch)
+    int cy_fast;        // conv_wp: 1-D grid, the channel blocks of a pixel tile adjacent in dispatch order and on one XCD
     const bf16_t* residual_b;   // conv_wp 3x3: a second plain residual (same shape as `residual`; training: gradient already in the buffer + the identity-residual gradient)
     int pool2;          // conv_wp 3x3: the epilogue sums every 2x2 block of output pixels and writes the (H/2, W/2) tensor (+ residual there): the
                         // data gradient of Upsample(x2, nearest) + conv lands in the low-resolution source's gradient without a full-size tensor
@@ -47,7 +47,6 @@ struct ConvParams {
     const float* fc_w;  // [2][Cout]
     const float* fc_b;  // [2]
     float* fc_out;
-    int dbg;            // diagnostic ablation bits (OFD_CONV_DBG), 0 in production
 };
 
 // GroupNorm partial sums written by the conv epilogues and added up by gn_finalize (blocks.hip), GROUP-major:

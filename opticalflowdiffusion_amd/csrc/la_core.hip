@@ -36,7 +36,6 @@ __device__ __forceinline__ bf16x8 lc_frag(const float* f) {
     return r;
 }
 
-constexpr int FC_CH = 96;             // forward pass 1 chunk (two 24 KB tiles + scan scratch within the 64 KB static LDS)
 // 32 channels of one head for this lane's pixel: accumulator register 4g+j holds channel 8g + 4*half + j.  One
 // v_permlane32_swap per dword pairs the half-waves so that every lane stores 16 bytes (8 consecutive channels):
 // half as many store instructions, 32 contiguous bytes per pixel and instruction.  All lanes must call it.
@@ -64,85 +63,6 @@ __device__ __forceinline__ void lc_load_head(const bf16_t* src, int half, float 
             f[4 * g + 2 * j + 1] = bf2f((bf16_t)(w4[j] >> 16));
         }
     }
-}
-
-// ---- forward pass 1: partial {m[32], l[32], ctx[32][32]} per (sample*head, part); grid (nparts, B) ----
-// workgroup = 4 waves = 4 heads; online max over chunks of 96 pixels (accumulators rescaled per row d)
-__global__ void __launch_bounds__(256) lc_ctx_partial_kernel(const bf16_t* __restrict__ qkv, float* __restrict__ partial, int n, int span, int nparts) {
-    __shared__ __attribute__((aligned(16))) unsigned char ks[FC_CH * 256];     // [pixel][128 k channels] bf16 (raw, then exp(k - m))
-    __shared__ __attribute__((aligned(16))) unsigned char vs[FC_CH * 256];     // [pixel][128 v channels]
-    __shared__ float mx2[2][128], m_s[128], f_s[128], l2[2][128];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, half = lane >> 5;
-    const int part = blockIdx.x, b = blockIdx.y;
-    const int n_begin = part * span, n_end = min(n, n_begin + span);
-    const int ch = tid & 127, ph = tid >> 7;           // channel scans: thread -> (channel, pixel parity half)
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-    float l_run = 0.0f;                                // threads < 128: running sum of channel tid
-    if (tid < 128) m_s[tid] = -3.0e38f;
-    for (int c0 = n_begin; c0 < n_end; c0 += FC_CH) {
-        const int cnt = min(FC_CH, n_end - c0);
-        __syncthreads();
-        // stage k and v: 128 px x (16 + 16) 16-byte units; pixels past the end: k = -inf-like, v = 0
-#pragma unroll
-        for (int i = 0; i < FC_CH / 8; ++i) {
-            const int id = tid + i * 256, p = id >> 5, u = id & 31;
-            const bool ok = p < cnt;
-            const bf16_t* row = qkv + ((size_t)b * n + c0 + min(p, cnt - 1)) * 384 + 128;
-            u32x4 v = *(const u32x4*)(row + u * 8);
-            if (!ok) {
-                const unsigned fill = (u < 16) ? 0xff7fff7fu : 0u;      // bf16 -3.4e38 | 0
-#pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = fill;
-            }
-            if (u < 16) *(u32x4*)(ks + p * 256 + u * 16) = v;
-            else *(u32x4*)(vs + p * 256 + (u - 16) * 16) = v;
-        }
-        __syncthreads();
-        {   // chunk max per channel
-            float mx = -3.0e38f;
-            for (int p = ph; p < FC_CH; p += 2) mx = fmaxf(mx, bf2f(*(const bf16_t*)(ks + p * 256 + ch * 2)));
-            mx2[ph][ch] = mx;
-        }
-        __syncthreads();
-        if (tid < 128) {
-            const float m_old = m_s[tid], m_new = fmaxf(m_old, fmaxf(mx2[0][tid], mx2[1][tid]));
-            f_s[tid] = __expf(m_old - m_new);
-            m_s[tid] = m_new;
-        }
-        __syncthreads();
-        {   // exponentiate in place (bf16), row sums of the values as the MFMA will see them
-            const float m = m_s[ch];
-            float sum = 0.0f;
-            for (int p = ph; p < FC_CH; p += 2) {
-                bf16_t* a = (bf16_t*)(ks + p * 256 + ch * 2);
-                const bf16_t e = f2bf(__expf(bf2f(*a) - m));
-                *a = e;
-                sum += bf2f(e);
-            }
-            l2[ph][ch] = sum;
-        }
-        __syncthreads();
-        if (tid < 128) l_run = l_run * f_s[tid] + l2[0][tid] + l2[1][tid];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] *= f_s[wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * half];
-#pragma unroll
-        for (int sl = 0; sl < FC_CH / 16; ++sl) {
-            const bf16x8 kf = tr_frag(ks + sl * 16 * 256 + wave * 64, 256, lane);      // rows = d
-            const bf16x8 vf = tr_frag(vs + sl * 16 * 256 + wave * 64, 256, lane);      // cols = e
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, vf, acc, 0, 0, 0);
-        }
-    }
-    __syncthreads();
-    float* o = partial + ((size_t)(b * 4 + wave) * nparts + part) * 1088;
-    if (tid < 128) {
-        float* oh = partial + ((size_t)(b * 4 + (tid >> 5)) * nparts + part) * 1088;
-        oh[tid & 31] = m_s[tid];
-        oh[32 + (tid & 31)] = l_run;
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[64 + ((r & 3) + 8 * (r >> 2) + 4 * half) * 32 + l31] = acc[r];
 }
 
 // context-shaped matrices of one sample as bf16 A operands in LDS: [4 heads][32 rows][40] (80-byte rows)
@@ -758,12 +678,8 @@ int launch_la_ctx_stored(const bf16_t* qkv, float* partial, int B, int n, hipStr
 
 int k_linear_attention_core(const bf16_t* qkv, float* partial, float* ctx, bf16_t* out, int B, int n, hipStream_t s, float* ml_out,
                             const bf16_t* wo, const float* bo, bf16_t* o2, int C, const bf16_t* xn, const bf16_t* wq) {
-    int nparts, span;
-    lc_parts(B, n, nparts, span);
-    // pass 1: the accumulator-layout kernel on the stored k, v (la_fused.hip la_ctx_stored_kernel); OFD_LA_CTX_STORED=0: the LDS-scan kernel above
-    static const int stored = getenv("OFD_LA_CTX_STORED") ? atoi(getenv("OFD_LA_CTX_STORED")) : 1;
-    if (stored) nparts = launch_la_ctx_stored(qkv, partial, B, n, s);
-    else lc_ctx_partial_kernel<<<dim3(nparts, B), 256, 0, s>>>(qkv, partial, n, span, nparts);
+    // pass 1: the accumulator-layout kernel on the stored k, v (la_fused.hip la_ctx_stored_kernel)
+    const int nparts = launch_la_ctx_stored(qkv, partial, B, n, s);
     launch_la_ctx_combine(partial, ctx, B, nparts, 1.0f / (float)n, ml_out, s);
     int gx = cdiv(n, 32);
     if (gx > 2048) gx = 2048;

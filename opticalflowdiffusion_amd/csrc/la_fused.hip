@@ -47,45 +47,11 @@ __device__ __forceinline__ void load_raw_x(const bf16_t* __restrict__ xrow, XRaw
 // raw tile -> normalised (no gain) bf16 fragments (LayerNorm over channels, DD:121-125).  r03: the two sums run on the PACKED words
 // (v_dot2_f32_bf16: x . (1, 1) and x . x, two channels per instruction, fp32 accumulate) and the variance is E[x^2] - mean^2 -- the
 // inputs are bf16 activations, |mean| / std stays far below the 2^12 at which fp32 cancellation would reach bf16 resolution -- so an
-// element costs unpack + one fma + convert instead of unpack + add + subtract + fma + multiply + convert (OFD_LA_TWO_PASS_LN=1 at
-// build time restores the centred form).
-#ifndef OFD_LA_TWO_PASS_LN
-#define OFD_LA_TWO_PASS_LN 0
-#endif
+// element costs unpack + one fma + convert instead of unpack + add + subtract + fma + multiply + convert.
 typedef __bf16 la_bf16x2 __attribute__((ext_vector_type(2)));
 template <int C>
 __device__ __forceinline__ void norm_x(const XRaw<C>& r, float eps, bf16x8 (&xs)[C / 16]) {
     constexpr int KS = C / 16;
-#if OFD_LA_TWO_PASS_LN
-    float v[KS][8];
-    float sum = 0.0f;
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint32_t w = r.v[s][j];
-            v[s][2 * j] = bf2f((bf16_t)(w & 0xffffu));
-            v[s][2 * j + 1] = bf2f((bf16_t)(w >> 16));
-            sum += v[s][2 * j] + v[s][2 * j + 1];
-        }
-    }
-    sum += __shfl_xor(sum, 32, 64);
-    const float mean = sum * (1.0f / C);
-    float q = 0.0f;
-#pragma unroll
-    for (int s = 0; s < KS; ++s)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            v[s][j] -= mean;
-            q += v[s][j] * v[s][j];
-        }
-    q += __shfl_xor(q, 32, 64);
-    const float rstd = rsqrtf(q * (1.0f / C) + eps);
-#pragma unroll
-    for (int s = 0; s < KS; ++s)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) xs[s][j] = (__bf16)(v[s][j] * rstd);
-#else
     const la_bf16x2 one = __builtin_bit_cast(la_bf16x2, 0x3f803f80u);
     float s1 = 0.0f, s2 = 0.0f;
 #pragma unroll
@@ -109,7 +75,6 @@ __device__ __forceinline__ void norm_x(const XRaw<C>& r, float eps, bf16x8 (&xs)
             xs[s][2 * j] = (__bf16)__builtin_fmaf(bf2f((bf16_t)(w & 0xffffu)), rstd, off);
             xs[s][2 * j + 1] = (__bf16)__builtin_fmaf(bf2f((bf16_t)(w >> 16)), rstd, off);
         }
-#endif
 }
 
 // Training form: the fragments ARE the LayerNorm output xn = x^ * g rounded to bf16 (what the unfused path stores and multiplies by the
@@ -329,8 +294,8 @@ __global__ void __launch_bounds__(256, 2) la_ctx_fused_kernel(const bf16_t* __re
 // ---- pass 1 on STORED k, v (the training forward: qkv is materialised for the backward): the online-softmax body of the kernel above,
 // with the projection MFMAs replaced by a layout change -- a k (v) tile read as an A operand (lane = pixel, 8 consecutive channels: one
 // 16-byte load) times the 32 x 32 identity gives the accumulator tile [rows = pixels][col = d] exactly (bf16 x 1.0, fp32 accumulate), which is
-// what the context MFMA wants as operands.  Replaces lc_ctx_partial_kernel (la_core.hip), whose per-channel max / exp scans walk an LDS tile
-// two bytes at a time: 1.3 ms -> 0.4 ms per full-resolution block.  Same partial format ([m 32 | l 32 | ctx 32 x 32] per (sample, head, part)).
+// what the context MFMA wants as operands.  Replaced an LDS-scan kernel (lc_ctx_partial_kernel), whose per-channel max / exp scans walk an
+// LDS tile two bytes at a time: 1.3 ms -> 0.4 ms per full-resolution block.  Same partial format ([m 32 | l 32 | ctx 32 x 32] per (sample, head, part)).
 __global__ void __launch_bounds__(256, 2) la_ctx_stored_kernel(const bf16_t* __restrict__ qkv, float* __restrict__ partial, int n) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, half = lane >> 5;
     const int b = blockIdx.y, wave_id = blockIdx.x * 4 + wave, nw = gridDim.x * 4, ntiles = (n + 31) / 32;
@@ -672,10 +637,10 @@ __global__ void __launch_bounds__(256) la_weight_prep_kernel(const float* __rest
     }
 }
 
-static float la_defer() {
-    static const float defer = getenv("OFD_LA_DEFER") ? (float)atof(getenv("OFD_LA_DEFER")) : 5.545177f;      // 8 ln 2; 0: the reference point follows every new maximum
-    return defer;
-}
+// how far a new maximum may pass the softmax reference point before the accumulators are rescaled: 8 ln 2 (0 would follow every new maximum)
+constexpr float LA_DEFER = 5.545177f;
+// second-pass workgroups per sample (at least 1024 over the batch: small batches need enough workgroups for the chip)
+constexpr int LA_GX2_CAP = 128;
 
 template <int C>
 static int launch_la(const bf16_t* x, const bf16_t* wq, const bf16_t* wkv, const bf16_t* woutp, const float* bias, const float* g2,
@@ -689,14 +654,11 @@ static int launch_la(const bf16_t* x, const bf16_t* wq, const bf16_t* wkv, const
         attr = true;
     }
     const int gx = la_fused_blocks(n, B);
-    const float defer = la_defer();
-    la_ctx_fused_kernel<C, false><<<dim3(gx, B), 256, LDS1, s>>>(x, wkv, partial, n, eps_pre, defer, nullptr, nullptr, nullptr);
+    la_ctx_fused_kernel<C, false><<<dim3(gx, B), 256, LDS1, s>>>(x, wkv, partial, n, eps_pre, LA_DEFER, nullptr, nullptr, nullptr);
     la_ctx_combine_frag_kernel<<<dim3(B * 4, 4), 256, 0, s>>>(partial, ctxfrag, gx, 1.0f / (float)n);
     int gx2 = cdiv(cdiv(n, 32), 4 * 4);     // >= 4 tiles per wave amortise the weight staging
     if (gx2 < 1) gx2 = 1;
-    static int gx2_cap = -1;
-    if (gx2_cap < 0) { const char* e = getenv("OFD_LA_GX2"); gx2_cap = e ? atoi(e) : 128; }
-    const int cap2 = (gx2_cap * B < 1024) ? 1024 / B : gx2_cap;          // small batches: enough workgroups for the chip
+    const int cap2 = (LA_GX2_CAP * B < 1024) ? 1024 / B : LA_GX2_CAP;
     if (gx2 > cap2) gx2 = cap2;
     la_out_fused_kernel<C, false><<<dim3(gx2, B), 256, LDS2, s>>>(x, wq, woutp, ctxfrag, bias, g2, y, n, eps_pre, eps_post, 0.17677669529663687f, nullptr, nullptr);
     OFD_LAUNCH_CHECK();
@@ -720,12 +682,12 @@ int k_linear_attention_fused_train(const bf16_t* x, const bf16_t* wq, const bf16
         attr = true;
     }
     const int gx = la_fused_blocks(n, B);
-    la_ctx_fused_kernel<64, true><<<dim3(gx, B), 256, LDS1, s>>>(x, wkv, partial, n, eps_pre, la_defer(), g_pre, xn, qkv);
+    la_ctx_fused_kernel<64, true><<<dim3(gx, B), 256, LDS1, s>>>(x, wkv, partial, n, eps_pre, LA_DEFER, g_pre, xn, qkv);
     la_ctx_combine_frag_kernel<<<dim3(B * 4, 4), 256, 0, s>>>(partial, ctxfrag, gx, 1.0f / (float)n);
     launch_la_ctx_combine(partial, ctx, B, gx, 1.0f / (float)n, ml, s);
     int gx2 = cdiv(cdiv(n, 32), 4 * 4);
     if (gx2 < 1) gx2 = 1;
-    const int cap2 = (128 * B < 1024) ? 1024 / B : 128;
+    const int cap2 = (LA_GX2_CAP * B < 1024) ? 1024 / B : LA_GX2_CAP;
     if (gx2 > cap2) gx2 = cap2;
     la_out_fused_kernel<64, true><<<dim3(gx2, B), 256, LDS2, s>>>(x, wq, woutp, ctxfrag, bias, g2, y, n, eps_pre, eps_post, 0.17677669529663687f, g_pre, o2);
     OFD_LAUNCH_CHECK();
@@ -733,11 +695,11 @@ int k_linear_attention_fused_train(const bf16_t* x, const bf16_t* wq, const bf16
 }
 
 // workgroups per sample of the first pass (= parts per (sample, head): each workgroup writes one): 64 at the batch sizes that fill the chip by
-// themselves, up to OFD_LA_GX1_TOTAL (default 256: one per CU; 128 / 192 / 384 / 512 measured slower at B = 1 1080p --
+// themselves, up to 256 over the batch (one per CU; 128 / 192 / 384 / 512 measured slower at B = 1 1080p --
 // beyond 256 the combine's chain over the parts costs more than the first pass gains) over the batch for small ones -- at B = 1 (1080p: BASELINE configs[4] per
 // GPU) 64 workgroups were a quarter of the CUs
 int la_fused_blocks(int n, int B) {
-    static const int total = getenv("OFD_LA_GX1_TOTAL") ? atoi(getenv("OFD_LA_GX1_TOTAL")) : 256;
+    constexpr int total = 256;
     int gx = cdiv(cdiv(n, 32), 8);
     int cap = total / (B < 1 ? 1 : B);
     if (cap < 64) cap = 64;

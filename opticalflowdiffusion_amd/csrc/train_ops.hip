@@ -448,8 +448,7 @@ __global__ void __launch_bounds__(256) time_mlp_bwd_weight_kernel(const float* _
 }
 
 static inline int tgrid(size_t total, int cap = 4096) {   // cap = 0: uncapped, see sgrid in blocks.hip
-    static const int env_cap = getenv("OFD_GRID_CAP") ? atoi(getenv("OFD_GRID_CAP")) : (1 << 22);
-    if (cap <= 0) cap = env_cap;
+    if (cap <= 0) cap = 1 << 22;
     size_t b = (total + 255) / 256;
     return (int)(b < 1 ? 1 : (b > (size_t)cap ? cap : b));
 }

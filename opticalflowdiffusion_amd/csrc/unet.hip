@@ -186,13 +186,13 @@ static Tensor resblock(Ctx& c, const std::string& name, const std::vector<Tensor
     SrcSpec hs; hs.t = h1;
     // inference, layers of several 128-channel output blocks: every block's workgroups would re-apply SiLU(GroupNorm(h1)) to the same staged tile
     // (an exp + a reciprocal per element, 2-4 times over); the small tensors of those levels are activated ONCE by an elementwise pass instead
-    static const int act1_min = getenv("OFD_ACT1_MATERIALIZE_MIN") ? atoi(getenv("OFD_ACT1_MATERIALIZE_MIN")) : 256;
+    constexpr int act1_min = 256;
     // training: the weight gradient of block2.proj reads a materialised act1 for every layer wider than 64 channels anyway (unet_train.hip): the
     // forward makes it (and multiplies by it) instead of the backward
-    static const int act1_train_min = getenv("OFD_ACT1_TRAIN_MIN") ? atoi(getenv("OFD_ACT1_TRAIN_MIN")) : 128;
+    constexpr int act1_train_min = 128;
     const int amin = c.train ? act1_train_min : act1_min;
     Tensor act1;
-    if (amin > 0 && Cout >= amin) {
+    if (Cout >= amin) {
         act1 = c.tmp(Cout, H, W);
         if (c.rc != OFD_OK) return out;
         c.begin(PC_MISC, 0, (double)B * H * W * Cout * 4.0);
@@ -273,15 +273,14 @@ static Tensor linattn(Ctx& c, const std::string& name, Tensor x) {
     RUN(k_layernorm_c(x.p, u->P(name + ".fn.norm.g"), nullptr, xn.p, npix, C, site_eps(u, name + ".fn.norm"), c.s));
     c.end();
     SrcSpec s; s.t = xn;
-    // training, 64 channels, every fusion on and OFD_LA_RECOMPUTE_Q: the passes that need q re-derive it from xn -- only k and v are computed
-    const bool rq_conv = c.train && la_train_no_ao(C) && la_recompute_q();
-    conv(c, name + ".fn.fn.to_qkv", {s}, qkv, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, rq_conv ? 128 : 0);
+    // training, 64 channels: the passes that need q re-derive it from xn -- only k and v are computed
+    const bool rq = c.train && la_train_fused(C);
+    conv(c, name + ".fn.fn.to_qkv", {s}, qkv, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, rq ? 128 : 0);
     c.begin(PC_LINATTN, 4.0 * npix * 4 * 32 * 32, (double)npix * (384 + 128 + 128) * 2);
-    if (C <= 128 && la_fuse_to_out()) {     // to_out.0 rides on the head-output tile of the core's second pass (la_core.hip lc_out_kernel)
+    if (C <= 128) {     // to_out.0 rides on the head-output tile of the core's second pass (la_core.hip lc_out_kernel)
         const ConvDesc& d = u->convs[u->cindex.at(name + ".fn.fn.to_out.0")];
-        // training, 64 channels, all fusions on: nothing reads the head outputs again (the backward derives what it needs from ctx and q)
-        bf16_t* ao_out = (c.train && la_train_no_ao(C)) ? nullptr : ao.p;
-        const bool rq = c.train && la_train_no_ao(C) && la_recompute_q();      // q re-derived from xn in every pass that needs it
+        // training, 64 channels: nothing reads the head outputs again (the backward derives what it needs from ctx and q)
+        bf16_t* ao_out = rq ? nullptr : ao.p;
         const ConvDesc& dq = u->convs[u->cindex.at(name + ".fn.fn.to_qkv")];
         RUN(k_linear_attention_core(qkv.p, partial, ctx, ao_out, B, n, c.s, ml, u->d_wbuf + d.w_off, u->P(name + ".fn.fn.to_out.0.bias"), o2.p, C,
                                     rq ? xn.p : nullptr, rq ? u->d_wbuf + dq.w_off : nullptr));
@@ -344,23 +343,20 @@ static void plain_conv(Ctx& c, const std::string& prefix, const std::vector<SrcS
 static void upsample_conv(Ctx& c, const std::string& prefix, const SrcSpec& src_up, Tensor out) {
     ofd_unet* u = c.u;
     const ConvDesc& d = u->convs[u->cindex.at(prefix)];
-    static int no_phase = -1;
-    if (no_phase < 0) { const char* e = getenv("OFD_NO_PHASE_UPSAMPLE"); no_phase = (e && atoi(e)) ? 1 : 0; }
-    if (d.phase_off < 0 || no_phase) { plain_conv(c, prefix, {src_up}, out); return; }
+    if (d.phase_off < 0) { plain_conv(c, prefix, {src_up}, out); return; }
     if (c.rc != OFD_OK) return;
     const Tensor& lo = src_up.t;
     const double px = (double)c.B * out.H * out.W;
     c.begin(PC_CONVUP, 2.0 * px * d.Cout * (double)d.Cin * 9 /* algorithmic: as the reference executes it */, px * 2.0 * (d.Cout + d.Cin / 4.0),
             prefix + " " + std::to_string(d.Cin) + "->" + std::to_string(d.Cout) + " @" + std::to_string(out.H) + "x" + std::to_string(out.W) + " (4 phases)");
-    static const int one_launch = getenv("OFD_PHASE_ONE_LAUNCH") ? atoi(getenv("OFD_PHASE_ONE_LAUNCH")) : 1;
-    for (int ph = 0; ph < (one_launch ? 1 : 4); ++ph) {
+    {
         ofd_conv_args a{};
         a.B = c.B; a.H = lo.H; a.W = lo.W; a.ksize = 2; a.n_src = 1; a.Cout = d.Cout;
         a.src[0].src = lo.p; a.src[0].channels = lo.C; a.src[0].src_channels = lo.C;
-        a.weight = u->d_wbuf + d.phase_off + (size_t)ph * 4 * d.Cin * d.Cout;
+        a.weight = u->d_wbuf + d.phase_off;
         a.bias = u->P(prefix + ".bias");
         a.out = out.p;
-        a.up2_phase = one_launch ? 5 : ph + 1;          // 5: the four phases in one launch (phases of a tile on one XCD: conv_params.h)
+        a.up2_phase = 5;                                // the four phases in one launch (phases of a tile on one XCD: conv_params.h)
         RUN(conv_forward_impl(&a, c.s));
     }
     c.end();
@@ -381,8 +377,7 @@ int run_forward(Ctx& c, const float* x, int Cx, const float* cond, int Cc, const
     // <= 8 input channels: 8-channel packing, the 7x7 pairs horizontally adjacent taps into one k-step (conv_igemm.hip Cfg::K7P).
     // Training keeps the same 8-channel tensor on the tape: its weight-gradient kernel reads either packing (conv_bwd.hip conv7_wgrad_kernel<8>;
     // r04: the 16-channel copy and its pack pass are gone).
-    static const bool no_pack8 = getenv("OFD_NO_CONV7_PACK8") && atoi(getenv("OFD_NO_CONV7_PACK8"));
-    const bool pack8 = !no_pack8 && u->convs[u->cindex.at("init_conv")].pack8_off >= 0;
+    const bool pack8 = u->convs[u->cindex.at("init_conv")].pack8_off >= 0;
     const int cpad = pack8 ? 8 : u->cin_pad;
     const int L = u->L;
     Tensor xin = c.keep(cpad, H, W);
@@ -468,10 +463,8 @@ int run_forward(Ctx& c, const float* x, int Cx, const float* cond, int Cc, const
     // inference: the final 1x1 conv (DD:361) rides on the tile of final_res_block's res_conv (conv1_wp.hip, FC): the block's 64-channel
     // output tensor is neither written nor read.  Off when the tensor itself is wanted (training tape, ofd_unet_set_debug_taps) or the
     // shape is not the streaming kernel's (out_dim 2, whole 128-pixel tiles)
-    static const bool no_fc = (getenv("OFD_NO_FC_FUSE") && atoi(getenv("OFD_NO_FC_FUSE"))) || (getenv("OFD_CONV1_WP") && atoi(getenv("OFD_CONV1_WP")) == 0) ||
-                              (getenv("OFD_CONV_DBG") && atoi(getenv("OFD_CONV_DBG")));
     const int glue = u->glue_out;             // (training: the backward differentiates the clamps, unet_train.hip)
-    const bool fuse_fc = !c.train && !u->debug_taps && !no_fc && !glue && u->cfg.out_dim == 2 && dim == 64 && ((long)H * W) % 128 == 0;
+    const bool fuse_fc = !c.train && !u->debug_taps && !glue && u->cfg.out_dim == 2 && dim == 64 && ((long)H * W) % 128 == 0;
     if (fuse_fc) {
         const FcFuse fc{u->P("final_conv.weight"), u->P("final_conv.bias"), out};
         if (c.rc == OFD_OK && !c.dry) {
@@ -580,7 +573,7 @@ extern "C" int ofd_unet_create(const ofd_unet_config* cfg, ofd_unet** out) {
     ofd_unet* u = new ofd_unet();
     u->cfg = *cfg;
     u->L = cfg->n_levels == 3 ? 3 : 4;
-    { const char* e = getenv("OFD_DETERMINISTIC"); u->deterministic = e && atoi(e) != 0; }      // default of ofd_unet_set_deterministic
+    u->deterministic = env_int("OFD_DETERMINISTIC", 0) != 0;      // default of ofd_unet_set_deterministic
     build_registry(u);
     if (hipMalloc(&u->d_params, u->n_param_floats * sizeof(float)) != hipSuccess ||
         hipMalloc(&u->d_wbuf, u->n_wbuf * sizeof(bf16_t)) != hipSuccess ||
@@ -913,23 +906,18 @@ extern "C" int ofd_unet_prof_dump_path(ofd_unet* u, const char* path) {
     return OFD_OK;
 }
 namespace ofd {
-// name of a profile class = the kernel that serves it under the switches this process runs with (the same environment variables, read the same
-// way, as the dispatch in conv_igemm.hip:conv_forward_impl and conv_wp.hip:launch_conv3x3_wp), followed by the layer group in brackets
+// name of a profile class = the kernel that serves it (under the reference switches OFD_CONV_PC / OFD_CONV7_PERSIST as this process first
+// reads them), followed by the layer group in brackets
 const char* prof_class_name(int cls) {
     static std::string names[PC_COUNT];
     static bool built = false;
     if (!built) {
-        auto env = [](const char* n, int dflt) { const char* e = getenv(n); return e ? atoi(e) : dflt; };
-        const int wp = env("OFD_CONV_WP", 7), wp16 = env("OFD_CONV_WP16", 1), bn256 = env("OFD_CONV_WP_BN256", 0);
-        const bool phase_wp = env("OFD_PHASE_WP", 1) != 0;
-        const bool pcw = env("OFD_CONV_PCW", 0) != 0;
-        names[PC_CONV3] = std::string(!(wp & 1) ? "conv_igemm_kernel<3,128>" : (bn256 ? "conv3x3_wp_kernel<8,1>|<4,1>" : (pcw ? "conv3x3_pcw_kernel" : (wp16 ? "conv3x3_wp16_kernel" : "conv3x3_wp_kernel<4,1>")))) +
-                          " [3x3, Cout a multiple of 128]";
-        const bool pc = env("OFD_CONV_PC", 1) != 0;
-        names[PC_CONV3_64] = std::string((wp & 2) ? (pc ? "conv3x3_pc_kernel" : "conv3x3_wp_kernel<2,2>") : "conv_igemm_kernel<3,64>") + " [3x3, Cin > 64 -> 64]";
-        names[PC_CONV3_PP] = std::string((wp & 4) ? (pc ? "conv3x3_pc_kernel" : "conv3x3_wp_kernel<2,2>") : "conv3x3_c64_pingpong_kernel") + " [3x3, 64 -> 64]";
+        const std::string c64 = env_int("OFD_CONV_PC", 1) ? "conv3x3_pc_kernel" : "conv3x3_wp_kernel<2,2>";
+        names[PC_CONV3] = "conv3x3_wp16_kernel [3x3, Cout a multiple of 128]";
+        names[PC_CONV3_64] = c64 + " [3x3, Cin > 64 -> 64]";
+        names[PC_CONV3_PP] = c64 + " [3x3, 64 -> 64]";
         names[PC_CONV1] = "conv1x1_wp_kernel | conv_igemm_kernel<1,BN> [1x1]";
-        names[PC_CONV7] = std::string(env("OFD_CONV7_PERSIST", 1) ? "conv7x7_c8_persist_kernel" : "conv_igemm_kernel<8,64>") + " [7x7 init conv]";
+        names[PC_CONV7] = std::string(env_int("OFD_CONV7_PERSIST", 1) ? "conv7x7_c8_persist_kernel" : "conv_igemm_kernel<8,64>") + " [7x7 init conv]";
         names[PC_GN] = "gn_finalize";
         names[PC_RESOUT] = "resblock_out";
         names[PC_LN] = "layernorm_c";
@@ -943,7 +931,7 @@ const char* prof_class_name(int cls) {
         names[PC_GNBWD] = "gn_silu_backward";
         names[PC_LABWD] = "linear_attention_backward";
         names[PC_FLASHBWD] = "flash_attention_backward";
-        names[PC_CONVUP] = std::string(phase_wp ? "conv_up2_phases_wp_kernel" : "conv_igemm_kernel<2,BN>") + " [Upsample x2 + 3x3 as four 2x2 phase convs]";
+        names[PC_CONVUP] = "conv_up2_phases_wp_kernel [Upsample x2 + 3x3 as four 2x2 phase convs]";
         names[PC_DGRAD7] = "conv7_dgrad_kernel [7x7 init conv data gradient]";
         built = true;
     }

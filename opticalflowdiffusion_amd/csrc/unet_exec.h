@@ -146,8 +146,8 @@ struct ofd_unet {
     // two half-batch forwards on two streams (ofd_unet_set_split_streams; OFD_SPLIT_STREAMS / OFD_SPLIT_OFFSET give the defaults)
     // -1 (default): on for even batches of at least 2^21 pixels in all (the BASELINE sizes: same-box A/B 31.24 -> 30.82 ms per denoise step at
     // 16 x 440 x 1024, profiles/r03_split_streams_ab.jsonl; small problems are launch-bound and would pay the second launch sequence), 0: off, 1: on
-    int split_streams = getenv("OFD_SPLIT_STREAMS") ? atoi(getenv("OFD_SPLIT_STREAMS")) : -1;
-    int split_offset = getenv("OFD_SPLIT_OFFSET") ? atoi(getenv("OFD_SPLIT_OFFSET")) : 1;   // blocks half 1 starts behind half 0
+    int split_streams = env_int("OFD_SPLIT_STREAMS", -1);
+    int split_offset = env_int("OFD_SPLIT_OFFSET", 1);   // blocks half 1 starts behind half 0
     hipStream_t s2 = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_phase = nullptr;
     std::map<std::string, Tensor> taps_half0;
@@ -259,19 +259,10 @@ struct Ctx {
     }
 };
 
-// switches of the training LinearAttention fusions, shared by the forward (unet.hip) and the backward (unet_train.hip)
-static inline bool la_env_on(const char* name) { const char* e = getenv(name); return e ? atoi(e) != 0 : true; }
-static inline bool la_fuse_to_out() { static const bool v = la_env_on("OFD_LA_FUSE_TO_OUT"); return v; }
-static inline bool la_bwd_fuse_qkv() { static const bool v = la_env_on("OFD_LA_BWD_FUSE_QKV"); return v; }
-static inline bool la_bwd_fuse_dao() { static const bool v = la_env_on("OFD_LA_BWD_FUSE_DAO"); return v; }
-static inline bool la_recompute_q() { static const bool v = la_env_on("OFD_LA_RECOMPUTE_Q"); return v; }
-// 64-channel block with every fusion on: the backward needs neither dout nor ao (the forward does not write ao then)
-static inline bool la_train_no_ao(int C) { return C == 64 && la_fuse_to_out() && la_bwd_fuse_qkv() && la_bwd_fuse_dao(); }
-// the training forward of a 64-channel block as the two fused passes (la_fused.hip TRAIN forms); OFD_LA_TRAIN_FUSED=0: LayerNorm + to_qkv conv + core
-static inline bool la_train_fused(int C) {
-    static const bool v = la_env_on("OFD_LA_TRAIN_FUSED");
-    return v && la_train_no_ao(C) && la_recompute_q();
-}
+// training LinearAttention of a 64-channel block: the forward is the two fused passes (la_fused.hip TRAIN forms), the
+// passes that need q re-derive it from xn, and the backward needs neither dout nor ao (the forward does not write ao); shared by the
+// forward (unet.hip) and the backward (unet_train.hip)
+static inline bool la_train_fused(int C) { return C == 64; }
 
 #define RUN(expr)                         \
     do {                                  \

@@ -231,8 +231,7 @@ static void resblock_backward(Bwd& b, const TapeRec& r, float* dss, float* dts) 
     // once; saves a write and a read of a 0.92 GB tensor per block).  Wider layers re-stage an input tile once per co-block and
     // would repeat the transcendental work: they read a materialised act1.  Same-box A/B of the training step at B=16,
     // 440x1024: never 162.5 ms, C <= 64: 160.9, C <= 128: 161.8, always: 162.3.
-    static const int act1_max = getenv("OFD_FUSE_ACT1_MAXC") ? atoi(getenv("OFD_FUSE_ACT1_MAXC")) : 64;      // A/B switch
-    const bool fuse_act1 = Cout <= act1_max;
+    const bool fuse_act1 = Cout <= 64;
     Tensor act1 = r.act1;                 // (the forward's own, when it materialised one)
     const bool have_act1 = act1.p != nullptr;
     if (!fuse_act1 && !have_act1) act1 = b.stmp(Cout, H, W);
@@ -317,34 +316,30 @@ static void linattn_backward(Bwd& b, const TapeRec& r) {
     RUN(k_layernorm_c_bwd(r.o2.p, u->P(name + ".fn.fn.to_out.1.g"), dy, r.o2.g, u->G(name + ".fn.fn.to_out.1.g"), npix, C,
                           site_eps(u, name + ".fn.fn.to_out.1"), 0, c.s));
     c.end();
-    SrcSpec sao; sao.t = r.ao;
-    const bool fuse_qkv = la_bwd_fuse_qkv(), fuse_dao = la_bwd_fuse_dao();
-    const bool fd = C == 64 && fuse_qkv && fuse_dao;       // the core backward forms dout = Wo^T do2 itself, and the to_out.0 weight / bias gradients
-    Tensor Dao;                                            // come out of its pixel reduction (la_core.hip lc_bwd_combine_kernel): no to_out.0 backward at all
-    if (!fd) Dao = conv_backward(b, name + ".fn.fn.to_out.0", {sao}, r.o2.g, H, W, true, nullptr);
-    if (c.rc != OFD_OK) return;
-    if (C == 64 && fuse_qkv) {
-        // the to_qkv backward rides on the core backward's dqkv tile (la_core.hip lc_bwd_apply_kernel<true>): no dqkv tensor
+    if (la_train_fused(C)) {
+        // the core backward forms dout = Wo^T do2 itself, and the to_out.0 weight / bias gradients come out of its pixel reduction
+        // (la_core.hip lc_bwd_combine_kernel): no to_out.0 backward at all; the to_qkv backward rides on the core backward's dqkv tile
+        // (la_core.hip lc_bwd_apply_kernel<true>): no dqkv tensor
         const ConvDesc& d = u->convs[u->cindex.at(name + ".fn.fn.to_qkv")];
         float* acc = u->d_wacc + d.w_off;
         Tensor Dx = b.stmp(C, H, W);
         if (c.rc != OFD_OK) return;
         c.begin(PC_LABWD, npix * (4.0 * 4 * 32 * 32 * 2 + 4.0 * 384 * 64), (double)npix * (384 + 128 + 64 + 64) * 2, name + " core + to_qkv bwd");
         const ConvDesc& dto = u->convs[u->cindex.at(name + ".fn.fn.to_out.0")];
-        if (fd) {
-            RUN(k_linear_attention_core_bwd(r.qkv.p, r.o2.g, r.ctx, r.ml, nullptr, ws, B, n, c.s, r.xn.p, u->d_wtbuf + d.w_off, acc, Dx.p,
-                                            u->d_wbuf + dto.w_off, u->d_wtbuf + dto.w_off, u->d_wacc + dto.w_off, u->G(name + ".fn.fn.to_out.0.bias"),
-                                            (la_train_no_ao(C) && la_recompute_q()) ? u->d_wbuf + d.w_off : nullptr));
-            RUN(det_flush_wacc(c, dto));
-            RUN(k_wgrad_finish(u->d_wacc + dto.w_off, u->P(dto.wname), u->G(dto.wname), dto.Cout, dto.Cin, dto.Cin_pad, dto.ksize, dto.ws_eps, dto.unshuffle, 0, c.s));
-        }
-        else RUN(k_linear_attention_core_bwd(r.qkv.p, Dao.p, r.ctx, r.ml, nullptr, ws, B, n, c.s, r.xn.p, u->d_wtbuf + d.w_off, acc, Dx.p));
+        RUN(k_linear_attention_core_bwd(r.qkv.p, r.o2.g, r.ctx, r.ml, nullptr, ws, B, n, c.s, r.xn.p, u->d_wtbuf + d.w_off, acc, Dx.p,
+                                        u->d_wbuf + dto.w_off, u->d_wtbuf + dto.w_off, u->d_wacc + dto.w_off, u->G(name + ".fn.fn.to_out.0.bias"),
+                                        u->d_wbuf + d.w_off));
+        RUN(det_flush_wacc(c, dto));
+        RUN(k_wgrad_finish(u->d_wacc + dto.w_off, u->P(dto.wname), u->G(dto.wname), dto.Cout, dto.Cin, dto.Cin_pad, dto.ksize, dto.ws_eps, dto.unshuffle, 0, c.s));
         RUN(det_flush_wacc(c, d));
         RUN(k_wgrad_finish(acc, u->P(d.wname), u->G(d.wname), d.Cout, d.Cin, d.Cin_pad, d.ksize, d.ws_eps, d.unshuffle, 0, c.s));
         c.end();
         attn_tail_backward(b, r, name + ".fn.fn.to_qkv", name + ".fn.norm.g", dy, &Dx);
         return;
     }
+    SrcSpec sao; sao.t = r.ao;
+    Tensor Dao = conv_backward(b, name + ".fn.fn.to_out.0", {sao}, r.o2.g, H, W, true, nullptr);
+    if (c.rc != OFD_OK) return;
     c.begin(PC_LABWD, npix * 4.0 * 4 * 32 * 32 * 2, (double)npix * (384 * 2 + 128) * 2, name + " core bwd");
     RUN(k_linear_attention_core_bwd(r.qkv.p, Dao.p, r.ctx, r.ml, r.qkv.g, ws, B, n, c.s));
     c.end();

@@ -371,7 +371,7 @@ def test_training_forward_vs_inference_forward_tap_by_tap(L, which):
     7x7 init conv and the 64-channel ResnetBlocks of level 0.  The first LinearAttention is where they part: inference runs the fused
     two-pass block (la_fused.hip, k_linear_attention_fused), training the TRAIN form that also leaves the tape (k_linear_attention_fused_train;
     C = 128 / 256: LayerNorm + to_qkv conv + la_core) -- and the 128-channel blocks, whose SiLU(GroupNorm(h1)) training materialises
-    (OFD_ACT1_TRAIN_MIN) where inference applies it in the conv's loader.  From there on the two differ by rounding: measured 2-11e-3
+    (unet.hip: act1_train_min) where inference applies it in the conv's loader.  From there on the two differ by rounding: measured 2-11e-3
     rel-L2 per tap, 8.9e-3 (encoder) / 2.8e-3 (decoder) at the glued output, each as close to the oracle as the tolerance the inference
     forward is held to."""
     torch.manual_seed(17)

@@ -262,7 +262,7 @@ def test_grid_sample_warp_full_size_properties(ofd):
 
 
 @pytest.mark.parametrize("B,H,W", [(16, 440, 1024), (3, 100, 1000), (1, 64, 64), (2, 40, 132), (1, 97, 260)])
-def test_grid_sample_warp_ring_kernel_against_the_oracle_at_size(ofd, B, H, W):
+def test_grid_sample_warp_band_kernel_against_the_oracle_at_size(ofd, B, H, W):
     """The C = 3 grid_sample warp at sizes: the BAND kernel (warp.hip: grid_warp_band_kernel, r04: a workgroup slides down a 128-column band
     over a 72-row LDS ring, counted waits, look-ahead window groups) where W >= 128 and H >= 32, else the 64 x 64 tile kernel.  At the
     BASELINE size every workgroup walks a 224-row segment of a band; (3, 100, 1000) has a partial band and a partial last step; (2, 40, 132)
