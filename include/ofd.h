@@ -18,6 +18,8 @@
  *   denoising_diffusion.py:666-698    p_mean_variance + p_sample update -> ofd_ddpm_update(_obj)
  *   denoising_diffusion.py:750-767    ddim_sample update                -> ofd_ddim_update(_obj)
  *   (not in the reference)            DPM-Solver++ multistep update     -> ofd_dpmpp_update
+ *   (not in the reference)            constrained (inpainting) updates  -> ofd_ddpm_update_known, ofd_ddim_update_known,
+ *                                                                          ofd_dpmpp_update_known
  *   denoising_diffusion.py:806-812    q_sample                          -> ofd_q_sample
  *   denoising_diffusion.py:844-879,985-993  p_losses noise / target     -> ofd_diffusion_prep
  *   denoising_diffusion.py:73-77      (un)normalize                     -> ofd_range_map
@@ -159,6 +161,38 @@ int ofd_ddim_update_obj(int objective, const float* x_t, const float* model_out,
 int ofd_dpmpp_update(int objective, int order, const float* x_t, const float* model_out, const float* xa, const float* xb,
                      const float* d_prev1, const float* d_prev2, const float* cx, const float* w0, const float* w1,
                      const float* w2, int last, float* out, float* d_out, int B, size_t n_per_sample, void* stream);
+/* Constrained sampling: the three reverse steps with part of the diffused tensor held at known values (replacement-based inpainting:
+ * Lugmayr et al., "RePaint", 2022; the imputation sampler of Song et al., "Score-Based Generative Modeling through SDEs", 2021; an
+ * addition, not in the reference).  The arguments are those of ofd_ddpm_update_obj / ofd_ddim_update_obj / ofd_dpmpp_update, plus
+ *   known           (B,C,H,W): a NaN element is FREE, any other is HELD at clamp(known, -1, 1); the mask is per element;
+ *   e0              (B,C,H,W): x_T, the start of the chain, read only by a step that has no noise of its own (NULL otherwise);
+ *                   it must outlive the chain: no step may write it;
+ *   sqrt_ac_next, sqrt_1mac_next  per-sample sqrt(ac_s), sqrt(1 - ac_s) of the level s the step goes TO; NULL on the final step
+ *                   (for the DDPM form, which has no `last`, NULL is what marks the final step, t = 0).
+ * For a step from level t to level s:
+ *   1. x_start (D0) is formed and clamped as in the unconstrained call, then overwritten by clamp(known) at held elements, before
+ *      it is written to x_start / d_out (so a multistep history's divided differences are exactly zero there);
+ *   2. free elements of out are the same bits the unconstrained entry point writes for the same inputs (the same device code);
+ *   3. held elements of out are sqrt_ac_next*clamp(known) + sqrt_1mac_next*e, each product rounded on its own, where e is the
+ *      element of `noise` when noise is non-NULL (the sampler drew noise at this step, whatever sigma is) and of e0 otherwise: a held
+ *      element then follows the deterministic trajectory of a point mass at known;
+ *   4. the final step writes clamp(known) itself at held elements.
+ * Same access pattern as the unconstrained kernels: one 16-byte access per operand when n_per_sample % 4 == 0, one dword otherwise;
+ * 4 reads (x_t, model_out, known, noise or e0) and up to 2 writes per element, plus the histories of the DPM-Solver++ form; out == x_t
+ * stays allowed there.  One launch, no atomics. */
+int ofd_ddpm_update_known(int objective, const float* x_t, const float* model_out, const float* noise,
+                          const float* coef1, const float* coef2, const float* sigma, const float* xa, const float* xb,
+                          const float* known, const float* e0, const float* sqrt_ac_next, const float* sqrt_1mac_next,
+                          float* out, float* x_start, int B, size_t n_per_sample, void* stream);
+int ofd_ddim_update_known(int objective, const float* x_t, const float* model_out, const float* noise,
+                          const float* sqrt_recip_ac, const float* sqrt_recipm1_ac, const float* xa, const float* xb,
+                          const float* sqrt_alpha_next, const float* c, const float* sigma, int last,
+                          const float* known, const float* e0, const float* sqrt_ac_next, const float* sqrt_1mac_next,
+                          float* out, float* x_start, int B, size_t n_per_sample, void* stream);
+int ofd_dpmpp_update_known(int objective, int order, const float* x_t, const float* model_out, const float* xa, const float* xb,
+                           const float* d_prev1, const float* d_prev2, const float* cx, const float* w0, const float* w1,
+                           const float* w2, int last, const float* known, const float* e0, const float* sqrt_ac_next,
+                           const float* sqrt_1mac_next, float* out, float* d_out, int B, size_t n_per_sample, void* stream);
 /* Training prep, one launch (DD:844-848, 806-812, 874-879, 985-993), x0 / noise / outputs (B,C,hw):
  *   x0n = normalize ? 2*x0 - 1 : x0;  nz = noise + offset_strength*offset[b,c] (offset (B,C), or NULL: no offset noise);
  *   x_t = sqrt_ac*x0n + sqrt_1mac*nz;  target = nz (pred_noise), x0n (pred_x0), sqrt_ac*nz - sqrt_1mac*x0n (pred_v).

@@ -64,29 +64,63 @@ __global__ void __launch_bounds__(256) diffusion_prep_kernel(const float* __rest
     }
 }
 
+// Constrained sampling (replacement-based inpainting; not in the reference).  `known` has the layout of x_t: a NaN element is free, any
+// other is held at clamp(known).  Each update kernel below takes an optional trailing KnownArgs: without it (K empty) it is the
+// unconstrained kernel, same parameters and same code as before; with it, free elements go through the same arithmetic and held
+// ones overwrite x_start and the output.  Held output: sqrt(ac_next) known + sqrt(1 - ac_next) e, each product rounded on its own,
+// with e this step's noise element when the step has one and the element of x_T (e0) otherwise; known itself on the final step.
+struct KnownArgs {
+    const float* known = nullptr;     // (B, n_per_sample)
+    const float* e = nullptr;         // the step's noise, or x_T where the step draws none; unused on the final step
+    const float* sa = nullptr;        // per-sample sqrt(ac_next), sqrt(1 - ac_next); null on the final step
+    const float* s1 = nullptr;
+};
+__device__ __forceinline__ KnownArgs known_args() { return KnownArgs{}; }
+__device__ __forceinline__ KnownArgs known_args(KnownArgs kn) { return kn; }
+__device__ __forceinline__ bool held(float k) { return k == k; }
+__device__ __forceinline__ float held_value(float kc, float ksa, float ks1, float e, bool fin) {
+    return fin ? kc : ksa * kc + ks1 * e;
+}
+
 // DDPM step (DD:666-698): x_start from the output, clamped in p_mean_variance (DD:670-671), posterior mean, noise.  xa / xb: the
 // start_from_output coefficients (unused for pred_x0).
-template <int OBJ, int VEC>
+template <int OBJ, int VEC, typename... K>
 __global__ void __launch_bounds__(256) ddpm_update_kernel(const float* __restrict__ x_t, const float* __restrict__ mo,
                                                           const float* __restrict__ noise, const float* __restrict__ c1,
                                                           const float* __restrict__ c2, const float* __restrict__ sg,
                                                           const float* __restrict__ xa, const float* __restrict__ xb,
-                                                          float* __restrict__ out, float* __restrict__ x_start, size_t n_per_sample) {
+                                                          float* __restrict__ out, float* __restrict__ x_start, size_t n_per_sample,
+                                                          K... known) {
+    constexpr bool KNOWN = sizeof...(K) != 0;
+    const KnownArgs kn = known_args(known...);
     const int s = blockIdx.y;
     const float k1 = c1[s], k2 = c2[s], ks = (noise && sg) ? sg[s] : 0.0f;
     float ka = 0.0f, kb = 0.0f;
     if constexpr (OBJ != PRED_X0) { ka = xa[s]; kb = xb[s]; }
+    const bool fin = KNOWN && !kn.sa;
+    const float ksa = (KNOWN && !fin) ? kn.sa[s] : 0.0f, ks1 = (KNOWN && !fin) ? kn.s1[s] : 0.0f;
     const size_t base = (size_t)s * n_per_sample, nv = n_per_sample / VEC;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (size_t)gridDim.x * blockDim.x) {
         const size_t e = base + i * VEC;
         const EwVec<VEC> m = ew_load<VEC>(mo + e), xt = ew_load<VEC>(x_t + e);
-        EwVec<VEC> nz, r, xs;
-        if (ks != 0.0f) nz = ew_load<VEC>(noise + e);
+        EwVec<VEC> nz, kv, r, xs;
+        if constexpr (KNOWN) {
+            kv = ew_load<VEC>(kn.known + e);
+            if (!fin || ks != 0.0f) nz = ew_load<VEC>(kn.e + e);         // kn.e is `noise` whenever ks != 0
+        } else {
+            if (ks != 0.0f) nz = ew_load<VEC>(noise + e);
+        }
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
-            const float x0 = clamp1(start_from_output<OBJ>(m.v[j], xt.v[j], ka, kb));   // DD:670-671
+            float x0 = clamp1(start_from_output<OBJ>(m.v[j], xt.v[j], ka, kb));   // DD:670-671
             float v = k1 * x0 + k2 * xt.v[j];                            // DD:615-618
             if (ks != 0.0f) v = v + ks * nz.v[j];                        // DD:688
+            if constexpr (KNOWN) {
+                if (held(kv.v[j])) {
+                    x0 = clamp1(kv.v[j]);
+                    v = held_value(x0, ksa, ks1, nz.v[j], fin);
+                }
+            }
             r.v[j] = v;
             xs.v[j] = x0;
         }
@@ -97,33 +131,48 @@ __global__ void __launch_bounds__(256) ddpm_update_kernel(const float* __restric
 
 // DDIM step (DD:731-774) with clip_x_start = rederive_pred_noise = True (DD:747): x_start clamped, eps re-derived from it for every
 // objective (DD:645-662), then x_start sqrt(an) + c eps + sigma z; the last step returns x_start.
-template <int OBJ, int VEC>
+template <int OBJ, int VEC, typename... K>
 __global__ void __launch_bounds__(256) ddim_update_kernel(const float* __restrict__ x_t, const float* __restrict__ mo,
                                                           const float* __restrict__ noise, const float* __restrict__ sr,
                                                           const float* __restrict__ srm1, const float* __restrict__ xa,
                                                           const float* __restrict__ xb, const float* __restrict__ san,
                                                           const float* __restrict__ cc, const float* __restrict__ sg, int last,
-                                                          float* __restrict__ out, float* __restrict__ x_start, size_t n_per_sample) {
+                                                          float* __restrict__ out, float* __restrict__ x_start, size_t n_per_sample,
+                                                          K... known) {
+    constexpr bool KNOWN = sizeof...(K) != 0;
+    const KnownArgs kn = known_args(known...);
     const int s = blockIdx.y;
     const float k_sr = sr[s], k_srm1 = srm1[s];
     const float k_an = last ? 0.0f : san[s], k_c = last ? 0.0f : cc[s], k_s = (last || !noise || !sg) ? 0.0f : sg[s];
     float ka = 0.0f, kb = 0.0f;
     if constexpr (OBJ != PRED_X0) { ka = xa[s]; kb = xb[s]; }
+    const float ksa = (KNOWN && !last) ? kn.sa[s] : 0.0f, ks1 = (KNOWN && !last) ? kn.s1[s] : 0.0f;
     const size_t base = (size_t)s * n_per_sample, nv = n_per_sample / VEC;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (size_t)gridDim.x * blockDim.x) {
         const size_t e = base + i * VEC;
         const EwVec<VEC> m = ew_load<VEC>(mo + e);
-        EwVec<VEC> xt, nz, r, xs;
+        EwVec<VEC> xt, nz, kv, r, xs;
         if (!last || OBJ != PRED_X0) xt = ew_load<VEC>(x_t + e);
-        if (k_s != 0.0f) nz = ew_load<VEC>(noise + e);
+        if constexpr (KNOWN) {
+            kv = ew_load<VEC>(kn.known + e);
+            if (!last) nz = ew_load<VEC>(kn.e + e);                      // kn.e is `noise` whenever k_s != 0
+        } else {
+            if (k_s != 0.0f) nz = ew_load<VEC>(noise + e);
+        }
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
-            const float x0 = clamp1(start_from_output<OBJ>(m.v[j], xt.v[j], ka, kb));   // clip_x_start (DD:655)
+            float x0 = clamp1(start_from_output<OBJ>(m.v[j], xt.v[j], ka, kb));   // clip_x_start (DD:655)
             float v = x0;
             if (!last) {
                 const float eps = (k_sr * xt.v[j] - x0) / k_srm1;        // DD:595-599
                 v = x0 * k_an + k_c * eps;                               // DD:765-766
                 if (k_s != 0.0f) v = v + k_s * nz.v[j];
+            }
+            if constexpr (KNOWN) {
+                if (held(kv.v[j])) {
+                    x0 = clamp1(kv.v[j]);
+                    v = held_value(x0, ksa, ks1, nz.v[j], last != 0);
+                }
             }
             r.v[j] = v;
             xs.v[j] = x0;
@@ -138,35 +187,48 @@ __global__ void __launch_bounds__(256) ddim_update_kernel(const float* __restric
 // per-sample coefficient rows folded on the host (ConditionalDiffusion._dpmpp_tables); last returns D0.  D0 is also written to d_out (the
 // caller's history slot).  x_t and out may alias (in place): each element is read before it is written, by the same thread, so neither
 // pointer is __restrict__.  ORDER 1 / 2 / 3 reads 0 / 1 / 2 history tensors: 16 / 20 / 24 B per element.
-template <int OBJ, int ORDER, int VEC>
+template <int OBJ, int ORDER, int VEC, typename... K>
 __global__ void __launch_bounds__(256) dpmpp_update_kernel(const float* x_t, const float* __restrict__ mo, const float* __restrict__ xa,
                                                            const float* __restrict__ xb, const float* __restrict__ d1,
                                                            const float* __restrict__ d2, const float* __restrict__ cx,
                                                            const float* __restrict__ w0, const float* __restrict__ w1,
                                                            const float* __restrict__ w2, int last, float* out, float* __restrict__ d_out,
-                                                           size_t n_per_sample) {
+                                                           size_t n_per_sample, K... known) {
+    constexpr bool KNOWN = sizeof...(K) != 0;
+    const KnownArgs kn = known_args(known...);
     const int s = blockIdx.y;
     const float k_x = last ? 0.0f : cx[s], k_0 = last ? 0.0f : w0[s];
     const float k_1 = (ORDER >= 2 && !last) ? w1[s] : 0.0f, k_2 = (ORDER >= 3 && !last) ? w2[s] : 0.0f;
     float ka = 0.0f, kb = 0.0f;
     if constexpr (OBJ != PRED_X0) { ka = xa[s]; kb = xb[s]; }
+    const float ksa = (KNOWN && !last) ? kn.sa[s] : 0.0f, ks1 = (KNOWN && !last) ? kn.s1[s] : 0.0f;
     const size_t base = (size_t)s * n_per_sample, nv = n_per_sample / VEC;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (size_t)gridDim.x * blockDim.x) {
         const size_t e = base + i * VEC;
         const EwVec<VEC> m = ew_load<VEC>(mo + e);
-        EwVec<VEC> xt, p1, p2, r, xs;
+        EwVec<VEC> xt, p1, p2, kv, ev, r, xs;
         if (!last || OBJ != PRED_X0) xt = ew_load<VEC>(x_t + e);
         if constexpr (ORDER >= 2) { if (!last) p1 = ew_load<VEC>(d1 + e); }
         if constexpr (ORDER >= 3) { if (!last) p2 = ew_load<VEC>(d2 + e); }
+        if constexpr (KNOWN) {
+            kv = ew_load<VEC>(kn.known + e);
+            if (!last) ev = ew_load<VEC>(kn.e + e);
+        }
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
-            const float x0 = clamp1(start_from_output<OBJ>(m.v[j], xt.v[j], ka, kb));   // as ddim_update_kernel
+            float x0 = clamp1(start_from_output<OBJ>(m.v[j], xt.v[j], ka, kb));   // as ddim_update_kernel
             float v = x0;
             if (!last) {
                 v = k_x * xt.v[j];                                       // each product rounded once, added in this order
                 v = v + k_0 * x0;
                 if constexpr (ORDER >= 2) v = v + k_1 * p1.v[j];
                 if constexpr (ORDER >= 3) v = v + k_2 * p2.v[j];
+            }
+            if constexpr (KNOWN) {
+                if (held(kv.v[j])) {
+                    x0 = clamp1(kv.v[j]);
+                    v = held_value(x0, ksa, ks1, ev.v[j], last != 0);
+                }
             }
             r.v[j] = v;
             xs.v[j] = x0;
@@ -303,6 +365,37 @@ extern "C" int ofd_ddpm_update_obj(int objective, const float* x_t, const float*
     return OFD_OK;
 }
 
+// the checks the three _known entry points share; `e` is the stream rule 3 of include/ofd.h reads: the step's noise, else e0
+#define OFD_KNOWN_ARGS_OK(name, fin, e)                                                                                      \
+    OFD_CHECK_ARG(known, name ": null known");                                                                                \
+    OFD_CHECK_ARG((fin) || (sqrt_ac_next && sqrt_1mac_next), name ": missing sqrt_ac_next / sqrt_1mac_next");                 \
+    OFD_CHECK_ARG((fin) || (e), name ": a step without noise needs e0")
+
+extern "C" int ofd_ddpm_update_known(int objective, const float* x_t, const float* model_out, const float* noise, const float* coef1,
+                                     const float* coef2, const float* sigma, const float* xa, const float* xb, const float* known,
+                                     const float* e0, const float* sqrt_ac_next, const float* sqrt_1mac_next, float* out,
+                                     float* x_start, int B, size_t n, void* stream) {
+    OFD_OBJ_OK(objective);
+    OFD_EW_ARGS_OK(B, n);
+    OFD_CHECK_ARG(x_t && model_out && coef1 && coef2 && out, "ddpm_update_known: null pointer");
+    OFD_CHECK_ARG(objective == PRED_X0 || (xa && xb), "ddpm_update_known: missing x_start coefficients");
+    const bool fin = !sqrt_ac_next || !sqrt_1mac_next;
+    const KnownArgs kn{known, noise ? noise : e0, fin ? nullptr : sqrt_ac_next, fin ? nullptr : sqrt_1mac_next};
+    OFD_KNOWN_ARGS_OK("ddpm_update_known", fin, kn.e);
+    OFD_CHECK_ARG(!fin || !noise, "ddpm_update_known: the final step (no sqrt_ac_next) takes no noise");
+    hipStream_t s = (hipStream_t)stream;
+    obj_dispatch(objective, [&](auto o) {
+        constexpr int OBJ = decltype(o)::value;
+        if (n % 4 == 0)
+            ddpm_update_kernel<OBJ, 4><<<ew_grid(B, n / 4), 256, 0, s>>>(x_t, model_out, noise, coef1, coef2, sigma, xa, xb, out, x_start, n,
+                                                                        kn);
+        else
+            ddpm_update_kernel<OBJ, 1><<<ew_grid(B, n), 256, 0, s>>>(x_t, model_out, noise, coef1, coef2, sigma, xa, xb, out, x_start, n, kn);
+    });
+    OFD_LAUNCH_CHECK();
+    return OFD_OK;
+}
+
 extern "C" int ofd_ddpm_update(const float* x_t, const float* model_out, const float* noise, const float* coef1,
                                const float* coef2, const float* sigma, float* out, float* x_start, int B, size_t n, void* stream) {
     return ofd_ddpm_update_obj(PRED_X0, x_t, model_out, noise, coef1, coef2, sigma, nullptr, nullptr, out, x_start, B, n, stream);
@@ -325,6 +418,32 @@ extern "C" int ofd_ddim_update_obj(int objective, const float* x_t, const float*
         else
             ddim_update_kernel<OBJ, 1><<<ew_grid(B, n), 256, 0, s>>>(x_t, model_out, noise, sqrt_recip_ac, sqrt_recipm1_ac, xa, xb,
                                                                     sqrt_alpha_next, c, sigma, last, out, x_start, n);
+    });
+    OFD_LAUNCH_CHECK();
+    return OFD_OK;
+}
+
+extern "C" int ofd_ddim_update_known(int objective, const float* x_t, const float* model_out, const float* noise,
+                                     const float* sqrt_recip_ac, const float* sqrt_recipm1_ac, const float* xa, const float* xb,
+                                     const float* sqrt_alpha_next, const float* c, const float* sigma, int last, const float* known,
+                                     const float* e0, const float* sqrt_ac_next, const float* sqrt_1mac_next, float* out,
+                                     float* x_start, int B, size_t n, void* stream) {
+    OFD_OBJ_OK(objective);
+    OFD_EW_ARGS_OK(B, n);
+    OFD_CHECK_ARG(x_t && model_out && sqrt_recip_ac && sqrt_recipm1_ac && out, "ddim_update_known: null pointer");
+    OFD_CHECK_ARG(last || (sqrt_alpha_next && c), "ddim_update_known: missing coefficients");
+    OFD_CHECK_ARG(objective == PRED_X0 || (xa && xb), "ddim_update_known: missing x_start coefficients");
+    const KnownArgs kn{known, noise ? noise : e0, sqrt_ac_next, sqrt_1mac_next};
+    OFD_KNOWN_ARGS_OK("ddim_update_known", last, kn.e);
+    hipStream_t s = (hipStream_t)stream;
+    obj_dispatch(objective, [&](auto o) {
+        constexpr int OBJ = decltype(o)::value;
+        if (n % 4 == 0)
+            ddim_update_kernel<OBJ, 4><<<ew_grid(B, n / 4), 256, 0, s>>>(x_t, model_out, noise, sqrt_recip_ac, sqrt_recipm1_ac, xa, xb,
+                                                                        sqrt_alpha_next, c, sigma, last, out, x_start, n, kn);
+        else
+            ddim_update_kernel<OBJ, 1><<<ew_grid(B, n), 256, 0, s>>>(x_t, model_out, noise, sqrt_recip_ac, sqrt_recipm1_ac, xa, xb,
+                                                                    sqrt_alpha_next, c, sigma, last, out, x_start, n, kn);
     });
     OFD_LAUNCH_CHECK();
     return OFD_OK;
@@ -360,6 +479,43 @@ extern "C" int ofd_dpmpp_update(int objective, int order, const float* x_t, cons
             else
                 dpmpp_update_kernel<OBJ, ORD, 1><<<ew_grid(B, n), 256, 0, s>>>(x_t, model_out, xa, xb, d_prev1, d_prev2, cx, w0, w1, w2,
                                                                               last, out, d_out, n);
+        };
+        if (ord == 3) go(std::integral_constant<int, 3>{});
+        else if (ord == 2) go(std::integral_constant<int, 2>{});
+        else go(std::integral_constant<int, 1>{});
+    });
+    OFD_LAUNCH_CHECK();
+    return OFD_OK;
+}
+
+extern "C" int ofd_dpmpp_update_known(int objective, int order, const float* x_t, const float* model_out, const float* xa,
+                                      const float* xb, const float* d_prev1, const float* d_prev2, const float* cx, const float* w0,
+                                      const float* w1, const float* w2, int last, const float* known, const float* e0,
+                                      const float* sqrt_ac_next, const float* sqrt_1mac_next, float* out, float* d_out, int B, size_t n,
+                                      void* stream) {
+    OFD_OBJ_OK(objective);
+    OFD_EW_ARGS_OK(B, n);
+    OFD_CHECK_ARG(order >= 1 && order <= 3, "dpmpp_update_known: bad order %d", order);
+    OFD_CHECK_ARG(x_t && model_out && out, "dpmpp_update_known: null pointer");
+    OFD_CHECK_ARG(objective == PRED_X0 || (xa && xb), "dpmpp_update_known: missing x_start coefficients");
+    OFD_CHECK_ARG(last || (cx && w0), "dpmpp_update_known: missing coefficients");
+    OFD_CHECK_ARG(last || order < 2 || (d_prev1 && w1), "dpmpp_update_known: order %d needs d_prev1 and w1", order);
+    OFD_CHECK_ARG(last || order < 3 || (d_prev2 && w2), "dpmpp_update_known: order 3 needs d_prev2 and w2");
+    const KnownArgs kn{known, e0, sqrt_ac_next, sqrt_1mac_next};
+    OFD_KNOWN_ARGS_OK("dpmpp_update_known", last, kn.e);
+    OFD_CHECK_ARG(last || e0 != out, "dpmpp_update_known: e0 (x_T) must outlive the chain: it cannot be the output");
+    const int ord = last ? 1 : order;                                  // the final evaluation reads no history
+    hipStream_t s = (hipStream_t)stream;
+    obj_dispatch(objective, [&](auto o) {
+        constexpr int OBJ = decltype(o)::value;
+        auto go = [&](auto oc) {
+            constexpr int ORD = decltype(oc)::value;
+            if (n % 4 == 0)
+                dpmpp_update_kernel<OBJ, ORD, 4><<<ew_grid(B, n / 4), 256, 0, s>>>(x_t, model_out, xa, xb, d_prev1, d_prev2, cx, w0, w1, w2,
+                                                                                  last, out, d_out, n, kn);
+            else
+                dpmpp_update_kernel<OBJ, ORD, 1><<<ew_grid(B, n), 256, 0, s>>>(x_t, model_out, xa, xb, d_prev1, d_prev2, cx, w0, w1, w2,
+                                                                              last, out, d_out, n, kn);
         };
         if (ord == 3) go(std::integral_constant<int, 3>{});
         else if (ord == 2) go(std::integral_constant<int, 2>{});

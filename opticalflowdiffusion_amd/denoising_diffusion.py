@@ -643,8 +643,10 @@ class ConditionalDiffusion(nn.Module):
 
     # -- DDPM --------------------------------------------------------------------------------
     @torch.no_grad()
-    def p_sample(self, x, t: int, x_self_cond=None, external_cond=None, additional_tgt=None, noise=None):
-        """DD:676-698: network call + one fused kernel for clamp / posterior mean / noise add."""
+    def p_sample(self, x, t: int, x_self_cond=None, external_cond=None, additional_tgt=None, noise=None, known=None):
+        """DD:676-698: network call + one fused kernel for clamp / posterior mean / noise add.  `known` (optional, not in the reference;
+        shaped like x, in x's range, NaN = free): the constrained step of `sample(known=)`."""
+        known = self._check_known(tuple(x.shape), known, 1, additional_tgt)
         b = x.shape[0]
         tab = self._sampling_tables(b, x.device)           # rows of per-(T, batch) tables: no fill / gather / exp launches per step
         bt = tab["t"][t]
@@ -662,6 +664,11 @@ class ConditionalDiffusion(nn.Module):
             noise = None                                                               # DD:687
         pred = torch.empty_like(x)
         x_start = torch.empty_like(x)
+        if known is not None:
+            L.check(L.lib().ofd_ddpm_update_known(self._obj, L.ptr(x), L.ptr(out), L.ptr(noise), L.ptr(c1), L.ptr(c2), L.ptr(sigma),
+                                                  *self._xab(tab, t), L.ptr(known), None, *self._known_rows(tab, t - 1), L.ptr(pred),
+                                                  L.ptr(x_start), b, x[0].numel(), L.stream()))
+            return pred, x_start, additional_out
         L.check(L.lib().ofd_ddpm_update_obj(self._obj, L.ptr(x), L.ptr(out), L.ptr(noise), L.ptr(c1), L.ptr(c2), L.ptr(sigma),
                                             *self._xab(tab, t), L.ptr(pred), L.ptr(x_start), b, x[0].numel(), L.stream()))
         return pred, x_start, additional_out
@@ -679,6 +686,34 @@ class ConditionalDiffusion(nn.Module):
             return None, None
         return L.ptr(tab["xa"][t]), L.ptr(tab["xb"][t])
 
+    @staticmethod
+    def _known_rows(tab, s):
+        """the rows sqrt(ac_s), sqrt(1 - ac_s) of the level a constrained step goes to (include/ofd.h: sqrt_ac_next, sqrt_1mac_next);
+        none below level 0: the final step writes known itself"""
+        if s < 0:
+            return None, None
+        return L.ptr(tab["sa"][s]), L.ptr(tab["s1"][s])
+
+    def _check_known(self, shape, known, resample=1, additional_tgt=None, ddpm=True):
+        """the argument rules of constrained sampling, checked before any engine call (ValueError); returns known as the kernels read
+        it (contiguous fp32 on the GPU), or None"""
+        if isinstance(resample, bool) or not isinstance(resample, int) or resample < 1:
+            raise ValueError(f"resample must be an integer >= 1, got {resample!r}")
+        if resample > 1 and not ddpm:
+            raise ValueError("resample > 1 repeats DDPM steps: it is not defined for the DDIM and DPM-Solver++ samplers")
+        if known is None:
+            if resample > 1:
+                raise ValueError("resample > 1 harmonises the free elements with the held ones: it needs `known`")
+            return None
+        if additional_tgt is not None:
+            raise ValueError("known cannot be combined with additional_tgt (FlowDiffuser target='target'): there the flow is an extra "
+                             "model output, not part of the diffused tensor")
+        if not torch.is_tensor(known) or tuple(known.shape) != tuple(shape):
+            raise ValueError(f"known must be a tensor shaped like the diffused tensor {tuple(shape)}, got "
+                             f"{tuple(known.shape) if torch.is_tensor(known) else type(known).__name__}")
+        L.require_gpu(known)
+        return L.f32c(known)
+
     def _sampling_tables(self, batch, device):
         """per-(T, batch) views of everything a reverse step reads that does not depend on the data: timestep tensors and the
         posterior coefficients, expanded once so that a step indexes a ROW (a view, no gather launch, no allocation)"""
@@ -686,7 +721,7 @@ class ConditionalDiffusion(nn.Module):
         # schedule, a dtype / device move or an in-place edit of a buffer rebuilds the tables instead of serving stale rows
         srcs = (self.posterior_mean_coef1, self.posterior_mean_coef2, self.posterior_log_variance_clipped,
                 self.sqrt_recip_alphas_cumprod, self.sqrt_recipm1_alphas_cumprod, self.sqrt_alphas_cumprod,
-                self.sqrt_one_minus_alphas_cumprod)
+                self.sqrt_one_minus_alphas_cumprod, self.betas)
         key = (batch, str(device), self.objective) + tuple((b.data_ptr(), b._version, b.dtype) for b in srcs)
         if getattr(self, "_samp_tab", None) is None or self._samp_tab[0] != key:
             T = self.num_timesteps
@@ -694,21 +729,30 @@ class ConditionalDiffusion(nn.Module):
             sigma = (0.5 * self.posterior_log_variance_clipped).exp()
             tab = dict(t=torch.arange(T, device=device, dtype=torch.long).reshape(T, 1).repeat(1, batch).contiguous(),
                        c1=rep(self.posterior_mean_coef1), c2=rep(self.posterior_mean_coef2), sigma=rep(sigma),
-                       sr=rep(self.sqrt_recip_alphas_cumprod), srm1=rep(self.sqrt_recipm1_alphas_cumprod))
+                       sr=rep(self.sqrt_recip_alphas_cumprod), srm1=rep(self.sqrt_recipm1_alphas_cumprod),
+                       # constrained sampling: the held elements' level rows, and the resampling jump x_t = ja x_{t-1} + jb e'
+                       sa=rep(self.sqrt_alphas_cumprod), s1=rep(self.sqrt_one_minus_alphas_cumprod),
+                       ja=rep((1.0 - self.betas).sqrt()), jb=rep(self.betas.sqrt()))
             if self.objective == "pred_noise":                                        # x_start = sr x - srm1 eps (DD:589-593)
                 tab.update(xa=tab["sr"], xb=tab["srm1"])
             elif self.objective == "pred_v":                                          # x_start = sqrt_ac x - sqrt_1mac v (DD:607-611)
-                tab.update(xa=rep(self.sqrt_alphas_cumprod), xb=rep(self.sqrt_one_minus_alphas_cumprod))
+                tab.update(xa=tab["sa"], xb=tab["s1"])
             self._samp_tab = (key, tab)
         return self._samp_tab[1]
 
     @torch.no_grad()
-    def p_sample_loop(self, shape, return_all_timesteps=False, external_cond=None, additional_tgt=None, verbose=False, x_T=None):
+    def p_sample_loop(self, shape, return_all_timesteps=False, external_cond=None, additional_tgt=None, verbose=False, x_T=None,
+                      known=None, resample=1):
         """DD:700-729 (no per-step print / host sync).  `x_T` (optional, not in the reference): the start of the chains (DD:705).
         A step is: one UNet call, one in-place normal_ into a reused buffer, one fused update kernel writing into the other of
-        two ping-pong images -- no per-step allocation, no coefficient gathers (rows of `_sampling_tables`)."""
+        two ping-pong images -- no per-step allocation, no coefficient gathers (rows of `_sampling_tables`).
+        `known` / `resample` (optional, not in the reference): constrained sampling, see `sample`; known is in the loop's own range
+        ([-1, 1]), as external_cond and x_T are."""
+        known = self._check_known(shape, known, resample, additional_tgt)
         img = torch.randn(shape, device=self.device) if x_T is None else L.f32c(x_T)
         assert tuple(img.shape) == tuple(shape)
+        if known is not None:
+            return self._p_sample_loop_known(img, return_all_timesteps, external_cond, known, resample)
         if additional_tgt is not None:                                                # target='target': the general step (DD:676-698)
             imgs, additionals = [img], [None]
             for i, t in enumerate(reversed(range(0, self.num_timesteps))):
@@ -737,11 +781,44 @@ class ConditionalDiffusion(nn.Module):
                 imgs.append(img.clone())
         return self.unnormalize(img if not return_all_timesteps else torch.stack(imgs, dim=1))             # DD:725-726
 
+    def _p_sample_loop_known(self, img, return_all_timesteps, external_cond, known, resample):
+        """p_sample_loop with held elements (ofd_ddpm_update_known) and RePaint's resampling: every step t > 0 is run `resample` times,
+        and between two runs the whole tensor goes back one level, x_t = sqrt(1 - beta_t) x_{t-1} + sqrt(beta_t) e' with a fresh draw
+        (ofd_q_sample on two cached rows).  resample * (T - 1) + 1 UNet calls; the trajectory keeps one frame per level."""
+        imgs = [img]
+        stride = self.trajectory_stride
+        b, n = img.shape[0], img[0].numel()
+        tab = self._sampling_tables(b, img.device)
+        pong = [torch.empty_like(img), torch.empty_like(img)]
+        noise, x_start = torch.empty_like(img), torch.empty_like(img)
+        lib, obj = L.lib(), self._obj
+        writes = 0                                                                    # img is x_T or pong[(writes - 1) & 1]
+        for i, t in enumerate(reversed(range(0, self.num_timesteps))):
+            for r in range(resample if t > 0 else 1):
+                if r > 0:                                                             # back to level t
+                    noise.normal_()
+                    nxt = pong[writes & 1]
+                    L.check(lib.ofd_q_sample(L.ptr(img), L.ptr(noise), L.ptr(tab["ja"][t]), L.ptr(tab["jb"][t]), L.ptr(nxt), b, n, L.stream()))
+                    img, writes = nxt, writes + 1
+                out = self._same_shape(L.f32c(self.model_with_condition(img, tab["t"][t], None, external_cond=external_cond)), img)
+                if t > 0:
+                    noise.normal_()                                                   # DD:687; the held elements ride on the same draw
+                nxt = pong[writes & 1]
+                L.check(lib.ofd_ddpm_update_known(obj, L.ptr(img), L.ptr(out), L.ptr(noise) if t > 0 else None, L.ptr(tab["c1"][t]),
+                                                  L.ptr(tab["c2"][t]), L.ptr(tab["sigma"][t]), *self._xab(tab, t), L.ptr(known), None,
+                                                  *self._known_rows(tab, t - 1), L.ptr(nxt), L.ptr(x_start), b, n, L.stream()))
+                img, writes = nxt, writes + 1
+            if return_all_timesteps and (stride is None or (i + 1) % stride == 0 or t == 0):
+                imgs.append(img.clone())
+        return self.unnormalize(img if not return_all_timesteps else torch.stack(imgs, dim=1))
+
     # -- DDIM --------------------------------------------------------------------------------
     @torch.no_grad()
-    def ddim_sample(self, shape, return_all_timesteps=False, external_cond=None, additional_tgt=None, x_T=None):
+    def ddim_sample(self, shape, return_all_timesteps=False, external_cond=None, additional_tgt=None, x_T=None, known=None, resample=1):
         """DD:731-774; accepts (and ignores) additional_tgt so that sample() can reach it.  `x_T` (optional, not in
-        the reference) starts the chains from a given tensor instead of a fresh draw (DD:741)."""
+        the reference) starts the chains from a given tensor instead of a fresh draw (DD:741).  `known` (optional, not in the
+        reference): constrained sampling, see `sample`; in the loop's own range ([-1, 1]).  resample > 1 is DDPM's: ValueError."""
+        known = self._check_known(shape, known, resample, additional_tgt, ddpm=False)
         batch, device, T, S, eta = shape[0], self.device, self.num_timesteps, self.sampling_timesteps, self.ddim_sampling_eta
         times = torch.linspace(-1, T - 1, steps=S + 1)
         times = list(reversed(times.int().tolist()))
@@ -759,7 +836,10 @@ class ConditionalDiffusion(nn.Module):
         alpha, alpha_next = ac[tt], ac[tn]
         sigma = eta * ((1 - alpha / alpha_next) * (1 - alpha_next) / (1 - alpha)).sqrt()
         c = (1 - alpha_next - sigma ** 2).sqrt()
-        coef = torch.stack((alpha_next.sqrt(), c, sigma), dim=1).to(torch.float32).reshape(len(time_pairs), 3, 1).repeat(1, 1, batch).contiguous()
+        # row 3, sqrt(1 - alpha_next), is read by the constrained step only (with row 0: the level the held elements go to)
+        coef = torch.stack((alpha_next.sqrt(), c, sigma, (1 - alpha_next).sqrt()), dim=1).to(torch.float32)
+        coef = coef.reshape(len(time_pairs), 4, 1).repeat(1, 1, batch).contiguous()
+        x_T = img                                                                        # never written: the loop writes to pong
         pong = [torch.empty_like(img), torch.empty_like(img)]
         noise = torch.empty_like(img) if (eta > 0 or self.ddim_draw_unused_noise) else None
         lib, obj = L.lib(), self._obj
@@ -769,10 +849,18 @@ class ConditionalDiffusion(nn.Module):
             if noise is not None and not last:
                 noise.normal_()                                                          # DD:763 (eta == 0: only with ddim_draw_unused_noise)
             nxt = pong[i & 1]
-            L.check(lib.ofd_ddim_update_obj(obj, L.ptr(img), L.ptr(out), L.ptr(noise) if not last else None, L.ptr(tab["sr"][time]),
-                                            L.ptr(tab["srm1"][time]), *self._xab(tab, time), None if last else L.ptr(coef[i, 0]),
-                                            None if last else L.ptr(coef[i, 1]), None if last else L.ptr(coef[i, 2]), int(last), L.ptr(nxt), None,
-                                            batch, n, L.stream()))
+            if known is not None:
+                L.check(lib.ofd_ddim_update_known(obj, L.ptr(img), L.ptr(out), L.ptr(noise) if not last else None, L.ptr(tab["sr"][time]),
+                                                  L.ptr(tab["srm1"][time]), *self._xab(tab, time), None if last else L.ptr(coef[i, 0]),
+                                                  None if last else L.ptr(coef[i, 1]), None if last else L.ptr(coef[i, 2]), int(last),
+                                                  L.ptr(known), None if (last or noise is not None) else L.ptr(x_T),
+                                                  None if last else L.ptr(coef[i, 0]), None if last else L.ptr(coef[i, 3]), L.ptr(nxt), None,
+                                                  batch, n, L.stream()))
+            else:
+                L.check(lib.ofd_ddim_update_obj(obj, L.ptr(img), L.ptr(out), L.ptr(noise) if not last else None, L.ptr(tab["sr"][time]),
+                                                L.ptr(tab["srm1"][time]), *self._xab(tab, time), None if last else L.ptr(coef[i, 0]),
+                                                None if last else L.ptr(coef[i, 1]), None if last else L.ptr(coef[i, 2]), int(last), L.ptr(nxt),
+                                                None, batch, n, L.stream()))
             img = nxt
             if return_all_timesteps and (stride is None or (i + 1) % stride == 0 or last):
                 imgs.append(img.clone())
@@ -780,27 +868,36 @@ class ConditionalDiffusion(nn.Module):
 
     # -- DPM-Solver++ (not in the reference) --------------------------------------------------
     def _dpmpp_tables(self, batch, device):
-        """(grid, per-step orders, (S, 4, batch) fp32 rows cx / w0 / w1 / w2) for this sampler's settings, computed once in float64 from
-        alphas_cumprod and cached like _sampling_tables: a step reads rows, no allocation, gather or host sync"""
+        """(grid, per-step orders, (S, 6, batch) fp32 rows cx / w0 / w1 / w2 and, for the constrained step, sqrt(ac) / sqrt(1 - ac) of the
+        next grid point) for this sampler's settings, computed once in float64 from alphas_cumprod and cached like _sampling_tables: a
+        step reads rows, no allocation, gather or host sync"""
         ac = self.alphas_cumprod
         key = (batch, str(device), self.sampling_timesteps, self.solver_order, self.sampler_spacing, ac.data_ptr(), ac._version, ac.dtype)
         if getattr(self, "_dpmpp_tab", None) is None or self._dpmpp_tab[0] != key:
             grid = dpmpp_grid(ac, self.sampling_timesteps, self.sampler_spacing)
             coef, orders = dpmpp_coefficients(ac, grid, self.solver_order)
-            rows = coef.to(torch.float32).reshape(len(grid), 4, 1).repeat(1, 1, batch).contiguous().to(device)
+            ac_next = torch.zeros(len(grid), dtype=torch.float64)                     # the last row (the final evaluation) stays zero
+            ac_next[:-1] = ac.detach().to("cpu", torch.float64)[torch.tensor(grid[1:], dtype=torch.long)]
+            coef = torch.cat((coef, ac_next.sqrt().reshape(-1, 1), (1.0 - ac_next).sqrt().reshape(-1, 1)), dim=1)
+            coef[-1] = 0.0
+            rows = coef.to(torch.float32).reshape(len(grid), 6, 1).repeat(1, 1, batch).contiguous().to(device)
             self._dpmpp_tab = (key, (grid, orders, rows))
         return self._dpmpp_tab[1]
 
     @torch.no_grad()
-    def dpmpp_sample(self, shape, return_all_timesteps=False, external_cond=None, additional_tgt=None, x_T=None):
+    def dpmpp_sample(self, shape, return_all_timesteps=False, external_cond=None, additional_tgt=None, x_T=None, known=None, resample=1):
         """DPM-Solver++ multistep sampling (include/ofd.h, ofd_dpmpp_update): one UNet call per grid point, S - 1 solver steps and a
         final evaluation that returns the clamped prediction.  Signature, x_T, trajectory_stride and the (B, S + 1, C, H, W)
         trajectory are ddim_sample's.  With additional_tgt (FlowDiffuser's target='target') the model's extra output channels are
         returned per step as p_sample_loop returns them: (images, [None, out_1, ..., out_S]).  A step is one UNet call and one fused
-        update launch; the predictions live in a three-slot ring rotated by pointer, the image in two ping-pong buffers."""
+        update launch; the predictions live in a three-slot ring rotated by pointer, the image in two ping-pong buffers.
+        `known`: constrained sampling, see `sample`; in the loop's own range ([-1, 1]).  The ring stores the predictions with the held
+        elements already replaced.  resample > 1 is DDPM's: ValueError."""
+        known = self._check_known(shape, known, resample, additional_tgt, ddpm=False)
         batch = shape[0]
         img = torch.randn(shape, device=self.device) if x_T is None else L.f32c(x_T)
         assert tuple(img.shape) == tuple(shape)
+        x_T = img                                                                        # never written: the loop writes to pong
         grid, orders, coef = self._dpmpp_tables(batch, img.device)
         tab = self._sampling_tables(batch, img.device)
         imgs, additionals = [img], [None]
@@ -819,10 +916,19 @@ class ConditionalDiffusion(nn.Module):
             order = 1 if last else orders[i]
             c = coef[i]
             nxt = pong[i & 1]
-            L.check(lib.ofd_dpmpp_update(obj, order, L.ptr(img), L.ptr(out), *self._xab(tab, t),
-                                         L.ptr(ring[(i - 1) % 3]) if order >= 2 else None, L.ptr(ring[(i - 2) % 3]) if order >= 3 else None,
-                                         L.ptr(c[0]), L.ptr(c[1]), L.ptr(c[2]), L.ptr(c[3]), int(last), L.ptr(nxt),
-                                         None if last else L.ptr(ring[i % 3]), batch, n, L.stream()))
+            if known is not None:
+                L.check(lib.ofd_dpmpp_update_known(obj, order, L.ptr(img), L.ptr(out), *self._xab(tab, t),
+                                                   L.ptr(ring[(i - 1) % 3]) if order >= 2 else None,
+                                                   L.ptr(ring[(i - 2) % 3]) if order >= 3 else None,
+                                                   L.ptr(c[0]), L.ptr(c[1]), L.ptr(c[2]), L.ptr(c[3]), int(last), L.ptr(known),
+                                                   None if last else L.ptr(x_T), None if last else L.ptr(c[4]),
+                                                   None if last else L.ptr(c[5]), L.ptr(nxt), None if last else L.ptr(ring[i % 3]),
+                                                   batch, n, L.stream()))
+            else:
+                L.check(lib.ofd_dpmpp_update(obj, order, L.ptr(img), L.ptr(out), *self._xab(tab, t),
+                                             L.ptr(ring[(i - 1) % 3]) if order >= 2 else None, L.ptr(ring[(i - 2) % 3]) if order >= 3 else None,
+                                             L.ptr(c[0]), L.ptr(c[1]), L.ptr(c[2]), L.ptr(c[3]), int(last), L.ptr(nxt),
+                                             None if last else L.ptr(ring[i % 3]), batch, n, L.stream()))
             img = nxt
             if return_all_timesteps and (stride is None or (i + 1) % stride == 0 or last):
                 imgs.append(img.clone())
@@ -830,19 +936,31 @@ class ConditionalDiffusion(nn.Module):
         return (res, additionals) if additional_tgt is not None else res
 
     @torch.no_grad()
-    def sample(self, batch_size=16, return_all_timesteps=False, external_cond=None, additional_tgt=None):
+    def sample(self, batch_size=16, return_all_timesteps=False, external_cond=None, additional_tgt=None, known=None, resample=1):
         """DD:776-784, with image_size allowed to be (H, W).  external_cond is normalised once per call (DD:778-779); the loops
-        unnormalise what they return."""
+        unnormalise what they return.
+
+        Constrained sampling (not in the reference): `known` is shaped like the result, (batch_size, channels, H, W),
+        in the range sample() returns, and normalised once per call as external_cond is.  A NaN element is free; any other is held:
+        the result has clamp(known) there, and every step of the chain carries the held elements at the step's noise level inside
+        the fused update launch (no extra pass).  `resample=r` (DDPM only, RePaint's harmonisation) runs each step t > 0 r times
+        with a one-level re-noising between the runs: r UNet calls per step, r (T - 1) + 1 in all.  known=None is the unconstrained
+        path, launch for launch."""
+        H, W = self._hw()
+        shape = (batch_size, self.channels, H, W)
+        ddpm = self.sampler != "dpmpp" and not self.is_ddim_sampling
+        known = self._check_known(shape, known, resample, additional_tgt, ddpm=ddpm)
         if external_cond is not None:
             external_cond = self.normalize(external_cond)
-        H, W = self._hw()
         if self.sampler == "dpmpp":
             fn = self.dpmpp_sample
         else:
             fn = self.p_sample_loop if not self.is_ddim_sampling else self.ddim_sample
         assert external_cond is None or external_cond.shape[0] == batch_size
-        return fn((batch_size, self.channels, H, W), return_all_timesteps=return_all_timesteps,
-                  external_cond=external_cond, additional_tgt=additional_tgt)
+        if known is None:
+            return fn(shape, return_all_timesteps=return_all_timesteps, external_cond=external_cond, additional_tgt=additional_tgt)
+        return fn(shape, return_all_timesteps=return_all_timesteps, external_cond=external_cond, known=self.normalize(known),
+                  resample=resample)
 
     # -- training loss -----------------------------------------------------------------------
     @torch.no_grad()

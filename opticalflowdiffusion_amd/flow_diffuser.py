@@ -223,8 +223,34 @@ class FlowDiffuser(_Base):
                               model_out_override=override)
         return self.model(tgt, external_cond=cond, model_out_override=override)
 
-    def sample(self, cond, flow):                                           # FD:189-215
+    def known_from_flow(self, known_flow):
+        """the `known` tensor of ConditionalDiffusion.sample for a (B, 2, H, W) flow in pixels whose NaN elements are free: scaled and
+        clamped as `preprocess` scales the ground-truth flow (NaNs stay NaN); target 'flow' diffuses exactly that tensor, 'joint'
+        carries it in its last two channels behind `dim` free image (or latent) channels.  Host logic: any device, no engine call."""
+        if not self.is_diffusion:
+            raise ValueError("known_flow needs a diffusion model: is_diffusion=False is a plain regression, there is no chain to constrain")
+        if self.target not in ("flow", "joint"):
+            raise ValueError(f"known_flow is not supported for target={self.target!r}: there the flow is an extra model output, not part "
+                             "of the diffused tensor")
+        if not torch.is_tensor(known_flow) or known_flow.dim() != 4 or known_flow.shape[1] != 2:
+            raise ValueError(f"known_flow must be a (B, 2, H, W) tensor of pixel displacements (NaN = free), got "
+                             f"{tuple(known_flow.shape) if torch.is_tensor(known_flow) else type(known_flow).__name__}")
+        known = torch.clamp(known_flow.float() / self.flow_max, -1.0, 1.0)
+        if self.target == "joint":
+            b, _, h, w = known.shape
+            known = torch.cat((torch.full((b, self.dim, h, w), float("nan"), dtype=known.dtype, device=known.device), known), dim=1)
+        return known
+
+    def sample(self, cond, flow, known_flow=None, resample=1):              # FD:189-215
+        """`known_flow` (optional, not in the reference): (B, 2, H, W) in pixels, NaN = free; the returned flow has
+        clamp(known_flow / flow_max) at the other elements and the sampler fills in the rest consistently (constrained sampling,
+        ConditionalDiffusion.sample).  target 'flow' or 'joint' only.  `resample` as there: DDPM only, `resample` UNet calls per step."""
         bsz = flow.shape[0]
+        kw = {}
+        if known_flow is not None:
+            kw = dict(known=self.known_from_flow(known_flow), resample=resample)
+        elif resample != 1:
+            raise ValueError("resample needs a known_flow to harmonise with")
         if not self.is_diffusion:                                           # FD:204-213
             if self.cfg.target in ["target", "joint"]:
                 samples = self.model(cond, additional_out=True) if self.cfg.target == "target" else self.model(cond)
@@ -234,11 +260,11 @@ class FlowDiffuser(_Base):
         if self.cfg.target == "target":
             samples, flow = self.model.sample(batch_size=bsz, external_cond=cond, additional_tgt=flow, return_all_timesteps=True)
         elif self.cfg.target == "joint":
-            joint = self.model.sample(batch_size=bsz, external_cond=cond, return_all_timesteps=True)
+            joint = self.model.sample(batch_size=bsz, external_cond=cond, return_all_timesteps=True, **kw)
             samples = joint[:, :, :self.dim]
             flow = joint[:, :, self.dim:]
         else:
-            flow = self.model.sample(batch_size=bsz, external_cond=cond, return_all_timesteps=True)
+            flow = self.model.sample(batch_size=bsz, external_cond=cond, return_all_timesteps=True, **kw)
             img = cond[:, :self.dim]
             samples = warp(img, None, flow[:, -1], mode="forward")
         return samples, flow

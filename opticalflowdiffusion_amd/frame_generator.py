@@ -70,20 +70,23 @@ class FrameGenerator(_Base):
     log_grad_norm_stat = FlowDiffuser.log_grad_norm_stat                                             # DA:103-125 == FD:367-388
 
     @torch.no_grad()
-    def sample(self, cond):
-        """one sampling chain per sample of cond (B, 5, H, W) in [0, 1]; returns (B, 3, H, W) in [0, 1]"""
-        return self.diffusion_model.sample(batch_size=cond.shape[0], external_cond=cond)
+    def sample(self, cond, known=None):
+        """one sampling chain per sample of cond (B, 5, H, W) in [0, 1]; returns (B, 3, H, W) in [0, 1].  `known` (optional, not in
+        the reference): (B, 3, H, W) in [0, 1], NaN = free -- inpainting of the next frame (ConditionalDiffusion.sample)."""
+        if known is None:
+            return self.diffusion_model.sample(batch_size=cond.shape[0], external_cond=cond)
+        return self.diffusion_model.sample(batch_size=cond.shape[0], external_cond=cond, known=known)
 
     @torch.no_grad()
-    def rollout(self, batch):
+    def rollout(self, batch, known=None):
         """DA:84-100: batch (B, V, 8, H, W); frame k is sampled with cond = batch[:, k, 3:], whose last-frame channels are replaced
-        by frame k-1's sample for k >= 1.  Returns (V, B, 3, H, W)."""
+        by frame k-1's sample for k >= 1.  Returns (V, B, 3, H, W).  `known` (optional): (B, V, 3, H, W), frame k's `known`."""
         samples = []
         for k in range(batch.shape[1]):
             cond = batch[:, k, 3:].clone()
             if k != 0:
                 cond[:, :3] = samples[-1][:, :3]                                                     # DA:90-91
-            samples.append(self.sample(cond))
+            samples.append(self.sample(cond) if known is None else self.sample(cond, known=known[:, k]))
         return torch.stack(samples, dim=0)
 
     def validation_step(self, batch, batch_idx):                                                     # DA:64-100

@@ -8,7 +8,13 @@ Kernel (ofd_dpmpp_update, pred_x0, orders 1 / 2 / 3 at 16 / 20 / 24 B per elemen
 back-to-back launches (HIP events), and TB/s against the bytes the call must move.  Sample: FlowDiffuser.sample wall time (HIP events
 around the whole chain, trajectory kept as validation_step keeps it) for DDIM-50, 2M-10, 2M-20 and 3M-20, with the number of UNet
 calls (the logsnr grid drops duplicate steps: S = 20 is 16 calls at T = 1000).  Mixture: RMS errors against the float64 3M solution
-over all 1000 steps, float64 on the host and fp32 through sample() on the GPU.  One JSON line per record."""
+over all 1000 steps, float64 on the host and fp32 through sample() on the GPU.  One JSON line per record.
+
+Constrained sampling (ofd_*_update_known, ConditionalDiffusion.sample(known=)): each _known kernel next to its unconstrained sibling,
+timed alternately in the same process on the same buffers, GB/s over each call's own algorithmic bytes (stated per record; half the
+elements held); FlowDiffuser.sample with and without a half-image known_flow for 2M-20 and DDIM-50; and, into
+`--conditioning-out`, the figures of tests/test_constrained_sampling_gpu.py::test_the_constraint_conditions_the_free_half (float64
+host restatement and GPU)."""
 import argparse
 import json
 import os
@@ -56,6 +62,95 @@ def kernel_records(shape, steps, warmup):
         recs.append(dict(what="dpmpp_update", order=order, objective="pred_x0", shape=list(shape), us=ms * 1e3 / LAUNCHES,
                          us_min=best * 1e3 / LAUNCHES, bytes=by, tbps=by / (ms * 1e-3 / LAUNCHES) / 1e12,
                          tbps_best=by / (best * 1e-3 / LAUNCHES) / 1e12))
+    return recs
+
+
+def known_kernel_records(shape, steps, warmup):
+    """every _known entry point against its sibling: (name, bytes per element, call) pairs timed in alternation.  Bytes: the reads
+    and writes the call must make -- x_t, model_out, [noise], [histories], out, x_start / d_out, and for _known also known and, where
+    no noise is read, e0.  The DDPM / DDIM pairs run a noisy step (sigma > 0: 20 B per element, 24 with known, whose held elements
+    ride on the same noise), the DPM-Solver++ pairs read e0 (12 + 4 order B per element, 8 more with known).  `footprint_mb` is the
+    distinct memory one call touches: below the 256 MiB Infinity Cache back-to-back launches are served partly from it."""
+    B = shape[0]
+    n = shape[1] * shape[2] * shape[3]
+    lib, st, P = L.lib(), L.stream(), L.ptr
+    x, mo, nz, d1, d2, out, xs, e0 = (torch.randn(shape, device="cuda") for _ in range(8))
+    known = torch.randn(shape, device="cuda")
+    known[torch.rand(shape, device="cuda") < 0.5] = float("nan")
+    co = [torch.rand(B, device="cuda") + 0.25 for _ in range(6)]
+    c = [P(v) for v in co]
+    pairs = [("ddpm", 20, 24,
+              lambda: lib.ofd_ddpm_update_obj(0, P(x), P(mo), P(nz), c[0], c[1], c[2], None, None, P(out), P(xs), B, n, st),
+              lambda: lib.ofd_ddpm_update_known(0, P(x), P(mo), P(nz), c[0], c[1], c[2], None, None, P(known), None, c[4], c[5], P(out),
+                                                P(xs), B, n, st)),
+             ("ddim", 20, 24,
+              lambda: lib.ofd_ddim_update_obj(0, P(x), P(mo), P(nz), c[0], c[1], None, None, c[2], c[3], c[4], 0, P(out), P(xs), B, n, st),
+              lambda: lib.ofd_ddim_update_known(0, P(x), P(mo), P(nz), c[0], c[1], None, None, c[2], c[3], c[4], 0, P(known), None, c[4],
+                                                c[5], P(out), P(xs), B, n, st))]
+    for order in (1, 2, 3):
+        h = (P(d1) if order >= 2 else None, P(d2) if order >= 3 else None)
+        pairs.append((f"dpmpp{order}", 12 + 4 * order, 20 + 4 * order,
+                      lambda h=h, order=order: lib.ofd_dpmpp_update(0, order, P(x), P(mo), None, None, *h, c[0], c[1], c[2], c[3], 0, P(out),
+                                                                    P(xs), B, n, st),
+                      lambda h=h, order=order: lib.ofd_dpmpp_update_known(0, order, P(x), P(mo), None, None, *h, c[0], c[1], c[2], c[3], 0,
+                                                                          P(known), P(e0), c[4], c[5], P(out), P(xs), B, n, st)))
+    recs = []
+    for name, by_plain, by_known, plain, constrained in pairs:
+        def batch(fn):
+            def run():
+                for _ in range(LAUNCHES):
+                    L.check(fn())
+            return run
+        ms = {"plain": [], "known": []}
+        for rnd in range(4):                                            # alternate the two, so that drift hits both alike
+            for key, fn in (("plain", plain), ("known", constrained)):
+                ms[key].append(timed(batch(fn), steps, warmup if rnd == 0 else 1))
+        rec = dict(what="known_kernel_pair", kernel=name, objective="pred_x0", shape=list(shape), held_fraction=0.5,
+                   launches_per_sample=LAUNCHES, samples_per_variant=4 * steps)
+        for key, by in (("plain", by_plain), ("known", by_known)):
+            mean = sum(m for m, _ in ms[key]) / len(ms[key])
+            best = min(b for _, b in ms[key])
+            rec[key] = dict(bytes_per_element=by, bytes=by * B * n, footprint_mb=by * B * n / 2 ** 20, us=mean * 1e3 / LAUNCHES, us_min=best * 1e3 / LAUNCHES,
+                            gbps=by * B * n / (mean * 1e-3 / LAUNCHES) / 1e9, gbps_best=by * B * n / (best * 1e-3 / LAUNCHES) / 1e9)
+        rec["known_over_plain_gbps"] = rec["known"]["gbps"] / rec["plain"]["gbps"]
+        recs.append(rec)
+    return recs
+
+
+def constrained_sample_records(B, H, W, targets, steps, warmup):
+    """FlowDiffuser.sample with and without a known_flow that holds the left half of the image at zero motion"""
+    recs = []
+    for target in targets:
+        for name, kw in CONFIGS:
+            if name not in ("2M-20", "ddim-50"):
+                continue
+            torch.manual_seed(0)
+            fd = FlowDiffuser(dict(target=target, image_size=[H, W], timesteps=1000, flow_max=20, zero_init=False, **kw)).cuda()
+            img = torch.rand(B, 3, H, W, device="cuda")
+            flow = (torch.rand(B, 2, H, W, device="cuda") * 2 - 1) * 10
+            kf = torch.full((B, 2, H, W), float("nan"), device="cuda")
+            kf[..., :W // 2] = 0.0
+            with torch.no_grad():
+                _, cond, flow_ = fd.preprocess((img, img, flow), aug=False)
+                plain = timed(lambda: fd.sample(cond, flow_), steps, warmup)
+                held = timed(lambda: fd.sample(cond, flow_, known_flow=kf), steps, warmup)
+            recs.append(dict(what="flow_diffuser.sample.known_flow", target=target, sampler=name, B=B, H=H, W=W, held="left half",
+                             ms_plain=plain[0], ms_plain_min=plain[1], ms_known=held[0], ms_known_min=held[1],
+                             known_over_plain=held[0] / plain[0]))
+            del fd
+            torch.cuda.empty_cache()
+    return recs
+
+
+def conditioning_records():
+    from test_constrained_sampling_cpu import restatement_figures
+    from test_constrained_sampling_gpu import gpu_conditioning_figures
+    names = ("unconstrained", "r1", "r4")
+    recs = []
+    for where, fig in (("host_f64_restatement", restatement_figures()), ("gpu_f32", gpu_conditioning_figures())):
+        recs.append(dict(what="rms(free half - 0.5), constant-image prior, left half held at 0.5", where=where, chains=64, size="1x32x32",
+                         sampler="ddpm", timesteps=50, beta_schedule="linear", rms={k: fig[k][0] for k in names},
+                         standard_error={k: fig[k][1] for k in names}))
     return recs
 
 
@@ -112,22 +207,29 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--skip-sample", action="store_true")
+    ap.add_argument("--skip-mixture", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sampler_bench.jsonl"))
+    ap.add_argument("--conditioning-out", default=os.path.join(ROOT, "profiles", "constrained_sampling.jsonl"))
     a = ap.parse_args()
     dev = torch.cuda.get_device_properties(0).name
     recs = []
     for s in a.kernel_shapes.split(","):
         recs += kernel_records(tuple(int(v) for v in s.split("x")), a.steps, a.warmup)
+    for s in a.kernel_shapes.split(","):                  # the second default shape is past the 256 MiB Infinity Cache for every pair
+        recs += known_kernel_records(tuple(int(v) for v in s.split("x")), a.steps, a.warmup)
     if not a.skip_sample:
         B, H, W = (int(v) for v in a.sample_size.split("x"))
         recs += sample_records(B, H, W, a.targets.split(","), max(2, a.steps // 10), 1)
-    recs += mixture_records()
-    with open(a.out, "w") as f:
-        for r in recs:
-            r["device"] = dev
-            line = json.dumps(r)
-            print(line)
-            f.write(line + "\n")
+        recs += constrained_sample_records(B, H, W, a.targets.split(","), max(2, a.steps // 10), 1)
+    if not a.skip_mixture:
+        recs += mixture_records()
+    for path, rs in ((a.out, recs), (a.conditioning_out, conditioning_records())):
+        with open(path, "w") as f:
+            for r in rs:
+                r["device"] = dev
+                line = json.dumps(r)
+                print(line)
+                f.write(line + "\n")
 
 
 if __name__ == "__main__":
