@@ -307,6 +307,13 @@ static inline dim3 ew_grid(int B, size_t nv) {
     return dim3((unsigned)b, (unsigned)B);
 }
 
+// The float4 / scalar choice of every elementwise launch: f(std::integral_constant<int, VEC>{}, grid, stream) with VEC = 4 when
+// n_per_sample % 4 == 0 (and vec_ok, the caller's own extra condition), else 1; grid = ew_grid(B, n / VEC), 256 threads per block.
+template <typename F> static void ew_launch(int B, size_t n, void* stream, F&& f, bool vec_ok = true) {
+    if (n % 4 == 0 && vec_ok) f(std::integral_constant<int, 4>{}, ew_grid(B, n / 4), (hipStream_t)stream);
+    else f(std::integral_constant<int, 1>{}, ew_grid(B, n), (hipStream_t)stream);
+}
+
 }  // namespace ofd
 using namespace ofd;
 
@@ -329,14 +336,11 @@ extern "C" int ofd_diffusion_prep(int objective, const float* x0, const float* n
     const size_t n = (size_t)C * hw;
     OFD_EW_ARGS_OK(B, n);
     OFD_CHECK_ARG(x0 && noise && sqrt_ac && sqrt_1mac && x_t, "diffusion_prep: null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    const bool v4 = n % 4 == 0 && (!offset || hw % 4 == 0);
     obj_dispatch(objective, [&](auto o) {
-        constexpr int OBJ = decltype(o)::value;
-        if (v4) diffusion_prep_kernel<OBJ, 4><<<ew_grid(B, n / 4), 256, 0, s>>>(x0, noise, offset, offset_strength, C, hw, sqrt_ac, sqrt_1mac,
-                                                                               normalize, x_t, target, x_norm, n);
-        else diffusion_prep_kernel<OBJ, 1><<<ew_grid(B, n), 256, 0, s>>>(x0, noise, offset, offset_strength, C, hw, sqrt_ac, sqrt_1mac,
-                                                                        normalize, x_t, target, x_norm, n);
+        ew_launch(B, n, stream, [&](auto vec, dim3 grid, hipStream_t s) {
+            diffusion_prep_kernel<decltype(o)::value, decltype(vec)::value><<<grid, 256, 0, s>>>(
+                x0, noise, offset, offset_strength, C, hw, sqrt_ac, sqrt_1mac, normalize, x_t, target, x_norm, n);
+        }, !offset || hw % 4 == 0);
     });
     OFD_LAUNCH_CHECK();
     return OFD_OK;
@@ -348,52 +352,54 @@ extern "C" int ofd_q_sample(const float* x0, const float* noise, const float* sq
     return ofd_diffusion_prep(PRED_X0, x0, noise, nullptr, 0.0f, sqrt_ac, sqrt_1mac, 0, out, nullptr, nullptr, B, 1, n, stream);
 }
 
-extern "C" int ofd_ddpm_update_obj(int objective, const float* x_t, const float* model_out, const float* noise, const float* coef1,
-                                   const float* coef2, const float* sigma, const float* xa, const float* xb, float* out, float* x_start,
-                                   int B, size_t n, void* stream) {
+// The reverse steps.  One implementation per step kind serves its plain and its _known entry point: `name` is the entry point's name in
+// the messages, `kn` the constrained step's KnownArgs (null: the plain step, launched without the trailing pack).  The checks a _known
+// entry point adds come after the ones it shares; `fin`: the step writes known itself and reads neither e nor the next level's rows.
+#define OFD_KNOWN_ARGS_OK(name, kn, fin)                                                                                      \
+    OFD_CHECK_ARG((kn)->known, "%s: null known", name);                                                                        \
+    OFD_CHECK_ARG((fin) || ((kn)->sa && (kn)->s1), "%s: missing sqrt_ac_next / sqrt_1mac_next", name);                         \
+    OFD_CHECK_ARG((fin) || (kn)->e, "%s: a step without noise needs e0", name)
+
+static int ddpm_update_impl(const char* name, int objective, const float* x_t, const float* model_out, const float* noise,
+                            const float* coef1, const float* coef2, const float* sigma, const float* xa, const float* xb,
+                            const KnownArgs* kn, float* out, float* x_start, int B, size_t n, void* stream) {
     OFD_OBJ_OK(objective);
     OFD_EW_ARGS_OK(B, n);
-    OFD_CHECK_ARG(x_t && model_out && coef1 && coef2 && out, "ddpm_update: null pointer");
-    OFD_CHECK_ARG(objective == PRED_X0 || (xa && xb), "ddpm_update: missing x_start coefficients");
-    hipStream_t s = (hipStream_t)stream;
-    obj_dispatch(objective, [&](auto o) {
-        constexpr int OBJ = decltype(o)::value;
-        if (n % 4 == 0) ddpm_update_kernel<OBJ, 4><<<ew_grid(B, n / 4), 256, 0, s>>>(x_t, model_out, noise, coef1, coef2, sigma, xa, xb, out, x_start, n);
-        else ddpm_update_kernel<OBJ, 1><<<ew_grid(B, n), 256, 0, s>>>(x_t, model_out, noise, coef1, coef2, sigma, xa, xb, out, x_start, n);
-    });
+    OFD_CHECK_ARG(x_t && model_out && coef1 && coef2 && out, "%s: null pointer", name);
+    OFD_CHECK_ARG(objective == PRED_X0 || (xa && xb), "%s: missing x_start coefficients", name);
+    if (kn) {
+        OFD_KNOWN_ARGS_OK(name, kn, !kn->sa);
+        OFD_CHECK_ARG(kn->sa || !noise, "%s: the final step (no sqrt_ac_next) takes no noise", name);
+    }
+    auto launch = [&](auto... k) {
+        obj_dispatch(objective, [&](auto o) {
+            ew_launch(B, n, stream, [&](auto vec, dim3 grid, hipStream_t s) {
+                ddpm_update_kernel<decltype(o)::value, decltype(vec)::value><<<grid, 256, 0, s>>>(
+                    x_t, model_out, noise, coef1, coef2, sigma, xa, xb, out, x_start, n, k...);
+            });
+        });
+    };
+    if (!kn) launch();
+    else launch(*kn);
     OFD_LAUNCH_CHECK();
     return OFD_OK;
 }
 
-// the checks the three _known entry points share; `e` is the stream rule 3 of include/ofd.h reads: the step's noise, else e0
-#define OFD_KNOWN_ARGS_OK(name, fin, e)                                                                                      \
-    OFD_CHECK_ARG(known, name ": null known");                                                                                \
-    OFD_CHECK_ARG((fin) || (sqrt_ac_next && sqrt_1mac_next), name ": missing sqrt_ac_next / sqrt_1mac_next");                 \
-    OFD_CHECK_ARG((fin) || (e), name ": a step without noise needs e0")
+extern "C" int ofd_ddpm_update_obj(int objective, const float* x_t, const float* model_out, const float* noise, const float* coef1,
+                                   const float* coef2, const float* sigma, const float* xa, const float* xb, float* out, float* x_start,
+                                   int B, size_t n, void* stream) {
+    return ddpm_update_impl("ddpm_update", objective, x_t, model_out, noise, coef1, coef2, sigma, xa, xb, nullptr, out, x_start, B, n,
+                            stream);
+}
 
 extern "C" int ofd_ddpm_update_known(int objective, const float* x_t, const float* model_out, const float* noise, const float* coef1,
                                      const float* coef2, const float* sigma, const float* xa, const float* xb, const float* known,
                                      const float* e0, const float* sqrt_ac_next, const float* sqrt_1mac_next, float* out,
                                      float* x_start, int B, size_t n, void* stream) {
-    OFD_OBJ_OK(objective);
-    OFD_EW_ARGS_OK(B, n);
-    OFD_CHECK_ARG(x_t && model_out && coef1 && coef2 && out, "ddpm_update_known: null pointer");
-    OFD_CHECK_ARG(objective == PRED_X0 || (xa && xb), "ddpm_update_known: missing x_start coefficients");
     const bool fin = !sqrt_ac_next || !sqrt_1mac_next;
     const KnownArgs kn{known, noise ? noise : e0, fin ? nullptr : sqrt_ac_next, fin ? nullptr : sqrt_1mac_next};
-    OFD_KNOWN_ARGS_OK("ddpm_update_known", fin, kn.e);
-    OFD_CHECK_ARG(!fin || !noise, "ddpm_update_known: the final step (no sqrt_ac_next) takes no noise");
-    hipStream_t s = (hipStream_t)stream;
-    obj_dispatch(objective, [&](auto o) {
-        constexpr int OBJ = decltype(o)::value;
-        if (n % 4 == 0)
-            ddpm_update_kernel<OBJ, 4><<<ew_grid(B, n / 4), 256, 0, s>>>(x_t, model_out, noise, coef1, coef2, sigma, xa, xb, out, x_start, n,
-                                                                        kn);
-        else
-            ddpm_update_kernel<OBJ, 1><<<ew_grid(B, n), 256, 0, s>>>(x_t, model_out, noise, coef1, coef2, sigma, xa, xb, out, x_start, n, kn);
-    });
-    OFD_LAUNCH_CHECK();
-    return OFD_OK;
+    return ddpm_update_impl("ddpm_update_known", objective, x_t, model_out, noise, coef1, coef2, sigma, xa, xb, &kn, out, x_start, B, n,
+                            stream);
 }
 
 extern "C" int ofd_ddpm_update(const float* x_t, const float* model_out, const float* noise, const float* coef1,
@@ -401,26 +407,37 @@ extern "C" int ofd_ddpm_update(const float* x_t, const float* model_out, const f
     return ofd_ddpm_update_obj(PRED_X0, x_t, model_out, noise, coef1, coef2, sigma, nullptr, nullptr, out, x_start, B, n, stream);
 }
 
+static int ddim_update_impl(const char* name, int objective, const float* x_t, const float* model_out, const float* noise,
+                            const float* sqrt_recip_ac, const float* sqrt_recipm1_ac, const float* xa, const float* xb,
+                            const float* sqrt_alpha_next, const float* c, const float* sigma, int last, const KnownArgs* kn, float* out,
+                            float* x_start, int B, size_t n, void* stream) {
+    OFD_OBJ_OK(objective);
+    OFD_EW_ARGS_OK(B, n);
+    OFD_CHECK_ARG(x_t && model_out && sqrt_recip_ac && sqrt_recipm1_ac && out, "%s: null pointer", name);
+    OFD_CHECK_ARG(last || (sqrt_alpha_next && c), "%s: missing coefficients", name);
+    OFD_CHECK_ARG(objective == PRED_X0 || (xa && xb), "%s: missing x_start coefficients", name);
+    if (kn) {
+        OFD_KNOWN_ARGS_OK(name, kn, last);
+    }
+    auto launch = [&](auto... k) {
+        obj_dispatch(objective, [&](auto o) {
+            ew_launch(B, n, stream, [&](auto vec, dim3 grid, hipStream_t s) {
+                ddim_update_kernel<decltype(o)::value, decltype(vec)::value><<<grid, 256, 0, s>>>(
+                    x_t, model_out, noise, sqrt_recip_ac, sqrt_recipm1_ac, xa, xb, sqrt_alpha_next, c, sigma, last, out, x_start, n, k...);
+            });
+        });
+    };
+    if (!kn) launch();
+    else launch(*kn);
+    OFD_LAUNCH_CHECK();
+    return OFD_OK;
+}
+
 extern "C" int ofd_ddim_update_obj(int objective, const float* x_t, const float* model_out, const float* noise, const float* sqrt_recip_ac,
                                    const float* sqrt_recipm1_ac, const float* xa, const float* xb, const float* sqrt_alpha_next,
                                    const float* c, const float* sigma, int last, float* out, float* x_start, int B, size_t n, void* stream) {
-    OFD_OBJ_OK(objective);
-    OFD_EW_ARGS_OK(B, n);
-    OFD_CHECK_ARG(x_t && model_out && sqrt_recip_ac && sqrt_recipm1_ac && out, "ddim_update: null pointer");
-    OFD_CHECK_ARG(last || (sqrt_alpha_next && c), "ddim_update: missing coefficients");
-    OFD_CHECK_ARG(objective == PRED_X0 || (xa && xb), "ddim_update: missing x_start coefficients");
-    hipStream_t s = (hipStream_t)stream;
-    obj_dispatch(objective, [&](auto o) {
-        constexpr int OBJ = decltype(o)::value;
-        if (n % 4 == 0)
-            ddim_update_kernel<OBJ, 4><<<ew_grid(B, n / 4), 256, 0, s>>>(x_t, model_out, noise, sqrt_recip_ac, sqrt_recipm1_ac, xa, xb,
-                                                                        sqrt_alpha_next, c, sigma, last, out, x_start, n);
-        else
-            ddim_update_kernel<OBJ, 1><<<ew_grid(B, n), 256, 0, s>>>(x_t, model_out, noise, sqrt_recip_ac, sqrt_recipm1_ac, xa, xb,
-                                                                    sqrt_alpha_next, c, sigma, last, out, x_start, n);
-    });
-    OFD_LAUNCH_CHECK();
-    return OFD_OK;
+    return ddim_update_impl("ddim_update", objective, x_t, model_out, noise, sqrt_recip_ac, sqrt_recipm1_ac, xa, xb, sqrt_alpha_next, c,
+                            sigma, last, nullptr, out, x_start, B, n, stream);
 }
 
 extern "C" int ofd_ddim_update_known(int objective, const float* x_t, const float* model_out, const float* noise,
@@ -428,25 +445,9 @@ extern "C" int ofd_ddim_update_known(int objective, const float* x_t, const floa
                                      const float* sqrt_alpha_next, const float* c, const float* sigma, int last, const float* known,
                                      const float* e0, const float* sqrt_ac_next, const float* sqrt_1mac_next, float* out,
                                      float* x_start, int B, size_t n, void* stream) {
-    OFD_OBJ_OK(objective);
-    OFD_EW_ARGS_OK(B, n);
-    OFD_CHECK_ARG(x_t && model_out && sqrt_recip_ac && sqrt_recipm1_ac && out, "ddim_update_known: null pointer");
-    OFD_CHECK_ARG(last || (sqrt_alpha_next && c), "ddim_update_known: missing coefficients");
-    OFD_CHECK_ARG(objective == PRED_X0 || (xa && xb), "ddim_update_known: missing x_start coefficients");
     const KnownArgs kn{known, noise ? noise : e0, sqrt_ac_next, sqrt_1mac_next};
-    OFD_KNOWN_ARGS_OK("ddim_update_known", last, kn.e);
-    hipStream_t s = (hipStream_t)stream;
-    obj_dispatch(objective, [&](auto o) {
-        constexpr int OBJ = decltype(o)::value;
-        if (n % 4 == 0)
-            ddim_update_kernel<OBJ, 4><<<ew_grid(B, n / 4), 256, 0, s>>>(x_t, model_out, noise, sqrt_recip_ac, sqrt_recipm1_ac, xa, xb,
-                                                                        sqrt_alpha_next, c, sigma, last, out, x_start, n, kn);
-        else
-            ddim_update_kernel<OBJ, 1><<<ew_grid(B, n), 256, 0, s>>>(x_t, model_out, noise, sqrt_recip_ac, sqrt_recipm1_ac, xa, xb,
-                                                                    sqrt_alpha_next, c, sigma, last, out, x_start, n, kn);
-    });
-    OFD_LAUNCH_CHECK();
-    return OFD_OK;
+    return ddim_update_impl("ddim_update_known", objective, x_t, model_out, noise, sqrt_recip_ac, sqrt_recipm1_ac, xa, xb,
+                            sqrt_alpha_next, c, sigma, last, &kn, out, x_start, B, n, stream);
 }
 
 extern "C" int ofd_ddim_update(const float* x_t, const float* model_out, const float* noise, const float* sqrt_recip_ac,
@@ -456,36 +457,47 @@ extern "C" int ofd_ddim_update(const float* x_t, const float* model_out, const f
                                last, out, x_start, B, n, stream);
 }
 
+static int dpmpp_update_impl(const char* name, int objective, int order, const float* x_t, const float* model_out, const float* xa,
+                             const float* xb, const float* d_prev1, const float* d_prev2, const float* cx, const float* w0,
+                             const float* w1, const float* w2, int last, const KnownArgs* kn, float* out, float* d_out, int B, size_t n,
+                             void* stream) {
+    OFD_OBJ_OK(objective);
+    OFD_EW_ARGS_OK(B, n);
+    OFD_CHECK_ARG(order >= 1 && order <= 3, "%s: bad order %d", name, order);
+    OFD_CHECK_ARG(x_t && model_out && out, "%s: null pointer", name);
+    OFD_CHECK_ARG(objective == PRED_X0 || (xa && xb), "%s: missing x_start coefficients", name);
+    OFD_CHECK_ARG(last || (cx && w0), "%s: missing coefficients", name);
+    OFD_CHECK_ARG(last || order < 2 || (d_prev1 && w1), "%s: order %d needs d_prev1 and w1", name, order);
+    OFD_CHECK_ARG(last || order < 3 || (d_prev2 && w2), "%s: order 3 needs d_prev2 and w2", name);
+    if (kn) {
+        OFD_KNOWN_ARGS_OK(name, kn, last);
+        OFD_CHECK_ARG(last || kn->e != out, "%s: e0 (x_T) must outlive the chain: it cannot be the output", name);
+    }
+    const int ord = last ? 1 : order;                                  // the final evaluation reads no history
+    auto launch = [&](auto... k) {
+        obj_dispatch(objective, [&](auto o) {
+            auto go = [&](auto oc) {
+                ew_launch(B, n, stream, [&](auto vec, dim3 grid, hipStream_t s) {
+                    dpmpp_update_kernel<decltype(o)::value, decltype(oc)::value, decltype(vec)::value><<<grid, 256, 0, s>>>(
+                        x_t, model_out, xa, xb, d_prev1, d_prev2, cx, w0, w1, w2, last, out, d_out, n, k...);
+                });
+            };
+            if (ord == 3) go(std::integral_constant<int, 3>{});
+            else if (ord == 2) go(std::integral_constant<int, 2>{});
+            else go(std::integral_constant<int, 1>{});
+        });
+    };
+    if (!kn) launch();
+    else launch(*kn);
+    OFD_LAUNCH_CHECK();
+    return OFD_OK;
+}
+
 extern "C" int ofd_dpmpp_update(int objective, int order, const float* x_t, const float* model_out, const float* xa, const float* xb,
                                 const float* d_prev1, const float* d_prev2, const float* cx, const float* w0, const float* w1,
                                 const float* w2, int last, float* out, float* d_out, int B, size_t n, void* stream) {
-    OFD_OBJ_OK(objective);
-    OFD_EW_ARGS_OK(B, n);
-    OFD_CHECK_ARG(order >= 1 && order <= 3, "dpmpp_update: bad order %d", order);
-    OFD_CHECK_ARG(x_t && model_out && out, "dpmpp_update: null pointer");
-    OFD_CHECK_ARG(objective == PRED_X0 || (xa && xb), "dpmpp_update: missing x_start coefficients");
-    OFD_CHECK_ARG(last || (cx && w0), "dpmpp_update: missing coefficients");
-    OFD_CHECK_ARG(last || order < 2 || (d_prev1 && w1), "dpmpp_update: order %d needs d_prev1 and w1", order);
-    OFD_CHECK_ARG(last || order < 3 || (d_prev2 && w2), "dpmpp_update: order 3 needs d_prev2 and w2");
-    const int ord = last ? 1 : order;                                  // the final evaluation reads no history
-    hipStream_t s = (hipStream_t)stream;
-    obj_dispatch(objective, [&](auto o) {
-        constexpr int OBJ = decltype(o)::value;
-        auto go = [&](auto oc) {
-            constexpr int ORD = decltype(oc)::value;
-            if (n % 4 == 0)
-                dpmpp_update_kernel<OBJ, ORD, 4><<<ew_grid(B, n / 4), 256, 0, s>>>(x_t, model_out, xa, xb, d_prev1, d_prev2, cx, w0, w1, w2,
-                                                                                  last, out, d_out, n);
-            else
-                dpmpp_update_kernel<OBJ, ORD, 1><<<ew_grid(B, n), 256, 0, s>>>(x_t, model_out, xa, xb, d_prev1, d_prev2, cx, w0, w1, w2,
-                                                                              last, out, d_out, n);
-        };
-        if (ord == 3) go(std::integral_constant<int, 3>{});
-        else if (ord == 2) go(std::integral_constant<int, 2>{});
-        else go(std::integral_constant<int, 1>{});
-    });
-    OFD_LAUNCH_CHECK();
-    return OFD_OK;
+    return dpmpp_update_impl("dpmpp_update", objective, order, x_t, model_out, xa, xb, d_prev1, d_prev2, cx, w0, w1, w2, last, nullptr, out,
+                             d_out, B, n, stream);
 }
 
 extern "C" int ofd_dpmpp_update_known(int objective, int order, const float* x_t, const float* model_out, const float* xa,
@@ -493,47 +505,16 @@ extern "C" int ofd_dpmpp_update_known(int objective, int order, const float* x_t
                                       const float* w1, const float* w2, int last, const float* known, const float* e0,
                                       const float* sqrt_ac_next, const float* sqrt_1mac_next, float* out, float* d_out, int B, size_t n,
                                       void* stream) {
-    OFD_OBJ_OK(objective);
-    OFD_EW_ARGS_OK(B, n);
-    OFD_CHECK_ARG(order >= 1 && order <= 3, "dpmpp_update_known: bad order %d", order);
-    OFD_CHECK_ARG(x_t && model_out && out, "dpmpp_update_known: null pointer");
-    OFD_CHECK_ARG(objective == PRED_X0 || (xa && xb), "dpmpp_update_known: missing x_start coefficients");
-    OFD_CHECK_ARG(last || (cx && w0), "dpmpp_update_known: missing coefficients");
-    OFD_CHECK_ARG(last || order < 2 || (d_prev1 && w1), "dpmpp_update_known: order %d needs d_prev1 and w1", order);
-    OFD_CHECK_ARG(last || order < 3 || (d_prev2 && w2), "dpmpp_update_known: order 3 needs d_prev2 and w2");
     const KnownArgs kn{known, e0, sqrt_ac_next, sqrt_1mac_next};
-    OFD_KNOWN_ARGS_OK("dpmpp_update_known", last, kn.e);
-    OFD_CHECK_ARG(last || e0 != out, "dpmpp_update_known: e0 (x_T) must outlive the chain: it cannot be the output");
-    const int ord = last ? 1 : order;                                  // the final evaluation reads no history
-    hipStream_t s = (hipStream_t)stream;
-    obj_dispatch(objective, [&](auto o) {
-        constexpr int OBJ = decltype(o)::value;
-        auto go = [&](auto oc) {
-            constexpr int ORD = decltype(oc)::value;
-            if (n % 4 == 0)
-                dpmpp_update_kernel<OBJ, ORD, 4><<<ew_grid(B, n / 4), 256, 0, s>>>(x_t, model_out, xa, xb, d_prev1, d_prev2, cx, w0, w1, w2,
-                                                                                  last, out, d_out, n, kn);
-            else
-                dpmpp_update_kernel<OBJ, ORD, 1><<<ew_grid(B, n), 256, 0, s>>>(x_t, model_out, xa, xb, d_prev1, d_prev2, cx, w0, w1, w2,
-                                                                              last, out, d_out, n, kn);
-        };
-        if (ord == 3) go(std::integral_constant<int, 3>{});
-        else if (ord == 2) go(std::integral_constant<int, 2>{});
-        else go(std::integral_constant<int, 1>{});
-    });
-    OFD_LAUNCH_CHECK();
-    return OFD_OK;
+    return dpmpp_update_impl("dpmpp_update_known", objective, order, x_t, model_out, xa, xb, d_prev1, d_prev2, cx, w0, w1, w2, last, &kn,
+                             out, d_out, B, n, stream);
 }
 
 extern "C" int ofd_range_map(const float* in, float* out, size_t n, int mode, void* stream) {
     OFD_CHECK_ARG(in && out && n > 0 && (mode == 0 || mode == 1), "range_map: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    const bool v4 = n % 4 == 0 && ((uintptr_t)in % 16) == 0 && ((uintptr_t)out % 16) == 0;
-    const size_t nv = v4 ? n / 4 : n;
-    size_t b = (nv + 255) / 256;
-    if (b > 2048) b = 2048;
-    if (v4) range_map_kernel<4><<<(unsigned)b, 256, 0, s>>>(in, out, nv, mode);
-    else range_map_kernel<1><<<(unsigned)b, 256, 0, s>>>(in, out, nv, mode);
+    ew_launch(1, n, stream, [&](auto vec, dim3 grid, hipStream_t s) {
+        range_map_kernel<decltype(vec)::value><<<grid, 256, 0, s>>>(in, out, n / decltype(vec)::value, mode);
+    }, ((uintptr_t)in % 16) == 0 && ((uintptr_t)out % 16) == 0);
     OFD_LAUNCH_CHECK();
     return OFD_OK;
 }
@@ -553,9 +534,7 @@ extern "C" size_t ofd_nan_mse_result_doubles(void) { return 2 + 2 * (size_t)NAN_
 extern "C" int ofd_nan_mse_grad(const float* pred, const float* target, size_t n, const double* result, const float* gout, float* dpred,
                                 void* stream) {
     OFD_CHECK_ARG(pred && target && result && gout && dpred && n > 0, "nan_mse_grad: bad argument");
-    size_t b = (n + 255) / 256;
-    if (b > 2048) b = 2048;
-    nan_mse_grad_kernel<<<(unsigned)b, 256, 0, (hipStream_t)stream>>>(pred, target, n, result, gout, dpred);
+    nan_mse_grad_kernel<<<ew_grid(1, n), 256, 0, (hipStream_t)stream>>>(pred, target, n, result, gout, dpred);
     OFD_LAUNCH_CHECK();
     return OFD_OK;
 }

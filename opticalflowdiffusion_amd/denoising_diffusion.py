@@ -657,21 +657,45 @@ class ConditionalDiffusion(nn.Module):
             out = out[:, :-1 * additional_tgt.shape[1]]
         x = L.f32c(x)
         out = self._same_shape(L.f32c(out), x)
-        c1, c2, sigma = tab["c1"][t], tab["c2"][t], tab["sigma"][t]
         if t > 0:
             noise = self._same_shape(L.f32c(default(noise, lambda: torch.randn_like(x))), x)
         else:
             noise = None                                                               # DD:687
         pred = torch.empty_like(x)
         x_start = torch.empty_like(x)
-        if known is not None:
-            L.check(L.lib().ofd_ddpm_update_known(self._obj, L.ptr(x), L.ptr(out), L.ptr(noise), L.ptr(c1), L.ptr(c2), L.ptr(sigma),
-                                                  *self._xab(tab, t), L.ptr(known), None, *self._known_rows(tab, t - 1), L.ptr(pred),
-                                                  L.ptr(x_start), b, x[0].numel(), L.stream()))
-            return pred, x_start, additional_out
-        L.check(L.lib().ofd_ddpm_update_obj(self._obj, L.ptr(x), L.ptr(out), L.ptr(noise), L.ptr(c1), L.ptr(c2), L.ptr(sigma),
-                                            *self._xab(tab, t), L.ptr(pred), L.ptr(x_start), b, x[0].numel(), L.stream()))
+        self._ddpm_step(tab, t, x, out, noise, pred, x_start, known)
         return pred, x_start, additional_out
+
+    # -- the fused update launches: the only callers of the six reverse-step entry points (include/ofd.h).  img / out / nxt: x_t, the
+    # model output and the tensor the step writes; `known` (or None) picks the constrained entry point and its trailing arguments.
+    def _ddpm_step(self, tab, t, img, out, noise, nxt, x_start, known):
+        """the DDPM step at level t; noise is None at t == 0 (DD:687).  A held element rides on the same noise: no e0."""
+        lib = L.lib()
+        kn = () if known is None else (L.ptr(known), None, *self._known_rows(tab, t - 1))
+        fn = lib.ofd_ddpm_update_obj if known is None else lib.ofd_ddpm_update_known
+        L.check(fn(self._obj, L.ptr(img), L.ptr(out), L.ptr(noise), L.ptr(tab["c1"][t]), L.ptr(tab["c2"][t]), L.ptr(tab["sigma"][t]),
+                   *self._xab(tab, t), *kn, L.ptr(nxt), L.ptr(x_start), img.shape[0], img.numel() // img.shape[0], L.stream()))
+
+    def _ddim_step(self, tab, t, img, out, noise, coef, nxt, known, x_T):
+        """the DDIM step from level t; coef: this pair's rows sqrt(alpha_next), c, sigma, sqrt(1 - alpha_next), or None on the last step
+        (which takes no noise).  A constrained step without noise reads x_T as e0."""
+        lib, last = L.lib(), coef is None
+        san, c, sigma, s1n = (None,) * 4 if last else (L.ptr(coef[0]), L.ptr(coef[1]), L.ptr(coef[2]), L.ptr(coef[3]))
+        kn = () if known is None else (L.ptr(known), None if (last or noise is not None) else L.ptr(x_T), san, s1n)
+        fn = lib.ofd_ddim_update_obj if known is None else lib.ofd_ddim_update_known
+        L.check(fn(self._obj, L.ptr(img), L.ptr(out), L.ptr(noise), L.ptr(tab["sr"][t]), L.ptr(tab["srm1"][t]), *self._xab(tab, t),
+                   san, c, sigma, int(last), *kn, L.ptr(nxt), None, img.shape[0], img.numel() // img.shape[0], L.stream()))
+
+    def _dpmpp_step(self, tab, t, order, img, out, d1, d2, coef, last, nxt, d_out, known, x_T):
+        """the DPM-Solver++ step from level t; coef: this grid point's six rows (_dpmpp_tables); d1 / d2 / d_out: the history the order
+        reads and the slot the prediction goes to (None where unused).  A constrained step reads x_T as e0."""
+        lib = L.lib()
+        kn = () if known is None else ((L.ptr(known), None, None, None) if last else
+                                       (L.ptr(known), L.ptr(x_T), L.ptr(coef[4]), L.ptr(coef[5])))
+        fn = lib.ofd_dpmpp_update if known is None else lib.ofd_dpmpp_update_known
+        L.check(fn(self._obj, order, L.ptr(img), L.ptr(out), *self._xab(tab, t), L.ptr(d1), L.ptr(d2), L.ptr(coef[0]), L.ptr(coef[1]),
+                   L.ptr(coef[2]), L.ptr(coef[3]), int(last), *kn, L.ptr(nxt), L.ptr(d_out), img.shape[0], img.numel() // img.shape[0],
+                   L.stream()))
 
     @staticmethod
     def _same_shape(out, x):
@@ -749,11 +773,10 @@ class ConditionalDiffusion(nn.Module):
         `known` / `resample` (optional, not in the reference): constrained sampling, see `sample`; known is in the loop's own range
         ([-1, 1]), as external_cond and x_T are."""
         known = self._check_known(shape, known, resample, additional_tgt)
-        img = torch.randn(shape, device=self.device) if x_T is None else L.f32c(x_T)
-        assert tuple(img.shape) == tuple(shape)
-        if known is not None:
-            return self._p_sample_loop_known(img, return_all_timesteps, external_cond, known, resample)
         if additional_tgt is not None:                                                # target='target': the general step (DD:676-698)
+            # kept on p_sample: this branch keeps every frame whatever trajectory_stride says, which the shared chain would not
+            img = torch.randn(shape, device=self.device) if x_T is None else L.f32c(x_T)
+            assert tuple(img.shape) == tuple(shape)
             imgs, additionals = [img], [None]
             for i, t in enumerate(reversed(range(0, self.num_timesteps))):
                 img, _, additional_out = self.p_sample(img, t, None, external_cond=external_cond, additional_tgt=additional_tgt)
@@ -761,56 +784,54 @@ class ConditionalDiffusion(nn.Module):
                     imgs.append(img)
                 additionals.append(additional_out)
             return self.unnormalize(img if not return_all_timesteps else torch.stack(imgs, dim=1)), additionals
-        imgs = [img]
-        stride = self.trajectory_stride
-        tab = self._sampling_tables(shape[0], img.device)
-        b, n = shape[0], img[0].numel()
-        pong = [torch.empty_like(img), torch.empty_like(img)]
-        noise, x_start = torch.empty_like(img), torch.empty_like(img)
-        lib, obj = L.lib(), self._obj
-        for i, t in enumerate(reversed(range(0, self.num_timesteps))):
-            out = self._same_shape(L.f32c(self.model_with_condition(img, tab["t"][t], None, external_cond=external_cond)), img)
-            if t > 0:
-                noise.normal_()                                                       # DD:687: z = 0 at t = 0
-            nxt = pong[i & 1]
-            L.check(lib.ofd_ddpm_update_obj(obj, L.ptr(img), L.ptr(out), L.ptr(noise) if t > 0 else None, L.ptr(tab["c1"][t]),
-                                            L.ptr(tab["c2"][t]), L.ptr(tab["sigma"][t]), *self._xab(tab, t), L.ptr(nxt), L.ptr(x_start), b, n,
-                                            L.stream()))
-            img = nxt
-            if return_all_timesteps and (stride is None or (i + 1) % stride == 0 or t == 0):
-                imgs.append(img.clone())
-        return self.unnormalize(img if not return_all_timesteps else torch.stack(imgs, dim=1))             # DD:725-726
 
-    def _p_sample_loop_known(self, img, return_all_timesteps, external_cond, known, resample):
-        """p_sample_loop with held elements (ofd_ddpm_update_known) and RePaint's resampling: every step t > 0 is run `resample` times,
-        and between two runs the whole tensor goes back one level, x_t = sqrt(1 - beta_t) x_{t-1} + sqrt(beta_t) e' with a fresh draw
-        (ofd_q_sample on two cached rows).  resample * (T - 1) + 1 UNet calls; the trajectory keeps one frame per level."""
-        imgs = [img]
-        stride = self.trajectory_stride
-        b, n = img.shape[0], img[0].numel()
-        tab = self._sampling_tables(b, img.device)
-        pong = [torch.empty_like(img), torch.empty_like(img)]
-        noise, x_start = torch.empty_like(img), torch.empty_like(img)
-        lib, obj = L.lib(), self._obj
-        writes = 0                                                                    # img is x_T or pong[(writes - 1) & 1]
-        for i, t in enumerate(reversed(range(0, self.num_timesteps))):
-            for r in range(resample if t > 0 else 1):
-                if r > 0:                                                             # back to level t
-                    noise.normal_()
-                    nxt = pong[writes & 1]
-                    L.check(lib.ofd_q_sample(L.ptr(img), L.ptr(noise), L.ptr(tab["ja"][t]), L.ptr(tab["jb"][t]), L.ptr(nxt), b, n, L.stream()))
-                    img, writes = nxt, writes + 1
-                out = self._same_shape(L.f32c(self.model_with_condition(img, tab["t"][t], None, external_cond=external_cond)), img)
+        def plan(x_T, tab):
+            noise, x_start = torch.empty_like(x_T), torch.empty_like(x_T)
+
+            def step(i, t, img, out, nxt):
                 if t > 0:
-                    noise.normal_()                                                   # DD:687; the held elements ride on the same draw
-                nxt = pong[writes & 1]
-                L.check(lib.ofd_ddpm_update_known(obj, L.ptr(img), L.ptr(out), L.ptr(noise) if t > 0 else None, L.ptr(tab["c1"][t]),
-                                                  L.ptr(tab["c2"][t]), L.ptr(tab["sigma"][t]), *self._xab(tab, t), L.ptr(known), None,
-                                                  *self._known_rows(tab, t - 1), L.ptr(nxt), L.ptr(x_start), b, n, L.stream()))
-                img, writes = nxt, writes + 1
-            if return_all_timesteps and (stride is None or (i + 1) % stride == 0 or t == 0):
+                    noise.normal_()                          # DD:687: z = 0 at t = 0; the held elements ride on the same draw
+                self._ddpm_step(tab, t, img, out, noise if t > 0 else None, nxt, x_start, known)
+
+            def renoise(t, img, nxt):                        # back to level t: x_t = sqrt(1 - beta_t) x_{t-1} + sqrt(beta_t) e'
+                noise.normal_()
+                L.check(L.lib().ofd_q_sample(L.ptr(img), L.ptr(noise), L.ptr(tab["ja"][t]), L.ptr(tab["jb"][t]), L.ptr(nxt),
+                                             img.shape[0], img.numel() // img.shape[0], L.stream()))
+
+            return [(t, resample if t > 0 else 1) for t in reversed(range(0, self.num_timesteps))], step, renoise
+
+        return self._run_chain(shape, x_T, plan, return_all_timesteps, external_cond)             # DD:725-726
+
+    def _run_chain(self, shape, x_T, plan, return_all_timesteps, external_cond, additional_tgt=None):
+        """The reverse chain p_sample_loop, ddim_sample and dpmpp_sample share.  It owns the start image (x_T or a fresh draw, made before
+        any table is built), the two ping-pong images, the model call on a row of `_sampling_tables`, the additional_tgt split, the
+        trajectory (x_T, every trajectory_stride-th schedule entry and the last) and the return form.  `plan(x_T, tab)` is the sampler:
+        it returns (schedule, step, renoise).  schedule: one (t, runs) per entry, t the level the model is called at; step(i, t, img,
+        out, nxt) draws the step's noise in place and makes the one fused update launch from img into nxt; an entry with runs > 1
+        (RePaint's resampling) is stepped `runs` times with renoise(t, img, nxt) between two runs.  Nothing is allocated, gathered or
+        synchronised per step apart from the clone of a kept frame."""
+        img = torch.randn(shape, device=self.device) if x_T is None else L.f32c(x_T)
+        assert tuple(img.shape) == tuple(shape)
+        tab = self._sampling_tables(shape[0], img.device)
+        schedule, step, renoise = plan(img, tab)                                      # img is x_T: never written, the loop writes to pong
+        pong = [torch.empty_like(img), torch.empty_like(img)]
+        imgs, additionals, stride = [img], [None], self.trajectory_stride
+        writes = 0                                                                    # img is x_T or pong[(writes - 1) & 1]
+        for i, (t, runs) in enumerate(schedule):
+            for r in range(runs):
+                if r > 0:
+                    renoise(t, img, pong[writes & 1])
+                    img, writes = pong[writes & 1], writes + 1
+                out = self.model_with_condition(img, tab["t"][t], None, external_cond=external_cond, additional_tgt=additional_tgt)
+                if additional_tgt is not None:
+                    additionals.append(out[:, -1 * additional_tgt.shape[1]:])
+                    out = out[:, :-1 * additional_tgt.shape[1]]
+                step(i, t, img, self._same_shape(L.f32c(out), img), pong[writes & 1])
+                img, writes = pong[writes & 1], writes + 1
+            if return_all_timesteps and (stride is None or (i + 1) % stride == 0 or i == len(schedule) - 1):
                 imgs.append(img.clone())
-        return self.unnormalize(img if not return_all_timesteps else torch.stack(imgs, dim=1))
+        res = self.unnormalize(img if not return_all_timesteps else torch.stack(imgs, dim=1))
+        return (res, additionals) if additional_tgt is not None else res
 
     # -- DDIM --------------------------------------------------------------------------------
     @torch.no_grad()
@@ -819,52 +840,33 @@ class ConditionalDiffusion(nn.Module):
         the reference) starts the chains from a given tensor instead of a fresh draw (DD:741).  `known` (optional, not in the
         reference): constrained sampling, see `sample`; in the loop's own range ([-1, 1]).  resample > 1 is DDPM's: ValueError."""
         known = self._check_known(shape, known, resample, additional_tgt, ddpm=False)
-        batch, device, T, S, eta = shape[0], self.device, self.num_timesteps, self.sampling_timesteps, self.ddim_sampling_eta
+        batch, T, S, eta = shape[0], self.num_timesteps, self.sampling_timesteps, self.ddim_sampling_eta
         times = torch.linspace(-1, T - 1, steps=S + 1)
         times = list(reversed(times.int().tolist()))
         time_pairs = list(zip(times[:-1], times[1:]))
-        img = torch.randn(shape, device=device) if x_T is None else L.f32c(x_T)
-        assert tuple(img.shape) == tuple(shape)
-        imgs = [img]
-        n = img[0].numel()
-        stride = self.trajectory_stride
-        tab = self._sampling_tables(batch, img.device)
-        # the per-pair scalars of DD:757-761 for ALL pairs at once, in the reference's fp32 operation order -> one (S, 3, batch) table
-        ac = self.alphas_cumprod
-        tt = torch.tensor([p[0] for p in time_pairs], device=ac.device)
-        tn = torch.tensor([max(p[1], 0) for p in time_pairs], device=ac.device)
-        alpha, alpha_next = ac[tt], ac[tn]
-        sigma = eta * ((1 - alpha / alpha_next) * (1 - alpha_next) / (1 - alpha)).sqrt()
-        c = (1 - alpha_next - sigma ** 2).sqrt()
-        # row 3, sqrt(1 - alpha_next), is read by the constrained step only (with row 0: the level the held elements go to)
-        coef = torch.stack((alpha_next.sqrt(), c, sigma, (1 - alpha_next).sqrt()), dim=1).to(torch.float32)
-        coef = coef.reshape(len(time_pairs), 4, 1).repeat(1, 1, batch).contiguous()
-        x_T = img                                                                        # never written: the loop writes to pong
-        pong = [torch.empty_like(img), torch.empty_like(img)]
-        noise = torch.empty_like(img) if (eta > 0 or self.ddim_draw_unused_noise) else None
-        lib, obj = L.lib(), self._obj
-        for i, (time, time_next) in enumerate(time_pairs):
-            out = self._same_shape(L.f32c(self.model_with_condition(img, tab["t"][time], None, external_cond=external_cond)), img)
-            last = time_next < 0
-            if noise is not None and not last:
-                noise.normal_()                                                          # DD:763 (eta == 0: only with ddim_draw_unused_noise)
-            nxt = pong[i & 1]
-            if known is not None:
-                L.check(lib.ofd_ddim_update_known(obj, L.ptr(img), L.ptr(out), L.ptr(noise) if not last else None, L.ptr(tab["sr"][time]),
-                                                  L.ptr(tab["srm1"][time]), *self._xab(tab, time), None if last else L.ptr(coef[i, 0]),
-                                                  None if last else L.ptr(coef[i, 1]), None if last else L.ptr(coef[i, 2]), int(last),
-                                                  L.ptr(known), None if (last or noise is not None) else L.ptr(x_T),
-                                                  None if last else L.ptr(coef[i, 0]), None if last else L.ptr(coef[i, 3]), L.ptr(nxt), None,
-                                                  batch, n, L.stream()))
-            else:
-                L.check(lib.ofd_ddim_update_obj(obj, L.ptr(img), L.ptr(out), L.ptr(noise) if not last else None, L.ptr(tab["sr"][time]),
-                                                L.ptr(tab["srm1"][time]), *self._xab(tab, time), None if last else L.ptr(coef[i, 0]),
-                                                None if last else L.ptr(coef[i, 1]), None if last else L.ptr(coef[i, 2]), int(last), L.ptr(nxt),
-                                                None, batch, n, L.stream()))
-            img = nxt
-            if return_all_timesteps and (stride is None or (i + 1) % stride == 0 or last):
-                imgs.append(img.clone())
-        return self.unnormalize(img if not return_all_timesteps else torch.stack(imgs, dim=1))             # DD:772-773
+
+        def plan(x_T, tab):
+            # the per-pair scalars of DD:757-761 for ALL pairs at once, in the reference's fp32 operation order -> one (S, 4, batch) table
+            ac = self.alphas_cumprod
+            tt = torch.tensor([p[0] for p in time_pairs], device=ac.device)
+            tn = torch.tensor([max(p[1], 0) for p in time_pairs], device=ac.device)
+            alpha, alpha_next = ac[tt], ac[tn]
+            sigma = eta * ((1 - alpha / alpha_next) * (1 - alpha_next) / (1 - alpha)).sqrt()
+            c = (1 - alpha_next - sigma ** 2).sqrt()
+            # row 3, sqrt(1 - alpha_next), is read by the constrained step only (with row 0: the level the held elements go to)
+            coef = torch.stack((alpha_next.sqrt(), c, sigma, (1 - alpha_next).sqrt()), dim=1).to(torch.float32)
+            coef = coef.reshape(len(time_pairs), 4, 1).repeat(1, 1, batch).contiguous()
+            noise = torch.empty_like(x_T) if (eta > 0 or self.ddim_draw_unused_noise) else None
+
+            def step(i, time, img, out, nxt):
+                last = time_pairs[i][1] < 0
+                if noise is not None and not last:
+                    noise.normal_()                                                      # DD:763 (eta == 0: only with ddim_draw_unused_noise)
+                self._ddim_step(tab, time, img, out, None if last else noise, None if last else coef[i], nxt, known, x_T)
+
+            return [(time, 1) for time, _ in time_pairs], step, None
+
+        return self._run_chain(shape, x_T, plan, return_all_timesteps, external_cond)              # DD:772-773
 
     # -- DPM-Solver++ (not in the reference) --------------------------------------------------
     def _dpmpp_tables(self, batch, device):
@@ -894,46 +896,20 @@ class ConditionalDiffusion(nn.Module):
         `known`: constrained sampling, see `sample`; in the loop's own range ([-1, 1]).  The ring stores the predictions with the held
         elements already replaced.  resample > 1 is DDPM's: ValueError."""
         known = self._check_known(shape, known, resample, additional_tgt, ddpm=False)
-        batch = shape[0]
-        img = torch.randn(shape, device=self.device) if x_T is None else L.f32c(x_T)
-        assert tuple(img.shape) == tuple(shape)
-        x_T = img                                                                        # never written: the loop writes to pong
-        grid, orders, coef = self._dpmpp_tables(batch, img.device)
-        tab = self._sampling_tables(batch, img.device)
-        imgs, additionals = [img], [None]
-        n = img[0].numel()
-        stride = self.trajectory_stride
-        pong = [torch.empty_like(img), torch.empty_like(img)]
-        ring = [torch.empty_like(img) for _ in range(3)]
-        lib, obj = L.lib(), self._obj
-        for i, t in enumerate(grid):
-            out = self.model_with_condition(img, tab["t"][t], None, external_cond=external_cond, additional_tgt=additional_tgt)
-            if additional_tgt is not None:
-                additionals.append(out[:, -1 * additional_tgt.shape[1]:])
-                out = out[:, :-1 * additional_tgt.shape[1]]
-            out = self._same_shape(L.f32c(out), img)
-            last = i == len(grid) - 1
-            order = 1 if last else orders[i]
-            c = coef[i]
-            nxt = pong[i & 1]
-            if known is not None:
-                L.check(lib.ofd_dpmpp_update_known(obj, order, L.ptr(img), L.ptr(out), *self._xab(tab, t),
-                                                   L.ptr(ring[(i - 1) % 3]) if order >= 2 else None,
-                                                   L.ptr(ring[(i - 2) % 3]) if order >= 3 else None,
-                                                   L.ptr(c[0]), L.ptr(c[1]), L.ptr(c[2]), L.ptr(c[3]), int(last), L.ptr(known),
-                                                   None if last else L.ptr(x_T), None if last else L.ptr(c[4]),
-                                                   None if last else L.ptr(c[5]), L.ptr(nxt), None if last else L.ptr(ring[i % 3]),
-                                                   batch, n, L.stream()))
-            else:
-                L.check(lib.ofd_dpmpp_update(obj, order, L.ptr(img), L.ptr(out), *self._xab(tab, t),
-                                             L.ptr(ring[(i - 1) % 3]) if order >= 2 else None, L.ptr(ring[(i - 2) % 3]) if order >= 3 else None,
-                                             L.ptr(c[0]), L.ptr(c[1]), L.ptr(c[2]), L.ptr(c[3]), int(last), L.ptr(nxt),
-                                             None if last else L.ptr(ring[i % 3]), batch, n, L.stream()))
-            img = nxt
-            if return_all_timesteps and (stride is None or (i + 1) % stride == 0 or last):
-                imgs.append(img.clone())
-        res = self.unnormalize(img if not return_all_timesteps else torch.stack(imgs, dim=1))
-        return (res, additionals) if additional_tgt is not None else res
+
+        def plan(x_T, tab):
+            grid, orders, coef = self._dpmpp_tables(shape[0], x_T.device)
+            ring = [torch.empty_like(x_T) for _ in range(3)]
+
+            def step(i, t, img, out, nxt):
+                last = i == len(grid) - 1
+                order = 1 if last else orders[i]
+                self._dpmpp_step(tab, t, order, img, out, ring[(i - 1) % 3] if order >= 2 else None,
+                                 ring[(i - 2) % 3] if order >= 3 else None, coef[i], last, nxt, None if last else ring[i % 3], known, x_T)
+
+            return [(t, 1) for t in grid], step, None
+
+        return self._run_chain(shape, x_T, plan, return_all_timesteps, external_cond, additional_tgt)
 
     @torch.no_grad()
     def sample(self, batch_size=16, return_all_timesteps=False, external_cond=None, additional_tgt=None, known=None, resample=1):
