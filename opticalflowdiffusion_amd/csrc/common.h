@@ -19,7 +19,17 @@ void set_error(const char* fmt, ...);
         }                                                          \
     } while (0)
 
-#define OFD_HIP(call)                                                                      \
+// a caller-provided workspace of `have` bytes where `need` are required: "<what>: workspace <have> < <need>"
+#define OFD_CHECK_WORKSPACE(have, need, what)                                              \
+    do {                                                                                   \
+        const size_t have_ = (have), need_ = (need);                                       \
+        if (have_ < need_) {                                                               \
+            ::ofd::set_error(what ": workspace %zu < %zu", have_, need_);                  \
+            return OFD_ERR_WORKSPACE;                                                      \
+        }                                                                                  \
+    } while (0)
+
+#define OFD_HIP(call)                                                                     \
     do {                                                                                   \
         hipError_t e_ = (call);                                                            \
         if (e_ != hipSuccess) {                                                            \

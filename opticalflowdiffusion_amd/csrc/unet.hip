@@ -735,10 +735,7 @@ extern "C" int ofd_unet_forward(ofd_unet* u, const float* x, int Cx, const float
                   H, W, mult, u->L - 1);
     OFD_CHECK_ARG(Cx + (cond ? Cc : 0) == u->cfg.channels, "unet_forward: %d + %d input channels, UNet has %d", Cx, cond ? Cc : 0, u->cfg.channels);
     if (!u->prepared) { set_error("unet_forward: call ofd_unet_prepare after setting parameters"); return OFD_ERR_STATE; }
-    if (workspace_bytes < ofd_unet_workspace_bytes(u, B, H, W)) {
-        set_error("unet_forward: workspace %zu < %zu", workspace_bytes, ofd_unet_workspace_bytes(u, B, H, W));
-        return OFD_ERR_WORKSPACE;
-    }
+    OFD_CHECK_WORKSPACE(workspace_bytes, ofd_unet_workspace_bytes(u, B, H, W), "unet_forward");
     OFD_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "unet_forward: workspace must be 256-byte aligned");
     // lays a forward context of batch `b` over `bytes` of workspace at `w_`
     auto layout = [&](Ctx& c, int b, char* w_, size_t bytes, hipStream_t s_, float*& temb_, float*& temb_silu_) {

@@ -591,7 +591,7 @@ extern "C" int ofd_unet_train_forward(ofd_unet* u, const float* x, int Cx, const
     int rc = plan(u, B, H, W, L);
     if (rc != OFD_OK) return rc;
     const size_t need = L.small_b + 2 * L.persist_b + L.scratch_b + 4096;
-    if (workspace_bytes < need) { set_error("unet_train_forward: workspace %zu < %zu", workspace_bytes, need); return OFD_ERR_WORKSPACE; }
+    OFD_CHECK_WORKSPACE(workspace_bytes, need, "unet_train_forward");
     rc = prepare_train(u, (hipStream_t)stream);
     if (rc != OFD_OK) return rc;
     Ctx c;

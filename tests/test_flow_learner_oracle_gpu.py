@@ -72,7 +72,7 @@ def test_splat_backward_kernels_at_every_training_scale(L):
 
 # ---- 2. the fused pyramid backward ------------------------------------------------------------------------------------------------
 def border_classes(flow, L):
-    """pyramid_border_list_kernel's classification restated (csrc/warp.hip, pyr_plain / pyr_plain_x / pyr_plain_y): counts of the
+    """pyramid_border_list_kernel's classification restated (csrc/splat_pyramid.hip and warp_common.h, pyr_plain / pyr_plain_x / pyr_plain_y): counts of the
     finite-target pixels that are plain, x-border only (class 1), y-border only (class 2) and border on both axes (class 0)."""
     B, _, H, W = flow.shape
     fx = torch.arange(W, dtype=torch.float32).view(1, 1, W) + flow[:, 0]

@@ -71,7 +71,7 @@ def test_splat_far_displacements_and_nonfinite(ofd):
 
 def test_splat_converging_flows_and_wide_dynamic_range(ofd):
     """The scale-1 forward splat keeps its accumulators as 64-bit fixed point, 44 fraction bits below the largest finite |in| of the
-    (sample, channel) plane (warp.hip: splat_tile_fast_kernel).  (1) flows converging on one tile overflow its survivor list: the
+    (sample, channel) plane (splat.hip: splat_tile_fast_kernel).  (1) flows converging on one tile overflow its survivor list: the
     overflow entries are accumulated in place; (2) a plane whose values span six decades keeps 1e-6 relative accuracy in its small
     region (the documented limit: relative error = 2^-44 x plane maximum / value); (3) non-finite inputs raise the IEEE result at
     their corners only.  Against oracle/splat_ref.c."""
@@ -263,7 +263,7 @@ def test_grid_sample_warp_full_size_properties(ofd):
 
 @pytest.mark.parametrize("B,H,W", [(16, 440, 1024), (3, 100, 1000), (1, 64, 64), (2, 40, 132), (1, 97, 260)])
 def test_grid_sample_warp_band_kernel_against_the_oracle_at_size(ofd, B, H, W):
-    """The C = 3 grid_sample warp at sizes: the BAND kernel (warp.hip: grid_warp_band_kernel, r04: a workgroup slides down a 128-column band
+    """The C = 3 grid_sample warp at sizes: the BAND kernel (grid_warp.hip: grid_warp_band_kernel, r04: a workgroup slides down a 128-column band
     over a 72-row LDS ring, counted waits, look-ahead window groups) where W >= 128 and H >= 32, else the 64 x 64 tile kernel.  At the
     BASELINE size every workgroup walks a 224-row segment of a band; (3, 100, 1000) has a partial band and a partial last step; (2, 40, 132)
     a 4-column band; (1, 97, 260) an odd height; one sample carries displacements beyond the staged window (the global-load fallback) and
@@ -319,6 +319,103 @@ def test_grid_sample_warp_band_kernel_equals_the_tile_kernel(ofd, B, H, W):
     torch.cuda.synchronize()
     assert torch.equal(m1, m0)
     assert torch.equal(o1, o0), float((o1 - o0).abs().max())
+
+
+_BORDER_RULE_REF = {}
+
+
+def _border_rule_case(B, C, H, W):
+    """Image, flow and oracle result of one shape of the border-rule test, computed once per shape.  The flow holds, in one field:
+    smooth interior flow; rows of integer flow (targets on exact pixel positions); targets 0.25 .. 1.25 px outside each of the four
+    borders and each corner, from a source pixel next to the target and from one far away; a block of +-45 px displacements (beyond the
+    24 px halo the tile and band kernels stage: their global-load fallback); NaN, +inf, -inf and +-1e30 entries.
+    The image holds signed powers of two (+-2^-3 .. +-2^3, independent per pixel and channel).  The kernels round every product
+    value * weight and every sum once (-ffp-contract=off); the torch CPU op contracts them into fused multiply-adds, so on an arbitrary
+    image about one value in six differs by one ulp (measured on the kernels before they shared the rule: 2708 of 15312 values at
+    (2, 3, 40, 64), max 1.2e-7; a CPU restatement of the kernels' operation order differs from the op at the same count).  A power of two
+    times a weight is exact, fused or not, so on this image torch.equal holds exactly where corners, weights, in-bounds bits and summation
+    order are right, and a wrong corner, weight or bit still changes the sum."""
+    key = (B, C, H, W)
+    if key not in _BORDER_RULE_REF:
+        g = torch.Generator().manual_seed(1000 * H + W + C)
+        img = torch.ldexp(torch.where(torch.rand(B, C, H, W, generator=g) < 0.5, -1.0, 1.0), torch.randint(-3, 4, (B, C, H, W), generator=g))
+        flow = torch.nn.functional.avg_pool2d(torch.randn(B, 2, H, W, generator=g) * 8 * 9, 9, 1, 4).clamp(-20, 20)
+        flow[:, :, 1:4] = torch.randint(-3, 4, (B, 2, 3, W), generator=g).float()
+        flow[-1, :, H // 2:, :W // 2] = (torch.rand(2, H - H // 2, W // 2, generator=g) * 2 - 1) * 45.0
+        # targets just outside the image: (ty, tx) per border and corner, each at several distances
+        xm, ym, k = float(W // 2) + 0.375, float(H // 2) + 0.625, 0
+        for e in (0.25, 0.5, 0.999, 1.0, 1.25):
+            xs = {"in": xm, "lo": -e, "hi": (W - 1) + e}
+            ys = {"in": ym, "lo": -e, "hi": (H - 1) + e}
+            for ky, kx in [("in", "lo"), ("in", "hi"), ("lo", "in"), ("hi", "in"), ("lo", "lo"), ("lo", "hi"), ("hi", "lo"), ("hi", "hi")]:
+                ty, tx = ys[ky], xs[kx]
+                near = (min(max(int(ty), 0), H - 1), min(max(int(tx) + (k % 5) - 2, 0), W - 1))      # within the staged window
+                far = (6 + k % (H - 12), 5 + (7 * k) % (W - 10))                                       # anywhere
+                for (y, x) in (near, far):
+                    flow[0, 0, y, x] = ty - y
+                    flow[0, 1, y, x] = tx - x
+                k += 1
+        bad = [float("nan"), float("inf"), -float("inf"), 1e30, -1e30]
+        for i in range(15):
+            flow[i % B, i % 2, (5 + 11 * i) % H, (3 + 17 * i) % W] = bad[i % 5]
+        flow[0, :, H // 3, W // 2] = float("nan")
+        finite = (torch.isfinite(flow) & (flow.abs() < 1e29)).all(dim=1)                               # (B, H, W)
+        ro, rm = WR.warp_backward_flow(img, torch.where(finite.unsqueeze(1), flow, torch.zeros(())))
+        # the oracle's coordinates: the fp32 operation order of WP:108-109 and ATen's un-normalisation
+        xx = torch.arange(W).view(1, 1, W).float() + flow[:, 1]
+        yy = torch.arange(H).view(1, H, 1).float() + flow[:, 0]
+        ix = torch.floor(((2.0 * xx / max(W - 1, 1) - 1.0 + 1) / 2) * (W - 1))
+        iy = torch.floor(((2.0 * yy / max(H - 1, 1) - 1.0 + 1) / 2) * (H - 1))
+        _BORDER_RULE_REF[key] = (img, flow, finite, ro, rm, ix, iy)
+    return _BORDER_RULE_REF[key]
+
+
+@pytest.mark.parametrize("shape,with_mask,band", [
+    ((2, 3, 37, 50), True, None),            # scalar kernel: W % 4 != 0
+    ((2, 1, 40, 64), True, None),            # tile kernel, CT = 1
+    ((2, 2, 40, 64), True, None),            # CT = 2
+    ((2, 3, 40, 64), True, None),            # CT = 3 (W < 128: no band)
+    ((2, 5, 40, 64), True, None),            # CT = 0: run-time channel count, two channel groups
+    ((1, 3, 64, 256), True, None),           # band kernel <MASK = true>
+    ((1, 3, 64, 256), False, None),          # band kernel <MASK = false>
+    ((1, 3, 64, 256), True, "0"),            # tile kernel at the band's shape
+])
+def test_grid_sample_warp_border_rule_on_every_forward_path(ofd, shape, with_mask, band):
+    """The corner / in-bounds / mask rule all forward kernels of ofd_grid_warp_fwd share (warp_common.h: grid_corner), at the smallest
+    shape that reaches each dispatch path.  Where the flow is finite: image and mask torch.equal to the CPU oracle (the torch op the
+    reference calls, WP:95-119) and ofd_grid_warp_corners equal to the floor of the oracle's coordinates.  Where the flow is NaN, +-inf
+    or +-1e30: image and mask exactly 0 in every channel (the kernels' rule: no corner is in bounds)."""
+    import os
+    from opticalflowdiffusion_amd._lib import lib, check, ptr, stream
+    from opticalflowdiffusion_amd.warp import grid_warp_corners
+    B, C, H, W = shape
+    img, flow, finite, ro, rm, ix, iy = _border_rule_case(B, C, H, W)
+    img_d, flow_d = img.cuda(), flow.cuda()
+    o = torch.full((B, C, H, W), -7.0, device="cuda")
+    m = torch.full((B, C, H, W), -7.0, device="cuda") if with_mask else None
+    old = os.environ.get("OFD_GW_BAND")
+    try:
+        if band is not None:
+            os.environ["OFD_GW_BAND"] = band
+        check(lib().ofd_grid_warp_fwd(ptr(img_d), ptr(flow_d), ptr(o), ptr(m) if with_mask else None, B, C, H, W, stream()))
+    finally:
+        if old is None:
+            os.environ.pop("OFD_GW_BAND", None)
+        else:
+            os.environ["OFD_GW_BAND"] = old
+    torch.cuda.synchronize()
+    ok = finite.unsqueeze(1).expand(B, C, H, W)
+    o = o.cpu()
+    print(shape, with_mask, band, "finite pixels", int(finite.sum()), "of", finite.numel(), "max |out - oracle|", float((o[ok] - ro[ok]).abs().max()),
+          "differing values", int((o[ok] != ro[ok]).sum()))
+    assert torch.equal(o[ok], ro[ok])
+    assert bool((o[~ok] == 0).all())
+    if with_mask:
+        m = m.cpu()
+        assert torch.equal(m[ok], rm[ok])
+        assert bool((m[~ok] == 0).all())
+    c = grid_warp_corners(flow_d).cpu()
+    assert torch.equal(c[..., 0][finite], ix[finite].int()) and torch.equal(c[..., 1][finite], iy[finite].int())
 
 
 def test_splat_full_size_properties(ofd):
