@@ -66,4 +66,14 @@ __device__ __forceinline__ uint32_t f2bf2(float lo, float hi) {
     return __builtin_bit_cast(uint32_t, h);
 }
 
+// XCD-aware tile order: workgroup i runs on XCD i % 8, so dispatch index `tile` is mapped to a tile such that the workgroups of one XCD
+// walk a contiguous run of tiles (what neighbouring tiles share -- halo rows, window overlap -- is then served by one L2)
+__device__ __forceinline__ int xcd_tile_order(int tile, int ntiles) {
+    if (ntiles >= 8) {
+        const int q = ntiles / 8, r = ntiles % 8, xcd = tile % 8, idx = tile / 8;
+        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    }
+    return tile;
+}
+
 }  // namespace ofd

@@ -21,9 +21,7 @@
 // atomics of the FC form).
 #include <cstdlib>
 #include <type_traits>
-#include "common.h"
-#include "conv_params.h"
-#include "mfma_util.h"
+#include "conv_common.h"
 
 namespace ofd {
 namespace c1 {
@@ -53,8 +51,6 @@ __device__ __forceinline__ void lds_wait(u4* x) {      // ties the registers to 
     else if constexpr (F == 2) asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(x[0]), "+v"(x[1]) : "n"(PEND) : "memory");
     else asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]) : "n"(PEND) : "memory");
 }
-
-__device__ __forceinline__ float silu_f(float y) { return y * __builtin_amdgcn_rcpf(1.0f + __expf(-y)); }
 
 struct Unit {            // 64 input channels of one source; output pixel (b, y, x) reads source pixel b * bs + y * ys + x * xs + c0
     const bf16_t* ptr;   // + channel offset
@@ -309,18 +305,8 @@ __global__ void __launch_bounds__(NTHREADS, CIN > 512 ? 1 : 2) conv1x1_wp_kernel
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 float v[4] = {acc[f][4 * g] + bias4[g].x, acc[f][4 * g + 1] + bias4[g].y, acc[f][4 * g + 2] + bias4[g].z, acc[f][4 * g + 3] + bias4[g].w};
-                if constexpr (PL) {
-                    v[0] += bf2f((bf16_t)(rq[g].x & 0xffffu));
-                    v[1] += bf2f((bf16_t)(rq[g].x >> 16));
-                    v[2] += bf2f((bf16_t)(rq[g].y & 0xffffu));
-                    v[3] += bf2f((bf16_t)(rq[g].y >> 16));
-                } else if constexpr (RA) {
-                    const float4 sc = sc4[g], sh = sh4[g];
-                    v[0] += silu_f(bf2f((bf16_t)(rq[g].x & 0xffffu)) * sc.x + sh.x);
-                    v[1] += silu_f(bf2f((bf16_t)(rq[g].x >> 16)) * sc.y + sh.y);
-                    v[2] += silu_f(bf2f((bf16_t)(rq[g].y & 0xffffu)) * sc.z + sh.z);
-                    v[3] += silu_f(bf2f((bf16_t)(rq[g].y >> 16)) * sc.w + sh.w);
-                }
+                if constexpr (PL) add_residual4(v, rq[g]);
+                else if constexpr (RA) add_silu_affine4(v, rq[g], sc4[g], sh4[g]);
                 qout[f][g] = make_uint2(f2bf2(v[0], v[1]), f2bf2(v[2], v[3]));
             }
         }

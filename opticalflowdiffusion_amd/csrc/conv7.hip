@@ -41,12 +41,7 @@ struct Tile { int b, oy0, ox0; };
 
 // XCD-aware order (as conv_igemm.hip): the virtual index v runs on XCD v % 8 and gets a contiguous run of tiles there
 __device__ __forceinline__ Tile tile_of(int v, int ntiles, int tiles_x, int tpi) {
-    int tile = v;
-    if (ntiles >= 8) {
-        const int q = ntiles / 8, r = ntiles % 8, xcd = v % 8, idx = v / 8;
-        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
-    tile = min(tile, ntiles - 1);                                  // (past the end: a valid tile, never loaded or stored)
+    const int tile = min(xcd_tile_order(v, ntiles), ntiles - 1);      // (past the end: a valid tile, never loaded or stored)
     const int b = tile / tpi, t_in = tile - b * tpi;
     return {b, (t_in / tiles_x) * TH, (t_in % tiles_x) * TW};
 }

@@ -18,14 +18,10 @@
 // (A = weights, B = pixels) so that a lane's accumulator registers are 4 consecutive output
 // channels of one pixel -> 8-byte NHWC stores.
 #include <cstdlib>
-#include "common.h"
-#include "conv_params.h"
+#include "conv_common.h"
 #include "blocks.h"
 
 namespace ofd {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 constexpr int TH = 8, TW = 32, NTHREADS = 256;
 
@@ -65,8 +61,6 @@ __device__ __forceinline__ int swz(int p) {
     return (CK == 64) ? ((p >> 1) & 7) : ((p >> 3) & 1);
 }
 
-__device__ __forceinline__ float silu_f(float y) { return y * __builtin_amdgcn_rcpf(1.0f + __expf(-y)); }
-
 __device__ __forceinline__ uint32_t pack2(float a, float b) { return f2bf2(a, b); }
 
 // reduce N per-lane values over the 64 lanes of a wave with ~N shuffles (butterfly that halves
@@ -96,8 +90,7 @@ __device__ __forceinline__ void wave_reduce_multi(float (&v)[N]) {
     WaveReduce<N, N, 32>::run(v);
 }
 
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;   // first-class vector value: always in registers
-template <int N>
+template <int N>                    // (u32x4 is a first-class vector value: always in registers)
 struct U4Arr {
     u32x4 v[N];
 };
@@ -155,10 +148,7 @@ __global__ void __launch_bounds__(NTHREADS, 2) conv_igemm_kernel(const ConvParam
         ph_pad_y = 1 - (ph >> 1); ph_pad_x = 1 - (ph & 1); ph_oy = ph >> 1; ph_ox = ph & 1;
         ph_weight = P.weight + (size_t)ph * 4 * P.Cin_total * P.Cout;
     }
-    if (ntiles >= 8) {
-        const int q = ntiles / 8, r = ntiles % 8, xcd = tile % 8, idx = tile / 8;
-        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    tile = xcd_tile_order(tile, ntiles);
     const int b = tile / (P.tiles_x * P.tiles_y);
     const int t_in = tile % (P.tiles_x * P.tiles_y);
     const int oy0 = (t_in / P.tiles_x) * TH, ox0 = (t_in % P.tiles_x) * TW;
@@ -210,6 +200,7 @@ __global__ void __launch_bounds__(NTHREADS, 2) conv_igemm_kernel(const ConvParam
 
     int src_i = 0, src_first = 0;   // source that owns chunk kc, and its first chunk
     for (int kc = 0; kc < P.total_chunks; ++kc) {
+        // (the source walk here and the prologue below stay pasted in this kernel: taking conv_common.h's prologue_octet reorders its instruction stream)
         while (kc >= src_first + P.src[src_i].chunks) {
             src_first += P.src[src_i].chunks;
             ++src_i;
@@ -345,30 +336,19 @@ __global__ void __launch_bounds__(NTHREADS, 2) conv_igemm_kernel(const ConvParam
             const int o_stride = P.split > 0 ? (second ? P.Cout - P.split : P.split) : P.Cout;
             const int o_c0 = n0 + nt * 32 - (second ? P.split : 0);
             uint2 q[4];
-            // epilogue inputs as 16-byte loads: a lane reads channels 8g + 8*half .. +7 (g even) and one permlane32_swap per
-            // dword hands every lane the two register quads (8g + 4*half, 8(g+1) + 4*half) it accumulates
-            uint2 ra[4], rr[4];
+            uint2 ra[4], rr[4];           // epilogue inputs: 16-byte loads, split into this lane's register quads (split_quads)
             if (P.res_act) {
 #pragma unroll
                 for (int g = 0; g < 4; g += 2) {
                     uint4 t4;
                     if constexpr (PRE) t4 = pre_ra[pt][nt][g >> 1];
                     else t4 = *(const uint4*)(P.res_act + pix * P.Cout + n0 + nt * 32 + 8 * g + 8 * half);
-                    const auto sx = __builtin_amdgcn_permlane32_swap(t4.x, t4.z, false, false);
-                    const auto sy = __builtin_amdgcn_permlane32_swap(t4.y, t4.w, false, false);
-                    ra[g] = make_uint2(sx[0], sy[0]);
-                    ra[g + 1] = make_uint2(sx[1], sy[1]);
+                    split_quads(t4, ra[g], ra[g + 1]);
                 }
             }
             if (r_base) {
 #pragma unroll
-                for (int g = 0; g < 4; g += 2) {
-                    const uint4 t4 = *(const uint4*)(r_base + pix * o_stride + o_c0 + 8 * g + 8 * half);
-                    const auto sx = __builtin_amdgcn_permlane32_swap(t4.x, t4.z, false, false);
-                    const auto sy = __builtin_amdgcn_permlane32_swap(t4.y, t4.w, false, false);
-                    rr[g] = make_uint2(sx[0], sy[0]);
-                    rr[g + 1] = make_uint2(sx[1], sy[1]);
-                }
+                for (int g = 0; g < 4; g += 2) split_quads(*(const uint4*)(r_base + pix * o_stride + o_c0 + 8 * g + 8 * half), rr[g], rr[g + 1]);
             }
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
@@ -380,22 +360,9 @@ __global__ void __launch_bounds__(NTHREADS, 2) conv_igemm_kernel(const ConvParam
                     const float4 bv = *(const float4*)(P.bias + c);
                     v[0] += bv.x; v[1] += bv.y; v[2] += bv.z; v[3] += bv.w;
                 }
-                if (P.res_act) {
-                    const uint2 r = ra[g];
-                    const float4 sc = *(const float4*)(P.res_scale + (size_t)b * P.Cout + c);
-                    const float4 sh = *(const float4*)(P.res_shift + (size_t)b * P.Cout + c);
-                    v[0] += silu_f(bf2f((bf16_t)(r.x & 0xffffu)) * sc.x + sh.x);
-                    v[1] += silu_f(bf2f((bf16_t)(r.x >> 16)) * sc.y + sh.y);
-                    v[2] += silu_f(bf2f((bf16_t)(r.y & 0xffffu)) * sc.z + sh.z);
-                    v[3] += silu_f(bf2f((bf16_t)(r.y >> 16)) * sc.w + sh.w);
-                }
-                if (r_base) {
-                    const uint2 r = rr[g];
-                    v[0] += bf2f((bf16_t)(r.x & 0xffffu));
-                    v[1] += bf2f((bf16_t)(r.x >> 16));
-                    v[2] += bf2f((bf16_t)(r.y & 0xffffu));
-                    v[3] += bf2f((bf16_t)(r.y >> 16));
-                }
+                if (P.res_act)
+                    add_silu_affine4(v, ra[g], *(const float4*)(P.res_scale + (size_t)b * P.Cout + c), *(const float4*)(P.res_shift + (size_t)b * P.Cout + c));
+                if (r_base) add_residual4(v, rr[g]);
                 q[g] = make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
                 if (P.gn_partial && ok) {   // statistics of the values as stored (bf16), DD:181
                     const float q0 = bf2f((bf16_t)(q[g].x & 0xffffu)), q1 = bf2f((bf16_t)(q[g].x >> 16));
@@ -531,7 +498,7 @@ __global__ void __launch_bounds__(256) upsample_phase_weight_prep_kernel(const f
 template <int KS, int BN>
 static int launch_conv(const ConvParams& P, hipStream_t s) {
     using C = Cfg<KS, BN>;
-    static bool attr_set = false;
+    static bool attr_set = false;      // per instantiation, once per process: the kernel's dynamic LDS size
     if (!attr_set) {
         OFD_HIP(hipFuncSetAttribute((const void*)conv_igemm_kernel<KS, BN>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES));
         attr_set = true;
@@ -545,7 +512,7 @@ static int launch_conv(const ConvParams& P, hipStream_t s) {
 
 int launch_conv3x3_wp(const ConvParams& P, bool wide, hipStream_t s);   // conv_wp.hip
 int launch_conv1x1_wp(const ConvParams& P, hipStream_t s);              // conv1_wp.hip: 1 = shape not served
-int launch_conv_up2_phases_wp(const ConvParams& P, hipStream_t s);      // conv_wp.hip: 1 = shape not served
+int launch_conv_up2_phases_wp(const ConvParams& P, hipStream_t s);      // conv_up2.hip: 1 = shape not served
 int launch_conv7x7_c8_persist(const ConvParams& P, hipStream_t s);      // conv7.hip: 1 = shape not served
 
 // the pooled epilogue exists in conv_wp.hip only: 3x3, even size, one output tensor, no fused GroupNorm statistics / activation residual
@@ -631,7 +598,7 @@ int conv_forward_impl(const ofd_conv_args* a, hipStream_t s, int cout0, int pool
     // workgroups
     const bool wide = (a->Cout % 128 == 0) && (long)P.tiles_x * P.tiles_y * P.B * (a->Cout / 128) >= 256;
     if (a->ksize == 3) {
-        // wave-private-weights kernels (conv_wp.hip) for same-size and up-sampled sources; the shared-slab kernel for unshuffled ones
+        // wave-private-weights kernels (conv_wp.hip, conv_pc.hip) for same-size and up-sampled sources; the shared-slab kernel for unshuffled ones
         bool modes_ok = true;
         for (int i = 0; i < a->n_src; ++i) modes_ok = modes_ok && P.src[i].mode != 2;
         if (modes_ok) return launch_conv3x3_wp(P, wide, s);
@@ -643,7 +610,7 @@ int conv_forward_impl(const ofd_conv_args* a, hipStream_t s, int cout0, int pool
     }
     OFD_CHECK_ARG(!P.fc_out, "conv: the fused final conv was requested for a shape the streaming 1x1 kernel does not serve");
     if (a->ksize == 1) return wide ? launch_conv<1, 128>(P, s) : launch_conv<1, 64>(P, s);
-    if (a->ksize == 2 && P.phase_all) {                  // the four phases as four wave pairs of one workgroup (conv_wp.hip)
+    if (a->ksize == 2 && P.phase_all) {                  // the four phases as four wave pairs of one workgroup (conv_up2.hip)
         const int r = launch_conv_up2_phases_wp(P, s);
         if (r != 1) return r;
     }

@@ -283,11 +283,7 @@ __global__ void __launch_bounds__(S_NT) splat_tile_fast_kernel(const float* __re
     // XCD-aware tile order: workgroups whose ids are equal mod 8 share an XCD (L2) and get a contiguous run of tiles, so the
     // window overlap of neighbouring tiles (3.06 visits per pixel) is served by one L2 instead of eight
     const int ntile = g.ntx * g.nty * g.B;
-    int t = blockIdx.x;
-    if (ntile >= 8) {
-        const int q = ntile / 8, r = ntile % 8, xcd = t % 8, idx = t / 8;
-        t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int t = xcd_tile_order(blockIdx.x, ntile);
     const int tx = t % g.ntx, ty = (t / g.ntx) % g.nty, n = t / (g.ntx * g.nty);
     const int X0 = tx * S_TW, Y0 = ty * S_TH;
 

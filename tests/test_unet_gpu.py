@@ -10,6 +10,7 @@ any tap) is asserted at ~1.5x that; the reference's own bf16-vs-fp32 floor on th
 (test_hip_unet_against_the_reference_module_outputs).
 """
 import ctypes
+import functools
 import math
 
 import pytest
@@ -125,7 +126,7 @@ def test_conv3x3_plain_and_ws(L, B, H, W, Cin, Cout):
 @pytest.mark.parametrize("B,H,W,cins,Cout,pro,up", [(2, 37, 70, (64,), 64, True, False), (1, 48, 96, (64, 64), 64, False, False), (2, 16, 64, (128,), 64, False, True),
                                                    (1, 24, 40, (64, 128), 128, True, False), (3, 16, 32, (64,), 192, False, False), (1, 200, 352, (64,), 64, True, False)])
 def test_conv3x3_producer_consumer_kernel_forms(L, B, H, W, cins, Cout, pro, up):
-    """conv3x3_pc_kernel (conv_wp.hip, r04: the 64-channel-block 3x3 as a persistent producer / consumer workgroup) over the forms it serves:
+    """conv3x3_pc_kernel (conv_pc.hip, r04: the 64-channel-block 3x3 as a persistent producer / consumer workgroup) over the forms it serves:
     one or two concatenated sources, a nearest-x2 source, the GroupNorm + SiLU prologue, several channel blocks per pixel tile (Cout 128 /
     192 on grids too small for the 128-channel-block kernel), partial tiles on both axes, more tiles than workgroups (200 x 352: every
     workgroup walks several items).  Against F.conv2d on the bf16-rounded operands AND against conv3x3_wp_kernel<2,2> (OFD_CONV_PC=0) on the
@@ -171,6 +172,71 @@ def test_conv3x3_producer_consumer_kernel_forms(L, B, H, W, cins, Cout, pro, up)
     assert torch.allclose(p1[..., 0], o.sum(dim=(2, 3, 4)), rtol=1e-4, atol=1e-2)
     assert torch.allclose(p1[..., 1], (o * o).sum(dim=(2, 3, 4)), rtol=1e-4, atol=1e-2)
     assert torch.allclose(p1, p0, rtol=2e-2, atol=0.5)           # (two kernels, two bf16 roundings of nearly equal sums)
+
+
+@functools.lru_cache(maxsize=None)
+def wide_case(B, H, W, cins, Cout, up, pro):
+    """Inputs and the F.conv2d reference of one wide-kernel case (CPU tensors, computed once and left unchanged: the cases that share a
+    shape share them)."""
+    torch.manual_seed(23)
+    hs, ws = (H // 2, W // 2) if up else (H, W)
+    xs = [q(torch.randn(B, c, hs, ws)) for c in cins]
+    xcat = torch.cat([F.interpolate(x, scale_factor=2, mode="nearest") if up else x for x in xs], 1)
+    Cin = xcat.shape[1]
+    w = torch.randn(Cout, Cin, 3, 3) / math.sqrt(Cin * 9)
+    b = torch.randn(Cout) * 0.1
+    a = s_ = None
+    if pro:
+        a, s_ = torch.rand(B, Cin) + 0.5, torch.randn(B, Cin) * 0.3
+        xcat = q(F.silu(xcat * a[:, :, None, None] + s_[:, :, None, None]))
+    return dict(xs=xs, w=w, b=b, a=a, s=s_, ref=F.conv2d(xcat, q(w), b, padding=1))
+
+
+WIDE_SHAPE = dict(B=1, H=61, W=500, Cout=256)            # 8 x 16 tiles, partial on both axes, two 128-channel blocks (cy_fast on)
+WIDE_CASES = {
+    "wp16": dict(WIDE_SHAPE, cins=(128,)),
+    "wp16_prologue_concat": dict(WIDE_SHAPE, cins=(64, 128), pro=True),
+    "wp_residual_forms": dict(WIDE_SHAPE, cins=(128,), epilogues=("residual", "res_act", "residual+prologue")),
+    "wp16_one_channel_block": dict(B=2, H=64, W=512, cins=(64,), Cout=128),          # cy_fast off
+    "wp16_upsample": dict(B=1, H=64, W=512, cins=(128,), Cout=256, up=True),         # one nearest-x2 source of 32 x 256
+}
+
+
+@pytest.mark.parametrize("case", list(WIDE_CASES))
+def test_conv3x3_wide_kernel_forms(L, case):
+    """The 128-channel-block 3x3 kernels on their own: conv3x3_wp16_kernel<false / true> (plain / prologue epilogue-free forms) and
+    conv3x3_wp_kernel<4,1,false / true> (the residual epilogues), which conv_forward_impl picks from 256 (tile, channel block) pairs on -- the
+    smallest shapes that reach them.  Values against F.conv2d on the bf16-rounded operands; the GroupNorm partial sums against float64 sums
+    over the stored output: sum of squares to rtol 1e-4, the plain sum to 1e-4 * sum |x| per (sample, octet) (fp32 accumulation error
+    scales with sum |x|, not with |sum x|); the nan-filled statistics buffer comes back finite everywhere."""
+    c = WIDE_CASES[case]
+    B, H, W, cins, Cout, up = c["B"], c["H"], c["W"], c["cins"], c["Cout"], c.get("up", False)
+    tiles = math.ceil(H / 8) * math.ceil(W / 32)
+    assert tiles * B * (Cout // 128) >= 256, "below conv_forward_impl's threshold: this would test the 64-channel-block kernels"
+    for epi in c.get("epilogues", ("plain",)):
+        pro = c.get("pro", False) or "prologue" in epi
+        d = wide_case(B, H, W, cins, Cout, up, pro)
+        ref, kw = d["ref"], {}
+        torch.manual_seed(29)
+        if "residual" in epi:
+            res = q(torch.randn(B, Cout, H, W))
+            ref, kw = ref + res, dict(residual=to_nhwc(res))
+        if epi == "res_act":
+            h = q(torch.randn(B, Cout, H, W))
+            ra, rs = torch.rand(B, Cout) + 0.5, torch.randn(B, Cout) * 0.3
+            ref = ref + F.silu(h * ra[:, :, None, None] + rs[:, :, None, None])
+            kw = dict(res_act=to_nhwc(h), res_scale=ra, res_shift=rs)
+        srcs = [dict(t=to_nhwc(x), upsample=1 if up else 0) for x in d["xs"]]
+        out, gn = run_conv(L, B, H, W, 3, srcs, Cout, prep_weight(L, d["w"], 3), bias=d["b"], in_scale=d["a"], in_shift=d["s"], want_gn=True, **kw)
+        o = from_nhwc(out)
+        check_close(o, ref, tol=2e-3 if pro or epi == "res_act" else PER_OP_TOL, what=f"{case} {epi}")
+        assert bool(torch.isfinite(gn).all()), f"{case} {epi}: statistics slots left unwritten"
+        p = gn_octet_sums(gn.double(), B, tiles, Cout)
+        oc = o.double().reshape(B, Cout // 8, 8, H, W)
+        s1, sabs, s2 = oc.sum(dim=(2, 3, 4)), oc.abs().sum(dim=(2, 3, 4)), (oc * oc).sum(dim=(2, 3, 4))
+        e1, e2 = float(((p[..., 0] - s1).abs() / sabs).max()), float(((p[..., 1] - s2).abs() / s2).max())
+        print(f"{case} {epi}: sum error / sum|x| {e1:.3e}, sum-of-squares relative error {e2:.3e}")
+        assert e1 <= 1e-4 and e2 <= 1e-4, f"{case} {epi}: sum error / sum|x| {e1:.3e}, sum-of-squares relative error {e2:.3e}"
 
 
 def test_conv3x3_concat_prologue_upsample_epilogues(L):
@@ -527,7 +593,7 @@ def test_upsample_conv_as_four_phase_convs(L, B, H, W, Cin, Cout):
     assert torch.isfinite(got).all()                       # every output pixel written by exactly one phase
     # vs the per-tap-rounded weights of the bf16c contract: two different bf16 roundings of the same fp32 kernel ...
     check_close(got, ref, tol=4e-3, what="phase-decomposed upsample conv")
-    # the four phases in ONE launch (up2_phase = 5, what the UNet runs): conv_up2_phases_wp_kernel (conv_wp.hip) -- the four phases as four
+    # the four phases in ONE launch (up2_phase = 5, what the UNet runs): conv_up2_phases_wp_kernel (conv_up2.hip) -- the four phases as four
     # wave pairs of one workgroup over ONE staged input tile; another summation order than the per-phase kernel: equal after rounding
     # except where the fp32 sums straddle a bf16 rounding boundary
     out1 = torch.full((B, 2 * H, 2 * W, Cout), float("nan"), dtype=torch.bfloat16, device="cuda")
