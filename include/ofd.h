@@ -224,6 +224,17 @@ int ofd_adam_chunk(void);
 int ofd_adam_step(const void* table, const unsigned* task_tensor, const unsigned* task_chunk, int n_tasks,
                   double* sqnorm_acc, float* clip_coef, float* total_norm, float max_norm, float lr,
                   float beta1, float beta2, float eps, float weight_decay, int step, void* stream);
+/* ofd_adam_step plus an exponential moving average (EMA) of the parameters, kept inside the same three launches: the step kernel
+ * has each new parameter value in a register and spends one more read and one more write per element on its average, instead
+ * of a second pass over every parameter.  Rows carry one more pointer: {float* param; const float* grad; float* exp_avg;
+ * float* exp_avg_sq; uint64 numel; float* ema}; every other argument is ofd_adam_step's, and param / exp_avg / exp_avg_sq come out
+ * bit for bit as from ofd_adam_step.  Per element, after p_new is stored: ema = ema_d * ema + ema_omd * p_new, the two products each
+ * rounded to fp32 and then added (no fused multiply-add).  ema_d = 0, ema_omd = 1 therefore leaves ema an exact copy of the new
+ * parameters.  The caller rounds ema_omd = 1 - d itself (optim.ema_decay_at), the kernel never forms 1 - ema_d. */
+int ofd_adam_step_ema(const void* table, const unsigned* task_tensor, const unsigned* task_chunk, int n_tasks,
+                      double* sqnorm_acc, float* clip_coef, float* total_norm, float max_norm, float lr,
+                      float beta1, float beta2, float eps, float weight_decay, int step, float ema_d, float ema_omd,
+                      void* stream);
 
 /* ------------------------------------------------------------------------ UNet (DD:272-417) -
  * Handle-based executor of the whole forward: one call runs every kernel of the network on

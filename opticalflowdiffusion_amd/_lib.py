@@ -77,6 +77,7 @@ SIGNATURES = {
     "ofd_nan_mse_result_doubles": (c_size_t, []),
     "ofd_adam_chunk": (c_int, []),
     "ofd_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p] + [c_float] * 6 + [c_int, c_void_p]),
+    "ofd_adam_step_ema": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p] + [c_float] * 6 + [c_int, c_float, c_float, c_void_p]),
     "ofd_unet_create": (c_int, [ctypes.POINTER(UnetConfig), ctypes.POINTER(c_void_p)]),
     "ofd_unet_destroy": (None, [c_void_p]),
     "ofd_unet_num_params": (c_int, [c_void_p]),

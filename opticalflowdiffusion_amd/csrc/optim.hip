@@ -2,7 +2,8 @@
 // torch.optim.Adam(lr, weight_decay) = Adam with L2 added to the gradient (not AdamW), betas
 // (0.9, 0.999), eps 1e-8, preceded by clip_grad_norm_(gradient_clip_val).  Multi-tensor kernels
 // over a device table of {param, grad, exp_avg, exp_avg_sq, numel}: three launches per step, no
-// host synchronisation (the clip coefficient stays on the device).
+// host synchronisation (the clip coefficient stays on the device).  ofd_adam_step_ema is the same step with an exponential moving
+// average of the parameters kept in the same pass (the weights a diffusion model is sampled from).
 #include "common.h"
 
 namespace ofd {
@@ -14,13 +15,29 @@ struct AdamTensor {
     float* v;
     unsigned long long n;
 };
+// the row of ofd_adam_step_ema: the same five fields, then the tensor's exponential moving average
+struct AdamTensorEma : AdamTensor {
+    float* ema;
+};
+// Optional trailing argument of adam_step_kernel.  Without it (E empty) the kernel is the plain step: same parameters and same
+// arithmetic as before.  With it, each freshly written parameter also updates its average, ema = d * ema + omd * p_new, both products
+// rounded on their own and then added (__fmul_rn / __fadd_rn: this file is compiled with contraction on, and the compiler's choice
+// of which product to fuse must not decide the average's bits).  d = 0, omd = 1 makes ema an exact copy of p_new.
+struct EmaArgs {
+    float d;
+    float omd;
+};
+__device__ __forceinline__ EmaArgs ema_args(EmaArgs a) { return a; }
+template <bool EMA> struct AdamRow { using type = AdamTensor; };
+template <> struct AdamRow<true> { using type = AdamTensorEma; };
 
 constexpr int OPT_CHUNK = 65536;   // elements per workgroup task
 
 // sum of squares of a task's chunk -> part[task] (double): no atomics, clip_coef_kernel adds the tasks up in a fixed order (the same
 // gradients give the same norm, bit for bit -- a double atomic per workgroup made the clip coefficient, and with it every parameter,
 // depend on the order the workgroups retired in)
-__global__ void __launch_bounds__(256) grad_sqnorm_kernel(const AdamTensor* __restrict__ tab, const unsigned* __restrict__ task_tensor,
+template <typename Row>
+__global__ void __launch_bounds__(256) grad_sqnorm_kernel(const Row* __restrict__ tab, const unsigned* __restrict__ task_tensor,
                                                           const unsigned* __restrict__ task_chunk, double* __restrict__ part) {
     const AdamTensor t = tab[task_tensor[blockIdx.x]];
     const unsigned long long start = (unsigned long long)task_chunk[blockIdx.x] * OPT_CHUNK;
@@ -58,14 +75,20 @@ __global__ void __launch_bounds__(256) clip_coef_kernel(double* __restrict__ acc
     *coef = c;
 }
 
-__global__ void __launch_bounds__(256) adam_step_kernel(const AdamTensor* __restrict__ tab, const unsigned* __restrict__ task_tensor,
+template <typename... E>
+__global__ void __launch_bounds__(256) adam_step_kernel(const typename AdamRow<sizeof...(E) != 0>::type* __restrict__ tab,
+                                                        const unsigned* __restrict__ task_tensor,
                                                         const unsigned* __restrict__ task_chunk, const float* __restrict__ coef, float lr,
-                                                        float beta1, float beta2, float eps, float weight_decay, float bc1, float bc2_sqrt) {
-    const AdamTensor t = tab[task_tensor[blockIdx.x]];
+                                                        float beta1, float beta2, float eps, float weight_decay, float bc1, float bc2_sqrt,
+                                                        E... ema) {
+    constexpr bool EMA = sizeof...(E) != 0;
+    const typename AdamRow<EMA>::type t = tab[task_tensor[blockIdx.x]];
     const unsigned long long start = (unsigned long long)task_chunk[blockIdx.x] * OPT_CHUNK;
     const unsigned long long stop = min(t.n, start + OPT_CHUNK);
     const float c = coef ? *coef : 1.0f;
     const float step_size = lr / bc1;
+    [[maybe_unused]] EmaArgs a{};
+    if constexpr (EMA) a = ema_args(ema...);
     for (unsigned long long i = start + threadIdx.x; i < stop; i += 256) {
         float p = t.p[i];
         float g = t.g[i] * c;
@@ -75,8 +98,26 @@ __global__ void __launch_bounds__(256) adam_step_kernel(const AdamTensor* __rest
         t.m[i] = m;
         t.v[i] = v;
         const float denom = sqrtf(v) / bc2_sqrt + eps;
-        t.p[i] = p - step_size * (m / denom);
+        const float p_new = p - step_size * (m / denom);
+        t.p[i] = p_new;
+        if constexpr (EMA) {
+            t.ema[i] = __fadd_rn(__fmul_rn(a.d, t.ema[i]), __fmul_rn(a.omd, p_new));
+        }
     }
+}
+
+// the three launches of a step; E empty: the plain step over AdamTensor rows, E = EmaArgs: over AdamTensorEma rows
+template <typename... E>
+static void adam_launch(const void* table, const unsigned* task_tensor, const unsigned* task_chunk, int n_tasks, double* sqnorm_acc,
+                        float* clip_coef, float* total_norm, float max_norm, float lr, float beta1, float beta2, float eps,
+                        float weight_decay, int step, hipStream_t s, E... ema) {
+    using Row = typename AdamRow<sizeof...(E) != 0>::type;
+    grad_sqnorm_kernel<Row><<<n_tasks, 256, 0, s>>>((const Row*)table, task_tensor, task_chunk, sqnorm_acc + 1);
+    clip_coef_kernel<<<1, 256, 0, s>>>(sqnorm_acc, n_tasks, max_norm, clip_coef, total_norm);
+    const float bc1 = 1.0f - powf(beta1, (float)step);
+    const float bc2_sqrt = sqrtf(1.0f - powf(beta2, (float)step));
+    adam_step_kernel<E...><<<n_tasks, 256, 0, s>>>((const Row*)table, task_tensor, task_chunk, clip_coef, lr, beta1, beta2, eps, weight_decay,
+                                                   bc1, bc2_sqrt, ema...);
 }
 
 }  // namespace ofd
@@ -87,12 +128,19 @@ extern "C" int ofd_adam_step(const void* table, const unsigned* task_tensor, con
                              float* clip_coef, float* total_norm, float max_norm, float lr, float beta1, float beta2, float eps,
                              float weight_decay, int step, void* stream) {
     OFD_CHECK_ARG(table && task_tensor && task_chunk && n_tasks > 0 && sqnorm_acc && clip_coef && step >= 1, "adam_step: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    grad_sqnorm_kernel<<<n_tasks, 256, 0, s>>>((const AdamTensor*)table, task_tensor, task_chunk, sqnorm_acc + 1);
-    clip_coef_kernel<<<1, 256, 0, s>>>(sqnorm_acc, n_tasks, max_norm, clip_coef, total_norm);
-    const float bc1 = 1.0f - powf(beta1, (float)step);
-    const float bc2_sqrt = sqrtf(1.0f - powf(beta2, (float)step));
-    adam_step_kernel<<<n_tasks, 256, 0, s>>>((const AdamTensor*)table, task_tensor, task_chunk, clip_coef, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt);
+    adam_launch(table, task_tensor, task_chunk, n_tasks, sqnorm_acc, clip_coef, total_norm, max_norm, lr, beta1, beta2, eps, weight_decay,
+                step, (hipStream_t)stream);
+    OFD_LAUNCH_CHECK();
+    return OFD_OK;
+}
+
+// table: n_tensors x {p, g, m, v, n, ema} (device); the step of ofd_adam_step, then ema = ema_d * ema + ema_omd * p_new per element
+extern "C" int ofd_adam_step_ema(const void* table, const unsigned* task_tensor, const unsigned* task_chunk, int n_tasks, double* sqnorm_acc,
+                                 float* clip_coef, float* total_norm, float max_norm, float lr, float beta1, float beta2, float eps,
+                                 float weight_decay, int step, float ema_d, float ema_omd, void* stream) {
+    OFD_CHECK_ARG(table && task_tensor && task_chunk && n_tasks > 0 && sqnorm_acc && clip_coef && step >= 1, "adam_step_ema: bad argument");
+    adam_launch(table, task_tensor, task_chunk, n_tasks, sqnorm_acc, clip_coef, total_norm, max_norm, lr, beta1, beta2, eps, weight_decay,
+                step, (hipStream_t)stream, EmaArgs{ema_d, ema_omd});
     OFD_LAUNCH_CHECK();
     return OFD_OK;
 }

@@ -8,6 +8,7 @@ PyTorch fallback.  `ConditionalDiffusion` restates DD:463-993 for the three obje
 pred_v), auto-normalisation and offset noise, with the elementwise steps fused into single HIP
 kernels, generalised to non-square `image_size=(H, W)` and with a working DDIM path.
 """
+import contextlib
 import ctypes
 import math
 from collections import namedtuple
@@ -192,6 +193,7 @@ class Unet(nn.Module):
         self._synced = None
         self._pflat = None
         self._poffsets = None
+        self._ema_bound = None         # inside ema_scope: the flat buffer the executor reads instead of _pflat
         self._ws = None
         self._train_ws = None
         self._gflat = None
@@ -243,7 +245,9 @@ class Unet(nn.Module):
         """The executor reads the parameters in place: every nn.Parameter is a view of one flat fp32 device
         tensor laid out like the executor's registry (bound once, zero copies per step).  Whenever a
         parameter's version changed (optimizer step, load_state_dict, manual edit) only the weight
-        preparation (standardise + bf16 pack) is re-run."""
+        preparation (standardise + bf16 pack) is re-run.  Inside `ema_scope` the executor stays on the scope's buffer."""
+        if self._ema_bound is not None:
+            return
         lib = L.lib()
         params = [self._param(n) for n in self._names]
         if self._poffsets is None:
@@ -266,6 +270,36 @@ class Unet(nn.Module):
         if self._synced != key:
             L.check(lib.ofd_unet_prepare(self._handle, L.stream()))
             self._synced = key
+
+    def flat_params(self, device):
+        """the flat fp32 buffer every parameter is a view of (parameter i at [offset_i, offset_i + numel_i), `_poffsets`)"""
+        self._sync_params(device)
+        return self._pflat
+
+    @contextlib.contextmanager
+    def ema_scope(self, flat_ema):
+        """Inside the scope the inference forward runs on `flat_ema` instead of the parameters: a flat fp32 device buffer in the layout
+        of `flat_params` (optim.FusedAdam keeps the parameters' exponential moving average in one).  Entering binds the executor to it
+        and re-runs the weight preparation; leaving binds the parameters' own buffer again and has the next forward re-prepare.  No
+        parameter is touched, so what is computed after the scope equals what was computed before it, bit for bit.  The training
+        forward raises OfdError inside the scope: its gradients would belong to weights the optimiser does not step."""
+        if self._ema_bound is not None:
+            raise L.OfdError("Unet.ema_scope: already inside an ema_scope")
+        L.require_gpu(flat_ema)
+        lib = L.lib()
+        need = lib.ofd_unet_param_floats(self._handle)
+        if flat_ema.dtype != torch.float32 or not flat_ema.is_contiguous() or flat_ema.numel() != need:
+            raise L.OfdError(f"Unet.ema_scope: needs a contiguous fp32 buffer of {need} floats")
+        own = self.flat_params(flat_ema.device)          # the buffer to come back to
+        L.check(lib.ofd_unet_bind_param_buffer(self._handle, L.ptr(flat_ema), flat_ema.numel()))
+        self._ema_bound = flat_ema
+        try:
+            L.check(lib.ofd_unet_prepare(self._handle, L.stream()))
+            yield self
+        finally:
+            self._ema_bound = None
+            L.check(lib.ofd_unet_bind_param_buffer(self._handle, L.ptr(own), own.numel()))
+            self._synced = None
 
     def _workspace(self, device, B, H, W):
         need = L.lib().ofd_unet_workspace_bytes(self._handle, B, H, W)
@@ -318,6 +352,8 @@ class Unet(nn.Module):
         return self._gflat
 
     def _train_forward(self, x, cond, t):
+        if self._ema_bound is not None:
+            raise L.OfdError("Unet: no training forward inside ema_scope (the executor holds the averaged weights, which are not trained)")
         lib = L.lib()
         B, Cx, H, W = x.shape
         Cc = cond.shape[1] if cond is not None else 0

@@ -5,11 +5,14 @@ frame and a few of its flow vectors (1-8 per frame).  Every other pixel of the s
 embedding.  The sampler, the loss and the null embedding's gradient are device kernels (csrc/completer.hip); the points where the
 reference cannot run as written are ported by its evident intent.
 """
+import contextlib
+
 import torch
 
 from . import _lib as L
 from .compat.shims.utils.image_prediction.logging import log_photos
 from .denoising_diffusion import Unet
+from .ema import EMA_DEFAULTS, EmaMixin, ema_optimizer_kwargs
 from .flow_diffuser import FlowDiffuser, _Base, _Cfg
 from .visualization import flow_to_image
 
@@ -18,9 +21,10 @@ MAX_PICKS = 8          # DA:170: randint(8) + 1 points per frame
 
 class _CompleterCfg(_Cfg):
     """configurations/algorithm/flow_completer.yaml, plus `clip` (the trainer's gradient_clip_val, folded into FusedAdam), `precision`
-    and `lmbd` (DA:149)"""
+    `lmbd` (DA:149) and the `ema_*` keys and `sample_with_ema` (ema.EMA_DEFAULTS)"""
 
-    _DEFAULTS = dict(name="flow_completer", image_size=64, lr=4.5e-6, weight_decay=2e-4, clip=0.0, precision="bf16", lmbd=0.2)
+    _DEFAULTS = dict(name="flow_completer", image_size=64, lr=4.5e-6, weight_decay=2e-4, clip=0.0, precision="bf16", lmbd=0.2,
+                     **EMA_DEFAULTS)
 
 
 def _hw(x):
@@ -114,7 +118,7 @@ def completer_loss(out, dense, amax, lmbd=0.2):
     return _CompleterLoss.apply(out, dense, amax, lmbd)
 
 
-class FlowCompleter(_Base):
+class FlowCompleter(EmaMixin, _Base):
     """DA:127-246.  `training_step` returns the loss (the trainer runs backward and the optimiser step, as for FrameGenerator);
     `on_before_optimizer_step` logs the gradient statistics (DA:198, 226-246).  `null_embedding` is a learnable 2-vector (state-dict
     keys null_embedding.0 / .1); a state dict without them (the reference's checkpoints) loads with the embedding at 1.0."""
@@ -135,8 +139,22 @@ class FlowCompleter(_Base):
         hyperparameters), as the HIP multi-tensor step; the clip norm, if set, spans both"""
         from .optim import FusedAdam
         self.optimizers = FusedAdam(list(self.model.parameters()) + list(self.null_embedding), lr=self.cfg.lr,
-                                    weight_decay=self.cfg.weight_decay, max_grad_norm=float(self.cfg.clip or 0.0))
+                                    weight_decay=self.cfg.weight_decay, max_grad_norm=float(self.cfg.clip or 0.0),
+                                    **ema_optimizer_kwargs(self.cfg, self._ema_unets()))
         return self.optimizers
+
+    def _ema_unets(self):
+        return [self.model]
+
+    @contextlib.contextmanager
+    def _ema_extra_scope(self, opt):
+        """inside ema_scope `null_vector` (what `complete` fills with) is the embedding's average"""
+        ema = opt.ema_tensors()
+        self._null_ema = [ema.get(id(p), p).detach() for p in self.null_embedding]
+        try:
+            yield
+        finally:
+            self._null_ema = None
 
     def load_state_dict(self, state_dict, strict=True, assign=False):
         """model.* alone (the reference never saves its embedding): the embedding is set to its initial 1.0"""
@@ -182,7 +200,7 @@ class FlowCompleter(_Base):
     log_grad_norm_stat = FlowDiffuser.log_grad_norm_stat                                                 # DA:226-246 == FD:367-388
 
     def null_vector(self):
-        return torch.cat([p.detach().reshape(1) for p in self.null_embedding])
+        return torch.cat([p.detach().reshape(1) for p in (self.__dict__.get("_null_ema") or self.null_embedding)])
 
     @torch.no_grad()
     def complete(self, frame, sparse):
@@ -194,8 +212,9 @@ class FlowCompleter(_Base):
         if C != 2 or tuple(frame.shape) != (B, 3, H, W):
             raise L.OfdError(f"complete: frame {tuple(frame.shape)}, sparse {tuple(sparse.shape)}")
         filled = torch.empty_like(sparse)
-        L.check(L.lib().ofd_sparse_flow_fill(L.ptr(sparse), L.ptr(self.null_vector().contiguous()), L.ptr(filled), B, H, W, L.stream()))
-        return self.model(filled, external_cond=L.f32c(frame))
+        with self._sampling_scope():                                         # the EMA weights and embedding when cfg.ema_decay is set
+            L.check(L.lib().ofd_sparse_flow_fill(L.ptr(sparse), L.ptr(self.null_vector().contiguous()), L.ptr(filled), B, H, W, L.stream()))
+            return self.model(filled, external_cond=L.f32c(frame))
 
     def validation_step(self, batch, batch_idx):                                                         # DA:200-224
         """(B, V, 8, H, W) video batches use their first frame (DA:201); (B, 8, H, W) and (img, tgt, flow) are taken as they are"""

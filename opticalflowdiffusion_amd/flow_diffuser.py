@@ -6,14 +6,16 @@ The reference class is a `pl.LightningModule`; Lightning, Hydra and W&B are opti
 with the hooks `experiments/exp_base.py` drives (`log_dict`, `configure_optimizers`,
 `training_step`, `validation_step`).  `cfg` may be a DictConfig, a dict or any attribute object
 with the keys of configurations/algorithm/flow_diffuser.yaml (+ optional `image_size: [H, W]`,
-`sampling_timesteps`, `precision`, `ae_checkpoint`, and the sampler keys `sampler`, `solver_order`,
-`sampler_spacing` of ConditionalDiffusion, which are not in the reference).
+`sampling_timesteps`, `precision`, `ae_checkpoint`, the sampler keys `sampler`, `solver_order`,
+`sampler_spacing` of ConditionalDiffusion, and the `ema_*` keys and `sample_with_ema` of ema.EMA_DEFAULTS, which are not
+in the reference).
 """
 import os
 
 import torch
 
 from .denoising_diffusion import Unet, ConditionalDiffusion
+from .ema import EMA_DEFAULTS, EmaMixin, ema_optimizer_kwargs
 from .warp import warp
 from . import _lib as L
 
@@ -41,7 +43,8 @@ class _Cfg:
     _DEFAULTS = dict(name="flow_diffuser", image_size=128, latent_dim=16, flow_max=20, latent_max=2, lr=1e-5,
                      flow_weight=0.0, weight_decay=1e-6, is_diffusion=True, latent=False, timesteps=1000,
                      target="joint", ae="px8q8g0m", noiser="image", zero_init=True,
-                     sampling_timesteps=None, precision="bf16", augment=True, sampler=None, solver_order=2, sampler_spacing="logsnr")
+                     sampling_timesteps=None, precision="bf16", augment=True, sampler=None, solver_order=2, sampler_spacing="logsnr",
+                     **EMA_DEFAULTS)
 
     def __init__(self, cfg):
         self._d = dict(self._DEFAULTS)
@@ -116,11 +119,12 @@ def ae_checkpoint_path(cfg):
     return p if p else os.path.join("outputs", "loaded_checkpoints", "diffusion_control", str(cfg.ae), "model.ckpt")
 
 
-class FlowDiffuser(_Base):
+class FlowDiffuser(EmaMixin, _Base):
     """FD:65-388: `training_step` is differentiable through the HIP training executor
     (`ofd_unet_train_forward` / `ofd_unet_backward` behind `denoising_diffusion._UnetTrain`).  latent=True runs the diffusion
     on the latents of the reference's frozen `Autoencoder` (flow_pred.py), loaded from a local Lightning checkpoint
-    (`ae_checkpoint_path`); nothing is downloaded."""
+    (`ae_checkpoint_path`); nothing is downloaded.  With cfg.ema_decay set, the optimiser keeps an EMA of the UNet (the frozen
+    Autoencoder has none) and `sample` -- and with it the sampling half of `validation_step` -- runs on it (`ema_scope`)."""
 
     def __init__(self, cfg):
         super().__init__()
@@ -176,8 +180,12 @@ class FlowDiffuser(_Base):
         gradient_clip_val (exp_base.py:205) into the same launches."""
         from .optim import FusedAdam
         clip = getattr(self.cfg, "clip", 0.0) if "clip" in self.cfg else 0.0
-        self.optimizers = FusedAdam(self.model.parameters(), lr=self.cfg.lr, weight_decay=self.cfg.weight_decay, max_grad_norm=clip)
+        self.optimizers = FusedAdam(self.model.parameters(), lr=self.cfg.lr, weight_decay=self.cfg.weight_decay, max_grad_norm=clip,
+                                    **ema_optimizer_kwargs(self.cfg, self._ema_unets()))
         return self.optimizers
+
+    def _ema_unets(self):
+        return [self.unet]
 
     def preprocess(self, batch, aug=True):
         """FD:136-168.  `aug=True` (what training_step passes, FD:219) runs the batched GPU `Augmentor` (augmentation.py of this
@@ -245,6 +253,13 @@ class FlowDiffuser(_Base):
         """`known_flow` (optional, not in the reference): (B, 2, H, W) in pixels, NaN = free; the returned flow has
         clamp(known_flow / flow_max) at the other elements and the sampler fills in the rest consistently (constrained sampling,
         ConditionalDiffusion.sample).  target 'flow' or 'joint' only.  `resample` as there: DDPM only, `resample` UNet calls per step."""
+        # a regression model called with autograd on runs the training forward, which has no EMA weights to run on
+        if self.is_diffusion or not torch.is_grad_enabled():
+            with self._sampling_scope():
+                return self._sample(cond, flow, known_flow, resample)
+        return self._sample(cond, flow, known_flow, resample)
+
+    def _sample(self, cond, flow, known_flow, resample):
         bsz = flow.shape[0]
         kw = {}
         if known_flow is not None:

@@ -10,6 +10,7 @@ filter representation, FL:75-81, which needs ConvToFilter / filter_to_flow: outs
 import torch
 
 from .denoising_diffusion import Unet
+from .ema import EMA_DEFAULTS, EmaMixin, ema_optimizer_kwargs
 from .flow_diffuser import UnetWithWarp, _Base, _Cfg
 from .softsplat import pyramid_charbonnier, pyramid_offsets, softsplat, softsplat_pyramid, splat_pyramid
 from .warp import charbonnier, edgeaware_smoothness1, fill_holes_nan, nan_charbonnier
@@ -19,7 +20,8 @@ LEVELS = (1, 2, 4, 5, 7, 8, 10, 11, 14, 16)          # FL:163
 
 class _LearnerCfg(_Cfg):
     _DEFAULTS = dict(name="flow_learner", image_size=128, flow_max=20, latent=False, zero_init=True, c2f=False, lr=8e-5,
-                     weight_decay=1e-6, sparsity_weight=0.0, occlusion_mask=True, train_aug=True, latent_dim=16, precision="bf16")
+                     weight_decay=1e-6, sparsity_weight=0.0, occlusion_mask=True, train_aug=True, latent_dim=16, precision="bf16",
+                     **EMA_DEFAULTS)
 
 
 def photometric_pyramid_loss(input_img, flow_pred, warp_weights, tgt, levels=LEVELS):
@@ -71,7 +73,7 @@ def photometric_pyramid_loss_fused_torch(input_img, flow_pred, warp_weights, tgt
     return sum(photo) / len(photo)
 
 
-class FlowLearner(_Base):
+class FlowLearner(EmaMixin, _Base):
     """FL:62-424, flow representation."""
 
     def __init__(self, cfg):
@@ -93,8 +95,12 @@ class FlowLearner(_Base):
     def configure_optimizers(self):                                         # FL:104-107
         from .optim import FusedAdam
         clip = getattr(self.cfg, "clip", 0.0) if "clip" in self.cfg else 0.0
-        self.optimizers = FusedAdam(self.model.parameters(), lr=self.cfg.lr, weight_decay=self.cfg.weight_decay, max_grad_norm=clip)
+        self.optimizers = FusedAdam(self.model.parameters(), lr=self.cfg.lr, weight_decay=self.cfg.weight_decay, max_grad_norm=clip,
+                                    **ema_optimizer_kwargs(self.cfg, self._ema_unets()))
         return self.optimizers
+
+    def _ema_unets(self):
+        return [self.unet.model]
 
     def preprocess(self, batch, aug=True):
         """FL:114-130 (the torchvision Augmentor is outside this path: aug is accepted and ignored)."""
@@ -146,7 +152,8 @@ class FlowLearner(_Base):
         tgt_, cond, flow_ = self.preprocess(batch, aug=False)
         loss = self.loss(tgt_, cond, flow_)
         ideal_loss = self.loss(tgt_, cond, flow_, override_flow=flow_)
-        samples, p_flows, _ = self.sample(cond, flow_)
+        with self._sampling_scope():                                        # the EMA weights when cfg.ema_decay is set; the losses stay online
+            samples, p_flows, _ = self.sample(cond, flow_)
         samples = torch.where(torch.isnan(samples), torch.zeros_like(samples), samples)
         self.log_dict({"val/loss": loss, "val/ideal_loss": ideal_loss,
                        "val/mse": torch.nn.functional.mse_loss(samples, tgt),

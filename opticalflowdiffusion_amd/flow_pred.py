@@ -12,6 +12,7 @@ import torch
 from torch import nn
 
 from .denoising_diffusion import Unet
+from .ema import EMA_DEFAULTS, EmaMixin, ema_optimizer_kwargs
 from .flow_diffuser import _Base, _Cfg
 from .warp import warp
 
@@ -58,10 +59,10 @@ class Autoencoder(nn.Module):
 
 class _PredCfg(_Cfg):
     """configurations/algorithm/flow_pred.yaml, plus `clip` (the trainer's gradient_clip_val, folded into FusedAdam), `augment`,
-    `precision` and `nan_holes` (see FlowPred)"""
+    `precision`, `nan_holes` (see FlowPred) and the `ema_*` keys (ema.EMA_DEFAULTS)"""
 
     _DEFAULTS = dict(name="flow_pred", image_size="128,128", lr=4e-5, weight_decay=1e-6, latent_dim=16, ae_frac=0.1, clip=0.0,
-                     nan_holes=False, augment=True, precision="bf16")
+                     nan_holes=False, augment=True, precision="bf16", **EMA_DEFAULTS)
 
 
 def parse_image_size(size):
@@ -75,7 +76,7 @@ def parse_image_size(size):
     return int(size), int(size)
 
 
-class FlowPred(_Base):
+class FlowPred(EmaMixin, _Base):
     """FP:60-124: trains the `Autoencoder` to reconstruct the target frame from the image and its flow-splatted latents.
 
     Deviation: the reference adds N(0, 1) noise to the flow and splats with NaN holes; a hole (a pixel no source
@@ -95,8 +96,11 @@ class FlowPred(_Base):
         """Adam(ae.parameters()) as the reference, as the HIP multi-tensor step (optim.FusedAdam)"""
         from .optim import FusedAdam
         self.optimizers = FusedAdam(self.ae.parameters(), lr=self.cfg.lr, weight_decay=self.cfg.weight_decay,
-                                    max_grad_norm=float(self.cfg.clip or 0.0))
+                                    max_grad_norm=float(self.cfg.clip or 0.0), **ema_optimizer_kwargs(self.cfg, self._ema_unets()))
         return self.optimizers
+
+    def _ema_unets(self):
+        return [self.ae.model_enc, self.ae.model_dec]
 
     def _augment(self, batch):
         if not self.cfg.augment:

@@ -10,20 +10,21 @@ import torch
 from .compat.shims.utils.image_prediction.logging import log_photos
 from .compat.shims.utils.video_prediction.visualization import log_video
 from .denoising_diffusion import ConditionalDiffusion, Unet
+from .ema import EMA_DEFAULTS, EmaMixin, ema_optimizer_kwargs
 from .flow_diffuser import FlowDiffuser, _Base, _Cfg
 from .flow_pred import parse_image_size
 
 
 class _FrameCfg(_Cfg):
     """configurations/algorithm/frame_generator.yaml, plus `clip` (the trainer's gradient_clip_val, folded into FusedAdam),
-    `precision`, `timesteps` and `sampling_timesteps` (DDIM when fewer than `timesteps`), and the sampler keys of ConditionalDiffusion
-    (`sampler`, `solver_order`, `sampler_spacing`; not in the reference)"""
+    `precision`, `timesteps` and `sampling_timesteps` (DDIM when fewer than `timesteps`), the sampler keys of ConditionalDiffusion
+    (`sampler`, `solver_order`, `sampler_spacing`; not in the reference) and the `ema_*` keys and `sample_with_ema` (ema.EMA_DEFAULTS)"""
 
     _DEFAULTS = dict(name="frame_generator", image_size=64, lr=7e-5, weight_decay=2e-4, clip=0.0, precision="bf16", timesteps=1000,
-                     sampling_timesteps=None, sampler=None, solver_order=2, sampler_spacing="logsnr")
+                     sampling_timesteps=None, sampler=None, solver_order=2, sampler_spacing="logsnr", **EMA_DEFAULTS)
 
 
-class FrameGenerator(_Base):
+class FrameGenerator(EmaMixin, _Base):
     """DA:14-125.  `training_step` returns the loss (the trainer runs backward and the optimiser step, as for FlowDiffuser);
     `on_before_optimizer_step` logs the reference's grad_norm / gpr statistics (DA:62, 103-125).  `validation_step` implements the
     evident intent of DA:64-100 (which raises at `batch.size[1]`): first-frame loss and samples, then `rollout`."""
@@ -45,8 +46,11 @@ class FrameGenerator(_Base):
         """Adam(lr, weight_decay) as the reference, as the HIP multi-tensor step (optim.FusedAdam)"""
         from .optim import FusedAdam
         self.optimizers = FusedAdam(self.diffusion_model.parameters(), lr=self.cfg.lr, weight_decay=self.cfg.weight_decay,
-                                    max_grad_norm=float(self.cfg.clip or 0.0))
+                                    max_grad_norm=float(self.cfg.clip or 0.0), **ema_optimizer_kwargs(self.cfg, self._ema_unets()))
         return self.optimizers
+
+    def _ema_unets(self):
+        return [self._model]
 
     @staticmethod
     def split(batch):
@@ -73,20 +77,22 @@ class FrameGenerator(_Base):
     def sample(self, cond, known=None):
         """one sampling chain per sample of cond (B, 5, H, W) in [0, 1]; returns (B, 3, H, W) in [0, 1].  `known` (optional, not in
         the reference): (B, 3, H, W) in [0, 1], NaN = free -- inpainting of the next frame (ConditionalDiffusion.sample)."""
-        if known is None:
-            return self.diffusion_model.sample(batch_size=cond.shape[0], external_cond=cond)
-        return self.diffusion_model.sample(batch_size=cond.shape[0], external_cond=cond, known=known)
+        with self._sampling_scope():                                     # the EMA weights when cfg.ema_decay is set
+            if known is None:
+                return self.diffusion_model.sample(batch_size=cond.shape[0], external_cond=cond)
+            return self.diffusion_model.sample(batch_size=cond.shape[0], external_cond=cond, known=known)
 
     @torch.no_grad()
     def rollout(self, batch, known=None):
         """DA:84-100: batch (B, V, 8, H, W); frame k is sampled with cond = batch[:, k, 3:], whose last-frame channels are replaced
         by frame k-1's sample for k >= 1.  Returns (V, B, 3, H, W).  `known` (optional): (B, V, 3, H, W), frame k's `known`."""
         samples = []
-        for k in range(batch.shape[1]):
-            cond = batch[:, k, 3:].clone()
-            if k != 0:
-                cond[:, :3] = samples[-1][:, :3]                                                     # DA:90-91
-            samples.append(self.sample(cond) if known is None else self.sample(cond, known=known[:, k]))
+        with self._sampling_scope():                                     # one rebind for the whole rollout
+            for k in range(batch.shape[1]):
+                cond = batch[:, k, 3:].clone()
+                if k != 0:
+                    cond[:, :3] = samples[-1][:, :3]                                                 # DA:90-91
+                samples.append(self.sample(cond) if known is None else self.sample(cond, known=known[:, k]))
         return torch.stack(samples, dim=0)
 
     def validation_step(self, batch, batch_idx):                                                     # DA:64-100

@@ -9,7 +9,8 @@ algorithm=flow_diffuser` does through Lightning (experiments/exp_base.py:177-214
   matrix_flow.yaml, configurations/algorithm/flow_diffuser.yaml); `--config file.yaml` and `--set a.b=v` override;
 * one process per GPU; gradients averaged inside every backward by the bucketed RCCL all-reduce (parallel.py);
 * checkpoints in Lightning's layout: {"state_dict" (keys unet.* / _model.* / model.*, 13 schedule buffers),
-  "optimizer_states", "global_step", "epoch"}; `--resume` continues bit-identically on the same seeds;
+  "optimizer_states", "global_step", "epoch"}; `--resume` continues bit-identically on the same seeds; with
+  `algorithm.ema_decay` set the optimiser state carries the EMA of the weights and `last_ema.ckpt` holds them as a plain state dict;
 * one JSON line per logged step on rank 0.
 """
 import argparse
@@ -74,6 +75,13 @@ def save_checkpoint(path, fd, opt, step, epoch):
     tmp = path + ".tmp"
     torch.save({"state_dict": fd.state_dict(), "optimizer_states": [opt.state_dict()], "global_step": step, "epoch": epoch,
                 "pytorch-lightning_version": "compat", "rng": torch.get_rng_state(), "cuda_rng": torch.cuda.get_rng_state()}, tmp)
+    os.replace(tmp, path)
+
+
+def save_ema_checkpoint(path, fd, step, epoch):
+    """the weights one ships: the model's state dict with the EMA values under the ordinary names (no optimiser state)"""
+    tmp = path + ".tmp"
+    torch.save({"state_dict": fd.ema_state_dict(), "global_step": step, "epoch": epoch, "pytorch-lightning_version": "compat"}, tmp)
     os.replace(tmp, path)
 
 
@@ -190,6 +198,8 @@ def main(argv=None):
     if a.ckpt_dir and rank == 0:
         os.makedirs(a.ckpt_dir, exist_ok=True)
         save_checkpoint(os.path.join(a.ckpt_dir, "last.ckpt"), fd, opt, step, epoch)
+        if getattr(opt, "ema", None) is not None:          # algorithm.ema_decay set: the averaged weights beside the training state
+            save_ema_checkpoint(os.path.join(a.ckpt_dir, "last_ema.ckpt"), fd, step, epoch)
     parallel.barrier(dev)
     return fd, logs
 
