@@ -385,6 +385,7 @@ int ofd_conv_weight_prep(const float* w_oihw, void* w_out, int Cout, int Cin, in
                          float ws_eps, int unshuffle, void* stream);
 
 /* ---------------------------------------------------------------- conv backward (training) --
+ * (conv_wgrad.hip: ofd_conv_wgrad, ofd_conv7_wgrad, ofd_conv7_wgrad_c, ofd_channel_sum; conv_bwd.hip: the layout kernels around them)
  * data gradient  : run ofd_conv_forward on dY (source, Cout channels) with the weights produced by
  *                  ofd_conv_dgrad_weight_prep (tap-flipped, in/out transposed); output has Cin channels;
  *                  ofd_grad_scatter applies the adjoint of concat / up-sample (mode 1) / unshuffle (mode 2).

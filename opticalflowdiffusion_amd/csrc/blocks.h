@@ -17,7 +17,7 @@ int conv_forward_impl(const ofd_conv_args* a, hipStream_t s, int cout0 = 0, int 
                                                                                    // for 64 -> 384 with cout0 = 128; everything else computes all channels)
 bool conv_pool2_supported(const ofd_conv_args* a);
 bool conv_residual_b_supported(const ofd_conv_args* a);                            // residual_b: ConvParams::residual_b (3x3 through conv_wp.hip only)                                 // pool2: ConvParams::pool2 (3x3 through conv_wp.hip only)
-// conv backward (conv_bwd.hip)
+// conv backward (conv_bwd.hip; k_conv_wgrad, k_conv7_wgrad, k_channel_sum: conv_wgrad.hip)
 int k_wt_transpose(const bf16_t* w, bf16_t* wt, int taps, int Cin, int Cout, hipStream_t s);
 int k_conv_wgrad(const ofd_conv_args* a, const bf16_t* dy, float* dw, hipStream_t s, float* dbias = nullptr);
 int k_conv7_wgrad(const bf16_t* x16, const bf16_t* dy, float* dw, int B, int H, int W, hipStream_t s, float* dbias = nullptr, int channels = 16);

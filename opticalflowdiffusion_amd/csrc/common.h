@@ -66,6 +66,16 @@ __device__ __forceinline__ uint32_t f2bf2(float lo, float hi) {
     return __builtin_bit_cast(uint32_t, h);
 }
 
+// a[0..7] += the eight bf16 of a 16-byte unit
+__device__ __forceinline__ void bf16_octet_add(float (&a)[8], const uint4& v) {
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        a[2 * j] += bf2f((bf16_t)(w[j] & 0xffffu));
+        a[2 * j + 1] += bf2f((bf16_t)(w[j] >> 16));
+    }
+}
+
 // XCD-aware tile order: workgroup i runs on XCD i % 8, so dispatch index `tile` is mapped to a tile such that the workgroups of one XCD
 // walk a contiguous run of tiles (what neighbouring tiles share -- halo rows, window overlap -- is then served by one L2)
 __device__ __forceinline__ int xcd_tile_order(int tile, int ntiles) {

@@ -1,4 +1,4 @@
-// Device-side descriptors shared by the forward (conv_igemm.hip) and backward (conv_bwd.hip) conv kernels.
+// Device-side descriptors shared by the forward (conv_igemm.hip) and backward (conv_wgrad.hip) conv kernels.
 #pragma once
 #include "common.h"
 

@@ -12,7 +12,9 @@
 // The kernels keep their float* arguments: gacc_add() looks the pointer up in the (at most DET_RANGES) registered fp32 buffers of the
 // executor and derives the shadow address; a pointer outside every range falls back to the float atomic and counts a miss
 // (DetCtx::misses, checked by the tests).  The context is a per-translation-unit __constant__ variable: OFD_DET_DEFINE_SETTER(name)
-// instantiates its host-side setter in each .hip that uses gacc_add.
+// instantiates its host-side setter in each .hip that uses gacc_add
+// (conv_wgrad.hip, la_core.hip, train_ops.hip), and ofd_unet_set_deterministic has to call every one of them: a file whose setter is not called
+// stays on float atomics without a word.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -59,7 +61,7 @@ __device__ __forceinline__ void gacc_add(float* p, float v) {
 #endif
 
 // setters of the translation units that accumulate gradients (each returns a hipError_t as int)
-int det_set_ctx_conv_bwd(const DetCtx* host_ctx, hipStream_t s);
+int det_set_ctx_conv_wgrad(const DetCtx* host_ctx, hipStream_t s);
 int det_set_ctx_la_core(const DetCtx* host_ctx, hipStream_t s);
 int det_set_ctx_train_ops(const DetCtx* host_ctx, hipStream_t s);
 // slot[i] += shadow[i] * 2^-38 ; shadow[i] = 0        (train_ops.hip)

@@ -375,7 +375,7 @@ int run_forward(Ctx& c, const float* x, int Cx, const float* cond, int Cc, const
     u->last_B = B;
     if (c.train) u->tape.clear();
     // <= 8 input channels: 8-channel packing, the 7x7 pairs horizontally adjacent taps into one k-step (conv_igemm.hip Cfg::K7P).
-    // Training keeps the same 8-channel tensor on the tape: its weight-gradient kernel reads either packing (conv_bwd.hip conv7_wgrad_kernel<8>;
+    // Training keeps the same 8-channel tensor on the tape: its weight-gradient kernel reads either packing (conv_wgrad.hip conv7_wgrad_kernel<8>;
     // r04: the 16-channel copy and its pack pass are gone).
     const bool pack8 = u->convs[u->cindex.at("init_conv")].pack8_off >= 0;
     const int cpad = pack8 ? 8 : u->cin_pad;

@@ -5,7 +5,7 @@
 // (bound by the caller, so torch's .grad tensors are views of it and the data-parallel all-reduce
 // works on contiguous ranges); a host callback reports each range as soon as its launches are
 // enqueued, in backward order, so the caller can overlap the collectives with the rest.
-// Host code only: kernels live in conv_igemm.hip / conv_bwd.hip / train_ops.hip / attn_bwd.hip.
+// Host code only: kernels live in conv_igemm.hip / conv_wgrad.hip / conv_bwd.hip / train_ops.hip / attn_bwd.hip.
 #include <set>
 #include "unet_exec.h"
 
@@ -30,7 +30,7 @@ struct Bwd {
 // ---- deterministic backward (det.h) ----------------------------------------------------------------
 // uploads `ctx` to the three translation units whose kernels accumulate gradients (stream-ordered)
 static int det_upload(const DetCtx* ctx, hipStream_t s) {
-    if (det_set_ctx_conv_bwd(ctx, s) != 0 || det_set_ctx_la_core(ctx, s) != 0 || det_set_ctx_train_ops(ctx, s) != 0) {
+    if (det_set_ctx_conv_wgrad(ctx, s) != 0 || det_set_ctx_la_core(ctx, s) != 0 || det_set_ctx_train_ops(ctx, s) != 0) {
         set_error("unet_backward: deterministic-mode context upload failed");
         return OFD_ERR_HIP;
     }

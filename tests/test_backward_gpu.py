@@ -34,6 +34,8 @@ def conv_args(L, B, H, W, ksize, srcs, Cout):
         a.src[i].upsample = s.get("upsample", 0)
         a.src[i].unshuffle = s.get("unshuffle", 0)
         a.src[i].p1, a.src[i].p2 = s.get("p1", 0), s.get("p2", 0)
+        if "in_scale" in s:               # fp32 [B][Cin] on the device: X = SiLU(x * in_scale + in_shift) while the input is staged
+            a.in_scale, a.in_shift = s["in_scale"].data_ptr(), s["in_shift"].data_ptr()
     return a
 
 
@@ -76,6 +78,37 @@ def test_conv3x3_backward(L, B, H, W, Cin, Cout):
     dyd = to_nhwc(dy)
     L.check(L.lib().ofd_channel_sum(L.ptr(dyd), L.ptr(out), B * H * W, Cout, L.stream()))
     assert rel_l2(out.cpu(), dy.sum(dim=(0, 2, 3))) < 1e-3
+
+
+@pytest.mark.parametrize("B,H,W,Cin,Cout", [(2, 13, 40, 64, 64), (1, 8, 32, 128, 64)])
+def test_conv3x3_weight_gradient_with_input_prologue(L, B, H, W, Cin, Cout):
+    """The weight gradient of a block's second conv reads h1 and applies the forward's GroupNorm-affine + SiLU prologue while the halo
+    tile is staged (conv_wgrad3_kernel<PRO>): per-sample scale / shift over two samples, tile overhang in both directions and all four
+    image borders; whole tiles over two ci blocks; against autograd through q(SiLU(x * s + b))."""
+    torch.manual_seed(13)
+    x = q(torch.randn(B, Cin, H, W))
+    sc, sh = 1 + 0.3 * torch.randn(B, Cin), 0.3 * torch.randn(B, Cin)
+    w = (torch.randn(Cout, Cin, 3, 3) / math.sqrt(Cin * 9)).requires_grad_(True)
+    dy = q(torch.randn(B, Cout, H, W))
+    F.conv2d(q(F.silu(x * sc[:, :, None, None] + sh[:, :, None, None])), w + (q(w) - w).detach(), padding=1).backward(dy)
+    scd, shd = sc.cuda().contiguous(), sh.cuda().contiguous()
+    got_w = wgrad(L, B, H, W, 3, [dict(t=to_nhwc(x), in_scale=scd, in_shift=shd)], Cout, to_nhwc(dy), w.detach())
+    print(f"prologue wgrad {(B, H, W, Cin, Cout)}: rel-L2 {rel_l2(got_w, w.grad):.3e}")
+    assert rel_l2(got_w, w.grad) < TOL, rel_l2(got_w, w.grad)
+
+
+@pytest.mark.parametrize("Cin,B,H,W", [(128, 2, 13, 21), (64, 3, 40, 56)])
+def test_conv1x1_weight_gradient_qkv_kernel(L, Cin, B, H, W):
+    """to_qkv shapes (DD:222, DD:252): Cout = 384 over one plain source (conv_wgrad1_qkv_kernel, a ci block and all 384 output channels
+    per workgroup); 546 pixels are no multiple of its 64-pixel tile, (3, 40, 56) gives a workgroup several tiles; against autograd."""
+    torch.manual_seed(17)
+    x = q(torch.randn(B, Cin, H, W))
+    w = (torch.randn(384, Cin, 1, 1) / math.sqrt(Cin)).requires_grad_(True)
+    dy = q(torch.randn(B, 384, H, W))
+    F.conv2d(x, w + (q(w) - w).detach()).backward(dy)
+    got_w = wgrad(L, B, H, W, 1, [dict(t=to_nhwc(x))], 384, to_nhwc(dy), w.detach())
+    print(f"qkv wgrad {(Cin, B, H, W)}: rel-L2 {rel_l2(got_w, w.grad):.3e}")
+    assert rel_l2(got_w, w.grad) < TOL, rel_l2(got_w, w.grad)
 
 
 @pytest.mark.parametrize("Cout,cins,B,H,W", [(64, (64, 64), 2, 13, 21), (128, (128, 128), 2, 13, 21), (192, (192, 192), 2, 13, 21), (256, (256, 256), 2, 13, 21),
