@@ -20,6 +20,9 @@
  *   (not in the reference)            DPM-Solver++ multistep update     -> ofd_dpmpp_update
  *   (not in the reference)            constrained (inpainting) updates  -> ofd_ddpm_update_known, ofd_ddim_update_known,
  *                                                                          ofd_dpmpp_update_known
+ *   (not in the reference)            classifier-free guided updates    -> ofd_ddpm_update_guided, ofd_ddim_update_guided,
+ *                                                                          ofd_dpmpp_update_guided
+ *   (not in the reference)            condition dropout (CFG training)  -> ofd_cond_drop
  *   denoising_diffusion.py:806-812    q_sample                          -> ofd_q_sample
  *   denoising_diffusion.py:844-879,985-993  p_losses noise / target     -> ofd_diffusion_prep
  *   denoising_diffusion.py:73-77      (un)normalize                     -> ofd_range_map
@@ -193,6 +196,39 @@ int ofd_dpmpp_update_known(int objective, int order, const float* x_t, const flo
                            const float* d_prev1, const float* d_prev2, const float* cx, const float* w0, const float* w1,
                            const float* w2, int last, const float* known, const float* e0, const float* sqrt_ac_next,
                            const float* sqrt_1mac_next, float* out, float* d_out, int B, size_t n_per_sample, void* stream);
+/* Classifier-free guidance (Ho & Salimans, "Classifier-Free Diffusion Guidance", 2022; an addition, not in the reference): the three
+ * reverse steps on two model outputs, the one of the condition (model_out) and the one of the null condition (model_out_uncond, with
+ * the layout of model_out).  The arguments are those of the _known entry points, plus, after model_out,
+ *   model_out_uncond  (B,C,H,W);
+ *   guidance          per-sample scale w, B floats like every other coefficient row: 0 = unconditional, 1 = conditional, > 1 extrapolates.
+ * known == NULL is the unconstrained step; e0, sqrt_ac_next and sqrt_1mac_next must then be NULL too.  Otherwise the constraint
+ * composes with the guidance.
+ *   G1. Per element m = u + w*(c - u) in fp32 (c of model_out, u of model_out_uncond, w = guidance[sample]; the product and both sums
+ *       rounded on their own), except that w == 0 gives u itself.  m is formed in registers and used wherever the unguided step uses
+ *       the model output: it goes through the objective's x_start formula and then the clamp.  eps, x0 and v are affine in each other
+ *       given x_t, so guiding the raw output is the same guidance for every objective.  No intermediate tensor is written: one launch,
+ *       reading one tensor more than the sibling (4 B per element).
+ *   G2. A guidance row of zeros gives the bits of the unguided entry point called on model_out_uncond (out, x_start, d_out), and
+ *       model_out is then not used (a NaN there does not reach the output).
+ *   G3. With known, held elements are the bits of the _known entry point (they do not depend on the model output); free elements are
+ *       the bits of the guided call without known.
+ *   G4. out == x_t stays allowed for the DPM-Solver++ form, with the same bits as out of place.
+ *   G5. Argument errors (a NULL model_out_uncond or guidance, constrained-only arguments without known, and everything the siblings
+ *       refuse) return an error and set ofd_last_error before any GPU work. */
+int ofd_ddpm_update_guided(int objective, const float* x_t, const float* model_out, const float* model_out_uncond,
+                           const float* guidance, const float* noise, const float* coef1, const float* coef2, const float* sigma,
+                           const float* xa, const float* xb, const float* known, const float* e0, const float* sqrt_ac_next,
+                           const float* sqrt_1mac_next, float* out, float* x_start, int B, size_t n_per_sample, void* stream);
+int ofd_ddim_update_guided(int objective, const float* x_t, const float* model_out, const float* model_out_uncond,
+                           const float* guidance, const float* noise, const float* sqrt_recip_ac, const float* sqrt_recipm1_ac,
+                           const float* xa, const float* xb, const float* sqrt_alpha_next, const float* c, const float* sigma, int last,
+                           const float* known, const float* e0, const float* sqrt_ac_next, const float* sqrt_1mac_next,
+                           float* out, float* x_start, int B, size_t n_per_sample, void* stream);
+int ofd_dpmpp_update_guided(int objective, int order, const float* x_t, const float* model_out, const float* model_out_uncond,
+                            const float* guidance, const float* xa, const float* xb, const float* d_prev1, const float* d_prev2,
+                            const float* cx, const float* w0, const float* w1, const float* w2, int last, const float* known,
+                            const float* e0, const float* sqrt_ac_next, const float* sqrt_1mac_next, float* out, float* d_out,
+                            int B, size_t n_per_sample, void* stream);
 /* Training prep, one launch (DD:844-848, 806-812, 874-879, 985-993), x0 / noise / outputs (B,C,hw):
  *   x0n = normalize ? 2*x0 - 1 : x0;  nz = noise + offset_strength*offset[b,c] (offset (B,C), or NULL: no offset noise);
  *   x_t = sqrt_ac*x0n + sqrt_1mac*nz;  target = nz (pred_noise), x0n (pred_x0), sqrt_ac*nz - sqrt_1mac*x0n (pred_v).
@@ -202,6 +238,12 @@ int ofd_diffusion_prep(int objective, const float* x0, const float* noise, const
                        int B, int C, size_t hw, void* stream);
 /* DD:73-77 over n floats: mode 0 -> 2*in - 1 (normalize), mode 1 -> (in + 1)*0.5 (unnormalize); in == out allowed. */
 int ofd_range_map(const float* in, float* out, size_t n, int mode, void* stream);
+/* Condition dropout of classifier-free guidance training (not in the reference), cond / out (B, n_per_sample), keep B floats:
+ * a sample with keep != 0 gets exactly what ofd_range_map(mode) writes (the same bits); a sample with keep == 0 gets +0.0 everywhere,
+ * whatever cond holds there (it is not read: a NaN or Inf cannot leak).  mode: ofd_range_map's 0 / 1, or OFD_COND_COPY (no mapping, for
+ * a condition that is already in the model's range).  One pass, one launch; cond == out is not allowed. */
+#define OFD_COND_COPY 2
+int ofd_cond_drop(const float* cond, const float* keep, int mode, float* out, int B, size_t n_per_sample, void* stream);
 /* sum and count over positions where neither pred nor target is NaN of (pred-target)^2.
  * result (device): ofd_nan_mse_result_doubles() doubles -- [0] sum, [1] count, the rest scratch (per-workgroup partial sums, added
  * in a fixed order: the same inputs give the same sum bit for bit). */

@@ -65,7 +65,7 @@ __global__ void __launch_bounds__(256) diffusion_prep_kernel(const float* __rest
 }
 
 // Constrained sampling (replacement-based inpainting; not in the reference).  `known` has the layout of x_t: a NaN element is free, any
-// other is held at clamp(known).  Each update kernel below takes an optional trailing KnownArgs: without it (K empty) it is the
+// other is held at clamp(known).  Each update kernel below takes an optional trailing KnownArgs: without it it is the
 // unconstrained kernel, same parameters and same code as before; with it, free elements go through the same arithmetic and held
 // ones overwrite x_start and the output.  Held output: sqrt(ac_next) known + sqrt(1 - ac_next) e, each product rounded on its own,
 // with e this step's noise element when the step has one and the element of x_T (e0) otherwise; known itself on the final step.
@@ -75,8 +75,35 @@ struct KnownArgs {
     const float* sa = nullptr;        // per-sample sqrt(ac_next), sqrt(1 - ac_next); null on the final step
     const float* s1 = nullptr;
 };
-__device__ __forceinline__ KnownArgs known_args() { return KnownArgs{}; }
-__device__ __forceinline__ KnownArgs known_args(KnownArgs kn) { return kn; }
+
+// Classifier-free guidance (Ho & Salimans 2022; not in the reference): a second optional trailing pack.  With it the kernel reads a second
+// model output, the one of the null condition, and uses m = u + w (c - u) (c = mo, u = uncond, w = w[sample]; fp32, the product and the
+// two sums rounded on their own; w == 0 selects u itself) wherever it uses the model output otherwise: formed in registers, before
+// start_from_output and the clamp.  4 B per element more than the same kernel without the pack.
+struct GuideArgs {
+    const float* uncond = nullptr;    // (B, n_per_sample), the layout of mo
+    const float* w = nullptr;         // per-sample guidance scale
+};
+__device__ __forceinline__ float guided(float c, float u, float w) { return w == 0.0f ? u : u + w * (c - u); }
+
+// The trailing packs of an update kernel: any of KnownArgs, GuideArgs, in that order.  has_args<T, K...>: T is among them;
+// get_args<T>(k...): it, or an empty T.  Without a pack the kernel has the parameters and the code it had before the pack existed.
+template <typename T, typename... K> constexpr bool has_args = (std::is_same_v<T, K> || ...);
+template <typename T> __device__ __forceinline__ T get_args() { return T{}; }
+template <typename T, typename K0, typename... K> __device__ __forceinline__ T get_args(K0 k0, K... k) {
+    if constexpr (std::is_same_v<T, K0>) return k0;
+    else return get_args<T>(k...);
+}
+// the model output of one element group: mo's, or the guided combination of mo's and uncond's
+template <int VEC, bool GUIDE> __device__ __forceinline__ EwVec<VEC> load_output(const float* mo, const GuideArgs& gd, float gw, size_t e) {
+    EwVec<VEC> m = ew_load<VEC>(mo + e);
+    if constexpr (GUIDE) {
+        const EwVec<VEC> u = ew_load<VEC>(gd.uncond + e);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) m.v[j] = guided(m.v[j], u.v[j], gw);
+    }
+    return m;
+}
 __device__ __forceinline__ bool held(float k) { return k == k; }
 __device__ __forceinline__ float held_value(float kc, float ksa, float ks1, float e, bool fin) {
     return fin ? kc : ksa * kc + ks1 * e;
@@ -90,10 +117,12 @@ __global__ void __launch_bounds__(256) ddpm_update_kernel(const float* __restric
                                                           const float* __restrict__ c2, const float* __restrict__ sg,
                                                           const float* __restrict__ xa, const float* __restrict__ xb,
                                                           float* __restrict__ out, float* __restrict__ x_start, size_t n_per_sample,
-                                                          K... known) {
-    constexpr bool KNOWN = sizeof...(K) != 0;
-    const KnownArgs kn = known_args(known...);
+                                                          K... packs) {
+    constexpr bool KNOWN = has_args<KnownArgs, K...>, GUIDE = has_args<GuideArgs, K...>;
+    const KnownArgs kn = get_args<KnownArgs>(packs...);
+    const GuideArgs gd = get_args<GuideArgs>(packs...);
     const int s = blockIdx.y;
+    const float gw = GUIDE ? gd.w[s] : 0.0f;
     const float k1 = c1[s], k2 = c2[s], ks = (noise && sg) ? sg[s] : 0.0f;
     float ka = 0.0f, kb = 0.0f;
     if constexpr (OBJ != PRED_X0) { ka = xa[s]; kb = xb[s]; }
@@ -102,7 +131,7 @@ __global__ void __launch_bounds__(256) ddpm_update_kernel(const float* __restric
     const size_t base = (size_t)s * n_per_sample, nv = n_per_sample / VEC;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (size_t)gridDim.x * blockDim.x) {
         const size_t e = base + i * VEC;
-        const EwVec<VEC> m = ew_load<VEC>(mo + e), xt = ew_load<VEC>(x_t + e);
+        const EwVec<VEC> m = load_output<VEC, GUIDE>(mo, gd, gw, e), xt = ew_load<VEC>(x_t + e);
         EwVec<VEC> nz, kv, r, xs;
         if constexpr (KNOWN) {
             kv = ew_load<VEC>(kn.known + e);
@@ -138,10 +167,12 @@ __global__ void __launch_bounds__(256) ddim_update_kernel(const float* __restric
                                                           const float* __restrict__ xb, const float* __restrict__ san,
                                                           const float* __restrict__ cc, const float* __restrict__ sg, int last,
                                                           float* __restrict__ out, float* __restrict__ x_start, size_t n_per_sample,
-                                                          K... known) {
-    constexpr bool KNOWN = sizeof...(K) != 0;
-    const KnownArgs kn = known_args(known...);
+                                                          K... packs) {
+    constexpr bool KNOWN = has_args<KnownArgs, K...>, GUIDE = has_args<GuideArgs, K...>;
+    const KnownArgs kn = get_args<KnownArgs>(packs...);
+    const GuideArgs gd = get_args<GuideArgs>(packs...);
     const int s = blockIdx.y;
+    const float gw = GUIDE ? gd.w[s] : 0.0f;
     const float k_sr = sr[s], k_srm1 = srm1[s];
     const float k_an = last ? 0.0f : san[s], k_c = last ? 0.0f : cc[s], k_s = (last || !noise || !sg) ? 0.0f : sg[s];
     float ka = 0.0f, kb = 0.0f;
@@ -150,7 +181,7 @@ __global__ void __launch_bounds__(256) ddim_update_kernel(const float* __restric
     const size_t base = (size_t)s * n_per_sample, nv = n_per_sample / VEC;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (size_t)gridDim.x * blockDim.x) {
         const size_t e = base + i * VEC;
-        const EwVec<VEC> m = ew_load<VEC>(mo + e);
+        const EwVec<VEC> m = load_output<VEC, GUIDE>(mo, gd, gw, e);
         EwVec<VEC> xt, nz, kv, r, xs;
         if (!last || OBJ != PRED_X0) xt = ew_load<VEC>(x_t + e);
         if constexpr (KNOWN) {
@@ -193,10 +224,12 @@ __global__ void __launch_bounds__(256) dpmpp_update_kernel(const float* x_t, con
                                                            const float* __restrict__ d2, const float* __restrict__ cx,
                                                            const float* __restrict__ w0, const float* __restrict__ w1,
                                                            const float* __restrict__ w2, int last, float* out, float* __restrict__ d_out,
-                                                           size_t n_per_sample, K... known) {
-    constexpr bool KNOWN = sizeof...(K) != 0;
-    const KnownArgs kn = known_args(known...);
+                                                           size_t n_per_sample, K... packs) {
+    constexpr bool KNOWN = has_args<KnownArgs, K...>, GUIDE = has_args<GuideArgs, K...>;
+    const KnownArgs kn = get_args<KnownArgs>(packs...);
+    const GuideArgs gd = get_args<GuideArgs>(packs...);
     const int s = blockIdx.y;
+    const float gw = GUIDE ? gd.w[s] : 0.0f;
     const float k_x = last ? 0.0f : cx[s], k_0 = last ? 0.0f : w0[s];
     const float k_1 = (ORDER >= 2 && !last) ? w1[s] : 0.0f, k_2 = (ORDER >= 3 && !last) ? w2[s] : 0.0f;
     float ka = 0.0f, kb = 0.0f;
@@ -205,7 +238,7 @@ __global__ void __launch_bounds__(256) dpmpp_update_kernel(const float* x_t, con
     const size_t base = (size_t)s * n_per_sample, nv = n_per_sample / VEC;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (size_t)gridDim.x * blockDim.x) {
         const size_t e = base + i * VEC;
-        const EwVec<VEC> m = ew_load<VEC>(mo + e);
+        const EwVec<VEC> m = load_output<VEC, GUIDE>(mo, gd, gw, e);
         EwVec<VEC> xt, p1, p2, kv, ev, r, xs;
         if (!last || OBJ != PRED_X0) xt = ew_load<VEC>(x_t + e);
         if constexpr (ORDER >= 2) { if (!last) p1 = ew_load<VEC>(d1 + e); }
@@ -238,14 +271,42 @@ __global__ void __launch_bounds__(256) dpmpp_update_kernel(const float* x_t, con
     }
 }
 
-// DD:73-77 on a whole tensor: mode 0 -> 2 v - 1, mode 1 -> (v + 1) * 0.5
+// DD:73-77 on one value: mode 0 -> 2 v - 1, mode 1 -> (v + 1) * 0.5
+__device__ __forceinline__ float range_map_value(float v, int mode) { return mode == 0 ? v * 2.0f - 1.0f : (v + 1.0f) * 0.5f; }
+
+// DD:73-77 on a whole tensor
 template <int VEC>
 __global__ void __launch_bounds__(256) range_map_kernel(const float* __restrict__ in, float* __restrict__ out, size_t nv, int mode) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (size_t)gridDim.x * blockDim.x) {
         EwVec<VEC> u = ew_load<VEC>(in + i * VEC);
 #pragma unroll
-        for (int j = 0; j < VEC; ++j) u.v[j] = mode == 0 ? u.v[j] * 2.0f - 1.0f : (u.v[j] + 1.0f) * 0.5f;
+        for (int j = 0; j < VEC; ++j) u.v[j] = range_map_value(u.v[j], mode);
         ew_store<VEC>(out + i * VEC, u);
+    }
+}
+
+// Condition dropout of classifier-free guidance training (not in the reference): the range map of a kept sample (keep[s] != 0; mode
+// OFD_COND_COPY: the sample itself), +0.0 for a dropped one.  A dropped sample is not read: whatever it holds (NaN, Inf) cannot reach out.
+template <int VEC>
+__global__ void __launch_bounds__(256) cond_drop_kernel(const float* __restrict__ in, const float* __restrict__ keep,
+                                                        float* __restrict__ out, size_t n_per_sample, int mode) {
+    const int s = blockIdx.y;
+    const bool kept = keep[s] != 0.0f;
+    const size_t base = (size_t)s * n_per_sample, nv = n_per_sample / VEC;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t e = base + i * VEC;
+        EwVec<VEC> u;
+        if (kept) {
+            u = ew_load<VEC>(in + e);
+            if (mode != OFD_COND_COPY) {
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) u.v[j] = range_map_value(u.v[j], mode);
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) u.v[j] = 0.0f;
+        }
+        ew_store<VEC>(out + e, u);
     }
 }
 
@@ -352,17 +413,34 @@ extern "C" int ofd_q_sample(const float* x0, const float* noise, const float* sq
     return ofd_diffusion_prep(PRED_X0, x0, noise, nullptr, 0.0f, sqrt_ac, sqrt_1mac, 0, out, nullptr, nullptr, B, 1, n, stream);
 }
 
-// The reverse steps.  One implementation per step kind serves its plain and its _known entry point: `name` is the entry point's name in
-// the messages, `kn` the constrained step's KnownArgs (null: the plain step, launched without the trailing pack).  The checks a _known
-// entry point adds come after the ones it shares; `fin`: the step writes known itself and reads neither e nor the next level's rows.
+// The reverse steps.  One implementation per step kind serves its plain, its _known and its _guided entry point: `name` is the entry
+// point's name in the messages, `kn` the constrained step's KnownArgs and `gd` the guided step's GuideArgs (null: launched without that
+// trailing pack).  The checks a _known entry point adds come after the ones it shares; `fin`: the step writes known itself and reads
+// neither e nor the next level's rows.  A _guided entry point takes the _known arguments too: known == NULL is the unconstrained step,
+// and then the arguments only a constrained step reads must be NULL as well.
 #define OFD_KNOWN_ARGS_OK(name, kn, fin)                                                                                      \
     OFD_CHECK_ARG((kn)->known, "%s: null known", name);                                                                        \
     OFD_CHECK_ARG((fin) || ((kn)->sa && (kn)->s1), "%s: missing sqrt_ac_next / sqrt_1mac_next", name);                         \
     OFD_CHECK_ARG((fin) || (kn)->e, "%s: a step without noise needs e0", name)
 
+#define OFD_GUIDE_ARGS_OK(name, gd) \
+    OFD_CHECK_ARG((gd)->uncond && (gd)->w, "%s: null model_out_uncond / guidance", name)
+
+// `known` of a _guided entry point: null when it is NULL, after checking that nothing constrained-only came with it
+#define OFD_GUIDED_KNOWN(name, known, e0, sa, s1) \
+    OFD_CHECK_ARG((known) || (!(e0) && !(sa) && !(s1)), "%s: e0 / sqrt_ac_next / sqrt_1mac_next are read with known only", name)
+
+// launch(packs...) with the packs that are present, KnownArgs first
+template <typename F> static void launch_packs(const KnownArgs* kn, const GuideArgs* gd, F&& launch) {
+    if (kn && gd) launch(*kn, *gd);
+    else if (kn) launch(*kn);
+    else if (gd) launch(*gd);
+    else launch();
+}
+
 static int ddpm_update_impl(const char* name, int objective, const float* x_t, const float* model_out, const float* noise,
                             const float* coef1, const float* coef2, const float* sigma, const float* xa, const float* xb,
-                            const KnownArgs* kn, float* out, float* x_start, int B, size_t n, void* stream) {
+                            const KnownArgs* kn, const GuideArgs* gd, float* out, float* x_start, int B, size_t n, void* stream) {
     OFD_OBJ_OK(objective);
     OFD_EW_ARGS_OK(B, n);
     OFD_CHECK_ARG(x_t && model_out && coef1 && coef2 && out, "%s: null pointer", name);
@@ -370,6 +448,9 @@ static int ddpm_update_impl(const char* name, int objective, const float* x_t, c
     if (kn) {
         OFD_KNOWN_ARGS_OK(name, kn, !kn->sa);
         OFD_CHECK_ARG(kn->sa || !noise, "%s: the final step (no sqrt_ac_next) takes no noise", name);
+    }
+    if (gd) {
+        OFD_GUIDE_ARGS_OK(name, gd);
     }
     auto launch = [&](auto... k) {
         obj_dispatch(objective, [&](auto o) {
@@ -379,8 +460,7 @@ static int ddpm_update_impl(const char* name, int objective, const float* x_t, c
             });
         });
     };
-    if (!kn) launch();
-    else launch(*kn);
+    launch_packs(kn, gd, launch);
     OFD_LAUNCH_CHECK();
     return OFD_OK;
 }
@@ -388,8 +468,8 @@ static int ddpm_update_impl(const char* name, int objective, const float* x_t, c
 extern "C" int ofd_ddpm_update_obj(int objective, const float* x_t, const float* model_out, const float* noise, const float* coef1,
                                    const float* coef2, const float* sigma, const float* xa, const float* xb, float* out, float* x_start,
                                    int B, size_t n, void* stream) {
-    return ddpm_update_impl("ddpm_update", objective, x_t, model_out, noise, coef1, coef2, sigma, xa, xb, nullptr, out, x_start, B, n,
-                            stream);
+    return ddpm_update_impl("ddpm_update", objective, x_t, model_out, noise, coef1, coef2, sigma, xa, xb, nullptr, nullptr, out, x_start,
+                            B, n, stream);
 }
 
 extern "C" int ofd_ddpm_update_known(int objective, const float* x_t, const float* model_out, const float* noise, const float* coef1,
@@ -398,8 +478,21 @@ extern "C" int ofd_ddpm_update_known(int objective, const float* x_t, const floa
                                      float* x_start, int B, size_t n, void* stream) {
     const bool fin = !sqrt_ac_next || !sqrt_1mac_next;
     const KnownArgs kn{known, noise ? noise : e0, fin ? nullptr : sqrt_ac_next, fin ? nullptr : sqrt_1mac_next};
-    return ddpm_update_impl("ddpm_update_known", objective, x_t, model_out, noise, coef1, coef2, sigma, xa, xb, &kn, out, x_start, B, n,
-                            stream);
+    return ddpm_update_impl("ddpm_update_known", objective, x_t, model_out, noise, coef1, coef2, sigma, xa, xb, &kn, nullptr, out,
+                            x_start, B, n, stream);
+}
+
+extern "C" int ofd_ddpm_update_guided(int objective, const float* x_t, const float* model_out, const float* model_out_uncond,
+                                      const float* guidance, const float* noise, const float* coef1, const float* coef2,
+                                      const float* sigma, const float* xa, const float* xb, const float* known, const float* e0,
+                                      const float* sqrt_ac_next, const float* sqrt_1mac_next, float* out, float* x_start, int B, size_t n,
+                                      void* stream) {
+    OFD_GUIDED_KNOWN("ddpm_update_guided", known, e0, sqrt_ac_next, sqrt_1mac_next);
+    const bool fin = !sqrt_ac_next || !sqrt_1mac_next;
+    const KnownArgs kn{known, noise ? noise : e0, fin ? nullptr : sqrt_ac_next, fin ? nullptr : sqrt_1mac_next};
+    const GuideArgs gd{model_out_uncond, guidance};
+    return ddpm_update_impl("ddpm_update_guided", objective, x_t, model_out, noise, coef1, coef2, sigma, xa, xb, known ? &kn : nullptr,
+                            &gd, out, x_start, B, n, stream);
 }
 
 extern "C" int ofd_ddpm_update(const float* x_t, const float* model_out, const float* noise, const float* coef1,
@@ -409,8 +502,8 @@ extern "C" int ofd_ddpm_update(const float* x_t, const float* model_out, const f
 
 static int ddim_update_impl(const char* name, int objective, const float* x_t, const float* model_out, const float* noise,
                             const float* sqrt_recip_ac, const float* sqrt_recipm1_ac, const float* xa, const float* xb,
-                            const float* sqrt_alpha_next, const float* c, const float* sigma, int last, const KnownArgs* kn, float* out,
-                            float* x_start, int B, size_t n, void* stream) {
+                            const float* sqrt_alpha_next, const float* c, const float* sigma, int last, const KnownArgs* kn,
+                            const GuideArgs* gd, float* out, float* x_start, int B, size_t n, void* stream) {
     OFD_OBJ_OK(objective);
     OFD_EW_ARGS_OK(B, n);
     OFD_CHECK_ARG(x_t && model_out && sqrt_recip_ac && sqrt_recipm1_ac && out, "%s: null pointer", name);
@@ -418,6 +511,9 @@ static int ddim_update_impl(const char* name, int objective, const float* x_t, c
     OFD_CHECK_ARG(objective == PRED_X0 || (xa && xb), "%s: missing x_start coefficients", name);
     if (kn) {
         OFD_KNOWN_ARGS_OK(name, kn, last);
+    }
+    if (gd) {
+        OFD_GUIDE_ARGS_OK(name, gd);
     }
     auto launch = [&](auto... k) {
         obj_dispatch(objective, [&](auto o) {
@@ -427,8 +523,7 @@ static int ddim_update_impl(const char* name, int objective, const float* x_t, c
             });
         });
     };
-    if (!kn) launch();
-    else launch(*kn);
+    launch_packs(kn, gd, launch);
     OFD_LAUNCH_CHECK();
     return OFD_OK;
 }
@@ -437,7 +532,7 @@ extern "C" int ofd_ddim_update_obj(int objective, const float* x_t, const float*
                                    const float* sqrt_recipm1_ac, const float* xa, const float* xb, const float* sqrt_alpha_next,
                                    const float* c, const float* sigma, int last, float* out, float* x_start, int B, size_t n, void* stream) {
     return ddim_update_impl("ddim_update", objective, x_t, model_out, noise, sqrt_recip_ac, sqrt_recipm1_ac, xa, xb, sqrt_alpha_next, c,
-                            sigma, last, nullptr, out, x_start, B, n, stream);
+                            sigma, last, nullptr, nullptr, out, x_start, B, n, stream);
 }
 
 extern "C" int ofd_ddim_update_known(int objective, const float* x_t, const float* model_out, const float* noise,
@@ -447,7 +542,19 @@ extern "C" int ofd_ddim_update_known(int objective, const float* x_t, const floa
                                      float* x_start, int B, size_t n, void* stream) {
     const KnownArgs kn{known, noise ? noise : e0, sqrt_ac_next, sqrt_1mac_next};
     return ddim_update_impl("ddim_update_known", objective, x_t, model_out, noise, sqrt_recip_ac, sqrt_recipm1_ac, xa, xb,
-                            sqrt_alpha_next, c, sigma, last, &kn, out, x_start, B, n, stream);
+                            sqrt_alpha_next, c, sigma, last, &kn, nullptr, out, x_start, B, n, stream);
+}
+
+extern "C" int ofd_ddim_update_guided(int objective, const float* x_t, const float* model_out, const float* model_out_uncond,
+                                      const float* guidance, const float* noise, const float* sqrt_recip_ac, const float* sqrt_recipm1_ac,
+                                      const float* xa, const float* xb, const float* sqrt_alpha_next, const float* c, const float* sigma,
+                                      int last, const float* known, const float* e0, const float* sqrt_ac_next,
+                                      const float* sqrt_1mac_next, float* out, float* x_start, int B, size_t n, void* stream) {
+    OFD_GUIDED_KNOWN("ddim_update_guided", known, e0, sqrt_ac_next, sqrt_1mac_next);
+    const KnownArgs kn{known, noise ? noise : e0, sqrt_ac_next, sqrt_1mac_next};
+    const GuideArgs gd{model_out_uncond, guidance};
+    return ddim_update_impl("ddim_update_guided", objective, x_t, model_out, noise, sqrt_recip_ac, sqrt_recipm1_ac, xa, xb,
+                            sqrt_alpha_next, c, sigma, last, known ? &kn : nullptr, &gd, out, x_start, B, n, stream);
 }
 
 extern "C" int ofd_ddim_update(const float* x_t, const float* model_out, const float* noise, const float* sqrt_recip_ac,
@@ -459,8 +566,8 @@ extern "C" int ofd_ddim_update(const float* x_t, const float* model_out, const f
 
 static int dpmpp_update_impl(const char* name, int objective, int order, const float* x_t, const float* model_out, const float* xa,
                              const float* xb, const float* d_prev1, const float* d_prev2, const float* cx, const float* w0,
-                             const float* w1, const float* w2, int last, const KnownArgs* kn, float* out, float* d_out, int B, size_t n,
-                             void* stream) {
+                             const float* w1, const float* w2, int last, const KnownArgs* kn, const GuideArgs* gd, float* out, float* d_out,
+                             int B, size_t n, void* stream) {
     OFD_OBJ_OK(objective);
     OFD_EW_ARGS_OK(B, n);
     OFD_CHECK_ARG(order >= 1 && order <= 3, "%s: bad order %d", name, order);
@@ -472,6 +579,9 @@ static int dpmpp_update_impl(const char* name, int objective, int order, const f
     if (kn) {
         OFD_KNOWN_ARGS_OK(name, kn, last);
         OFD_CHECK_ARG(last || kn->e != out, "%s: e0 (x_T) must outlive the chain: it cannot be the output", name);
+    }
+    if (gd) {
+        OFD_GUIDE_ARGS_OK(name, gd);
     }
     const int ord = last ? 1 : order;                                  // the final evaluation reads no history
     auto launch = [&](auto... k) {
@@ -487,8 +597,7 @@ static int dpmpp_update_impl(const char* name, int objective, int order, const f
             else go(std::integral_constant<int, 1>{});
         });
     };
-    if (!kn) launch();
-    else launch(*kn);
+    launch_packs(kn, gd, launch);
     OFD_LAUNCH_CHECK();
     return OFD_OK;
 }
@@ -496,8 +605,8 @@ static int dpmpp_update_impl(const char* name, int objective, int order, const f
 extern "C" int ofd_dpmpp_update(int objective, int order, const float* x_t, const float* model_out, const float* xa, const float* xb,
                                 const float* d_prev1, const float* d_prev2, const float* cx, const float* w0, const float* w1,
                                 const float* w2, int last, float* out, float* d_out, int B, size_t n, void* stream) {
-    return dpmpp_update_impl("dpmpp_update", objective, order, x_t, model_out, xa, xb, d_prev1, d_prev2, cx, w0, w1, w2, last, nullptr, out,
-                             d_out, B, n, stream);
+    return dpmpp_update_impl("dpmpp_update", objective, order, x_t, model_out, xa, xb, d_prev1, d_prev2, cx, w0, w1, w2, last, nullptr, nullptr,
+                             out, d_out, B, n, stream);
 }
 
 extern "C" int ofd_dpmpp_update_known(int objective, int order, const float* x_t, const float* model_out, const float* xa,
@@ -507,7 +616,19 @@ extern "C" int ofd_dpmpp_update_known(int objective, int order, const float* x_t
                                       void* stream) {
     const KnownArgs kn{known, e0, sqrt_ac_next, sqrt_1mac_next};
     return dpmpp_update_impl("dpmpp_update_known", objective, order, x_t, model_out, xa, xb, d_prev1, d_prev2, cx, w0, w1, w2, last, &kn,
-                             out, d_out, B, n, stream);
+                             nullptr, out, d_out, B, n, stream);
+}
+
+extern "C" int ofd_dpmpp_update_guided(int objective, int order, const float* x_t, const float* model_out, const float* model_out_uncond,
+                                       const float* guidance, const float* xa, const float* xb, const float* d_prev1,
+                                       const float* d_prev2, const float* cx, const float* w0, const float* w1, const float* w2, int last,
+                                       const float* known, const float* e0, const float* sqrt_ac_next, const float* sqrt_1mac_next,
+                                       float* out, float* d_out, int B, size_t n, void* stream) {
+    OFD_GUIDED_KNOWN("dpmpp_update_guided", known, e0, sqrt_ac_next, sqrt_1mac_next);
+    const KnownArgs kn{known, e0, sqrt_ac_next, sqrt_1mac_next};
+    const GuideArgs gd{model_out_uncond, guidance};
+    return dpmpp_update_impl("dpmpp_update_guided", objective, order, x_t, model_out, xa, xb, d_prev1, d_prev2, cx, w0, w1, w2, last,
+                             known ? &kn : nullptr, &gd, out, d_out, B, n, stream);
 }
 
 extern "C" int ofd_range_map(const float* in, float* out, size_t n, int mode, void* stream) {
@@ -515,6 +636,17 @@ extern "C" int ofd_range_map(const float* in, float* out, size_t n, int mode, vo
     ew_launch(1, n, stream, [&](auto vec, dim3 grid, hipStream_t s) {
         range_map_kernel<decltype(vec)::value><<<grid, 256, 0, s>>>(in, out, n / decltype(vec)::value, mode);
     }, ((uintptr_t)in % 16) == 0 && ((uintptr_t)out % 16) == 0);
+    OFD_LAUNCH_CHECK();
+    return OFD_OK;
+}
+
+extern "C" int ofd_cond_drop(const float* cond, const float* keep, int mode, float* out, int B, size_t n_per_sample, void* stream) {
+    OFD_EW_ARGS_OK(B, n_per_sample);
+    OFD_CHECK_ARG(cond && keep && out, "cond_drop: null pointer");
+    OFD_CHECK_ARG(mode == 0 || mode == 1 || mode == OFD_COND_COPY, "cond_drop: bad mode %d", mode);
+    ew_launch(B, n_per_sample, stream, [&](auto vec, dim3 grid, hipStream_t s) {
+        cond_drop_kernel<decltype(vec)::value><<<grid, 256, 0, s>>>(cond, keep, out, n_per_sample, mode);
+    }, ((uintptr_t)cond % 16) == 0 && ((uintptr_t)out % 16) == 0);
     OFD_LAUNCH_CHECK();
     return OFD_OK;
 }

@@ -107,6 +107,29 @@ def _range_map(x, mode):
     return out
 
 
+COND_COPY = 2                           # OFD_COND_COPY (include/ofd.h): ofd_cond_drop without a range map
+UNSET = object()                        # sample(guidance_scale=UNSET): the constructor's value
+
+
+def _cond_drop(cond, keep, mode):
+    """condition dropout as one HIP launch into a new tensor (include/ofd.h, ofd_cond_drop): sample b is range-mapped by `mode` where
+    keep[b] != 0 and +0.0 where it is 0"""
+    L.require_gpu(cond, keep)
+    cond, keep = L.f32c(cond), L.f32c(keep)
+    out = torch.empty_like(cond)
+    L.check(L.lib().ofd_cond_drop(L.ptr(cond), L.ptr(keep), mode, L.ptr(out), cond.shape[0], cond[0].numel(), L.stream()))
+    return out
+
+
+def _guidance_value(value, what="guidance_scale"):
+    """None, or the scale as a finite float (ValueError otherwise)"""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not math.isfinite(value):
+        raise ValueError(f"{what} must be None or a finite number, got {value!r}")
+    return float(value)
+
+
 def normalize_to_neg_one_to_one(img):
     """DD:73-74"""
     return _range_map(img, 0)
@@ -512,8 +535,17 @@ class ConditionalDiffusion(nn.Module):
                  beta_schedule="sigmoid", schedule_fn_kwargs=dict(), ddim_sampling_eta=0.0, auto_normalize=True,
                  offset_noise_strength=0.0, min_snr_loss_weight=False, min_snr_gamma=5, conditioned=True,
                  channels=3, noise_space="image", ddim_draw_unused_noise=False, sampler=None, solver_order=2,
-                 sampler_spacing="logsnr"):
+                 sampler_spacing="logsnr", cond_drop_prob=0.0, guidance_scale=None):
         super().__init__()
+        # classifier-free guidance (not in the reference): cond_drop_prob = the probability with which forward() replaces a
+        # training sample's condition by the null condition (zeros in the normalised range); guidance_scale = w of
+        # out = out_uncond + w (out_cond - out_uncond) in sample(): None or 1.0 is the conditional model (one model call per step)
+        if isinstance(cond_drop_prob, bool) or not isinstance(cond_drop_prob, (int, float)) or not 0.0 <= cond_drop_prob < 1.0:
+            raise ValueError(f"cond_drop_prob must be a number in [0, 1), got {cond_drop_prob!r}")
+        self.cond_drop_prob = float(cond_drop_prob)
+        self.guidance_scale = _guidance_value(guidance_scale)
+        if self.cond_drop_prob > 0.0 or self.guidance_scale not in (None, 1.0):
+            self._guidance_model_ok(model, conditioned)
         # sampler (not in the reference): None = the reference's rule (DDPM, or DDIM when sampling_timesteps < timesteps); "ddim" forces
         # DDIM; "dpmpp" = DPM-Solver++ multistep of order solver_order over sampling_timesteps model calls on the sampler_spacing grid
         if sampler not in SAMPLERS:
@@ -679,14 +711,20 @@ class ConditionalDiffusion(nn.Module):
 
     # -- DDPM --------------------------------------------------------------------------------
     @torch.no_grad()
-    def p_sample(self, x, t: int, x_self_cond=None, external_cond=None, additional_tgt=None, noise=None, known=None):
+    def p_sample(self, x, t: int, x_self_cond=None, external_cond=None, additional_tgt=None, noise=None, known=None,
+                 guidance_scale=UNSET):
         """DD:676-698: network call + one fused kernel for clamp / posterior mean / noise add.  `known` (optional, not in the reference;
-        shaped like x, in x's range, NaN = free): the constrained step of `sample(known=)`."""
+        shaped like x, in x's range, NaN = free): the constrained step of `sample(known=)`.  `guidance_scale`: as `sample`'s."""
         known = self._check_known(tuple(x.shape), known, 1, additional_tgt)
+        w = self._check_guidance(guidance_scale, additional_tgt, external_cond)
         b = x.shape[0]
         tab = self._sampling_tables(b, x.device)           # rows of per-(T, batch) tables: no fill / gather / exp launches per step
         bt = tab["t"][t]
         out = self.model_with_condition(x, bt, x_self_cond, external_cond=external_cond, additional_tgt=additional_tgt)
+        guide = None
+        if w is not None:
+            guide = (self._same_shape(L.f32c(self.model_with_condition(x, bt, x_self_cond, external_cond=torch.zeros_like(external_cond))), x),
+                     self._guidance_row(b, x.device, w))
         additional_out = None
         if additional_tgt is not None:
             additional_out = out[:, -1 * additional_tgt.shape[1]:]
@@ -699,37 +737,46 @@ class ConditionalDiffusion(nn.Module):
             noise = None                                                               # DD:687
         pred = torch.empty_like(x)
         x_start = torch.empty_like(x)
-        self._ddpm_step(tab, t, x, out, noise, pred, x_start, known)
+        self._ddpm_step(tab, t, x, out, noise, pred, x_start, known, guide)
         return pred, x_start, additional_out
 
-    # -- the fused update launches: the only callers of the six reverse-step entry points (include/ofd.h).  img / out / nxt: x_t, the
-    # model output and the tensor the step writes; `known` (or None) picks the constrained entry point and its trailing arguments.
-    def _ddpm_step(self, tab, t, img, out, noise, nxt, x_start, known):
+    # -- the fused update launches: the only callers of the nine reverse-step entry points (include/ofd.h).  img / out / nxt: x_t, the
+    # model output and the tensor the step writes; `known` (or None) picks the constrained entry point and its trailing arguments;
+    # `guide` (or None): (the null condition's model output, the guidance row) picks the guided entry point, which takes the
+    # constrained step's arguments too (all NULL without `known`).
+    @staticmethod
+    def _step_fn(lib, kind, plain, known, guide, kn):
+        """(entry point, the arguments after model_out, the constrained arguments) of a step"""
+        if guide is not None:
+            return getattr(lib, f"ofd_{kind}_update_guided"), (L.ptr(guide[0]), L.ptr(guide[1])), kn if known is not None else (None,) * 4
+        if known is not None:
+            return getattr(lib, f"ofd_{kind}_update_known"), (), kn
+        return getattr(lib, plain), (), ()
+
+    def _ddpm_step(self, tab, t, img, out, noise, nxt, x_start, known, guide=None):
         """the DDPM step at level t; noise is None at t == 0 (DD:687).  A held element rides on the same noise: no e0."""
-        lib = L.lib()
         kn = () if known is None else (L.ptr(known), None, *self._known_rows(tab, t - 1))
-        fn = lib.ofd_ddpm_update_obj if known is None else lib.ofd_ddpm_update_known
-        L.check(fn(self._obj, L.ptr(img), L.ptr(out), L.ptr(noise), L.ptr(tab["c1"][t]), L.ptr(tab["c2"][t]), L.ptr(tab["sigma"][t]),
+        fn, gd, kn = self._step_fn(L.lib(), "ddpm", "ofd_ddpm_update_obj", known, guide, kn)
+        L.check(fn(self._obj, L.ptr(img), L.ptr(out), *gd, L.ptr(noise), L.ptr(tab["c1"][t]), L.ptr(tab["c2"][t]), L.ptr(tab["sigma"][t]),
                    *self._xab(tab, t), *kn, L.ptr(nxt), L.ptr(x_start), img.shape[0], img.numel() // img.shape[0], L.stream()))
 
-    def _ddim_step(self, tab, t, img, out, noise, coef, nxt, known, x_T):
+    def _ddim_step(self, tab, t, img, out, noise, coef, nxt, known, x_T, guide=None):
         """the DDIM step from level t; coef: this pair's rows sqrt(alpha_next), c, sigma, sqrt(1 - alpha_next), or None on the last step
         (which takes no noise).  A constrained step without noise reads x_T as e0."""
-        lib, last = L.lib(), coef is None
+        last = coef is None
         san, c, sigma, s1n = (None,) * 4 if last else (L.ptr(coef[0]), L.ptr(coef[1]), L.ptr(coef[2]), L.ptr(coef[3]))
         kn = () if known is None else (L.ptr(known), None if (last or noise is not None) else L.ptr(x_T), san, s1n)
-        fn = lib.ofd_ddim_update_obj if known is None else lib.ofd_ddim_update_known
-        L.check(fn(self._obj, L.ptr(img), L.ptr(out), L.ptr(noise), L.ptr(tab["sr"][t]), L.ptr(tab["srm1"][t]), *self._xab(tab, t),
+        fn, gd, kn = self._step_fn(L.lib(), "ddim", "ofd_ddim_update_obj", known, guide, kn)
+        L.check(fn(self._obj, L.ptr(img), L.ptr(out), *gd, L.ptr(noise), L.ptr(tab["sr"][t]), L.ptr(tab["srm1"][t]), *self._xab(tab, t),
                    san, c, sigma, int(last), *kn, L.ptr(nxt), None, img.shape[0], img.numel() // img.shape[0], L.stream()))
 
-    def _dpmpp_step(self, tab, t, order, img, out, d1, d2, coef, last, nxt, d_out, known, x_T):
+    def _dpmpp_step(self, tab, t, order, img, out, d1, d2, coef, last, nxt, d_out, known, x_T, guide=None):
         """the DPM-Solver++ step from level t; coef: this grid point's six rows (_dpmpp_tables); d1 / d2 / d_out: the history the order
         reads and the slot the prediction goes to (None where unused).  A constrained step reads x_T as e0."""
-        lib = L.lib()
         kn = () if known is None else ((L.ptr(known), None, None, None) if last else
                                        (L.ptr(known), L.ptr(x_T), L.ptr(coef[4]), L.ptr(coef[5])))
-        fn = lib.ofd_dpmpp_update if known is None else lib.ofd_dpmpp_update_known
-        L.check(fn(self._obj, order, L.ptr(img), L.ptr(out), *self._xab(tab, t), L.ptr(d1), L.ptr(d2), L.ptr(coef[0]), L.ptr(coef[1]),
+        fn, gd, kn = self._step_fn(L.lib(), "dpmpp", "ofd_dpmpp_update", known, guide, kn)
+        L.check(fn(self._obj, order, L.ptr(img), L.ptr(out), *gd, *self._xab(tab, t), L.ptr(d1), L.ptr(d2), L.ptr(coef[0]), L.ptr(coef[1]),
                    L.ptr(coef[2]), L.ptr(coef[3]), int(last), *kn, L.ptr(nxt), L.ptr(d_out), img.shape[0], img.numel() // img.shape[0],
                    L.stream()))
 
@@ -774,6 +821,39 @@ class ConditionalDiffusion(nn.Module):
         L.require_gpu(known)
         return L.f32c(known)
 
+    @staticmethod
+    def _guidance_model_ok(model, conditioned):
+        """classifier-free guidance and condition dropout replace the condition by the null condition (zeros), which means something only
+        where the condition enters the model through the network input alone"""
+        if not conditioned:
+            raise ValueError("cond_drop_prob / guidance_scale need conditioned=True: without a condition there is nothing to drop or guide by")
+        if hasattr(model, "_warp"):
+            raise ValueError("cond_drop_prob / guidance_scale are not supported for a model that warps its condition (UnetWithWarp, "
+                             "FlowDiffuser target 'target' / 'joint'): its image output is the condition itself, warped by the predicted "
+                             "flow, so a null (all-zero) condition has no meaning there; use them with the engine's Unet")
+
+    def _check_guidance(self, guidance_scale=UNSET, additional_tgt=None, external_cond=None):
+        """the argument rules of guided sampling, checked before any engine call (ValueError); returns the scale w of a guided chain, or
+        None when guidance is off: guidance_scale (UNSET: the constructor's) None or exactly 1.0, which is the conditional model"""
+        w = self.guidance_scale if guidance_scale is UNSET else _guidance_value(guidance_scale)
+        if w is None or w == 1.0:
+            return None
+        self._guidance_model_ok(self.model, self.conditioned)
+        if additional_tgt is not None:
+            raise ValueError("guidance_scale cannot be combined with additional_tgt (FlowDiffuser target='target'): that model warps its "
+                             "condition, for which the null condition has no meaning")
+        if not torch.is_tensor(external_cond):
+            raise ValueError("guidance_scale needs external_cond: the guided chain calls the model on it and on the null condition")
+        return w
+
+    def _guidance_row(self, batch, device, w):
+        """the per-sample guidance row of the guided entry points (include/ofd.h: guidance), built once per (batch, device, w) like a
+        row of `_sampling_tables`: a step reads it, no fill launch per step"""
+        key = (batch, str(device), w)
+        if getattr(self, "_guide_row", None) is None or self._guide_row[0] != key:
+            self._guide_row = (key, torch.full((batch,), w, dtype=torch.float32, device=device))
+        return self._guide_row[1]
+
     def _sampling_tables(self, batch, device):
         """per-(T, batch) views of everything a reverse step reads that does not depend on the data: timestep tensors and the
         posterior coefficients, expanded once so that a step indexes a ROW (a view, no gather launch, no allocation)"""
@@ -802,13 +882,14 @@ class ConditionalDiffusion(nn.Module):
 
     @torch.no_grad()
     def p_sample_loop(self, shape, return_all_timesteps=False, external_cond=None, additional_tgt=None, verbose=False, x_T=None,
-                      known=None, resample=1):
+                      known=None, resample=1, guidance_scale=UNSET):
         """DD:700-729 (no per-step print / host sync).  `x_T` (optional, not in the reference): the start of the chains (DD:705).
         A step is: one UNet call, one in-place normal_ into a reused buffer, one fused update kernel writing into the other of
         two ping-pong images -- no per-step allocation, no coefficient gathers (rows of `_sampling_tables`).
         `known` / `resample` (optional, not in the reference): constrained sampling, see `sample`; known is in the loop's own range
-        ([-1, 1]), as external_cond and x_T are."""
+        ([-1, 1]), as external_cond and x_T are.  `guidance_scale`: classifier-free guidance, see `sample`."""
         known = self._check_known(shape, known, resample, additional_tgt)
+        w = self._check_guidance(guidance_scale, additional_tgt, external_cond)
         if additional_tgt is not None:                                                # target='target': the general step (DD:676-698)
             # kept on p_sample: this branch keeps every frame whatever trajectory_stride says, which the shared chain would not
             img = torch.randn(shape, device=self.device) if x_T is None else L.f32c(x_T)
@@ -824,10 +905,10 @@ class ConditionalDiffusion(nn.Module):
         def plan(x_T, tab):
             noise, x_start = torch.empty_like(x_T), torch.empty_like(x_T)
 
-            def step(i, t, img, out, nxt):
+            def step(i, t, img, out, nxt, guide):
                 if t > 0:
                     noise.normal_()                          # DD:687: z = 0 at t = 0; the held elements ride on the same draw
-                self._ddpm_step(tab, t, img, out, noise if t > 0 else None, nxt, x_start, known)
+                self._ddpm_step(tab, t, img, out, noise if t > 0 else None, nxt, x_start, known, guide)
 
             def renoise(t, img, nxt):                        # back to level t: x_t = sqrt(1 - beta_t) x_{t-1} + sqrt(beta_t) e'
                 noise.normal_()
@@ -836,19 +917,24 @@ class ConditionalDiffusion(nn.Module):
 
             return [(t, resample if t > 0 else 1) for t in reversed(range(0, self.num_timesteps))], step, renoise
 
-        return self._run_chain(shape, x_T, plan, return_all_timesteps, external_cond)             # DD:725-726
+        return self._run_chain(shape, x_T, plan, return_all_timesteps, external_cond, guidance=w)   # DD:725-726
 
-    def _run_chain(self, shape, x_T, plan, return_all_timesteps, external_cond, additional_tgt=None):
+    def _run_chain(self, shape, x_T, plan, return_all_timesteps, external_cond, additional_tgt=None, guidance=None):
         """The reverse chain p_sample_loop, ddim_sample and dpmpp_sample share.  It owns the start image (x_T or a fresh draw, made before
         any table is built), the two ping-pong images, the model call on a row of `_sampling_tables`, the additional_tgt split, the
         trajectory (x_T, every trajectory_stride-th schedule entry and the last) and the return form.  `plan(x_T, tab)` is the sampler:
         it returns (schedule, step, renoise).  schedule: one (t, runs) per entry, t the level the model is called at; step(i, t, img,
-        out, nxt) draws the step's noise in place and makes the one fused update launch from img into nxt; an entry with runs > 1
+        out, nxt, guide) draws the step's noise in place and makes the one fused update launch from img into nxt; an entry with runs > 1
         (RePaint's resampling) is stepped `runs` times with renoise(t, img, nxt) between two runs.  Nothing is allocated, gathered or
-        synchronised per step apart from the clone of a kept frame."""
+        synchronised per step apart from the clone of a kept frame.  `guidance` (the scale w of _check_guidance, or None): every step
+        calls the model twice on the same img, on external_cond and then on the null condition (zeros shaped like external_cond, made
+        once here), and hands step() guide = (the second output, the guidance row) for the guided entry point."""
         img = torch.randn(shape, device=self.device) if x_T is None else L.f32c(x_T)
         assert tuple(img.shape) == tuple(shape)
         tab = self._sampling_tables(shape[0], img.device)
+        null_cond = row = None
+        if guidance is not None:
+            null_cond, row = torch.zeros_like(external_cond), self._guidance_row(shape[0], img.device, guidance)
         schedule, step, renoise = plan(img, tab)                                      # img is x_T: never written, the loop writes to pong
         pong = [torch.empty_like(img), torch.empty_like(img)]
         imgs, additionals, stride = [img], [None], self.trajectory_stride
@@ -862,7 +948,10 @@ class ConditionalDiffusion(nn.Module):
                 if additional_tgt is not None:
                     additionals.append(out[:, -1 * additional_tgt.shape[1]:])
                     out = out[:, :-1 * additional_tgt.shape[1]]
-                step(i, t, img, self._same_shape(L.f32c(out), img), pong[writes & 1])
+                guide = None
+                if guidance is not None:
+                    guide = (self._same_shape(L.f32c(self.model_with_condition(img, tab["t"][t], None, external_cond=null_cond)), img), row)
+                step(i, t, img, self._same_shape(L.f32c(out), img), pong[writes & 1], guide)
                 img, writes = pong[writes & 1], writes + 1
             if return_all_timesteps and (stride is None or (i + 1) % stride == 0 or i == len(schedule) - 1):
                 imgs.append(img.clone())
@@ -871,11 +960,13 @@ class ConditionalDiffusion(nn.Module):
 
     # -- DDIM --------------------------------------------------------------------------------
     @torch.no_grad()
-    def ddim_sample(self, shape, return_all_timesteps=False, external_cond=None, additional_tgt=None, x_T=None, known=None, resample=1):
+    def ddim_sample(self, shape, return_all_timesteps=False, external_cond=None, additional_tgt=None, x_T=None, known=None, resample=1,
+                    guidance_scale=UNSET):
         """DD:731-774; accepts (and ignores) additional_tgt so that sample() can reach it.  `x_T` (optional, not in
         the reference) starts the chains from a given tensor instead of a fresh draw (DD:741).  `known` (optional, not in the
         reference): constrained sampling, see `sample`; in the loop's own range ([-1, 1]).  resample > 1 is DDPM's: ValueError."""
         known = self._check_known(shape, known, resample, additional_tgt, ddpm=False)
+        w = self._check_guidance(guidance_scale, additional_tgt, external_cond)
         batch, T, S, eta = shape[0], self.num_timesteps, self.sampling_timesteps, self.ddim_sampling_eta
         times = torch.linspace(-1, T - 1, steps=S + 1)
         times = list(reversed(times.int().tolist()))
@@ -894,15 +985,15 @@ class ConditionalDiffusion(nn.Module):
             coef = coef.reshape(len(time_pairs), 4, 1).repeat(1, 1, batch).contiguous()
             noise = torch.empty_like(x_T) if (eta > 0 or self.ddim_draw_unused_noise) else None
 
-            def step(i, time, img, out, nxt):
+            def step(i, time, img, out, nxt, guide):
                 last = time_pairs[i][1] < 0
                 if noise is not None and not last:
                     noise.normal_()                                                      # DD:763 (eta == 0: only with ddim_draw_unused_noise)
-                self._ddim_step(tab, time, img, out, None if last else noise, None if last else coef[i], nxt, known, x_T)
+                self._ddim_step(tab, time, img, out, None if last else noise, None if last else coef[i], nxt, known, x_T, guide)
 
             return [(time, 1) for time, _ in time_pairs], step, None
 
-        return self._run_chain(shape, x_T, plan, return_all_timesteps, external_cond)              # DD:772-773
+        return self._run_chain(shape, x_T, plan, return_all_timesteps, external_cond, guidance=w)  # DD:772-773
 
     # -- DPM-Solver++ (not in the reference) --------------------------------------------------
     def _dpmpp_tables(self, batch, device):
@@ -923,7 +1014,8 @@ class ConditionalDiffusion(nn.Module):
         return self._dpmpp_tab[1]
 
     @torch.no_grad()
-    def dpmpp_sample(self, shape, return_all_timesteps=False, external_cond=None, additional_tgt=None, x_T=None, known=None, resample=1):
+    def dpmpp_sample(self, shape, return_all_timesteps=False, external_cond=None, additional_tgt=None, x_T=None, known=None, resample=1,
+                     guidance_scale=UNSET):
         """DPM-Solver++ multistep sampling (include/ofd.h, ofd_dpmpp_update): one UNet call per grid point, S - 1 solver steps and a
         final evaluation that returns the clamped prediction.  Signature, x_T, trajectory_stride and the (B, S + 1, C, H, W)
         trajectory are ddim_sample's.  With additional_tgt (FlowDiffuser's target='target') the model's extra output channels are
@@ -932,23 +1024,26 @@ class ConditionalDiffusion(nn.Module):
         `known`: constrained sampling, see `sample`; in the loop's own range ([-1, 1]).  The ring stores the predictions with the held
         elements already replaced.  resample > 1 is DDPM's: ValueError."""
         known = self._check_known(shape, known, resample, additional_tgt, ddpm=False)
+        w = self._check_guidance(guidance_scale, additional_tgt, external_cond)
 
         def plan(x_T, tab):
             grid, orders, coef = self._dpmpp_tables(shape[0], x_T.device)
             ring = [torch.empty_like(x_T) for _ in range(3)]
 
-            def step(i, t, img, out, nxt):
+            def step(i, t, img, out, nxt, guide):
                 last = i == len(grid) - 1
                 order = 1 if last else orders[i]
                 self._dpmpp_step(tab, t, order, img, out, ring[(i - 1) % 3] if order >= 2 else None,
-                                 ring[(i - 2) % 3] if order >= 3 else None, coef[i], last, nxt, None if last else ring[i % 3], known, x_T)
+                                 ring[(i - 2) % 3] if order >= 3 else None, coef[i], last, nxt, None if last else ring[i % 3], known, x_T,
+                                 guide)
 
             return [(t, 1) for t in grid], step, None
 
-        return self._run_chain(shape, x_T, plan, return_all_timesteps, external_cond, additional_tgt)
+        return self._run_chain(shape, x_T, plan, return_all_timesteps, external_cond, additional_tgt, guidance=w)
 
     @torch.no_grad()
-    def sample(self, batch_size=16, return_all_timesteps=False, external_cond=None, additional_tgt=None, known=None, resample=1):
+    def sample(self, batch_size=16, return_all_timesteps=False, external_cond=None, additional_tgt=None, known=None, resample=1,
+               guidance_scale=UNSET):
         """DD:776-784, with image_size allowed to be (H, W).  external_cond is normalised once per call (DD:778-779); the loops
         unnormalise what they return.
 
@@ -957,11 +1052,19 @@ class ConditionalDiffusion(nn.Module):
         the result has clamp(known) there, and every step of the chain carries the held elements at the step's noise level inside
         the fused update launch (no extra pass).  `resample=r` (DDPM only, RePaint's harmonisation) runs each step t > 0 r times
         with a one-level re-noising between the runs: r UNet calls per step, r (T - 1) + 1 in all.  known=None is the unconstrained
-        path, launch for launch."""
+        path, launch for launch.
+
+        Classifier-free guidance (not in the reference): `guidance_scale` overrides the constructor's value for this
+        call.  None or exactly 1.0 is the conditional model: one model call per step, the unguided entry points, launch for launch.
+        Any other w makes two model calls per step on the same x_t, on external_cond and on the null condition (zeros in the
+        normalised range), and the fused update uses out_uncond + w (out_cond - out_uncond) as the model output (0 = unconditional,
+        > 1 extrapolates past the conditional model).  It composes with `known` / `resample`."""
         H, W = self._hw()
         shape = (batch_size, self.channels, H, W)
         ddpm = self.sampler != "dpmpp" and not self.is_ddim_sampling
         known = self._check_known(shape, known, resample, additional_tgt, ddpm=ddpm)
+        self._check_guidance(guidance_scale, additional_tgt, external_cond)
+        guide = {} if guidance_scale is UNSET else dict(guidance_scale=guidance_scale)
         if external_cond is not None:
             external_cond = self.normalize(external_cond)
         if self.sampler == "dpmpp":
@@ -970,9 +1073,9 @@ class ConditionalDiffusion(nn.Module):
             fn = self.p_sample_loop if not self.is_ddim_sampling else self.ddim_sample
         assert external_cond is None or external_cond.shape[0] == batch_size
         if known is None:
-            return fn(shape, return_all_timesteps=return_all_timesteps, external_cond=external_cond, additional_tgt=additional_tgt)
+            return fn(shape, return_all_timesteps=return_all_timesteps, external_cond=external_cond, additional_tgt=additional_tgt, **guide)
         return fn(shape, return_all_timesteps=return_all_timesteps, external_cond=external_cond, known=self.normalize(known),
-                  resample=resample)
+                  resample=resample, **guide)
 
     # -- training loss -----------------------------------------------------------------------
     @torch.no_grad()
@@ -1068,11 +1171,19 @@ class ConditionalDiffusion(nn.Module):
         return num / den.float()
 
     def forward(self, img, external_cond=None, *args, **kwargs):
-        """DD:985-993.  img is normalised inside the prep launch, external_cond by one range_map launch (auto_normalize)."""
+        """DD:985-993.  img is normalised inside the prep launch, external_cond by one range_map launch (auto_normalize).  In train mode
+        with cond_drop_prob > 0 (not in the reference) that launch is ofd_cond_drop instead: each sample's condition becomes the null
+        condition (zeros in the normalised range) with that probability, drawn on the device after t; eval mode never drops."""
         b, c, h, w = img.shape
         H, W = self._hw()
         assert h == H and w == W, f"height and width of image must be {(H, W)}"
         t = torch.randint(0, self.num_timesteps, (b,), device=img.device).long()
-        if external_cond is not None:
+        if self.training and self.cond_drop_prob > 0.0 and external_cond is not None:
+            if external_cond.requires_grad:
+                raise ValueError("cond_drop_prob: external_cond must not require grad (the dropout launch has no backward)")
+            with torch.no_grad():
+                keep = (torch.rand(b, device=img.device) >= self.cond_drop_prob).float()
+                external_cond = _cond_drop(external_cond, keep, 0 if self.auto_normalize else COND_COPY)
+        elif external_cond is not None:
             external_cond = self.normalize(external_cond)
         return self._p_losses(img, t, *args, external_cond=external_cond, normalize=self.auto_normalize, **kwargs)

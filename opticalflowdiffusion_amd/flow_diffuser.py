@@ -7,14 +7,14 @@ with the hooks `experiments/exp_base.py` drives (`log_dict`, `configure_optimize
 `training_step`, `validation_step`).  `cfg` may be a DictConfig, a dict or any attribute object
 with the keys of configurations/algorithm/flow_diffuser.yaml (+ optional `image_size: [H, W]`,
 `sampling_timesteps`, `precision`, `ae_checkpoint`, the sampler keys `sampler`, `solver_order`,
-`sampler_spacing` of ConditionalDiffusion, and the `ema_*` keys and `sample_with_ema` of ema.EMA_DEFAULTS, which are not
-in the reference).
+`sampler_spacing` of ConditionalDiffusion, its classifier-free guidance keys `cond_drop_prob`, `guidance_scale` (target 'flow'
+only), and the `ema_*` keys and `sample_with_ema` of ema.EMA_DEFAULTS, which are not in the reference).
 """
 import os
 
 import torch
 
-from .denoising_diffusion import Unet, ConditionalDiffusion
+from .denoising_diffusion import UNSET, Unet, ConditionalDiffusion
 from .ema import EMA_DEFAULTS, EmaMixin, ema_optimizer_kwargs
 from .warp import warp
 from . import _lib as L
@@ -44,7 +44,7 @@ class _Cfg:
                      flow_weight=0.0, weight_decay=1e-6, is_diffusion=True, latent=False, timesteps=1000,
                      target="joint", ae="px8q8g0m", noiser="image", zero_init=True,
                      sampling_timesteps=None, precision="bf16", augment=True, sampler=None, solver_order=2, sampler_spacing="logsnr",
-                     **EMA_DEFAULTS)
+                     cond_drop_prob=0.0, guidance_scale=None, **EMA_DEFAULTS)
 
     def __init__(self, cfg):
         self._d = dict(self._DEFAULTS)
@@ -160,6 +160,9 @@ class FlowDiffuser(EmaMixin, _Base):
             self._model = UnetWithWarp(cfg, self.unet, full_output=cfg.target == "joint")
         else:
             self._model = self.unet
+        if (cfg.cond_drop_prob or cfg.guidance_scale is not None) and not self.is_diffusion:
+            raise ValueError("cond_drop_prob / guidance_scale need a diffusion model: is_diffusion=False is a plain regression, there is "
+                             "no chain to guide and no condition dropout to train it for")
         if not self.is_diffusion:                                           # FD:128-129: plain regression cond -> flow
             self.model = self._model
             return
@@ -170,7 +173,8 @@ class FlowDiffuser(EmaMixin, _Base):
             channels={"target": self.dim, "joint": self.dim + 2}.get(cfg.target, 2),
             auto_normalize=False, noise_space="image" if cfg.noiser == "image" else "flow",
             timesteps=cfg.timesteps, sampling_timesteps=cfg.sampling_timesteps, min_snr_loss_weight=True,
-            sampler=cfg.sampler, solver_order=int(cfg.solver_order), sampler_spacing=cfg.sampler_spacing)   # not in the reference
+            sampler=cfg.sampler, solver_order=int(cfg.solver_order), sampler_spacing=cfg.sampler_spacing,   # not in the reference
+            cond_drop_prob=cfg.cond_drop_prob, guidance_scale=cfg.guidance_scale)    # target 'flow' only: ValueError for a warping model
         if "trajectory_stride" in cfg:                                      # optional key, default = every frame as the reference
             self.model.trajectory_stride = cfg.trajectory_stride
 
@@ -249,23 +253,29 @@ class FlowDiffuser(EmaMixin, _Base):
             known = torch.cat((torch.full((b, self.dim, h, w), float("nan"), dtype=known.dtype, device=known.device), known), dim=1)
         return known
 
-    def sample(self, cond, flow, known_flow=None, resample=1):              # FD:189-215
+    def sample(self, cond, flow, known_flow=None, resample=1, guidance_scale=UNSET):              # FD:189-215
         """`known_flow` (optional, not in the reference): (B, 2, H, W) in pixels, NaN = free; the returned flow has
         clamp(known_flow / flow_max) at the other elements and the sampler fills in the rest consistently (constrained sampling,
-        ConditionalDiffusion.sample).  target 'flow' or 'joint' only.  `resample` as there: DDPM only, `resample` UNet calls per step."""
+        ConditionalDiffusion.sample).  target 'flow' or 'joint' only.  `resample` as there: DDPM only, `resample` UNet calls per step.
+        `guidance_scale` (optional, not in the reference): classifier-free guidance for this call instead of cfg.guidance_scale
+        (ConditionalDiffusion.sample); target 'flow' only; composes with known_flow."""
         # a regression model called with autograd on runs the training forward, which has no EMA weights to run on
         if self.is_diffusion or not torch.is_grad_enabled():
             with self._sampling_scope():
-                return self._sample(cond, flow, known_flow, resample)
-        return self._sample(cond, flow, known_flow, resample)
+                return self._sample(cond, flow, known_flow, resample, guidance_scale)
+        return self._sample(cond, flow, known_flow, resample, guidance_scale)
 
-    def _sample(self, cond, flow, known_flow, resample):
+    def _sample(self, cond, flow, known_flow, resample, guidance_scale=UNSET):
         bsz = flow.shape[0]
         kw = {}
         if known_flow is not None:
             kw = dict(known=self.known_from_flow(known_flow), resample=resample)
         elif resample != 1:
             raise ValueError("resample needs a known_flow to harmonise with")
+        if guidance_scale is not UNSET:
+            if not self.is_diffusion:
+                raise ValueError("guidance_scale needs a diffusion model: is_diffusion=False is a plain regression, there is no chain to guide")
+            kw["guidance_scale"] = guidance_scale
         if not self.is_diffusion:                                           # FD:204-213
             if self.cfg.target in ["target", "joint"]:
                 samples = self.model(cond, additional_out=True) if self.cfg.target == "target" else self.model(cond)
@@ -273,7 +283,7 @@ class FlowDiffuser(EmaMixin, _Base):
             flow = self.model(cond)
             return warp(cond[:, :self.dim], None, flow, mode="forward"), flow
         if self.cfg.target == "target":
-            samples, flow = self.model.sample(batch_size=bsz, external_cond=cond, additional_tgt=flow, return_all_timesteps=True)
+            samples, flow = self.model.sample(batch_size=bsz, external_cond=cond, additional_tgt=flow, return_all_timesteps=True, **kw)
         elif self.cfg.target == "joint":
             joint = self.model.sample(batch_size=bsz, external_cond=cond, return_all_timesteps=True, **kw)
             samples = joint[:, :, :self.dim]

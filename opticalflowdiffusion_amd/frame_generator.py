@@ -9,7 +9,7 @@ import torch
 
 from .compat.shims.utils.image_prediction.logging import log_photos
 from .compat.shims.utils.video_prediction.visualization import log_video
-from .denoising_diffusion import ConditionalDiffusion, Unet
+from .denoising_diffusion import UNSET, ConditionalDiffusion, Unet
 from .ema import EMA_DEFAULTS, EmaMixin, ema_optimizer_kwargs
 from .flow_diffuser import FlowDiffuser, _Base, _Cfg
 from .flow_pred import parse_image_size
@@ -18,10 +18,12 @@ from .flow_pred import parse_image_size
 class _FrameCfg(_Cfg):
     """configurations/algorithm/frame_generator.yaml, plus `clip` (the trainer's gradient_clip_val, folded into FusedAdam),
     `precision`, `timesteps` and `sampling_timesteps` (DDIM when fewer than `timesteps`), the sampler keys of ConditionalDiffusion
-    (`sampler`, `solver_order`, `sampler_spacing`; not in the reference) and the `ema_*` keys and `sample_with_ema` (ema.EMA_DEFAULTS)"""
+    (`sampler`, `solver_order`, `sampler_spacing`; not in the reference), its classifier-free guidance keys (`cond_drop_prob`,
+    `guidance_scale`; not in the reference) and the `ema_*` keys and `sample_with_ema` (ema.EMA_DEFAULTS)"""
 
     _DEFAULTS = dict(name="frame_generator", image_size=64, lr=7e-5, weight_decay=2e-4, clip=0.0, precision="bf16", timesteps=1000,
-                     sampling_timesteps=None, sampler=None, solver_order=2, sampler_spacing="logsnr", **EMA_DEFAULTS)
+                     sampling_timesteps=None, sampler=None, solver_order=2, sampler_spacing="logsnr", cond_drop_prob=0.0, guidance_scale=None,
+                     **EMA_DEFAULTS)
 
 
 class FrameGenerator(EmaMixin, _Base):
@@ -40,7 +42,8 @@ class FrameGenerator(EmaMixin, _Base):
         self.diffusion_model = ConditionalDiffusion(self._model, self.image_size, objective="pred_noise",   # DA:30-34
                                                     timesteps=int(cfg.timesteps), sampling_timesteps=cfg.sampling_timesteps,
                                                     sampler=cfg.sampler, solver_order=int(cfg.solver_order),
-                                                    sampler_spacing=cfg.sampler_spacing)
+                                                    sampler_spacing=cfg.sampler_spacing, cond_drop_prob=cfg.cond_drop_prob,
+                                                    guidance_scale=cfg.guidance_scale)
 
     def configure_optimizers(self):                                                                  # DA:36-41
         """Adam(lr, weight_decay) as the reference, as the HIP multi-tensor step (optim.FusedAdam)"""
@@ -74,25 +77,31 @@ class FrameGenerator(EmaMixin, _Base):
     log_grad_norm_stat = FlowDiffuser.log_grad_norm_stat                                             # DA:103-125 == FD:367-388
 
     @torch.no_grad()
-    def sample(self, cond, known=None):
+    def sample(self, cond, known=None, guidance_scale=UNSET):
         """one sampling chain per sample of cond (B, 5, H, W) in [0, 1]; returns (B, 3, H, W) in [0, 1].  `known` (optional, not in
-        the reference): (B, 3, H, W) in [0, 1], NaN = free -- inpainting of the next frame (ConditionalDiffusion.sample)."""
+        the reference): (B, 3, H, W) in [0, 1], NaN = free -- inpainting of the next frame (ConditionalDiffusion.sample).
+        `guidance_scale` (optional, not in the reference): classifier-free guidance for this call instead of cfg.guidance_scale."""
+        kw = {} if known is None else dict(known=known)
+        if guidance_scale is not UNSET:
+            kw["guidance_scale"] = guidance_scale
         with self._sampling_scope():                                     # the EMA weights when cfg.ema_decay is set
-            if known is None:
-                return self.diffusion_model.sample(batch_size=cond.shape[0], external_cond=cond)
-            return self.diffusion_model.sample(batch_size=cond.shape[0], external_cond=cond, known=known)
+            return self.diffusion_model.sample(batch_size=cond.shape[0], external_cond=cond, **kw)
 
     @torch.no_grad()
-    def rollout(self, batch, known=None):
+    def rollout(self, batch, known=None, guidance_scale=UNSET):
         """DA:84-100: batch (B, V, 8, H, W); frame k is sampled with cond = batch[:, k, 3:], whose last-frame channels are replaced
-        by frame k-1's sample for k >= 1.  Returns (V, B, 3, H, W).  `known` (optional): (B, V, 3, H, W), frame k's `known`."""
+        by frame k-1's sample for k >= 1.  Returns (V, B, 3, H, W).  `known` (optional): (B, V, 3, H, W), frame k's `known`;
+        `guidance_scale` (optional): every frame's."""
         samples = []
+        kw = {} if guidance_scale is UNSET else dict(guidance_scale=guidance_scale)
         with self._sampling_scope():                                     # one rebind for the whole rollout
             for k in range(batch.shape[1]):
                 cond = batch[:, k, 3:].clone()
                 if k != 0:
                     cond[:, :3] = samples[-1][:, :3]                                                 # DA:90-91
-                samples.append(self.sample(cond) if known is None else self.sample(cond, known=known[:, k]))
+                if known is not None:
+                    kw["known"] = known[:, k]
+                samples.append(self.sample(cond, **kw))                  # the optional arguments only when given
         return torch.stack(samples, dim=0)
 
     def validation_step(self, batch, batch_idx):                                                     # DA:64-100
