@@ -23,6 +23,8 @@
  *   (not in the reference)            classifier-free guided updates    -> ofd_ddpm_update_guided, ofd_ddim_update_guided,
  *                                                                          ofd_dpmpp_update_guided
  *   (not in the reference)            condition dropout (CFG training)  -> ofd_cond_drop
+ *   (not in the reference)            dynamic thresholding              -> ofd_x0_abs_quantile, ofd_ddpm_update_thresh,
+ *                                                                          ofd_ddim_update_thresh, ofd_dpmpp_update_thresh
  *   denoising_diffusion.py:806-812    q_sample                          -> ofd_q_sample
  *   denoising_diffusion.py:844-879,985-993  p_losses noise / target     -> ofd_diffusion_prep
  *   denoising_diffusion.py:73-77      (un)normalize                     -> ofd_range_map
@@ -229,6 +231,55 @@ int ofd_dpmpp_update_guided(int objective, int order, const float* x_t, const fl
                             const float* cx, const float* w0, const float* w1, const float* w2, int last, const float* known,
                             const float* e0, const float* sqrt_ac_next, const float* sqrt_1mac_next, float* out, float* d_out,
                             int B, size_t n_per_sample, void* stream);
+/* Dynamic thresholding (Saharia et al., "Photorealistic Text-to-Image Diffusion Models with Deep Language Understanding", 2022, section
+ * 2.3; an addition, not in the reference): instead of the static clamp to [-1, 1], x_start is clamped to [-s, s] and divided by s, with
+ * s a per-sample order statistic of |x_start|, raised to at least 1.  Two pieces: the statistic, and the three reverse steps reading it.
+ *
+ * ofd_x0_abs_quantile: thresh[b] = min(max(q_b, 1), max_value), q_b the rank-th smallest |x_start| over sample b's n_per_sample
+ * elements (1 <= rank <= n_per_sample; an exact order statistic, no interpolation, no histogram approximation).  x_start is the
+ * UNCLAMPED value the step forms from the same arguments: model_out (pred_x0) or xa*x_t - xb*model_out, with model_out replaced by the
+ * guided combination G1 when model_out_uncond / guidance are given (both, or both NULL) -- the same device functions as the steps,
+ * each product rounded on its own, so the value ranked is the value the step clamps.  x_t, xa and xb may be NULL for OFD_PRED_X0.  A
+ * non-finite magnitude ranks above every finite one (Inf below NaN); a non-finite q_b gives max_value (finite, >= 1), so the row is
+ * always finite and >= 1.  Elements a constrained step holds are not excluded: the statistic is over the model's prediction.
+ * The bits of a non-negative float are monotone as an unsigned integer, so the selection is a radix select over the bits of |x_start|:
+ * three passes of 11 / 11 / 10 bits, each one launch that counts digits (per-workgroup LDS histograms, merged into a (B, 2048) histogram
+ * with integer atomics) and one small launch per pass that picks the digit and leaves the prefix and the remaining rank in the
+ * workspace for the next pass.  Every pass re-forms x_start (4 to 12 B read per element and pass); nothing tensor-sized is written.  No
+ * host synchronisation, no float atomics: the same inputs give the same bits.  workspace: ofd_x0_abs_quantile_ws_bytes(B) bytes,
+ * 4-byte aligned, contents irrelevant on entry.  n_per_sample < 2^32. */
+size_t ofd_x0_abs_quantile_ws_bytes(int B);
+int ofd_x0_abs_quantile(int objective, const float* x_t, const float* model_out, const float* model_out_uncond, const float* guidance,
+                        const float* xa, const float* xb, int B, size_t n_per_sample, size_t rank, float max_value, float* thresh,
+                        void* workspace, size_t workspace_bytes, void* stream);
+/* The thresholded reverse steps.  The arguments are those of the _guided entry points plus, after guidance,
+ *   thresh            per-sample threshold s, B floats, s >= 1 (what ofd_x0_abs_quantile writes).
+ * model_out_uncond and guidance are both NULL for an unguided step; known, e0, sqrt_ac_next and sqrt_1mac_next are all NULL for an
+ * unconstrained one.
+ *   T1. The x_start of a free element is clamp(x, -s, s) / s (the division correctly rounded) with x exactly the unclamped value the
+ *       sibling clamps to [-1, 1]; it is what the posterior mean, the DDIM eps re-derivation and the DPM-Solver++ update use, and what is
+ *       written to x_start / d_out.  Nothing else changes.
+ *   T2. A row of ones gives the bits of the corresponding sibling (plain, _known, _guided, _guided with known) for out, x_start and
+ *       d_out.
+ *   T3. Held elements are the bits of the _known entry point: clamp(known, -1, 1), not thresholded.
+ *   T4. out == x_t stays allowed for the DPM-Solver++ form, with the same bits as out of place.
+ *   T5. Argument errors (a NULL thresh, model_out_uncond without guidance or the reverse, and everything the siblings refuse) return
+ *       an error and set ofd_last_error before any GPU work. */
+int ofd_ddpm_update_thresh(int objective, const float* x_t, const float* model_out, const float* model_out_uncond,
+                           const float* guidance, const float* thresh, const float* noise, const float* coef1, const float* coef2,
+                           const float* sigma, const float* xa, const float* xb, const float* known, const float* e0,
+                           const float* sqrt_ac_next, const float* sqrt_1mac_next, float* out, float* x_start, int B,
+                           size_t n_per_sample, void* stream);
+int ofd_ddim_update_thresh(int objective, const float* x_t, const float* model_out, const float* model_out_uncond,
+                           const float* guidance, const float* thresh, const float* noise, const float* sqrt_recip_ac,
+                           const float* sqrt_recipm1_ac, const float* xa, const float* xb, const float* sqrt_alpha_next, const float* c,
+                           const float* sigma, int last, const float* known, const float* e0, const float* sqrt_ac_next,
+                           const float* sqrt_1mac_next, float* out, float* x_start, int B, size_t n_per_sample, void* stream);
+int ofd_dpmpp_update_thresh(int objective, int order, const float* x_t, const float* model_out, const float* model_out_uncond,
+                            const float* guidance, const float* thresh, const float* xa, const float* xb, const float* d_prev1,
+                            const float* d_prev2, const float* cx, const float* w0, const float* w1, const float* w2, int last,
+                            const float* known, const float* e0, const float* sqrt_ac_next, const float* sqrt_1mac_next, float* out,
+                            float* d_out, int B, size_t n_per_sample, void* stream);
 /* Training prep, one launch (DD:844-848, 806-812, 874-879, 985-993), x0 / noise / outputs (B,C,hw):
  *   x0n = normalize ? 2*x0 - 1 : x0;  nz = noise + offset_strength*offset[b,c] (offset (B,C), or NULL: no offset noise);
  *   x_t = sqrt_ac*x0n + sqrt_1mac*nz;  target = nz (pred_noise), x0n (pred_x0), sqrt_ac*nz - sqrt_1mac*x0n (pred_v).

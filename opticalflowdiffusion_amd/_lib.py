@@ -74,6 +74,11 @@ SIGNATURES = {
     "ofd_ddpm_update_guided": (c_int, [c_int] + [c_void_p] * 16 + [c_int, c_size_t, c_void_p]),
     "ofd_ddim_update_guided": (c_int, [c_int] + [c_void_p] * 12 + [c_int] + [c_void_p] * 6 + [c_int, c_size_t, c_void_p]),
     "ofd_dpmpp_update_guided": (c_int, [c_int, c_int] + [c_void_p] * 12 + [c_int] + [c_void_p] * 6 + [c_int, c_size_t, c_void_p]),
+    "ofd_ddpm_update_thresh": (c_int, [c_int] + [c_void_p] * 17 + [c_int, c_size_t, c_void_p]),
+    "ofd_ddim_update_thresh": (c_int, [c_int] + [c_void_p] * 13 + [c_int] + [c_void_p] * 6 + [c_int, c_size_t, c_void_p]),
+    "ofd_dpmpp_update_thresh": (c_int, [c_int, c_int] + [c_void_p] * 13 + [c_int] + [c_void_p] * 6 + [c_int, c_size_t, c_void_p]),
+    "ofd_x0_abs_quantile_ws_bytes": (c_size_t, [c_int]),
+    "ofd_x0_abs_quantile": (c_int, [c_int] + [c_void_p] * 6 + [c_int, c_size_t, c_size_t, c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ofd_cond_drop": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_size_t, c_void_p]),
     "ofd_diffusion_prep": (c_int, [c_int] + [c_void_p] * 3 + [c_float] + [c_void_p] * 2 + [c_int] + [c_void_p] * 3 + [c_int, c_int, c_size_t, c_void_p]),
     "ofd_range_map": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p]),

@@ -1,37 +1,11 @@
 // Diffusion elementwise steps (denoising_diffusion.py:589-623, 666-698, 750-767, 806-812), the DPM-Solver++ multistep step, and the
 // NaN-masked squared-error reduction (warp.py:260-271 + torch.nanmean, DD:908,973).
 // HBM-bound streaming kernels: float4 accesses, per-sample scalar coefficients.
-#include <type_traits>
-
-#include "common.h"
+#include "diffusion_common.h"
 
 namespace ofd {
 
 __device__ __forceinline__ float clamp1(float v) { return fminf(fmaxf(v, -1.0f), 1.0f); }
-
-// The objective of a reverse step / training prep (DD:589-611, 634-664, 874-879): what the network predicts.
-enum Objective { PRED_X0 = OFD_PRED_X0, PRED_NOISE = OFD_PRED_NOISE, PRED_V = OFD_PRED_V };
-
-// one element group of VEC consecutive floats: a single dwordx4 access per operand when VEC == 4 (scalar dword accesses at a 16-byte lane
-// stride run these kernels at ~2.3 TB/s; a lane-contiguous float4 form streams)
-template <int VEC> struct EwVec { float v[VEC]; };
-template <int VEC> __device__ __forceinline__ EwVec<VEC> ew_load(const float* p) {
-    EwVec<VEC> r;
-    if constexpr (VEC == 4) { const float4 u = *(const float4*)p; r.v[0] = u.x; r.v[1] = u.y; r.v[2] = u.z; r.v[3] = u.w; }
-    else r.v[0] = p[0];
-    return r;
-}
-template <int VEC> __device__ __forceinline__ void ew_store(float* p, const EwVec<VEC>& r) {
-    if constexpr (VEC == 4) *(float4*)p = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
-    else p[0] = r.v[0];
-}
-
-// x_start from the model output before any clamp: pred_x0 -> mo; pred_noise -> sr x - srm1 eps (DD:589-593); pred_v -> sqrt_ac x - sqrt_1mac v
-// (DD:607-611).  ka / kb are (sr, srm1) or (sqrt_ac, sqrt_1mac); the two products are rounded separately (-ffp-contract=off), as torch does.
-template <int OBJ> __device__ __forceinline__ float start_from_output(float mo, float xt, float ka, float kb) {
-    if constexpr (OBJ == PRED_X0) return mo;
-    else return ka * xt - kb * mo;
-}
 
 // Training prep (DD:844-848, 806-812, 874-879, 985-993), one launch: x0n = normalize ? 2 x0 - 1 : x0; nz' = noise + strength * offset[b, c];
 // x_t = sqrt_ac x0n + sqrt_1mac nz'; target = nz' (pred_noise), x0n (pred_x0), sqrt_ac nz' - sqrt_1mac x0n (pred_v).  x_norm / target may be
@@ -76,33 +50,25 @@ struct KnownArgs {
     const float* s1 = nullptr;
 };
 
-// Classifier-free guidance (Ho & Salimans 2022; not in the reference): a second optional trailing pack.  With it the kernel reads a second
-// model output, the one of the null condition, and uses m = u + w (c - u) (c = mo, u = uncond, w = w[sample]; fp32, the product and the
-// two sums rounded on their own; w == 0 selects u itself) wherever it uses the model output otherwise: formed in registers, before
-// start_from_output and the clamp.  4 B per element more than the same kernel without the pack.
-struct GuideArgs {
-    const float* uncond = nullptr;    // (B, n_per_sample), the layout of mo
-    const float* w = nullptr;         // per-sample guidance scale
+// Dynamic thresholding (Saharia et al. 2022, "Imagen", section 2.3; not in the reference): a third optional trailing pack.  With it the
+// clamp of a free element's x_start is clamp(x0, -s, s) / s with s = s[sample] (>= 1: ofd_x0_abs_quantile) instead of clamp1(x0); a row of
+// ones is clamp1's bits (x / 1.0f is x).  Held elements stay clamp1(known).  Nothing more is read per element.
+struct ThreshArgs {
+    const float* s = nullptr;         // per-sample threshold
 };
-__device__ __forceinline__ float guided(float c, float u, float w) { return w == 0.0f ? u : u + w * (c - u); }
+// the clamp of a free element's x_start: the static one, or the thresholded one with the pack
+template <bool THRESH> __device__ __forceinline__ float clamp_start(float v, float ts) {
+    if constexpr (THRESH) return fminf(fmaxf(v, -ts), ts) / ts;
+    else return clamp1(v);
+}
 
-// The trailing packs of an update kernel: any of KnownArgs, GuideArgs, in that order.  has_args<T, K...>: T is among them;
+// The trailing packs of an update kernel: any of KnownArgs, GuideArgs, ThreshArgs, in that order.  has_args<T, K...>: T is among them;
 // get_args<T>(k...): it, or an empty T.  Without a pack the kernel has the parameters and the code it had before the pack existed.
 template <typename T, typename... K> constexpr bool has_args = (std::is_same_v<T, K> || ...);
 template <typename T> __device__ __forceinline__ T get_args() { return T{}; }
 template <typename T, typename K0, typename... K> __device__ __forceinline__ T get_args(K0 k0, K... k) {
     if constexpr (std::is_same_v<T, K0>) return k0;
     else return get_args<T>(k...);
-}
-// the model output of one element group: mo's, or the guided combination of mo's and uncond's
-template <int VEC, bool GUIDE> __device__ __forceinline__ EwVec<VEC> load_output(const float* mo, const GuideArgs& gd, float gw, size_t e) {
-    EwVec<VEC> m = ew_load<VEC>(mo + e);
-    if constexpr (GUIDE) {
-        const EwVec<VEC> u = ew_load<VEC>(gd.uncond + e);
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) m.v[j] = guided(m.v[j], u.v[j], gw);
-    }
-    return m;
 }
 __device__ __forceinline__ bool held(float k) { return k == k; }
 __device__ __forceinline__ float held_value(float kc, float ksa, float ks1, float e, bool fin) {
@@ -118,11 +84,13 @@ __global__ void __launch_bounds__(256) ddpm_update_kernel(const float* __restric
                                                           const float* __restrict__ xa, const float* __restrict__ xb,
                                                           float* __restrict__ out, float* __restrict__ x_start, size_t n_per_sample,
                                                           K... packs) {
-    constexpr bool KNOWN = has_args<KnownArgs, K...>, GUIDE = has_args<GuideArgs, K...>;
+    constexpr bool KNOWN = has_args<KnownArgs, K...>, GUIDE = has_args<GuideArgs, K...>, THRESH = has_args<ThreshArgs, K...>;
     const KnownArgs kn = get_args<KnownArgs>(packs...);
     const GuideArgs gd = get_args<GuideArgs>(packs...);
+    const ThreshArgs th = get_args<ThreshArgs>(packs...);
     const int s = blockIdx.y;
     const float gw = GUIDE ? gd.w[s] : 0.0f;
+    const float ts = THRESH ? th.s[s] : 1.0f;
     const float k1 = c1[s], k2 = c2[s], ks = (noise && sg) ? sg[s] : 0.0f;
     float ka = 0.0f, kb = 0.0f;
     if constexpr (OBJ != PRED_X0) { ka = xa[s]; kb = xb[s]; }
@@ -141,7 +109,7 @@ __global__ void __launch_bounds__(256) ddpm_update_kernel(const float* __restric
         }
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
-            float x0 = clamp1(start_from_output<OBJ>(m.v[j], xt.v[j], ka, kb));   // DD:670-671
+            float x0 = clamp_start<THRESH>(start_from_output<OBJ>(m.v[j], xt.v[j], ka, kb), ts);   // DD:670-671
             float v = k1 * x0 + k2 * xt.v[j];                            // DD:615-618
             if (ks != 0.0f) v = v + ks * nz.v[j];                        // DD:688
             if constexpr (KNOWN) {
@@ -168,11 +136,13 @@ __global__ void __launch_bounds__(256) ddim_update_kernel(const float* __restric
                                                           const float* __restrict__ cc, const float* __restrict__ sg, int last,
                                                           float* __restrict__ out, float* __restrict__ x_start, size_t n_per_sample,
                                                           K... packs) {
-    constexpr bool KNOWN = has_args<KnownArgs, K...>, GUIDE = has_args<GuideArgs, K...>;
+    constexpr bool KNOWN = has_args<KnownArgs, K...>, GUIDE = has_args<GuideArgs, K...>, THRESH = has_args<ThreshArgs, K...>;
     const KnownArgs kn = get_args<KnownArgs>(packs...);
     const GuideArgs gd = get_args<GuideArgs>(packs...);
+    const ThreshArgs th = get_args<ThreshArgs>(packs...);
     const int s = blockIdx.y;
     const float gw = GUIDE ? gd.w[s] : 0.0f;
+    const float ts = THRESH ? th.s[s] : 1.0f;
     const float k_sr = sr[s], k_srm1 = srm1[s];
     const float k_an = last ? 0.0f : san[s], k_c = last ? 0.0f : cc[s], k_s = (last || !noise || !sg) ? 0.0f : sg[s];
     float ka = 0.0f, kb = 0.0f;
@@ -192,7 +162,7 @@ __global__ void __launch_bounds__(256) ddim_update_kernel(const float* __restric
         }
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
-            float x0 = clamp1(start_from_output<OBJ>(m.v[j], xt.v[j], ka, kb));   // clip_x_start (DD:655)
+            float x0 = clamp_start<THRESH>(start_from_output<OBJ>(m.v[j], xt.v[j], ka, kb), ts);   // clip_x_start (DD:655)
             float v = x0;
             if (!last) {
                 const float eps = (k_sr * xt.v[j] - x0) / k_srm1;        // DD:595-599
@@ -225,11 +195,13 @@ __global__ void __launch_bounds__(256) dpmpp_update_kernel(const float* x_t, con
                                                            const float* __restrict__ w0, const float* __restrict__ w1,
                                                            const float* __restrict__ w2, int last, float* out, float* __restrict__ d_out,
                                                            size_t n_per_sample, K... packs) {
-    constexpr bool KNOWN = has_args<KnownArgs, K...>, GUIDE = has_args<GuideArgs, K...>;
+    constexpr bool KNOWN = has_args<KnownArgs, K...>, GUIDE = has_args<GuideArgs, K...>, THRESH = has_args<ThreshArgs, K...>;
     const KnownArgs kn = get_args<KnownArgs>(packs...);
     const GuideArgs gd = get_args<GuideArgs>(packs...);
+    const ThreshArgs th = get_args<ThreshArgs>(packs...);
     const int s = blockIdx.y;
     const float gw = GUIDE ? gd.w[s] : 0.0f;
+    const float ts = THRESH ? th.s[s] : 1.0f;
     const float k_x = last ? 0.0f : cx[s], k_0 = last ? 0.0f : w0[s];
     const float k_1 = (ORDER >= 2 && !last) ? w1[s] : 0.0f, k_2 = (ORDER >= 3 && !last) ? w2[s] : 0.0f;
     float ka = 0.0f, kb = 0.0f;
@@ -249,7 +221,7 @@ __global__ void __launch_bounds__(256) dpmpp_update_kernel(const float* x_t, con
         }
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
-            float x0 = clamp1(start_from_output<OBJ>(m.v[j], xt.v[j], ka, kb));   // as ddim_update_kernel
+            float x0 = clamp_start<THRESH>(start_from_output<OBJ>(m.v[j], xt.v[j], ka, kb), ts);   // as ddim_update_kernel
             float v = x0;
             if (!last) {
                 v = k_x * xt.v[j];                                       // each product rounded once, added in this order
@@ -361,33 +333,8 @@ __global__ void __launch_bounds__(256) nan_mse_grad_kernel(const float* __restri
     }
 }
 
-static inline dim3 ew_grid(int B, size_t nv) {
-    size_t b = (nv + 255) / 256;
-    if (b < 1) b = 1;
-    if (b > 2048) b = 2048;
-    return dim3((unsigned)b, (unsigned)B);
-}
-
-// The float4 / scalar choice of every elementwise launch: f(std::integral_constant<int, VEC>{}, grid, stream) with VEC = 4 when
-// n_per_sample % 4 == 0 (and vec_ok, the caller's own extra condition), else 1; grid = ew_grid(B, n / VEC), 256 threads per block.
-template <typename F> static void ew_launch(int B, size_t n, void* stream, F&& f, bool vec_ok = true) {
-    if (n % 4 == 0 && vec_ok) f(std::integral_constant<int, 4>{}, ew_grid(B, n / 4), (hipStream_t)stream);
-    else f(std::integral_constant<int, 1>{}, ew_grid(B, n), (hipStream_t)stream);
-}
-
 }  // namespace ofd
 using namespace ofd;
-
-#define OFD_EW_ARGS_OK(B, n) OFD_CHECK_ARG((B) > 0 && (B) <= 65535 && (n) > 0, "bad B=%d n_per_sample=%zu", (B), (size_t)(n))
-
-#define OFD_OBJ_OK(o) OFD_CHECK_ARG((o) == PRED_X0 || (o) == PRED_NOISE || (o) == PRED_V, "bad objective %d", (o))
-
-// f(std::integral_constant<int, OBJ>{}) for the runtime objective: one kernel instantiation per objective
-template <typename F> static void obj_dispatch(int obj, F&& f) {
-    if (obj == PRED_NOISE) f(std::integral_constant<int, PRED_NOISE>{});
-    else if (obj == PRED_V) f(std::integral_constant<int, PRED_V>{});
-    else f(std::integral_constant<int, PRED_X0>{});
-}
 
 extern "C" int ofd_diffusion_prep(int objective, const float* x0, const float* noise, const float* offset, float offset_strength,
                                   const float* sqrt_ac, const float* sqrt_1mac, int normalize, float* x_t, float* target, float* x_norm,
@@ -413,9 +360,9 @@ extern "C" int ofd_q_sample(const float* x0, const float* noise, const float* sq
     return ofd_diffusion_prep(PRED_X0, x0, noise, nullptr, 0.0f, sqrt_ac, sqrt_1mac, 0, out, nullptr, nullptr, B, 1, n, stream);
 }
 
-// The reverse steps.  One implementation per step kind serves its plain, its _known and its _guided entry point: `name` is the entry
-// point's name in the messages, `kn` the constrained step's KnownArgs and `gd` the guided step's GuideArgs (null: launched without that
-// trailing pack).  The checks a _known entry point adds come after the ones it shares; `fin`: the step writes known itself and reads
+// The reverse steps.  One implementation per step kind serves its plain, its _known, its _guided and its _thresh entry point: `name` is
+// the entry point's name in the messages, `kn` the constrained step's KnownArgs, `gd` the guided step's GuideArgs and `th` the
+// thresholded step's ThreshArgs (null: launched without that trailing pack).  The checks a _known entry point adds come after the ones it shares; `fin`: the step writes known itself and reads
 // neither e nor the next level's rows.  A _guided entry point takes the _known arguments too: known == NULL is the unconstrained step,
 // and then the arguments only a constrained step reads must be NULL as well.
 #define OFD_KNOWN_ARGS_OK(name, kn, fin)                                                                                      \
@@ -423,24 +370,26 @@ extern "C" int ofd_q_sample(const float* x0, const float* noise, const float* sq
     OFD_CHECK_ARG((fin) || ((kn)->sa && (kn)->s1), "%s: missing sqrt_ac_next / sqrt_1mac_next", name);                         \
     OFD_CHECK_ARG((fin) || (kn)->e, "%s: a step without noise needs e0", name)
 
-#define OFD_GUIDE_ARGS_OK(name, gd) \
-    OFD_CHECK_ARG((gd)->uncond && (gd)->w, "%s: null model_out_uncond / guidance", name)
-
 // `known` of a _guided entry point: null when it is NULL, after checking that nothing constrained-only came with it
 #define OFD_GUIDED_KNOWN(name, known, e0, sa, s1) \
     OFD_CHECK_ARG((known) || (!(e0) && !(sa) && !(s1)), "%s: e0 / sqrt_ac_next / sqrt_1mac_next are read with known only", name)
 
-// launch(packs...) with the packs that are present, KnownArgs first
-template <typename F> static void launch_packs(const KnownArgs* kn, const GuideArgs* gd, F&& launch) {
-    if (kn && gd) launch(*kn, *gd);
-    else if (kn) launch(*kn);
-    else if (gd) launch(*gd);
-    else launch();
+// launch(packs...) with the packs that are present, in the order KnownArgs, GuideArgs, ThreshArgs
+template <typename F> static void launch_packs(const KnownArgs* kn, const GuideArgs* gd, const ThreshArgs* th, F&& launch) {
+    auto tail = [&](auto... k) {
+        if (th) launch(k..., *th);
+        else launch(k...);
+    };
+    if (kn && gd) tail(*kn, *gd);
+    else if (kn) tail(*kn);
+    else if (gd) tail(*gd);
+    else tail();
 }
 
 static int ddpm_update_impl(const char* name, int objective, const float* x_t, const float* model_out, const float* noise,
                             const float* coef1, const float* coef2, const float* sigma, const float* xa, const float* xb,
-                            const KnownArgs* kn, const GuideArgs* gd, float* out, float* x_start, int B, size_t n, void* stream) {
+                            const KnownArgs* kn, const GuideArgs* gd, const ThreshArgs* th, float* out, float* x_start, int B, size_t n,
+                            void* stream) {
     OFD_OBJ_OK(objective);
     OFD_EW_ARGS_OK(B, n);
     OFD_CHECK_ARG(x_t && model_out && coef1 && coef2 && out, "%s: null pointer", name);
@@ -452,6 +401,9 @@ static int ddpm_update_impl(const char* name, int objective, const float* x_t, c
     if (gd) {
         OFD_GUIDE_ARGS_OK(name, gd);
     }
+    if (th) {
+        OFD_CHECK_ARG(th->s, "%s: null thresh", name);
+    }
     auto launch = [&](auto... k) {
         obj_dispatch(objective, [&](auto o) {
             ew_launch(B, n, stream, [&](auto vec, dim3 grid, hipStream_t s) {
@@ -460,7 +412,7 @@ static int ddpm_update_impl(const char* name, int objective, const float* x_t, c
             });
         });
     };
-    launch_packs(kn, gd, launch);
+    launch_packs(kn, gd, th, launch);
     OFD_LAUNCH_CHECK();
     return OFD_OK;
 }
@@ -468,7 +420,7 @@ static int ddpm_update_impl(const char* name, int objective, const float* x_t, c
 extern "C" int ofd_ddpm_update_obj(int objective, const float* x_t, const float* model_out, const float* noise, const float* coef1,
                                    const float* coef2, const float* sigma, const float* xa, const float* xb, float* out, float* x_start,
                                    int B, size_t n, void* stream) {
-    return ddpm_update_impl("ddpm_update", objective, x_t, model_out, noise, coef1, coef2, sigma, xa, xb, nullptr, nullptr, out, x_start,
+    return ddpm_update_impl("ddpm_update", objective, x_t, model_out, noise, coef1, coef2, sigma, xa, xb, nullptr, nullptr, nullptr, out, x_start,
                             B, n, stream);
 }
 
@@ -478,7 +430,7 @@ extern "C" int ofd_ddpm_update_known(int objective, const float* x_t, const floa
                                      float* x_start, int B, size_t n, void* stream) {
     const bool fin = !sqrt_ac_next || !sqrt_1mac_next;
     const KnownArgs kn{known, noise ? noise : e0, fin ? nullptr : sqrt_ac_next, fin ? nullptr : sqrt_1mac_next};
-    return ddpm_update_impl("ddpm_update_known", objective, x_t, model_out, noise, coef1, coef2, sigma, xa, xb, &kn, nullptr, out,
+    return ddpm_update_impl("ddpm_update_known", objective, x_t, model_out, noise, coef1, coef2, sigma, xa, xb, &kn, nullptr, nullptr, out,
                             x_start, B, n, stream);
 }
 
@@ -492,7 +444,7 @@ extern "C" int ofd_ddpm_update_guided(int objective, const float* x_t, const flo
     const KnownArgs kn{known, noise ? noise : e0, fin ? nullptr : sqrt_ac_next, fin ? nullptr : sqrt_1mac_next};
     const GuideArgs gd{model_out_uncond, guidance};
     return ddpm_update_impl("ddpm_update_guided", objective, x_t, model_out, noise, coef1, coef2, sigma, xa, xb, known ? &kn : nullptr,
-                            &gd, out, x_start, B, n, stream);
+                            &gd, nullptr, out, x_start, B, n, stream);
 }
 
 extern "C" int ofd_ddpm_update(const float* x_t, const float* model_out, const float* noise, const float* coef1,
@@ -503,7 +455,7 @@ extern "C" int ofd_ddpm_update(const float* x_t, const float* model_out, const f
 static int ddim_update_impl(const char* name, int objective, const float* x_t, const float* model_out, const float* noise,
                             const float* sqrt_recip_ac, const float* sqrt_recipm1_ac, const float* xa, const float* xb,
                             const float* sqrt_alpha_next, const float* c, const float* sigma, int last, const KnownArgs* kn,
-                            const GuideArgs* gd, float* out, float* x_start, int B, size_t n, void* stream) {
+                            const GuideArgs* gd, const ThreshArgs* th, float* out, float* x_start, int B, size_t n, void* stream) {
     OFD_OBJ_OK(objective);
     OFD_EW_ARGS_OK(B, n);
     OFD_CHECK_ARG(x_t && model_out && sqrt_recip_ac && sqrt_recipm1_ac && out, "%s: null pointer", name);
@@ -515,6 +467,9 @@ static int ddim_update_impl(const char* name, int objective, const float* x_t, c
     if (gd) {
         OFD_GUIDE_ARGS_OK(name, gd);
     }
+    if (th) {
+        OFD_CHECK_ARG(th->s, "%s: null thresh", name);
+    }
     auto launch = [&](auto... k) {
         obj_dispatch(objective, [&](auto o) {
             ew_launch(B, n, stream, [&](auto vec, dim3 grid, hipStream_t s) {
@@ -523,7 +478,7 @@ static int ddim_update_impl(const char* name, int objective, const float* x_t, c
             });
         });
     };
-    launch_packs(kn, gd, launch);
+    launch_packs(kn, gd, th, launch);
     OFD_LAUNCH_CHECK();
     return OFD_OK;
 }
@@ -532,7 +487,7 @@ extern "C" int ofd_ddim_update_obj(int objective, const float* x_t, const float*
                                    const float* sqrt_recipm1_ac, const float* xa, const float* xb, const float* sqrt_alpha_next,
                                    const float* c, const float* sigma, int last, float* out, float* x_start, int B, size_t n, void* stream) {
     return ddim_update_impl("ddim_update", objective, x_t, model_out, noise, sqrt_recip_ac, sqrt_recipm1_ac, xa, xb, sqrt_alpha_next, c,
-                            sigma, last, nullptr, nullptr, out, x_start, B, n, stream);
+                            sigma, last, nullptr, nullptr, nullptr, out, x_start, B, n, stream);
 }
 
 extern "C" int ofd_ddim_update_known(int objective, const float* x_t, const float* model_out, const float* noise,
@@ -542,7 +497,7 @@ extern "C" int ofd_ddim_update_known(int objective, const float* x_t, const floa
                                      float* x_start, int B, size_t n, void* stream) {
     const KnownArgs kn{known, noise ? noise : e0, sqrt_ac_next, sqrt_1mac_next};
     return ddim_update_impl("ddim_update_known", objective, x_t, model_out, noise, sqrt_recip_ac, sqrt_recipm1_ac, xa, xb,
-                            sqrt_alpha_next, c, sigma, last, &kn, nullptr, out, x_start, B, n, stream);
+                            sqrt_alpha_next, c, sigma, last, &kn, nullptr, nullptr, out, x_start, B, n, stream);
 }
 
 extern "C" int ofd_ddim_update_guided(int objective, const float* x_t, const float* model_out, const float* model_out_uncond,
@@ -554,7 +509,7 @@ extern "C" int ofd_ddim_update_guided(int objective, const float* x_t, const flo
     const KnownArgs kn{known, noise ? noise : e0, sqrt_ac_next, sqrt_1mac_next};
     const GuideArgs gd{model_out_uncond, guidance};
     return ddim_update_impl("ddim_update_guided", objective, x_t, model_out, noise, sqrt_recip_ac, sqrt_recipm1_ac, xa, xb,
-                            sqrt_alpha_next, c, sigma, last, known ? &kn : nullptr, &gd, out, x_start, B, n, stream);
+                            sqrt_alpha_next, c, sigma, last, known ? &kn : nullptr, &gd, nullptr, out, x_start, B, n, stream);
 }
 
 extern "C" int ofd_ddim_update(const float* x_t, const float* model_out, const float* noise, const float* sqrt_recip_ac,
@@ -566,7 +521,8 @@ extern "C" int ofd_ddim_update(const float* x_t, const float* model_out, const f
 
 static int dpmpp_update_impl(const char* name, int objective, int order, const float* x_t, const float* model_out, const float* xa,
                              const float* xb, const float* d_prev1, const float* d_prev2, const float* cx, const float* w0,
-                             const float* w1, const float* w2, int last, const KnownArgs* kn, const GuideArgs* gd, float* out, float* d_out,
+                             const float* w1, const float* w2, int last, const KnownArgs* kn, const GuideArgs* gd, const ThreshArgs* th,
+                             float* out, float* d_out,
                              int B, size_t n, void* stream) {
     OFD_OBJ_OK(objective);
     OFD_EW_ARGS_OK(B, n);
@@ -583,6 +539,9 @@ static int dpmpp_update_impl(const char* name, int objective, int order, const f
     if (gd) {
         OFD_GUIDE_ARGS_OK(name, gd);
     }
+    if (th) {
+        OFD_CHECK_ARG(th->s, "%s: null thresh", name);
+    }
     const int ord = last ? 1 : order;                                  // the final evaluation reads no history
     auto launch = [&](auto... k) {
         obj_dispatch(objective, [&](auto o) {
@@ -597,7 +556,7 @@ static int dpmpp_update_impl(const char* name, int objective, int order, const f
             else go(std::integral_constant<int, 1>{});
         });
     };
-    launch_packs(kn, gd, launch);
+    launch_packs(kn, gd, th, launch);
     OFD_LAUNCH_CHECK();
     return OFD_OK;
 }
@@ -606,7 +565,7 @@ extern "C" int ofd_dpmpp_update(int objective, int order, const float* x_t, cons
                                 const float* d_prev1, const float* d_prev2, const float* cx, const float* w0, const float* w1,
                                 const float* w2, int last, float* out, float* d_out, int B, size_t n, void* stream) {
     return dpmpp_update_impl("dpmpp_update", objective, order, x_t, model_out, xa, xb, d_prev1, d_prev2, cx, w0, w1, w2, last, nullptr, nullptr,
-                             out, d_out, B, n, stream);
+                             nullptr, out, d_out, B, n, stream);
 }
 
 extern "C" int ofd_dpmpp_update_known(int objective, int order, const float* x_t, const float* model_out, const float* xa,
@@ -616,7 +575,7 @@ extern "C" int ofd_dpmpp_update_known(int objective, int order, const float* x_t
                                       void* stream) {
     const KnownArgs kn{known, e0, sqrt_ac_next, sqrt_1mac_next};
     return dpmpp_update_impl("dpmpp_update_known", objective, order, x_t, model_out, xa, xb, d_prev1, d_prev2, cx, w0, w1, w2, last, &kn,
-                             nullptr, out, d_out, B, n, stream);
+                             nullptr, nullptr, out, d_out, B, n, stream);
 }
 
 extern "C" int ofd_dpmpp_update_guided(int objective, int order, const float* x_t, const float* model_out, const float* model_out_uncond,
@@ -628,7 +587,58 @@ extern "C" int ofd_dpmpp_update_guided(int objective, int order, const float* x_
     const KnownArgs kn{known, e0, sqrt_ac_next, sqrt_1mac_next};
     const GuideArgs gd{model_out_uncond, guidance};
     return dpmpp_update_impl("dpmpp_update_guided", objective, order, x_t, model_out, xa, xb, d_prev1, d_prev2, cx, w0, w1, w2, last,
-                             known ? &kn : nullptr, &gd, out, d_out, B, n, stream);
+                             known ? &kn : nullptr, &gd, nullptr, out, d_out, B, n, stream);
+}
+
+// The thresholded steps: the _guided argument lists plus `thresh` after guidance.  model_out_uncond and guidance come together or not at
+// all (NULL, NULL: an unguided step); known as in the _guided entry points.
+#define OFD_THRESH_ARGS_OK(name, uncond, guidance, thresh)                                                                    \
+    OFD_CHECK_ARG(thresh, "%s: null thresh", name);                                                                            \
+    OFD_CHECK_ARG(!(uncond) == !(guidance), "%s: model_out_uncond and guidance come together (both NULL: an unguided step)", name)
+
+extern "C" int ofd_ddpm_update_thresh(int objective, const float* x_t, const float* model_out, const float* model_out_uncond,
+                                      const float* guidance, const float* thresh, const float* noise, const float* coef1,
+                                      const float* coef2, const float* sigma, const float* xa, const float* xb, const float* known,
+                                      const float* e0, const float* sqrt_ac_next, const float* sqrt_1mac_next, float* out, float* x_start,
+                                      int B, size_t n, void* stream) {
+    OFD_THRESH_ARGS_OK("ddpm_update_thresh", model_out_uncond, guidance, thresh);
+    OFD_GUIDED_KNOWN("ddpm_update_thresh", known, e0, sqrt_ac_next, sqrt_1mac_next);
+    const bool fin = !sqrt_ac_next || !sqrt_1mac_next;
+    const KnownArgs kn{known, noise ? noise : e0, fin ? nullptr : sqrt_ac_next, fin ? nullptr : sqrt_1mac_next};
+    const GuideArgs gd{model_out_uncond, guidance};
+    const ThreshArgs th{thresh};
+    return ddpm_update_impl("ddpm_update_thresh", objective, x_t, model_out, noise, coef1, coef2, sigma, xa, xb, known ? &kn : nullptr,
+                            guidance ? &gd : nullptr, &th, out, x_start, B, n, stream);
+}
+
+extern "C" int ofd_ddim_update_thresh(int objective, const float* x_t, const float* model_out, const float* model_out_uncond,
+                                      const float* guidance, const float* thresh, const float* noise, const float* sqrt_recip_ac,
+                                      const float* sqrt_recipm1_ac, const float* xa, const float* xb, const float* sqrt_alpha_next,
+                                      const float* c, const float* sigma, int last, const float* known, const float* e0,
+                                      const float* sqrt_ac_next, const float* sqrt_1mac_next, float* out, float* x_start, int B, size_t n,
+                                      void* stream) {
+    OFD_THRESH_ARGS_OK("ddim_update_thresh", model_out_uncond, guidance, thresh);
+    OFD_GUIDED_KNOWN("ddim_update_thresh", known, e0, sqrt_ac_next, sqrt_1mac_next);
+    const KnownArgs kn{known, noise ? noise : e0, sqrt_ac_next, sqrt_1mac_next};
+    const GuideArgs gd{model_out_uncond, guidance};
+    const ThreshArgs th{thresh};
+    return ddim_update_impl("ddim_update_thresh", objective, x_t, model_out, noise, sqrt_recip_ac, sqrt_recipm1_ac, xa, xb,
+                            sqrt_alpha_next, c, sigma, last, known ? &kn : nullptr, guidance ? &gd : nullptr, &th, out, x_start, B, n,
+                            stream);
+}
+
+extern "C" int ofd_dpmpp_update_thresh(int objective, int order, const float* x_t, const float* model_out, const float* model_out_uncond,
+                                       const float* guidance, const float* thresh, const float* xa, const float* xb,
+                                       const float* d_prev1, const float* d_prev2, const float* cx, const float* w0, const float* w1,
+                                       const float* w2, int last, const float* known, const float* e0, const float* sqrt_ac_next,
+                                       const float* sqrt_1mac_next, float* out, float* d_out, int B, size_t n, void* stream) {
+    OFD_THRESH_ARGS_OK("dpmpp_update_thresh", model_out_uncond, guidance, thresh);
+    OFD_GUIDED_KNOWN("dpmpp_update_thresh", known, e0, sqrt_ac_next, sqrt_1mac_next);
+    const KnownArgs kn{known, e0, sqrt_ac_next, sqrt_1mac_next};
+    const GuideArgs gd{model_out_uncond, guidance};
+    const ThreshArgs th{thresh};
+    return dpmpp_update_impl("dpmpp_update_thresh", objective, order, x_t, model_out, xa, xb, d_prev1, d_prev2, cx, w0, w1, w2, last,
+                             known ? &kn : nullptr, guidance ? &gd : nullptr, &th, out, d_out, B, n, stream);
 }
 
 extern "C" int ofd_range_map(const float* in, float* out, size_t n, int mode, void* stream) {

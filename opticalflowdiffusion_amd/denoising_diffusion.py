@@ -130,6 +130,33 @@ def _guidance_value(value, what="guidance_scale"):
     return float(value)
 
 
+FLT_MAX = 3.4028234663852886e38          # the largest finite float32: threshold_max=None (unbounded) as ofd_x0_abs_quantile takes it
+
+
+def threshold_rank(p, n):
+    """the rank (1 = smallest) of the order statistic dynamic thresholding takes as the p-quantile of n values: min(n, max(1, ceil(p n))),
+    the product in float64; p = 1 is the maximum.  The kernel is handed this integer (include/ofd.h, ofd_x0_abs_quantile)."""
+    return min(int(n), max(1, math.ceil(float(p) * int(n))))
+
+
+def _threshold_value(value, what="dynamic_threshold"):
+    """None, or the percentile p as a float in (0, 1] (ValueError otherwise)"""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not 0.0 < value <= 1.0:
+        raise ValueError(f"{what} must be None or a number in (0, 1], got {value!r}")
+    return float(value)
+
+
+def _threshold_max_value(value, what="threshold_max"):
+    """None (unbounded), or the cap of the threshold as a finite float >= 1 (ValueError otherwise)"""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not math.isfinite(value) or value < 1.0:
+        raise ValueError(f"{what} must be None or a finite number >= 1, got {value!r}")
+    return float(value)
+
+
 def normalize_to_neg_one_to_one(img):
     """DD:73-74"""
     return _range_map(img, 0)
@@ -535,8 +562,14 @@ class ConditionalDiffusion(nn.Module):
                  beta_schedule="sigmoid", schedule_fn_kwargs=dict(), ddim_sampling_eta=0.0, auto_normalize=True,
                  offset_noise_strength=0.0, min_snr_loss_weight=False, min_snr_gamma=5, conditioned=True,
                  channels=3, noise_space="image", ddim_draw_unused_noise=False, sampler=None, solver_order=2,
-                 sampler_spacing="logsnr", cond_drop_prob=0.0, guidance_scale=None):
+                 sampler_spacing="logsnr", cond_drop_prob=0.0, guidance_scale=None, dynamic_threshold=None,
+                 threshold_max=None):
         super().__init__()
+        # dynamic thresholding (Imagen, section 2.3; not in the reference): dynamic_threshold = p in (0, 1]: every reverse
+        # step clamps x_start to [-s, s] and divides by s, s = the p-quantile of |x_start| per sample, at least 1 and at most
+        # threshold_max (None: unbounded), instead of clamping to [-1, 1].  None is the static clamp, the present path.
+        self.dynamic_threshold = _threshold_value(dynamic_threshold)
+        self.threshold_max = _threshold_max_value(threshold_max)
         # classifier-free guidance (not in the reference): cond_drop_prob = the probability with which forward() replaces a
         # training sample's condition by the null condition (zeros in the normalised range); guidance_scale = w of
         # out = out_uncond + w (out_cond - out_uncond) in sample(): None or 1.0 is the conditional model (one model call per step)
@@ -712,11 +745,13 @@ class ConditionalDiffusion(nn.Module):
     # -- DDPM --------------------------------------------------------------------------------
     @torch.no_grad()
     def p_sample(self, x, t: int, x_self_cond=None, external_cond=None, additional_tgt=None, noise=None, known=None,
-                 guidance_scale=UNSET):
+                 guidance_scale=UNSET, dynamic_threshold=UNSET, threshold_max=UNSET, _qplan=None):
         """DD:676-698: network call + one fused kernel for clamp / posterior mean / noise add.  `known` (optional, not in the reference;
-        shaped like x, in x's range, NaN = free): the constrained step of `sample(known=)`.  `guidance_scale`: as `sample`'s."""
+        shaped like x, in x's range, NaN = free): the constrained step of `sample(known=)`.  `guidance_scale`, `dynamic_threshold`,
+        `threshold_max`: as `sample`'s.  `_qplan`: a loop's own `_threshold_plan`, made once per chain; a single step makes its own."""
         known = self._check_known(tuple(x.shape), known, 1, additional_tgt)
         w = self._check_guidance(guidance_scale, additional_tgt, external_cond)
+        th = self._check_threshold(dynamic_threshold, threshold_max)
         b = x.shape[0]
         tab = self._sampling_tables(b, x.device)           # rows of per-(T, batch) tables: no fill / gather / exp launches per step
         bt = tab["t"][t]
@@ -737,45 +772,52 @@ class ConditionalDiffusion(nn.Module):
             noise = None                                                               # DD:687
         pred = torch.empty_like(x)
         x_start = torch.empty_like(x)
-        self._ddpm_step(tab, t, x, out, noise, pred, x_start, known, guide)
+        thresh = None
+        if th is not None:
+            thresh = self._x0_quantile(tab, t, x, out, guide, self._threshold_plan(th, x) if _qplan is None else _qplan)
+        self._ddpm_step(tab, t, x, out, noise, pred, x_start, known, guide, thresh)
         return pred, x_start, additional_out
 
-    # -- the fused update launches: the only callers of the nine reverse-step entry points (include/ofd.h).  img / out / nxt: x_t, the
+    # -- the fused update launches: the only callers of the twelve reverse-step entry points (include/ofd.h).  img / out / nxt: x_t, the
     # model output and the tensor the step writes; `known` (or None) picks the constrained entry point and its trailing arguments;
     # `guide` (or None): (the null condition's model output, the guidance row) picks the guided entry point, which takes the
-    # constrained step's arguments too (all NULL without `known`).
+    # constrained step's arguments too (all NULL without `known`); `thresh` (or None): the threshold row of this step (_x0_quantile)
+    # picks the thresholded entry point, which takes the guided step's arguments (both NULL without `guide`) and thresh after them.
     @staticmethod
-    def _step_fn(lib, kind, plain, known, guide, kn):
+    def _step_fn(lib, kind, plain, known, guide, kn, thresh=None):
         """(entry point, the arguments after model_out, the constrained arguments) of a step"""
+        if thresh is not None:
+            gd = (None, None) if guide is None else (L.ptr(guide[0]), L.ptr(guide[1]))
+            return getattr(lib, f"ofd_{kind}_update_thresh"), (*gd, L.ptr(thresh)), kn if known is not None else (None,) * 4
         if guide is not None:
             return getattr(lib, f"ofd_{kind}_update_guided"), (L.ptr(guide[0]), L.ptr(guide[1])), kn if known is not None else (None,) * 4
         if known is not None:
             return getattr(lib, f"ofd_{kind}_update_known"), (), kn
         return getattr(lib, plain), (), ()
 
-    def _ddpm_step(self, tab, t, img, out, noise, nxt, x_start, known, guide=None):
+    def _ddpm_step(self, tab, t, img, out, noise, nxt, x_start, known, guide=None, thresh=None):
         """the DDPM step at level t; noise is None at t == 0 (DD:687).  A held element rides on the same noise: no e0."""
         kn = () if known is None else (L.ptr(known), None, *self._known_rows(tab, t - 1))
-        fn, gd, kn = self._step_fn(L.lib(), "ddpm", "ofd_ddpm_update_obj", known, guide, kn)
+        fn, gd, kn = self._step_fn(L.lib(), "ddpm", "ofd_ddpm_update_obj", known, guide, kn, thresh)
         L.check(fn(self._obj, L.ptr(img), L.ptr(out), *gd, L.ptr(noise), L.ptr(tab["c1"][t]), L.ptr(tab["c2"][t]), L.ptr(tab["sigma"][t]),
                    *self._xab(tab, t), *kn, L.ptr(nxt), L.ptr(x_start), img.shape[0], img.numel() // img.shape[0], L.stream()))
 
-    def _ddim_step(self, tab, t, img, out, noise, coef, nxt, known, x_T, guide=None):
+    def _ddim_step(self, tab, t, img, out, noise, coef, nxt, known, x_T, guide=None, thresh=None):
         """the DDIM step from level t; coef: this pair's rows sqrt(alpha_next), c, sigma, sqrt(1 - alpha_next), or None on the last step
         (which takes no noise).  A constrained step without noise reads x_T as e0."""
         last = coef is None
         san, c, sigma, s1n = (None,) * 4 if last else (L.ptr(coef[0]), L.ptr(coef[1]), L.ptr(coef[2]), L.ptr(coef[3]))
         kn = () if known is None else (L.ptr(known), None if (last or noise is not None) else L.ptr(x_T), san, s1n)
-        fn, gd, kn = self._step_fn(L.lib(), "ddim", "ofd_ddim_update_obj", known, guide, kn)
+        fn, gd, kn = self._step_fn(L.lib(), "ddim", "ofd_ddim_update_obj", known, guide, kn, thresh)
         L.check(fn(self._obj, L.ptr(img), L.ptr(out), *gd, L.ptr(noise), L.ptr(tab["sr"][t]), L.ptr(tab["srm1"][t]), *self._xab(tab, t),
                    san, c, sigma, int(last), *kn, L.ptr(nxt), None, img.shape[0], img.numel() // img.shape[0], L.stream()))
 
-    def _dpmpp_step(self, tab, t, order, img, out, d1, d2, coef, last, nxt, d_out, known, x_T, guide=None):
+    def _dpmpp_step(self, tab, t, order, img, out, d1, d2, coef, last, nxt, d_out, known, x_T, guide=None, thresh=None):
         """the DPM-Solver++ step from level t; coef: this grid point's six rows (_dpmpp_tables); d1 / d2 / d_out: the history the order
         reads and the slot the prediction goes to (None where unused).  A constrained step reads x_T as e0."""
         kn = () if known is None else ((L.ptr(known), None, None, None) if last else
                                        (L.ptr(known), L.ptr(x_T), L.ptr(coef[4]), L.ptr(coef[5])))
-        fn, gd, kn = self._step_fn(L.lib(), "dpmpp", "ofd_dpmpp_update", known, guide, kn)
+        fn, gd, kn = self._step_fn(L.lib(), "dpmpp", "ofd_dpmpp_update", known, guide, kn, thresh)
         L.check(fn(self._obj, order, L.ptr(img), L.ptr(out), *gd, *self._xab(tab, t), L.ptr(d1), L.ptr(d2), L.ptr(coef[0]), L.ptr(coef[1]),
                    L.ptr(coef[2]), L.ptr(coef[3]), int(last), *kn, L.ptr(nxt), L.ptr(d_out), img.shape[0], img.numel() // img.shape[0],
                    L.stream()))
@@ -846,6 +888,32 @@ class ConditionalDiffusion(nn.Module):
             raise ValueError("guidance_scale needs external_cond: the guided chain calls the model on it and on the null condition")
         return w
 
+    def _check_threshold(self, dynamic_threshold=UNSET, threshold_max=UNSET):
+        """the argument rules of dynamic thresholding, checked before any engine call (ValueError); returns (p, the cap as the engine
+        takes it) of a thresholded chain, or None when it is off: dynamic_threshold (UNSET: the constructor's) None"""
+        p = self.dynamic_threshold if dynamic_threshold is UNSET else _threshold_value(dynamic_threshold)
+        cap = self.threshold_max if threshold_max is UNSET else _threshold_max_value(threshold_max)
+        if p is None:
+            return None
+        return p, FLT_MAX if cap is None else cap
+
+    @staticmethod
+    def _threshold_plan(th, img):
+        """what the quantile launches of a chain on `img`-shaped tensors need, allocated once per chain: (the threshold row, the
+        workspace, rank, cap)"""
+        batch, n = img.shape[0], img.numel() // img.shape[0]
+        ws = torch.empty(int(L.lib().ofd_x0_abs_quantile_ws_bytes(batch)), dtype=torch.uint8, device=img.device)
+        return torch.empty(batch, dtype=torch.float32, device=img.device), ws, threshold_rank(th[0], n), th[1]
+
+    def _x0_quantile(self, tab, t, img, out, guide, plan):
+        """the quantile launches of a thresholded step at level t (include/ofd.h, ofd_x0_abs_quantile) on the arguments the update launch
+        gets; returns the threshold row, written in stream order: no allocation, no host sync"""
+        row, ws, rank, cap = plan
+        gd = (None, None) if guide is None else (L.ptr(guide[0]), L.ptr(guide[1]))
+        L.check(L.lib().ofd_x0_abs_quantile(self._obj, L.ptr(img), L.ptr(out), *gd, *self._xab(tab, t), img.shape[0],
+                                            img.numel() // img.shape[0], rank, cap, L.ptr(row), L.ptr(ws), ws.numel(), L.stream()))
+        return row
+
     def _guidance_row(self, batch, device, w):
         """the per-sample guidance row of the guided entry points (include/ofd.h: guidance), built once per (batch, device, w) like a
         row of `_sampling_tables`: a step reads it, no fill launch per step"""
@@ -882,21 +950,26 @@ class ConditionalDiffusion(nn.Module):
 
     @torch.no_grad()
     def p_sample_loop(self, shape, return_all_timesteps=False, external_cond=None, additional_tgt=None, verbose=False, x_T=None,
-                      known=None, resample=1, guidance_scale=UNSET):
+                      known=None, resample=1, guidance_scale=UNSET, dynamic_threshold=UNSET, threshold_max=UNSET):
         """DD:700-729 (no per-step print / host sync).  `x_T` (optional, not in the reference): the start of the chains (DD:705).
         A step is: one UNet call, one in-place normal_ into a reused buffer, one fused update kernel writing into the other of
         two ping-pong images -- no per-step allocation, no coefficient gathers (rows of `_sampling_tables`).
         `known` / `resample` (optional, not in the reference): constrained sampling, see `sample`; known is in the loop's own range
-        ([-1, 1]), as external_cond and x_T are.  `guidance_scale`: classifier-free guidance, see `sample`."""
+        ([-1, 1]), as external_cond and x_T are.  `guidance_scale`: classifier-free guidance, see `sample`.
+        `dynamic_threshold` / `threshold_max`: dynamic thresholding, see `sample`."""
         known = self._check_known(shape, known, resample, additional_tgt)
         w = self._check_guidance(guidance_scale, additional_tgt, external_cond)
+        th = self._check_threshold(dynamic_threshold, threshold_max)
         if additional_tgt is not None:                                                # target='target': the general step (DD:676-698)
             # kept on p_sample: this branch keeps every frame whatever trajectory_stride says, which the shared chain would not
             img = torch.randn(shape, device=self.device) if x_T is None else L.f32c(x_T)
             assert tuple(img.shape) == tuple(shape)
             imgs, additionals = [img], [None]
+            # the resolved values go down, None included: a per-call None must not fall back to the constructor's value in p_sample
+            thresh_kw = dict(dynamic_threshold=None) if th is None else dict(dynamic_threshold=th[0], threshold_max=th[1],
+                                                                             _qplan=self._threshold_plan(th, img))
             for i, t in enumerate(reversed(range(0, self.num_timesteps))):
-                img, _, additional_out = self.p_sample(img, t, None, external_cond=external_cond, additional_tgt=additional_tgt)
+                img, _, additional_out = self.p_sample(img, t, None, external_cond=external_cond, additional_tgt=additional_tgt, **thresh_kw)
                 if return_all_timesteps:
                     imgs.append(img)
                 additionals.append(additional_out)
@@ -905,10 +978,10 @@ class ConditionalDiffusion(nn.Module):
         def plan(x_T, tab):
             noise, x_start = torch.empty_like(x_T), torch.empty_like(x_T)
 
-            def step(i, t, img, out, nxt, guide):
+            def step(i, t, img, out, nxt, guide, thresh=None):
                 if t > 0:
                     noise.normal_()                          # DD:687: z = 0 at t = 0; the held elements ride on the same draw
-                self._ddpm_step(tab, t, img, out, noise if t > 0 else None, nxt, x_start, known, guide)
+                self._ddpm_step(tab, t, img, out, noise if t > 0 else None, nxt, x_start, known, guide, thresh)
 
             def renoise(t, img, nxt):                        # back to level t: x_t = sqrt(1 - beta_t) x_{t-1} + sqrt(beta_t) e'
                 noise.normal_()
@@ -917,9 +990,9 @@ class ConditionalDiffusion(nn.Module):
 
             return [(t, resample if t > 0 else 1) for t in reversed(range(0, self.num_timesteps))], step, renoise
 
-        return self._run_chain(shape, x_T, plan, return_all_timesteps, external_cond, guidance=w)   # DD:725-726
+        return self._run_chain(shape, x_T, plan, return_all_timesteps, external_cond, guidance=w, threshold=th)   # DD:725-726
 
-    def _run_chain(self, shape, x_T, plan, return_all_timesteps, external_cond, additional_tgt=None, guidance=None):
+    def _run_chain(self, shape, x_T, plan, return_all_timesteps, external_cond, additional_tgt=None, guidance=None, threshold=None):
         """The reverse chain p_sample_loop, ddim_sample and dpmpp_sample share.  It owns the start image (x_T or a fresh draw, made before
         any table is built), the two ping-pong images, the model call on a row of `_sampling_tables`, the additional_tgt split, the
         trajectory (x_T, every trajectory_stride-th schedule entry and the last) and the return form.  `plan(x_T, tab)` is the sampler:
@@ -928,13 +1001,17 @@ class ConditionalDiffusion(nn.Module):
         (RePaint's resampling) is stepped `runs` times with renoise(t, img, nxt) between two runs.  Nothing is allocated, gathered or
         synchronised per step apart from the clone of a kept frame.  `guidance` (the scale w of _check_guidance, or None): every step
         calls the model twice on the same img, on external_cond and then on the null condition (zeros shaped like external_cond, made
-        once here), and hands step() guide = (the second output, the guidance row) for the guided entry point."""
+        once here), and hands step() guide = (the second output, the guidance row) for the guided entry point.  `threshold` (what
+        _check_threshold returns, or None): the threshold row and the quantile workspace are made once here; every step runs the
+        quantile launches on the diffused channels of the model output(s), after the additional_tgt split, and hands step() the row
+        as its last argument for the thresholded entry point.  Without it step() is called as before."""
         img = torch.randn(shape, device=self.device) if x_T is None else L.f32c(x_T)
         assert tuple(img.shape) == tuple(shape)
         tab = self._sampling_tables(shape[0], img.device)
         null_cond = row = None
         if guidance is not None:
             null_cond, row = torch.zeros_like(external_cond), self._guidance_row(shape[0], img.device, guidance)
+        qplan = None if threshold is None else self._threshold_plan(threshold, img)
         schedule, step, renoise = plan(img, tab)                                      # img is x_T: never written, the loop writes to pong
         pong = [torch.empty_like(img), torch.empty_like(img)]
         imgs, additionals, stride = [img], [None], self.trajectory_stride
@@ -951,7 +1028,11 @@ class ConditionalDiffusion(nn.Module):
                 guide = None
                 if guidance is not None:
                     guide = (self._same_shape(L.f32c(self.model_with_condition(img, tab["t"][t], None, external_cond=null_cond)), img), row)
-                step(i, t, img, self._same_shape(L.f32c(out), img), pong[writes & 1], guide)
+                out = self._same_shape(L.f32c(out), img)
+                if qplan is None:
+                    step(i, t, img, out, pong[writes & 1], guide)
+                else:
+                    step(i, t, img, out, pong[writes & 1], guide, self._x0_quantile(tab, t, img, out, guide, qplan))
                 img, writes = pong[writes & 1], writes + 1
             if return_all_timesteps and (stride is None or (i + 1) % stride == 0 or i == len(schedule) - 1):
                 imgs.append(img.clone())
@@ -961,12 +1042,13 @@ class ConditionalDiffusion(nn.Module):
     # -- DDIM --------------------------------------------------------------------------------
     @torch.no_grad()
     def ddim_sample(self, shape, return_all_timesteps=False, external_cond=None, additional_tgt=None, x_T=None, known=None, resample=1,
-                    guidance_scale=UNSET):
+                    guidance_scale=UNSET, dynamic_threshold=UNSET, threshold_max=UNSET):
         """DD:731-774; accepts (and ignores) additional_tgt so that sample() can reach it.  `x_T` (optional, not in
         the reference) starts the chains from a given tensor instead of a fresh draw (DD:741).  `known` (optional, not in the
         reference): constrained sampling, see `sample`; in the loop's own range ([-1, 1]).  resample > 1 is DDPM's: ValueError."""
         known = self._check_known(shape, known, resample, additional_tgt, ddpm=False)
         w = self._check_guidance(guidance_scale, additional_tgt, external_cond)
+        th = self._check_threshold(dynamic_threshold, threshold_max)
         batch, T, S, eta = shape[0], self.num_timesteps, self.sampling_timesteps, self.ddim_sampling_eta
         times = torch.linspace(-1, T - 1, steps=S + 1)
         times = list(reversed(times.int().tolist()))
@@ -985,15 +1067,15 @@ class ConditionalDiffusion(nn.Module):
             coef = coef.reshape(len(time_pairs), 4, 1).repeat(1, 1, batch).contiguous()
             noise = torch.empty_like(x_T) if (eta > 0 or self.ddim_draw_unused_noise) else None
 
-            def step(i, time, img, out, nxt, guide):
+            def step(i, time, img, out, nxt, guide, thresh=None):
                 last = time_pairs[i][1] < 0
                 if noise is not None and not last:
                     noise.normal_()                                                      # DD:763 (eta == 0: only with ddim_draw_unused_noise)
-                self._ddim_step(tab, time, img, out, None if last else noise, None if last else coef[i], nxt, known, x_T, guide)
+                self._ddim_step(tab, time, img, out, None if last else noise, None if last else coef[i], nxt, known, x_T, guide, thresh)
 
             return [(time, 1) for time, _ in time_pairs], step, None
 
-        return self._run_chain(shape, x_T, plan, return_all_timesteps, external_cond, guidance=w)  # DD:772-773
+        return self._run_chain(shape, x_T, plan, return_all_timesteps, external_cond, guidance=w, threshold=th)  # DD:772-773
 
     # -- DPM-Solver++ (not in the reference) --------------------------------------------------
     def _dpmpp_tables(self, batch, device):
@@ -1015,7 +1097,7 @@ class ConditionalDiffusion(nn.Module):
 
     @torch.no_grad()
     def dpmpp_sample(self, shape, return_all_timesteps=False, external_cond=None, additional_tgt=None, x_T=None, known=None, resample=1,
-                     guidance_scale=UNSET):
+                     guidance_scale=UNSET, dynamic_threshold=UNSET, threshold_max=UNSET):
         """DPM-Solver++ multistep sampling (include/ofd.h, ofd_dpmpp_update): one UNet call per grid point, S - 1 solver steps and a
         final evaluation that returns the clamped prediction.  Signature, x_T, trajectory_stride and the (B, S + 1, C, H, W)
         trajectory are ddim_sample's.  With additional_tgt (FlowDiffuser's target='target') the model's extra output channels are
@@ -1025,25 +1107,26 @@ class ConditionalDiffusion(nn.Module):
         elements already replaced.  resample > 1 is DDPM's: ValueError."""
         known = self._check_known(shape, known, resample, additional_tgt, ddpm=False)
         w = self._check_guidance(guidance_scale, additional_tgt, external_cond)
+        th = self._check_threshold(dynamic_threshold, threshold_max)
 
         def plan(x_T, tab):
             grid, orders, coef = self._dpmpp_tables(shape[0], x_T.device)
             ring = [torch.empty_like(x_T) for _ in range(3)]
 
-            def step(i, t, img, out, nxt, guide):
+            def step(i, t, img, out, nxt, guide, thresh=None):
                 last = i == len(grid) - 1
                 order = 1 if last else orders[i]
                 self._dpmpp_step(tab, t, order, img, out, ring[(i - 1) % 3] if order >= 2 else None,
                                  ring[(i - 2) % 3] if order >= 3 else None, coef[i], last, nxt, None if last else ring[i % 3], known, x_T,
-                                 guide)
+                                 guide, thresh)
 
             return [(t, 1) for t in grid], step, None
 
-        return self._run_chain(shape, x_T, plan, return_all_timesteps, external_cond, additional_tgt, guidance=w)
+        return self._run_chain(shape, x_T, plan, return_all_timesteps, external_cond, additional_tgt, guidance=w, threshold=th)
 
     @torch.no_grad()
     def sample(self, batch_size=16, return_all_timesteps=False, external_cond=None, additional_tgt=None, known=None, resample=1,
-               guidance_scale=UNSET):
+               guidance_scale=UNSET, dynamic_threshold=UNSET, threshold_max=UNSET):
         """DD:776-784, with image_size allowed to be (H, W).  external_cond is normalised once per call (DD:778-779); the loops
         unnormalise what they return.
 
@@ -1058,13 +1141,27 @@ class ConditionalDiffusion(nn.Module):
         call.  None or exactly 1.0 is the conditional model: one model call per step, the unguided entry points, launch for launch.
         Any other w makes two model calls per step on the same x_t, on external_cond and on the null condition (zeros in the
         normalised range), and the fused update uses out_uncond + w (out_cond - out_uncond) as the model output (0 = unconditional,
-        > 1 extrapolates past the conditional model).  It composes with `known` / `resample`."""
+        > 1 extrapolates past the conditional model).  It composes with `known` / `resample`.
+
+        Dynamic thresholding (Imagen, section 2.3; not in the reference): `dynamic_threshold` = p in (0, 1] and
+        `threshold_max` override the constructor's values for this call.  Every step then clamps x_start to [-s, s] and divides by s,
+        with s per sample the `threshold_rank(p, n)`-th smallest |x_start| over the n diffused elements, at least 1 and at most
+        threshold_max (None: unbounded), instead of clamping to [-1, 1]: a prediction that guidance pushes past the range is scaled
+        back rather than saturated.  A step is the UNet call(s), the quantile launches and one fused update launch; the row and the
+        workspace are allocated once per chain.  None is the static clamp: the entry points called today, launch for launch.  It
+        composes with every sampler and objective, `known` / `resample` (held elements stay clamp(known)), `guidance_scale` and
+        `additional_tgt` (the statistic is over the diffused channels)."""
         H, W = self._hw()
         shape = (batch_size, self.channels, H, W)
         ddpm = self.sampler != "dpmpp" and not self.is_ddim_sampling
         known = self._check_known(shape, known, resample, additional_tgt, ddpm=ddpm)
         self._check_guidance(guidance_scale, additional_tgt, external_cond)
-        guide = {} if guidance_scale is UNSET else dict(guidance_scale=guidance_scale)
+        self._check_threshold(dynamic_threshold, threshold_max)
+        per_call = {} if guidance_scale is UNSET else dict(guidance_scale=guidance_scale)      # the optional arguments only when given
+        if dynamic_threshold is not UNSET:
+            per_call["dynamic_threshold"] = dynamic_threshold
+        if threshold_max is not UNSET:
+            per_call["threshold_max"] = threshold_max
         if external_cond is not None:
             external_cond = self.normalize(external_cond)
         if self.sampler == "dpmpp":
@@ -1073,9 +1170,9 @@ class ConditionalDiffusion(nn.Module):
             fn = self.p_sample_loop if not self.is_ddim_sampling else self.ddim_sample
         assert external_cond is None or external_cond.shape[0] == batch_size
         if known is None:
-            return fn(shape, return_all_timesteps=return_all_timesteps, external_cond=external_cond, additional_tgt=additional_tgt, **guide)
+            return fn(shape, return_all_timesteps=return_all_timesteps, external_cond=external_cond, additional_tgt=additional_tgt, **per_call)
         return fn(shape, return_all_timesteps=return_all_timesteps, external_cond=external_cond, known=self.normalize(known),
-                  resample=resample, **guide)
+                  resample=resample, **per_call)
 
     # -- training loss -----------------------------------------------------------------------
     @torch.no_grad()

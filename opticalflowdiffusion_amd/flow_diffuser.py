@@ -8,7 +8,7 @@ with the hooks `experiments/exp_base.py` drives (`log_dict`, `configure_optimize
 with the keys of configurations/algorithm/flow_diffuser.yaml (+ optional `image_size: [H, W]`,
 `sampling_timesteps`, `precision`, `ae_checkpoint`, the sampler keys `sampler`, `solver_order`,
 `sampler_spacing` of ConditionalDiffusion, its classifier-free guidance keys `cond_drop_prob`, `guidance_scale` (target 'flow'
-only), and the `ema_*` keys and `sample_with_ema` of ema.EMA_DEFAULTS, which are not in the reference).
+only), its dynamic thresholding keys `dynamic_threshold`, `threshold_max`, and the `ema_*` keys and `sample_with_ema` of ema.EMA_DEFAULTS, which are not in the reference).
 """
 import os
 
@@ -44,7 +44,7 @@ class _Cfg:
                      flow_weight=0.0, weight_decay=1e-6, is_diffusion=True, latent=False, timesteps=1000,
                      target="joint", ae="px8q8g0m", noiser="image", zero_init=True,
                      sampling_timesteps=None, precision="bf16", augment=True, sampler=None, solver_order=2, sampler_spacing="logsnr",
-                     cond_drop_prob=0.0, guidance_scale=None, **EMA_DEFAULTS)
+                     cond_drop_prob=0.0, guidance_scale=None, dynamic_threshold=None, threshold_max=None, **EMA_DEFAULTS)
 
     def __init__(self, cfg):
         self._d = dict(self._DEFAULTS)
@@ -163,6 +163,9 @@ class FlowDiffuser(EmaMixin, _Base):
         if (cfg.cond_drop_prob or cfg.guidance_scale is not None) and not self.is_diffusion:
             raise ValueError("cond_drop_prob / guidance_scale need a diffusion model: is_diffusion=False is a plain regression, there is "
                              "no chain to guide and no condition dropout to train it for")
+        if (cfg.dynamic_threshold is not None or cfg.threshold_max is not None) and not self.is_diffusion:
+            raise ValueError("dynamic_threshold / threshold_max need a diffusion model: is_diffusion=False is a plain regression, there is "
+                             "no reverse step whose x_start could be thresholded")
         if not self.is_diffusion:                                           # FD:128-129: plain regression cond -> flow
             self.model = self._model
             return
@@ -174,7 +177,8 @@ class FlowDiffuser(EmaMixin, _Base):
             auto_normalize=False, noise_space="image" if cfg.noiser == "image" else "flow",
             timesteps=cfg.timesteps, sampling_timesteps=cfg.sampling_timesteps, min_snr_loss_weight=True,
             sampler=cfg.sampler, solver_order=int(cfg.solver_order), sampler_spacing=cfg.sampler_spacing,   # not in the reference
-            cond_drop_prob=cfg.cond_drop_prob, guidance_scale=cfg.guidance_scale)    # target 'flow' only: ValueError for a warping model
+            cond_drop_prob=cfg.cond_drop_prob, guidance_scale=cfg.guidance_scale,   # target 'flow' only: ValueError for a warping model
+            dynamic_threshold=cfg.dynamic_threshold, threshold_max=cfg.threshold_max)
         if "trajectory_stride" in cfg:                                      # optional key, default = every frame as the reference
             self.model.trajectory_stride = cfg.trajectory_stride
 
@@ -253,19 +257,23 @@ class FlowDiffuser(EmaMixin, _Base):
             known = torch.cat((torch.full((b, self.dim, h, w), float("nan"), dtype=known.dtype, device=known.device), known), dim=1)
         return known
 
-    def sample(self, cond, flow, known_flow=None, resample=1, guidance_scale=UNSET):              # FD:189-215
+    def sample(self, cond, flow, known_flow=None, resample=1, guidance_scale=UNSET, dynamic_threshold=UNSET,
+               threshold_max=UNSET):                                                              # FD:189-215
         """`known_flow` (optional, not in the reference): (B, 2, H, W) in pixels, NaN = free; the returned flow has
         clamp(known_flow / flow_max) at the other elements and the sampler fills in the rest consistently (constrained sampling,
         ConditionalDiffusion.sample).  target 'flow' or 'joint' only.  `resample` as there: DDPM only, `resample` UNet calls per step.
         `guidance_scale` (optional, not in the reference): classifier-free guidance for this call instead of cfg.guidance_scale
-        (ConditionalDiffusion.sample); target 'flow' only; composes with known_flow."""
+        (ConditionalDiffusion.sample); target 'flow' only; composes with known_flow.
+        `dynamic_threshold`, `threshold_max` (optional, not in the reference): dynamic thresholding for this call instead of the cfg
+        keys (ConditionalDiffusion.sample); every target; composes with known_flow and guidance_scale."""
+        thresh = {k: v for k, v in (("dynamic_threshold", dynamic_threshold), ("threshold_max", threshold_max)) if v is not UNSET}
         # a regression model called with autograd on runs the training forward, which has no EMA weights to run on
         if self.is_diffusion or not torch.is_grad_enabled():
             with self._sampling_scope():
-                return self._sample(cond, flow, known_flow, resample, guidance_scale)
-        return self._sample(cond, flow, known_flow, resample, guidance_scale)
+                return self._sample(cond, flow, known_flow, resample, guidance_scale, thresh)
+        return self._sample(cond, flow, known_flow, resample, guidance_scale, thresh)
 
-    def _sample(self, cond, flow, known_flow, resample, guidance_scale=UNSET):
+    def _sample(self, cond, flow, known_flow, resample, guidance_scale=UNSET, thresh=None):
         bsz = flow.shape[0]
         kw = {}
         if known_flow is not None:
@@ -276,6 +284,11 @@ class FlowDiffuser(EmaMixin, _Base):
             if not self.is_diffusion:
                 raise ValueError("guidance_scale needs a diffusion model: is_diffusion=False is a plain regression, there is no chain to guide")
             kw["guidance_scale"] = guidance_scale
+        if thresh:
+            if not self.is_diffusion:
+                raise ValueError("dynamic_threshold / threshold_max need a diffusion model: is_diffusion=False is a plain regression, "
+                                 "there is no reverse step whose x_start could be thresholded")
+            kw.update(thresh)
         if not self.is_diffusion:                                           # FD:204-213
             if self.cfg.target in ["target", "joint"]:
                 samples = self.model(cond, additional_out=True) if self.cfg.target == "target" else self.model(cond)

@@ -19,11 +19,12 @@ class _FrameCfg(_Cfg):
     """configurations/algorithm/frame_generator.yaml, plus `clip` (the trainer's gradient_clip_val, folded into FusedAdam),
     `precision`, `timesteps` and `sampling_timesteps` (DDIM when fewer than `timesteps`), the sampler keys of ConditionalDiffusion
     (`sampler`, `solver_order`, `sampler_spacing`; not in the reference), its classifier-free guidance keys (`cond_drop_prob`,
-    `guidance_scale`; not in the reference) and the `ema_*` keys and `sample_with_ema` (ema.EMA_DEFAULTS)"""
+    `guidance_scale`; not in the reference), its dynamic thresholding keys (`dynamic_threshold`, `threshold_max`; not in the reference)
+    and the `ema_*` keys and `sample_with_ema` (ema.EMA_DEFAULTS)"""
 
     _DEFAULTS = dict(name="frame_generator", image_size=64, lr=7e-5, weight_decay=2e-4, clip=0.0, precision="bf16", timesteps=1000,
                      sampling_timesteps=None, sampler=None, solver_order=2, sampler_spacing="logsnr", cond_drop_prob=0.0, guidance_scale=None,
-                     **EMA_DEFAULTS)
+                     dynamic_threshold=None, threshold_max=None, **EMA_DEFAULTS)
 
 
 class FrameGenerator(EmaMixin, _Base):
@@ -43,7 +44,8 @@ class FrameGenerator(EmaMixin, _Base):
                                                     timesteps=int(cfg.timesteps), sampling_timesteps=cfg.sampling_timesteps,
                                                     sampler=cfg.sampler, solver_order=int(cfg.solver_order),
                                                     sampler_spacing=cfg.sampler_spacing, cond_drop_prob=cfg.cond_drop_prob,
-                                                    guidance_scale=cfg.guidance_scale)
+                                                    guidance_scale=cfg.guidance_scale, dynamic_threshold=cfg.dynamic_threshold,
+                                                    threshold_max=cfg.threshold_max)
 
     def configure_optimizers(self):                                                                  # DA:36-41
         """Adam(lr, weight_decay) as the reference, as the HIP multi-tensor step (optim.FusedAdam)"""
@@ -77,23 +79,26 @@ class FrameGenerator(EmaMixin, _Base):
     log_grad_norm_stat = FlowDiffuser.log_grad_norm_stat                                             # DA:103-125 == FD:367-388
 
     @torch.no_grad()
-    def sample(self, cond, known=None, guidance_scale=UNSET):
+    def sample(self, cond, known=None, guidance_scale=UNSET, dynamic_threshold=UNSET, threshold_max=UNSET):
         """one sampling chain per sample of cond (B, 5, H, W) in [0, 1]; returns (B, 3, H, W) in [0, 1].  `known` (optional, not in
         the reference): (B, 3, H, W) in [0, 1], NaN = free -- inpainting of the next frame (ConditionalDiffusion.sample).
-        `guidance_scale` (optional, not in the reference): classifier-free guidance for this call instead of cfg.guidance_scale."""
+        `guidance_scale` (optional, not in the reference): classifier-free guidance for this call instead of cfg.guidance_scale.
+        `dynamic_threshold`, `threshold_max` (optional, not in the reference): dynamic thresholding for this call instead of the cfg keys."""
         kw = {} if known is None else dict(known=known)
-        if guidance_scale is not UNSET:
-            kw["guidance_scale"] = guidance_scale
+        for key, value in (("guidance_scale", guidance_scale), ("dynamic_threshold", dynamic_threshold), ("threshold_max", threshold_max)):
+            if value is not UNSET:
+                kw[key] = value
         with self._sampling_scope():                                     # the EMA weights when cfg.ema_decay is set
             return self.diffusion_model.sample(batch_size=cond.shape[0], external_cond=cond, **kw)
 
     @torch.no_grad()
-    def rollout(self, batch, known=None, guidance_scale=UNSET):
+    def rollout(self, batch, known=None, guidance_scale=UNSET, dynamic_threshold=UNSET, threshold_max=UNSET):
         """DA:84-100: batch (B, V, 8, H, W); frame k is sampled with cond = batch[:, k, 3:], whose last-frame channels are replaced
         by frame k-1's sample for k >= 1.  Returns (V, B, 3, H, W).  `known` (optional): (B, V, 3, H, W), frame k's `known`;
-        `guidance_scale` (optional): every frame's."""
+        `guidance_scale`, `dynamic_threshold`, `threshold_max` (optional): every frame's."""
         samples = []
-        kw = {} if guidance_scale is UNSET else dict(guidance_scale=guidance_scale)
+        kw = {key: value for key, value in (("guidance_scale", guidance_scale), ("dynamic_threshold", dynamic_threshold),
+                                            ("threshold_max", threshold_max)) if value is not UNSET}
         with self._sampling_scope():                                     # one rebind for the whole rollout
             for k in range(batch.shape[1]):
                 cond = batch[:, k, 3:].clone()
