@@ -304,6 +304,26 @@ int ofd_nan_mse_sum(const float* pred, const float* target, size_t n, double* re
  * result is what ofd_nan_mse_sum left, gout a device scalar */
 int ofd_nan_mse_grad(const float* pred, const float* target, size_t n, const double* result, const float* gout,
                      float* dpred, void* stream);
+/* The same reduction per sample, for a per-sample loss weight (min-SNR weighting, Hang et al., "Efficient Diffusion Training via Min-SNR
+ * Weighting Strategy", 2023; an addition: the reference builds the weight table and leaves it unused, DD:975-980).  pred / target are
+ * contiguous (B, n_per_sample); weight is B floats on the device, or NULL; result is ofd_nan_mse_rows_result_doubles(B) doubles.
+ *   R1. result[2 + 2b] = S_b, the sum over sample b of (float)(p - t) squared in fp32, over the elements where neither side is NaN,
+ *       accumulated in double; result[3 + 2b] = N_b, the number of such elements.  A sample with no such element has S_b = 0, N_b = 0.
+ *   R2. result[0] = sum_b (double)weight[b] * S_b, added in ascending b; result[1] = sum_b N_b.  weight == NULL means every weight is 1.
+ *       The rest of result is scratch.
+ *   R3. No float atomics and a fixed summation order: the same inputs give the same bits in every element of result[0 .. 2 + 2B), run
+ *       to run.  Workgroups are assigned per sample (per-workgroup partials, then a fixed-order total, as ofd_nan_mse_sum), for any
+ *       B >= 1 -- more samples than workgroups included -- and any n_per_sample >= 1.  Loads and stores are 16 bytes wide when
+ *       n_per_sample % 4 == 0 and the pointers are 16-byte aligned, scalar otherwise.
+ *   R4. ofd_nan_mse_rows_grad: dpred[b, i] = 0 where either side is NaN, otherwise
+ *       (float)(2.0 * gout[0] * weight[b] / result[1]) * (p - t): the backward of result[0] / result[1].  A result whose [1] is 1.0 gives
+ *       the gradient of the plain weighted sum result[0].  gout is a device scalar; only result[1] is read.
+ * Argument errors (a NULL pred / target / result / gout / dpred, B < 1, n_per_sample == 0) return before any GPU work. */
+size_t ofd_nan_mse_rows_result_doubles(int B);
+int ofd_nan_mse_rows(const float* pred, const float* target, const float* weight, int B, size_t n_per_sample, double* result,
+                     void* stream);
+int ofd_nan_mse_rows_grad(const float* pred, const float* target, const float* weight, int B, size_t n_per_sample,
+                          const double* result, const float* gout, float* dpred, void* stream);
 
 /* ---------------------------------------------------------------- optimiser (FD:131-134) ---
  * torch.optim.Adam(lr, weight_decay) semantics (L2 in the gradient) preceded by

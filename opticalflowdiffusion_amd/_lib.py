@@ -84,6 +84,9 @@ SIGNATURES = {
     "ofd_range_map": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     "ofd_nan_mse_sum": (c_int, [c_void_p] * 2 + [c_size_t, c_void_p, c_void_p]),
     "ofd_nan_mse_result_doubles": (c_size_t, []),
+    "ofd_nan_mse_rows_result_doubles": (c_size_t, [c_int]),
+    "ofd_nan_mse_rows": (c_int, [c_void_p] * 3 + [c_int, c_size_t, c_void_p, c_void_p]),
+    "ofd_nan_mse_rows_grad": (c_int, [c_void_p] * 3 + [c_int, c_size_t] + [c_void_p] * 4),
     "ofd_adam_chunk": (c_int, []),
     "ofd_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p] + [c_float] * 6 + [c_int, c_void_p]),
     "ofd_adam_step_ema": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p] + [c_float] * 6 + [c_int, c_float, c_float, c_void_p]),

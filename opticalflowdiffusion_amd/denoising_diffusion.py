@@ -41,6 +41,16 @@ OBJECTIVES = {"pred_x0": 0, "pred_noise": 1, "pred_v": 2}     # OFD_PRED_X0 / OF
 
 SAMPLERS = (None, "ddim", "dpmpp")      # None: the reference's rule (DDPM when sampling_timesteps == timesteps, else DDIM)
 SAMPLER_SPACINGS = ("logsnr", "ddim")
+LOSS_WEIGHTINGS = (None, "snr")         # None: the reference's unweighted loss; "snr": sample b weighted by loss_weight[t_b]
+
+
+def loss_by_timestep(t, S, N, num_timesteps, buckets=4):
+    """the unweighted loss per timestep bucket, a (buckets,) tensor like S: bucket k = buckets * t // num_timesteps, its value
+    sum S / sum N over the samples that fall into it, NaN (0 / 0) for an empty bucket.  t (B,) integer, S / N (B,) per-sample sums and
+    counts (ConditionalDiffusion.last_per_sample).  A few B-element torch ops on the tensors' device (CPU tensors too), no host sync."""
+    k = torch.div(t.long() * buckets, num_timesteps, rounding_mode="floor")
+    member = (k.reshape(1, -1) == torch.arange(buckets, device=t.device).reshape(-1, 1)).to(S.dtype)      # (buckets, B)
+    return (member * S.reshape(1, -1)).sum(dim=1) / (member * N.reshape(1, -1).to(S.dtype)).sum(dim=1)
 
 
 def _half_logsnr(ac):
@@ -563,8 +573,17 @@ class ConditionalDiffusion(nn.Module):
                  offset_noise_strength=0.0, min_snr_loss_weight=False, min_snr_gamma=5, conditioned=True,
                  channels=3, noise_space="image", ddim_draw_unused_noise=False, sampler=None, solver_order=2,
                  sampler_spacing="logsnr", cond_drop_prob=0.0, guidance_scale=None, dynamic_threshold=None,
-                 threshold_max=None):
+                 threshold_max=None, loss_weighting=None, loss_by_timestep=False):
         super().__init__()
+        # SNR-weighted loss (min-SNR, Hang et al. 2023): loss_weighting = "snr" makes _loss weight sample b by
+        # loss_weight[t_b], the table min_snr_loss_weight / min_snr_gamma / objective define below (the reference builds it and leaves
+        # it unused, DD:975-980).  loss_by_timestep keeps the level-1 per-sample sums of every _loss call in last_per_sample, for
+        # logging.  Either one runs the per-sample reductions (ofd_nan_mse_rows); None / False is the present path, launch for launch.
+        if loss_weighting not in LOSS_WEIGHTINGS:
+            raise ValueError(f"unknown loss_weighting {loss_weighting!r}: expected one of {LOSS_WEIGHTINGS}")
+        self.loss_weighting = loss_weighting
+        self.loss_by_timestep = bool(loss_by_timestep)
+        self.last_per_sample = None
         # dynamic thresholding (Imagen, section 2.3; not in the reference): dynamic_threshold = p in (0, 1]: every reverse
         # step clamps x_start to [-s, s] and divides by s, s = the p-quantile of |x_start| per sample, at least 1 and at most
         # threshold_max (None: unbounded), instead of clamping to [-1, 1].  None is the static clamp, the present path.
@@ -1242,15 +1261,30 @@ class ConditionalDiffusion(nn.Module):
             return self._loss(model_out[:, :3], target[:, :3], t, target[:, 3:], external_cond, model_out[:, 3:], 0.0)
         return self._loss(model_out[:, :3], target[:, :3], t)
 
-    def _loss(self, image_out, target, t=None, flow_tgt=None, external_cond=None, flow_out=None, additional_weight=None):
+    def _loss(self, image_out, target, t=None, flow_tgt=None, external_cond=None, flow_out=None, additional_weight=None,
+              loss_weighting=UNSET):
         """DD:893-983.  Level 1: NaN-masked squared error of the (warped) image.  With a flow target the
         reference adds pyramid levels 2, 4, 8, 16: the condition image splatted by the PREDICTED flow at
         1/level resolution (`self.model._warp(cond, flow_out, scale=level)`) against the target image
         splatted by zero flow at the same scale, weighted level^4; the loss is the `nanmean` of the
         concatenation of all levels = sum_L L^4 S_L / sum_L N_L.  (The flow-MSE term, the SNR weighting,
         anomaly mode and the prints are disabled / dropped as in the reference, DD:963-980.)  Every piece
-        is a HIP kernel with its own backward: splat (forward, d/dflow), NaN-masked reductions."""
+        is a HIP kernel with its own backward: splat (forward, d/dflow), NaN-masked reductions.
+
+        loss_weighting="snr" (the constructor's, or this call's `loss_weighting`; not in the reference, which leaves DD:975-979
+        commented out) weights sample b by w_b = loss_weight[t_b], gathered on the device: the loss is
+        sum_L L^4 sum_b w_b S_{L,b} / sum_L sum_b N_{L,b} with S_{L,b}, N_{L,b} the per-sample sum and count of level L
+        (ofd_nan_mse_rows), today's value when every w_b is 1.  It needs t.  In that mode, and with loss_by_timestep, every call
+        leaves last_per_sample = (t, S_1, N_1), the level-1 per-sample sums as device tensors; there is no host sync."""
         from .warp import nan_sq_sum
+        weighting = self.loss_weighting if loss_weighting is UNSET else loss_weighting
+        if weighting not in LOSS_WEIGHTINGS:
+            raise ValueError(f"unknown loss_weighting {weighting!r}: expected one of {LOSS_WEIGHTINGS}")
+        if weighting == "snr" and t is None:
+            raise ValueError("loss_weighting='snr' needs t: the weight of a sample is loss_weight[t]")
+        if weighting == "snr" or (self.loss_by_timestep and t is not None):
+            return self._loss_rows(image_out, target, t, self.loss_weight[t].contiguous() if weighting == "snr" else None,
+                                   flow_tgt, external_cond, flow_out)
         if flow_tgt is None:
             return nan_mse(image_out, target, reduction="mean")
         levels = [1, 2, 4, 8, 16]                                                      # DD:896
@@ -1265,6 +1299,31 @@ class ConditionalDiffusion(nn.Module):
             num = num + s * float(level ** 4)                                          # DD:956
             den = den + n
             self.last_levels.append((level, s.detach(), n))
+        return num / den.float()
+
+    def _loss_rows(self, image_out, target, t, weight, flow_tgt, external_cond, flow_out):
+        """_loss through the per-sample reductions: the same tensors compared level by level, each level's weighted sum and count from
+        one ofd_nan_mse_rows call (weight None: unit weights, a NULL pointer)"""
+        from .warp import _rows
+        if tuple(t.shape) != (image_out.shape[0],):
+            raise ValueError(f"t must hold one timestep per sample: got {tuple(t.shape)} for a batch of {image_out.shape[0]}")
+        if flow_tgt is None:
+            loss, _res, S, N = _rows(image_out, target, weight, True)
+            self.last_per_sample = (t, S, N)
+            return loss
+        levels = [1, 2, 4, 8, 16]                                                      # DD:896
+        num, res, S, N = _rows(image_out, target, weight, False)
+        den = res[1]
+        self.last_per_sample = (t, S, N)
+        self.last_levels = [(1, num.detach(), den)]                                    # (level, sum_b w_b S_{L,b}, N_L)
+        for level in levels[1:]:
+            image_out_ = self.model._warp(external_cond, flow_out, scale=level)       # DD:936
+            with torch.no_grad():
+                image_out_tgt = self.model._warp(target, torch.zeros_like(flow_out), scale=level)   # DD:941
+            s, res, _S, _N = _rows(image_out_, image_out_tgt, weight, False)
+            num = num + s * float(level ** 4)                                          # DD:956
+            den = den + res[1]
+            self.last_levels.append((level, s.detach(), res[1]))
         return num / den.float()
 
     def forward(self, img, external_cond=None, *args, **kwargs):

@@ -8,13 +8,14 @@ with the hooks `experiments/exp_base.py` drives (`log_dict`, `configure_optimize
 with the keys of configurations/algorithm/flow_diffuser.yaml (+ optional `image_size: [H, W]`,
 `sampling_timesteps`, `precision`, `ae_checkpoint`, the sampler keys `sampler`, `solver_order`,
 `sampler_spacing` of ConditionalDiffusion, its classifier-free guidance keys `cond_drop_prob`, `guidance_scale` (target 'flow'
-only), its dynamic thresholding keys `dynamic_threshold`, `threshold_max`, and the `ema_*` keys and `sample_with_ema` of ema.EMA_DEFAULTS, which are not in the reference).
+only), its dynamic thresholding keys `dynamic_threshold`, `threshold_max`, its training-loss keys `loss_weighting`,
+`min_snr_loss_weight`, `min_snr_gamma`, `loss_by_timestep`, and the `ema_*` keys and `sample_with_ema` of ema.EMA_DEFAULTS, which are not in the reference).
 """
 import os
 
 import torch
 
-from .denoising_diffusion import UNSET, Unet, ConditionalDiffusion
+from .denoising_diffusion import UNSET, Unet, ConditionalDiffusion, loss_by_timestep
 from .ema import EMA_DEFAULTS, EmaMixin, ema_optimizer_kwargs
 from .warp import warp
 from . import _lib as L
@@ -44,7 +45,8 @@ class _Cfg:
                      flow_weight=0.0, weight_decay=1e-6, is_diffusion=True, latent=False, timesteps=1000,
                      target="joint", ae="px8q8g0m", noiser="image", zero_init=True,
                      sampling_timesteps=None, precision="bf16", augment=True, sampler=None, solver_order=2, sampler_spacing="logsnr",
-                     cond_drop_prob=0.0, guidance_scale=None, dynamic_threshold=None, threshold_max=None, **EMA_DEFAULTS)
+                     cond_drop_prob=0.0, guidance_scale=None, dynamic_threshold=None, threshold_max=None,
+                     loss_weighting=None, min_snr_loss_weight=True, min_snr_gamma=5, loss_by_timestep=False, **EMA_DEFAULTS)
 
     def __init__(self, cfg):
         self._d = dict(self._DEFAULTS)
@@ -67,6 +69,16 @@ class _Cfg:
 
     def __contains__(self, k):
         return k in self._d
+
+
+def timestep_losses(diffusion):
+    """{"train/loss_t0": ..., "train/loss_t3": ...}: the unweighted level-1 loss of the last training call per quarter of the timestep
+    range (denoising_diffusion.loss_by_timestep over ConditionalDiffusion.last_per_sample), NaN for a quarter no sample fell into;
+    device scalars, no host sync"""
+    with torch.no_grad():
+        t, S, N = diffusion.last_per_sample
+        q = loss_by_timestep(t, S, N, diffusion.num_timesteps, 4).float()
+    return {f"train/loss_t{k}": q[k] for k in range(4)}
 
 
 class UnetWithWarp(torch.nn.Module):
@@ -166,6 +178,9 @@ class FlowDiffuser(EmaMixin, _Base):
         if (cfg.dynamic_threshold is not None or cfg.threshold_max is not None) and not self.is_diffusion:
             raise ValueError("dynamic_threshold / threshold_max need a diffusion model: is_diffusion=False is a plain regression, there is "
                              "no reverse step whose x_start could be thresholded")
+        if (cfg.loss_weighting is not None or cfg.loss_by_timestep) and not self.is_diffusion:
+            raise ValueError("loss_weighting / loss_by_timestep need a diffusion model: is_diffusion=False is a plain regression, there is "
+                             "no timestep whose SNR could weight or bucket the loss")
         if not self.is_diffusion:                                           # FD:128-129: plain regression cond -> flow
             self.model = self._model
             return
@@ -175,7 +190,9 @@ class FlowDiffuser(EmaMixin, _Base):
             self._model, cfg.image_size, objective="pred_x0",
             channels={"target": self.dim, "joint": self.dim + 2}.get(cfg.target, 2),
             auto_normalize=False, noise_space="image" if cfg.noiser == "image" else "flow",
-            timesteps=cfg.timesteps, sampling_timesteps=cfg.sampling_timesteps, min_snr_loss_weight=True,
+            timesteps=cfg.timesteps, sampling_timesteps=cfg.sampling_timesteps,
+            min_snr_loss_weight=bool(cfg.min_snr_loss_weight), min_snr_gamma=cfg.min_snr_gamma,   # the table; "snr" is what applies it
+            loss_weighting=cfg.loss_weighting, loss_by_timestep=bool(cfg.loss_by_timestep),       # not in the reference
             sampler=cfg.sampler, solver_order=int(cfg.solver_order), sampler_spacing=cfg.sampler_spacing,   # not in the reference
             cond_drop_prob=cfg.cond_drop_prob, guidance_scale=cfg.guidance_scale,   # target 'flow' only: ValueError for a warping model
             dynamic_threshold=cfg.dynamic_threshold, threshold_max=cfg.threshold_max)
@@ -330,6 +347,8 @@ class FlowDiffuser(EmaMixin, _Base):
             "train/cond_min": c_min, "train/cond_max": c_max, "train/cond_mean": c_mean, "train/cond_std": c_std,
             "train/flow_min": f_min, "train/flow_max": f_max, "train/flow_mean": f_mean, "train/flow_std": f_std,
         })
+        if self.is_diffusion and self.cfg.loss_by_timestep:
+            self.log_dict(timestep_losses(self.model))
         return loss
 
     def _log_image(self, key, images):
@@ -445,7 +464,9 @@ class FlowDiffuser(EmaMixin, _Base):
         if self.is_diffusion and warped_target:                              # FD:351-364: descent direction of the pyramid loss w.r.t. the flow
             with torch.set_grad_enabled(True):
                 pf = p_flows.detach().clone().requires_grad_(True)
-                gl = self.model._loss(warp(cond, None, pf, mode="forward"), tgt_[:, :self.dim], None, flow_, cond, pf / self.flow_max, 0.0)
+                # there is no timestep here: the unweighted pyramid loss, whatever cfg.loss_weighting is
+                gl = self.model._loss(warp(cond, None, pf, mode="forward"), tgt_[:, :self.dim], None, flow_, cond, pf / self.flow_max, 0.0,
+                                      loss_weighting=None)
                 gl.backward()
                 grad_flow = -pf.grad.clone()
             self._log_image("grad_flow", list(torch.chunk(flow_to_image(grad_flow) / 255.0, bsz, dim=0)))

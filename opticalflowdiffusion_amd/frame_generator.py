@@ -11,7 +11,7 @@ from .compat.shims.utils.image_prediction.logging import log_photos
 from .compat.shims.utils.video_prediction.visualization import log_video
 from .denoising_diffusion import UNSET, ConditionalDiffusion, Unet
 from .ema import EMA_DEFAULTS, EmaMixin, ema_optimizer_kwargs
-from .flow_diffuser import FlowDiffuser, _Base, _Cfg
+from .flow_diffuser import FlowDiffuser, _Base, _Cfg, timestep_losses
 from .flow_pred import parse_image_size
 
 
@@ -19,12 +19,13 @@ class _FrameCfg(_Cfg):
     """configurations/algorithm/frame_generator.yaml, plus `clip` (the trainer's gradient_clip_val, folded into FusedAdam),
     `precision`, `timesteps` and `sampling_timesteps` (DDIM when fewer than `timesteps`), the sampler keys of ConditionalDiffusion
     (`sampler`, `solver_order`, `sampler_spacing`; not in the reference), its classifier-free guidance keys (`cond_drop_prob`,
-    `guidance_scale`; not in the reference), its dynamic thresholding keys (`dynamic_threshold`, `threshold_max`; not in the reference)
-    and the `ema_*` keys and `sample_with_ema` (ema.EMA_DEFAULTS)"""
+    `guidance_scale`; not in the reference), its dynamic thresholding keys (`dynamic_threshold`, `threshold_max`; not in the reference),
+    its training-loss keys (`loss_weighting`, `min_snr_loss_weight`, `min_snr_gamma`, `loss_by_timestep`; not in the reference) and the `ema_*` keys and `sample_with_ema` (ema.EMA_DEFAULTS)"""
 
     _DEFAULTS = dict(name="frame_generator", image_size=64, lr=7e-5, weight_decay=2e-4, clip=0.0, precision="bf16", timesteps=1000,
                      sampling_timesteps=None, sampler=None, solver_order=2, sampler_spacing="logsnr", cond_drop_prob=0.0, guidance_scale=None,
-                     dynamic_threshold=None, threshold_max=None, **EMA_DEFAULTS)
+                     dynamic_threshold=None, threshold_max=None, loss_weighting=None, min_snr_loss_weight=False, min_snr_gamma=5,
+                     loss_by_timestep=False, **EMA_DEFAULTS)
 
 
 class FrameGenerator(EmaMixin, _Base):
@@ -45,7 +46,9 @@ class FrameGenerator(EmaMixin, _Base):
                                                     sampler=cfg.sampler, solver_order=int(cfg.solver_order),
                                                     sampler_spacing=cfg.sampler_spacing, cond_drop_prob=cfg.cond_drop_prob,
                                                     guidance_scale=cfg.guidance_scale, dynamic_threshold=cfg.dynamic_threshold,
-                                                    threshold_max=cfg.threshold_max)
+                                                    threshold_max=cfg.threshold_max,
+                                                    min_snr_loss_weight=bool(cfg.min_snr_loss_weight), min_snr_gamma=cfg.min_snr_gamma,
+                                                    loss_weighting=cfg.loss_weighting, loss_by_timestep=bool(cfg.loss_by_timestep))
 
     def configure_optimizers(self):                                                                  # DA:36-41
         """Adam(lr, weight_decay) as the reference, as the HIP multi-tensor step (optim.FusedAdam)"""
@@ -70,6 +73,8 @@ class FrameGenerator(EmaMixin, _Base):
         target, cond = self.split(batch)
         loss = self.diffusion_model(target, cond)
         self.log_dict({"train/loss": loss})
+        if self.cfg.loss_by_timestep:
+            self.log_dict(timestep_losses(self.diffusion_model))
         return loss
 
     def on_before_optimizer_step(self, optimizer):

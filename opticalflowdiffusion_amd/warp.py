@@ -188,8 +188,62 @@ class _NanSqSum(torch.autograd.Function):
         return dp.view(ctx.shape), None
 
 
-def nan_sq_sum(pred, target):
-    """returns (sum of squared errors over non-NaN pairs [differentiable], count [fp64 0-dim])."""
+class _NanMseRows(torch.autograd.Function):
+    """the per-sample reduction (rules R1-R4 of include/ofd.h): value = sum_b weight[b] S_b / sum_b N_b (mean=True) or the weighted sum
+    itself (mean=False), differentiable w.r.t. the prediction, and the result buffer holding S_b, N_b.  weight: (B,) fp32 on the device,
+    or None for unit weights (a NULL pointer: nothing is allocated)."""
+
+    @staticmethod
+    def forward(ctx, pred, target, weight, mean):
+        B = pred.shape[0]
+        p, t = L.f32c(pred).reshape(B, -1), L.f32c(target).reshape(B, -1)
+        w = None if weight is None else L.f32c(weight).reshape(B)
+        res = torch.empty(L.lib().ofd_nan_mse_rows_result_doubles(B), dtype=torch.float64, device=p.device)
+        L.check(L.lib().ofd_nan_mse_rows(L.ptr(p), L.ptr(t), L.ptr(w), B, p.shape[1], L.ptr(res), L.stream()))
+        ctx.save_for_backward(p, t, w, res if mean else None)
+        ctx.shape = pred.shape
+        ctx.mark_non_differentiable(res)
+        return (res[0] / res[1]).float() if mean else res[0].float(), res
+
+    @staticmethod
+    def backward(ctx, gval, _gres):
+        p, t, w, res = ctx.saved_tensors
+        if res is None:                                                     # the weighted sum: count 1, the kernel divides by it
+            res = torch.tensor([0.0, 1.0], dtype=torch.float64, device=p.device)
+        g = L.f32c(gval).reshape(1)
+        dp = torch.empty_like(p)
+        L.check(L.lib().ofd_nan_mse_rows_grad(L.ptr(p), L.ptr(t), L.ptr(w), p.shape[0], p.shape[1], L.ptr(res), L.ptr(g), L.ptr(dp),
+                                              L.stream()))
+        return dp.view(ctx.shape), None, None, None
+
+
+def _rows(pred, target, weight, mean):
+    """(value, result buffer, S, N) of the per-sample reduction; S, N: fp64 (B,) views of the buffer"""
+    L.require_gpu(pred, target, weight)
+    if pred.dim() < 1 or pred.shape != target.shape or pred.shape[0] < 1 or pred[0].numel() < 1:
+        raise ValueError(f"per-sample reduction: pred and target must be equal (B, ...) shapes, got {tuple(pred.shape)} and "
+                         f"{tuple(target.shape)}")
+    if weight is not None and tuple(weight.shape) != (pred.shape[0],):
+        raise ValueError(f"weight must hold one value per sample: got {tuple(weight.shape)} for a batch of {pred.shape[0]}")
+    value, res = _NanMseRows.apply(pred, target, weight, mean)
+    B = pred.shape[0]
+    return value, res, res[2:2 + 2 * B:2], res[3:3 + 2 * B:2]
+
+
+def nan_mse_rows(pred, target, weight=None):
+    """(loss, S, N) over (B, ...) tensors: S[b], N[b] the squared-error sum and the count of sample b over the pairs without a NaN (fp64
+    (B,), not differentiable), loss = sum_b weight[b] S[b] / sum_b N[b] (fp32, differentiable w.r.t. pred).  weight: (B,) on the
+    device, None = ones.  One fused reduction and a fixed-order total: no host sync, the same bits run to run."""
+    loss, _res, S, N = _rows(pred, target, weight, True)
+    return loss, S, N
+
+
+def nan_sq_sum(pred, target, weight=None):
+    """returns (sum of squared errors over non-NaN pairs [differentiable], count [fp64 0-dim]).  With `weight` ((B,) on the device)
+    the tensors are (B, ...) and the sum is sum_b weight[b] S_b, from the per-sample kernels."""
+    if weight is not None:
+        s, res, _S, _N = _rows(pred, target, weight, False)
+        return s, res[1]
     L.require_gpu(pred, target)
     s, res = _NanSqSum.apply(pred, target)
     return s, res[1]
