@@ -103,6 +103,23 @@ int ofd_pyramid_charbonnier_bwd(const float* Tin, const float* Ttg, const double
 int ofd_warp_prep(const float* first, float* ten_in, int B, int C, int H, int W, int square, void* stream);
 int ofd_warp_holes(const float* splat, float* img, int B, int C, int Ho, int Wo, int mode, int set_nans, void* stream);
 
+/* Push-pull hole filling (Gortler et al., "The Lumigraph", 1996, section 3.4).  An addition: the reference's fill_holes_nan
+ * (WP:273-276) only writes NaN where nothing was splatted, nothing fills the holes.  All arithmetic fp32.
+ * x: (B,C,H,W), weight: (B,1,H,W) or NULL (= 1), out: (B,C,H,W), never NaN.  premultiplied == 0: x is a colour image and weight its
+ * confidence; != 0: x is the splat accumulator sum(colour * splat weight) and weight the accumulated splat weight, i.e. channels :C
+ * and C of ofd_splat_fwd's result.  Layout: x and weight are two contiguous tensors, EXCEPT when weight == x + C*H*W: then they
+ * are read in place as the planes of one contiguous (B,C+1,H,W) splat result (sample stride (C+1)*H*W for both; no copy is needed).
+ *   level 0  bad = any channel of x non-finite, or weight NaN or <= 0; w0 = bad ? 0 : min(gain * weight, 1);
+ *            c0 = (premultiplied ? x / weight : x) * w0, 0 where bad.
+ *   pull     H' = ceil(H / 2): S_w, S_c = 2x2 block sums (children outside the level count 0); w' = min(S_w, 1), c' = S_c / max(S_w, 1);
+ *            up to the 1x1 level, f = w > 0 ? c / w : 0 there (a sample without a valid pixel comes back as zeros).
+ *   push     f_l = c_l + (1 - w_l) * up2(f_{l+1}), up2 = x2 bilinear, half-pixel centres (taps 9/16, 3/16, 3/16, 1/16), edge-clamped.
+ * Three launches for any size, no atomics, fixed summation order: the same input gives the same bits.  gain: finite, >= 1.
+ * workspace: ofd_pushpull_workspace(B,C,H,W) bytes (0 for a bad shape), 16-byte aligned; a smaller one is an error. */
+size_t ofd_pushpull_workspace(int B, int C, int H, int W);
+int ofd_pushpull_fill(const float* x, const float* weight, float* out, void* workspace, size_t workspace_bytes,
+                      int B, int C, int H, int W, int premultiplied, float gain, void* stream);
+
 /* ------------------------------------------------------------ grid_sample warp (WP:95-119) -
  * second: (B,C,H,W), flow: (B,2,H,W) exactly as handed to the reference's warp(mode='backward'):
  * after its flip(1) channel 1 displaces x and channel 0 displaces y (WP:105-106).

@@ -9,7 +9,7 @@ with the keys of configurations/algorithm/flow_diffuser.yaml (+ optional `image_
 `sampling_timesteps`, `precision`, `ae_checkpoint`, the sampler keys `sampler`, `solver_order`,
 `sampler_spacing` of ConditionalDiffusion, its classifier-free guidance keys `cond_drop_prob`, `guidance_scale` (target 'flow'
 only), its dynamic thresholding keys `dynamic_threshold`, `threshold_max`, its training-loss keys `loss_weighting`,
-`min_snr_loss_weight`, `min_snr_gamma`, `loss_by_timestep`, and the `ema_*` keys and `sample_with_ema` of ema.EMA_DEFAULTS, which are not in the reference).
+`min_snr_loss_weight`, `min_snr_gamma`, `loss_by_timestep`, `log_animation` (N > 0: validation_step also logs an N-frame `animate` strip), and the `ema_*` keys and `sample_with_ema` of ema.EMA_DEFAULTS, which are not in the reference).
 """
 import os
 
@@ -46,7 +46,8 @@ class _Cfg:
                      target="joint", ae="px8q8g0m", noiser="image", zero_init=True,
                      sampling_timesteps=None, precision="bf16", augment=True, sampler=None, solver_order=2, sampler_spacing="logsnr",
                      cond_drop_prob=0.0, guidance_scale=None, dynamic_threshold=None, threshold_max=None,
-                     loss_weighting=None, min_snr_loss_weight=True, min_snr_gamma=5, loss_by_timestep=False, **EMA_DEFAULTS)
+                     loss_weighting=None, min_snr_loss_weight=True, min_snr_gamma=5, loss_by_timestep=False, log_animation=0,
+                     **EMA_DEFAULTS)
 
     def __init__(self, cfg):
         self._d = dict(self._DEFAULTS)
@@ -129,6 +130,27 @@ def ae_checkpoint_path(cfg):
     outputs/loaded_checkpoints/diffusion_control/<ae>/model.ckpt relative to the working directory (FD:84-85)"""
     p = cfg.ae_checkpoint if "ae_checkpoint" in cfg else None
     return p if p else os.path.join("outputs", "loaded_checkpoints", "diffusion_control", str(cfg.ae), "model.ckpt")
+
+
+# `FlowDiffuser.animate` hands the engine at most this many pixels (samples x H x W) per warp call: a quarter of the splat's
+# B*H*W < 2^31 limit, 4.3 GB of fp32 accumulators, frames and pyramid at three channels
+ANIMATE_MAX_PIXELS = 1 << 28
+
+
+def animation_times(frames=8, times=None):
+    """the frame times of `FlowDiffuser.animate` as a list of floats: `times` if given (a non-empty sequence of finite numbers), else
+    k / frames for k = 1..frames.  Host logic: no engine call."""
+    if times is not None:
+        try:
+            out = [float(t) for t in times]
+        except TypeError:
+            raise ValueError(f"animate: times must be a sequence of numbers, got {times!r}")
+        if not out or not all(t == t and abs(t) != float("inf") for t in out):
+            raise ValueError(f"animate: times must be a non-empty sequence of finite numbers, got {times!r}")
+        return out
+    if isinstance(frames, bool) or not isinstance(frames, int) or frames < 1:
+        raise ValueError(f"animate: frames must be a positive integer, got {frames!r}")
+    return [k / frames for k in range(1, frames + 1)]
 
 
 class FlowDiffuser(EmaMixin, _Base):
@@ -324,6 +346,44 @@ class FlowDiffuser(EmaMixin, _Base):
             samples = warp(img, None, flow[:, -1], mode="forward")
         return samples, flow
 
+    def animate(self, cond, flow=None, frames=8, times=None, fill_holes=True, fill_gain=1.0, **sample_kw):
+        """A short clip from a still (not in the reference, which stops at one raw splat): (video, flow).
+        cond: (B, 3, H, W) as for `sample` (2 * img - 1).  flow: (B, 2, H, W) in units of flow_max, i.e. the last trajectory frame of
+        what `sample` returns; None samples it with `self.sample(cond, ..., **sample_kw)` (known_flow, guidance_scale,
+        dynamic_threshold, ...; the EMA scope applies as there; a diffusion model only).  With a flow given no UNet call is made.
+        times: the frame times, default k / frames for k = 1..frames; any sequence of finite floats (0 reproduces cond, values above 1
+        extrapolate).  Frame k is the forward warp of cond[:, :3] by flow * (times[k] * flow_max); all frames go through the engine as
+        one batch of B * frames samples -- one prep, one splat, one fill -- in chunks of at most ANIMATE_MAX_PIXELS pixels.
+        video: (B, frames, 3, H, W) in cond's range; fill_holes=True: the push-pull filled splat (`warp(..., fill_holes=True,
+        fill_gain=fill_gain)`), no NaN; False: the plain normalised splat (warp_style="linear") with NaN holes.  Forward only."""
+        if self.latent:
+            raise ValueError("animate: latent=True is not supported (every frame would have to be decoded by the Autoencoder)")
+        times = animation_times(frames, times)
+        if not torch.is_tensor(cond) or cond.dim() != 4 or cond.shape[1] < 3:
+            raise ValueError(f"animate: cond must be (B, 3, H, W), got {tuple(cond.shape) if torch.is_tensor(cond) else type(cond).__name__}")
+        B, _, H, W = cond.shape
+        L.require_gpu(cond, flow)
+        with torch.no_grad():
+            if flow is None:
+                if not self.is_diffusion:
+                    raise ValueError("animate: flow=None needs a diffusion model to sample the flow from; pass the flow")
+                _samples, fl = self.sample(cond, cond.new_zeros(B, 2, H, W), **sample_kw)
+                flow = fl[-1] if isinstance(fl, (list, tuple)) else fl[:, -1]
+            elif sample_kw:
+                raise ValueError(f"animate: {sorted(sample_kw)} are sampling arguments; with a flow given nothing is sampled")
+            if tuple(flow.shape) != (B, 2, H, W):
+                raise ValueError(f"animate: flow must be (B, 2, H, W) = {(B, 2, H, W)}, got {tuple(flow.shape)}")
+            flow = flow.detach().float()
+            n = len(times)
+            t = torch.tensor(times, dtype=torch.float32, device=cond.device).view(1, n, 1, 1, 1)
+            flows = (flow[:, None] * (t * float(self.flow_max))).reshape(B * n, 2, H, W)
+            imgs = cond[:, None, :3].detach().float().expand(B, n, 3, H, W).reshape(B * n, 3, H, W)
+            kw = dict(fill_holes=True, fill_gain=fill_gain) if fill_holes else dict(warp_style="linear")
+            per = max(1, ANIMATE_MAX_PIXELS // (H * W))
+            parts = [warp(imgs[i:i + per], None, flows[i:i + per], mode="forward", **kw) for i in range(0, B * n, per)]
+            video = parts[0] if len(parts) == 1 else torch.cat(parts)
+        return video.view(B, n, 3, H, W), flow
+
     @staticmethod
     def _batch_stats(x):
         """(min, max, mean, mean(std(x, dim=0))) of a (B, ...) tensor as 0-dim views of one 4-float result: what FD:218-235 logs, in one pass
@@ -437,6 +497,9 @@ class FlowDiffuser(EmaMixin, _Base):
                 self._log_image("dec_gt", chunk(self.ae(img, flow)))
             else:
                 self._log_image("samples", chunk(samples))
+            if self.cfg.log_animation and self.is_diffusion and not self.latent:    # opt-in, not in the reference: N hole-free frames
+                video, _ = self.animate(cond, p_flows / self.flow_max, frames=int(self.cfg.log_animation))
+                self._log_image("animation", chunk(torch.clamp((torch.cat(video.unbind(1), dim=-1) + 1.0) * 0.5, 0.0, 1.0)))
 
             if self.is_diffusion and warped_target:                          # FD:317-338: strips of every 50th step
                 if self.latent:                                              # FD:316-320: every strip frame decoded

@@ -63,10 +63,70 @@ class _WarpForward(torch.autograd.Function):
         return g_first, g_flow, None, None, None, None, None, None
 
 
-def warp_forward_flow(first, second, flow, scale=1, set_nans=True, get_variance=False, offset=[0, 0], warp_style="sum"):
-    """WP:121-156."""
+_fill_ws = {}                                          # device index -> the fill's pyramid workspace (grown on demand)
+
+
+def _pushpull(x, weight, B, C, H, W, premultiplied, gain):
+    """ofd_pushpull_fill on device pointers `x`, `weight` (None = confidence 1) of fp32 planes laid out as include/ofd.h says"""
+    lib = L.lib()
+    out = torch.empty(B, C, H, W, dtype=torch.float32, device=x.device)
+    nbytes = lib.ofd_pushpull_workspace(B, C, H, W)
+    ws = _fill_ws.get(x.device.index)
+    if ws is None or ws.numel() < nbytes:
+        ws = _fill_ws[x.device.index] = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    L.check(lib.ofd_pushpull_fill(L.ptr(x), L.ptr(weight), L.ptr(out), L.ptr(ws), ws.numel(), B, C, H, W, int(bool(premultiplied)),
+                                  float(gain), L.stream()))
+    return out
+
+
+def fill_holes(img, weight=None, premultiplied=False, gain=1.0):
+    """Push-pull hole filling (Gortler et al. 1996; not in the reference, whose fill_holes_nan only marks the holes): a new fp32
+    (B, C, H, W) tensor without NaN.  img: (B, C, H, W); weight: (B, 1, H, W) confidence, None = 1.  A pixel is a hole where any channel
+    of img is non-finite or its weight is NaN or <= 0; confidence = min(gain * weight, 1), gain >= 1 (a large gain: trust every
+    touched pixel, fill only true holes).  premultiplied=True: img holds colour * weight sums and weight their weights, as the forward
+    splat accumulates them.  Pixels of confidence 1 keep their colour, the others are blended with (holes: replaced by) a
+    confidence-weighted average of their surroundings; a sample with no valid pixel comes back as zeros.  Semantics: include/ofd.h
+    (`ofd_pushpull_fill`).  Forward only: the result carries no grad_fn.  Inputs are not modified; the same input gives the same bits."""
+    L.require_gpu(img, weight)
+    if img.dim() != 4 or img.numel() == 0:
+        raise ValueError(f"fill_holes: img must be a non-empty (B, C, H, W) tensor, got {tuple(img.shape)}")
+    B, C, H, W = img.shape
+    if weight is not None and tuple(weight.shape) != (B, 1, H, W):
+        raise ValueError(f"fill_holes: weight must be (B, 1, H, W) = {(B, 1, H, W)}, got {tuple(weight.shape)}")
+    if not gain >= 1.0 or gain == float("inf"):
+        raise ValueError(f"fill_holes: gain must be finite and >= 1, got {gain}")
+    with torch.no_grad():
+        img = L.f32c(img.detach())
+        weight = None if weight is None else L.f32c(weight.detach())
+        return _pushpull(img, weight, B, C, H, W, premultiplied, gain)
+
+
+def _warp_forward_filled(first, flow, scale, ox, oy, gain):
+    """prep -> splat -> push-pull fill of the splat's accumulators, read in place: three launch groups, no `ofd_warp_holes` pass"""
+    first, flow = L.f32c(first), L.f32c(flow)
+    B, C, H, W = first.shape
+    ten_in = torch.empty(B, C + 1, H, W, dtype=torch.float32, device=first.device)
+    L.check(L.lib().ofd_warp_prep(L.ptr(first), L.ptr(ten_in), B, C, H, W, 0, L.stream()))
+    ten_out = splat_forward(ten_in, flow, scale, ox, oy)
+    Ho, Wo = ten_out.shape[-2:]
+    return _pushpull(ten_out, ten_out[:, C:], B, C, Ho, Wo, True, gain)       # weight == x + C*Ho*Wo: the (B,C+1,Ho,Wo) layout
+
+
+def warp_forward_flow(first, second, flow, scale=1, set_nans=True, get_variance=False, offset=[0, 0], warp_style="sum",
+                      fill_holes=False, fill_gain=1.0):
+    """WP:121-156.  fill_holes=True (not in the reference): the splat's accumulators go through the push-pull fill (`fill_holes`,
+    premultiplied, gain=fill_gain) instead of the holes pass: normalised colour whatever `warp_style`, no NaN, not differentiable."""
     L.require_gpu(first, flow)
     offset = [o % scale for o in offset]
+    if fill_holes:
+        if get_variance:
+            raise ValueError("warp: fill_holes=True does not combine with get_variance=True (a variance has no colour to fill in)")
+        if first.requires_grad or flow.requires_grad:
+            raise L.OfdError("warp: fill_holes=True is forward only (the push-pull fill has no backward pass): detach the inputs")
+        if not fill_gain >= 1.0 or fill_gain == float("inf"):
+            raise ValueError(f"warp: fill_gain must be finite and >= 1, got {fill_gain}")
+        with torch.no_grad():
+            return _warp_forward_filled(first, flow, scale, offset[0], offset[1], fill_gain)
     linear = warp_style != "sum"
     img = _WarpForward.apply(first, flow, scale, offset[0], offset[1], bool(set_nans) and not get_variance, linear, False)
     if get_variance:                                  # WP:142-152: splat(x^2) - splat(x)^2
