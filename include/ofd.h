@@ -557,6 +557,10 @@ int ofd_gn_silu_backward(const void* g, const void* h, const float* a, const flo
 int ofd_affine_silu(const void* h, const float* a, const float* s, void* out, int B, int H, int W, int C, void* stream);
 int ofd_layernorm_c_backward(const void* x, const float* g, const void* dy, void* dx, float* dg, size_t npix, int C,
                              float eps, int accumulate, void* stream);
+/* the same with `extra` [npix][C] bf16 (may be NULL: then exactly ofd_layernorm_c_backward) added to dx in fp32 before the one rounding:
+ * the gradient of a residual branch around the LayerNorm (PreNorm inside Residual: extra = dy of the block).  C = 64, 128, 256, 512. */
+int ofd_layernorm_c_backward_residual(const void* x, const float* g, const void* dy, const void* extra, void* dx, float* dg, size_t npix,
+                                      int C, float eps, int accumulate, void* stream);
 /* DD:361 forward: x NHWC bf16 (C channels) -> out NCHW fp32 (out_dim <= 16), with the glue epilogue of ofd_unet_set_glue (out_mode, out_div) */
 int ofd_final_conv(const void* x, const float* w, const float* b, float* out, int B, int H, int W, int C, int out_dim, int out_mode,
                    float out_div, void* stream);
@@ -578,6 +582,48 @@ size_t ofd_la_bwd_workspace_floats(int B, int n);
 int ofd_linear_attention_core(const void* qkv, void* out, float* ctx, float* ml, float* workspace, int B, int n, void* stream);
 int ofd_linear_attention_core_backward(const void* qkv, const void* dout, const float* ctx, const float* ml, void* dqkv,
                                        float* workspace, int B, int n, void* stream);
+/* --------------------------------------------------- fused LinearAttention block, one call at a time ------
+ * The executor's own launches of a Residual(PreNorm(LinearAttention)) block (DD:81-87, DD:127-135, DD:216-244), exported so that one
+ * block can be run and checked alone.  x / y / xn / o2 / dy / dx: [B][n][C] bf16 (pixel-major), C = 64 or 128 as stated per call.
+ * Any n >= 1 is legal in every call below (rows are whole 16-byte units for every C; pixels past the end of a partial 32-pixel tile
+ * are read from a clamped row and masked).  Pointers named x, y and every weight pointer must be 16-byte aligned.
+ *
+ * Weights in fragment layout (bf16), made by ofd_la_weight_prep from the fp32 parameters wqkv [384][C] (q | k | v rows), g [C] and
+ * wout [C][128]:
+ *     wq    [C/8][128][8]   128*C elements   = Wq  . diag(g)     (g == NULL: the plain rows -- what the training form takes)
+ *     wkv   [C/8][256][8]   256*C elements   = Wkv . diag(g)
+ *     woutp [8][2][C][8]    128*C elements   (wout == NULL / woutp == NULL: not written)
+ *   No kernel reads past those counts: the buffers need no slack.
+ * Scratch: partial = ofd_la_workspace_floats(B, n) floats; ctxfrag = B * 4096 bf16 (8 KB per sample: the combined context of the four
+ *   heads as MFMA operand fragments).  Kept for the backward: ctx [B*4][32][32] and ml [B*4][64] fp32, as ofd_linear_attention_core.
+ *
+ * ofd_linear_attention_block (C = 64, 128): inference form; y = x + LayerNorm_g2(to_out.0(attention(LayerNorm_g(x)))); wq / wkv carry g.
+ *   Three launches, no atomics: the same inputs give the same bits.
+ * ofd_linear_attention_block_train (C = 64): the training forward; wq / wkv are the PLAIN weights (g == NULL), g_pre is applied to the
+ *   LayerNorm output.  Also writes the tape: xn [B][n][64], channels 128..383 (k | v) of qkv [B][n][384] -- channels 0..127 are NOT
+ *   written --, o2 [B][n][64] (to_out.0's output), ctx, ml.
+ * ofd_linear_attention_core_proj (C = 128, the training forward at that width): ofd_linear_attention_core with the to_out.0 1x1 conv
+ *   on the head-output tile: o2 [B][n][C] = wo . out + bo; wo from ofd_conv_weight_prep(Cout = C, Cin = 128, ksize 1): [16][C][8];
+ *   bo fp32 [C] or NULL; out may be NULL (the head outputs are then not written).
+ * ofd_linear_attention_block_backward (C = 64): the core backward with to_out.0 and to_qkv folded in.  do2 [B][n][64] is the gradient
+ *   of the to_out.0 OUTPUT; qkv is read in channels 128..383 only (q is recomputed from xn); dxn [B][n][64] is written;
+ *   dw_acc [64][384], dwo_acc [128][64] and dbo [64] (fp32) are ADDED to -- zero them first; ofd_conv_wgrad_finish turns the two
+ *   accumulators into OIHW gradients.  Weights (bf16): wq_fwd = ofd_conv_weight_prep(to_qkv: Cout 384, Cin 64, ksize 1) [8][384][8],
+ *   wqkv_t = ofd_conv_dgrad_weight_prep of it [48][64][8], wo_fwd = ofd_conv_weight_prep(to_out.0: Cout 64, Cin 128) [16][64][8],
+ *   wo_t = ofd_conv_dgrad_weight_prep of it [8][128][8].  workspace: ofd_la_bwd_workspace_floats(B, n) floats. */
+int ofd_la_weight_prep(const float* wqkv, const float* g, const float* wout, void* wq, void* wkv, void* woutp, int C, void* stream);
+int ofd_linear_attention_block(const void* x, const void* wq, const void* wkv, const void* woutp, const float* bias, const float* g2,
+                               float* partial, void* ctxfrag, void* y, int B, int n, int C, float eps_pre, float eps_post, void* stream);
+int ofd_linear_attention_block_train(const void* x, const void* wq, const void* wkv, const void* woutp, const float* bias,
+                                     const float* g_pre, const float* g2, float* partial, void* ctxfrag, float* ctx, float* ml,
+                                     void* xn, void* qkv, void* o2, void* y, int B, int n, int C, float eps_pre, float eps_post,
+                                     void* stream);
+int ofd_linear_attention_core_proj(const void* qkv, void* out, float* ctx, float* ml, float* workspace, const void* wo,
+                                   const float* bo, void* o2, int C, int B, int n, void* stream);
+int ofd_linear_attention_block_backward(const void* qkv, const void* do2, const float* ctx, const float* ml, float* workspace,
+                                        const void* xn, const void* wqkv_t, float* dw_acc, void* dxn, const void* wo_fwd,
+                                        const void* wo_t, float* dwo_acc, float* dbo, const void* wq_fwd, int C, int B, int n,
+                                        void* stream);
 int ofd_flash_attention(const void* qkv, void* out, float* lse, int B, int n, void* stream);
 int ofd_flash_attention_backward(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
                                  float* delta, int B, int n, void* stream);

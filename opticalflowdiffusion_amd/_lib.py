@@ -141,6 +141,12 @@ SIGNATURES = {
     "ofd_la_bwd_workspace_floats": (c_size_t, [c_int, c_int]),
     "ofd_linear_attention_core": (c_int, [c_void_p] * 5 + [c_int, c_int, c_void_p]),
     "ofd_linear_attention_core_backward": (c_int, [c_void_p] * 6 + [c_int, c_int, c_void_p]),
+    "ofd_la_weight_prep": (c_int, [c_void_p] * 6 + [c_int, c_void_p]),
+    "ofd_linear_attention_block": (c_int, [c_void_p] * 9 + [c_int] * 3 + [c_float, c_float, c_void_p]),
+    "ofd_linear_attention_block_train": (c_int, [c_void_p] * 15 + [c_int] * 3 + [c_float, c_float, c_void_p]),
+    "ofd_linear_attention_core_proj": (c_int, [c_void_p] * 8 + [c_int] * 3 + [c_void_p]),
+    "ofd_linear_attention_block_backward": (c_int, [c_void_p] * 14 + [c_int] * 3 + [c_void_p]),
+    "ofd_layernorm_c_backward_residual": (c_int, [c_void_p] * 6 + [c_size_t, c_int, c_float, c_int, c_void_p]),
     "ofd_flash_attention": (c_int, [c_void_p] * 3 + [c_int, c_int, c_void_p]),
     "ofd_flash_attention_backward": (c_int, [c_void_p] * 6 + [c_int, c_int, c_void_p]),
     "ofd_unet_train_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),

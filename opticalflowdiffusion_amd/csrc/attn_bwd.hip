@@ -245,6 +245,57 @@ extern "C" int ofd_linear_attention_core_backward(const void* qkv, const void* d
     OFD_CHECK_ARG(qkv && dout && ctx && ml && dqkv && workspace && B > 0 && n > 0, "linear_attention_core_backward: bad argument");
     return k_linear_attention_core_bwd((const bf16_t*)qkv, (const bf16_t*)dout, ctx, ml, (bf16_t*)dqkv, workspace, B, n, (hipStream_t)stream);
 }
+// ---- the fused LinearAttention block, one executor call per entry point (unet.hip linattn, unet_train.hip linattn_backward)
+static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+extern "C" int ofd_la_weight_prep(const float* wqkv, const float* g, const float* wout, void* wq, void* wkv, void* woutp, int C, void* stream) {
+    OFD_CHECK_ARG(wqkv && wq && wkv && (woutp == nullptr) == (wout == nullptr), "la_weight_prep: null argument (wout and woutp go together)");
+    OFD_CHECK_ARG(C == 64 || C == 128, "la_weight_prep: C=%d (64 or 128)", C);
+    OFD_CHECK_ARG(al16(wq) && al16(wkv) && al16(woutp), "la_weight_prep: weight buffers must be 16-byte aligned");
+    return k_la_weight_prep(wqkv, g, wout, (bf16_t*)wq, (bf16_t*)wkv, (bf16_t*)woutp, C, (hipStream_t)stream);
+}
+extern "C" int ofd_linear_attention_block(const void* x, const void* wq, const void* wkv, const void* woutp, const float* bias, const float* g2,
+                                          float* partial, void* ctxfrag, void* y, int B, int n, int C, float eps_pre, float eps_post, void* stream) {
+    OFD_CHECK_ARG(x && wq && wkv && woutp && bias && g2 && partial && ctxfrag && y, "linear_attention_block: null argument");
+    OFD_CHECK_ARG(C == 64 || C == 128, "linear_attention_block: C=%d (64 or 128)", C);
+    OFD_CHECK_ARG(B > 0 && n > 0, "linear_attention_block: B=%d n=%d", B, n);
+    OFD_CHECK_ARG(al16(x) && al16(y) && al16(wq) && al16(wkv) && al16(woutp) && al16(ctxfrag), "linear_attention_block: x, y, ctxfrag and the weights must be 16-byte aligned");
+    return k_linear_attention_fused((const bf16_t*)x, (const bf16_t*)wq, (const bf16_t*)wkv, (const bf16_t*)woutp, bias, g2, partial, (bf16_t*)ctxfrag,
+                                    (bf16_t*)y, B, n, C, eps_pre, eps_post, (hipStream_t)stream);
+}
+extern "C" int ofd_linear_attention_block_train(const void* x, const void* wq, const void* wkv, const void* woutp, const float* bias, const float* g_pre,
+                                                const float* g2, float* partial, void* ctxfrag, float* ctx, float* ml, void* xn, void* qkv, void* o2,
+                                                void* y, int B, int n, int C, float eps_pre, float eps_post, void* stream) {
+    OFD_CHECK_ARG(x && wq && wkv && woutp && bias && g_pre && g2 && partial && ctxfrag && ctx && ml && xn && qkv && o2 && y,
+                  "linear_attention_block_train: null argument");
+    OFD_CHECK_ARG(C == 64, "linear_attention_block_train: C=%d (64)", C);
+    OFD_CHECK_ARG(B > 0 && n > 0, "linear_attention_block_train: B=%d n=%d", B, n);
+    OFD_CHECK_ARG(al16(x) && al16(y) && al16(wq) && al16(wkv) && al16(woutp) && al16(ctxfrag) && al16(xn) && al16(qkv) && al16(o2),
+                  "linear_attention_block_train: x, y, xn, qkv, o2, ctxfrag and the weights must be 16-byte aligned");
+    return k_linear_attention_fused_train((const bf16_t*)x, (const bf16_t*)wq, (const bf16_t*)wkv, (const bf16_t*)woutp, bias, g_pre, g2, partial,
+                                          (bf16_t*)ctxfrag, ctx, ml, (bf16_t*)xn, (bf16_t*)qkv, (bf16_t*)o2, (bf16_t*)y, B, n, C, eps_pre, eps_post,
+                                          (hipStream_t)stream);
+}
+extern "C" int ofd_linear_attention_core_proj(const void* qkv, void* out, float* ctx, float* ml, float* workspace, const void* wo, const float* bo,
+                                              void* o2, int C, int B, int n, void* stream) {
+    OFD_CHECK_ARG(qkv && ctx && ml && workspace && wo && o2, "linear_attention_core_proj: null argument");
+    OFD_CHECK_ARG(C == 128, "linear_attention_core_proj: C=%d (128: the only width the executor runs this form at)", C);
+    OFD_CHECK_ARG(B > 0 && n > 0, "linear_attention_core_proj: B=%d n=%d", B, n);
+    OFD_CHECK_ARG(al16(qkv) && al16(out) && al16(wo) && al16(o2) && al16(bo), "linear_attention_core_proj: qkv, out, o2, wo and bo must be 16-byte aligned");
+    return k_linear_attention_core((const bf16_t*)qkv, workspace, ctx, (bf16_t*)out, B, n, (hipStream_t)stream, ml, (const bf16_t*)wo, bo, (bf16_t*)o2, C);
+}
+extern "C" int ofd_linear_attention_block_backward(const void* qkv, const void* do2, const float* ctx, const float* ml, float* workspace, const void* xn,
+                                                   const void* wqkv_t, float* dw_acc, void* dxn, const void* wo_fwd, const void* wo_t, float* dwo_acc,
+                                                   float* dbo, const void* wq_fwd, int C, int B, int n, void* stream) {
+    OFD_CHECK_ARG(qkv && do2 && ctx && ml && workspace && xn && wqkv_t && dw_acc && dxn && wo_fwd && wo_t && dwo_acc && dbo && wq_fwd,
+                  "linear_attention_block_backward: null argument");
+    OFD_CHECK_ARG(C == 64, "linear_attention_block_backward: C=%d (64)", C);
+    OFD_CHECK_ARG(B > 0 && n > 0, "linear_attention_block_backward: B=%d n=%d", B, n);
+    OFD_CHECK_ARG(al16(qkv) && al16(do2) && al16(xn) && al16(dxn) && al16(wqkv_t) && al16(wo_fwd) && al16(wo_t) && al16(wq_fwd),
+                  "linear_attention_block_backward: qkv, do2, xn, dxn and the weights must be 16-byte aligned");
+    return k_linear_attention_core_bwd((const bf16_t*)qkv, (const bf16_t*)do2, ctx, ml, nullptr, workspace, B, n, (hipStream_t)stream, (const bf16_t*)xn,
+                                       (const bf16_t*)wqkv_t, dw_acc, (bf16_t*)dxn, (const bf16_t*)wo_fwd, (const bf16_t*)wo_t, dwo_acc, dbo,
+                                       (const bf16_t*)wq_fwd);
+}
 extern "C" int ofd_flash_attention(const void* qkv, void* out, float* lse, int B, int n, void* stream) {
     OFD_CHECK_ARG(qkv && out && B > 0 && n > 0, "flash_attention: bad argument");
     return k_flash_attention((const bf16_t*)qkv, (bf16_t*)out, B, n, (hipStream_t)stream, lse);

@@ -74,6 +74,26 @@ __device__ __forceinline__ void lc_stage_matrix(unsigned char* lds, const float*
         *(bf16_t*)(lds + ((h * 32 + rr) * 40 + cc) * 2) = f2bf(v);
     }
 }
+// ctx of one sample as the A operand of the backward's dq MFMA, with every column's mean over d taken off in fp32 BEFORE the rounding to
+// bf16.  dq_raw = sm(q) * (dq - <sm(q), dq>) does not change when one row vector is added to every row d of ctx (it shifts dq[d] and
+// <sm(q), dq> alike), and the rows of ctx share most of their magnitude -- sum_n k[d][n] = 1, so every row is a weighted mean of v / n,
+// and v has a mean over the pixels.  Rounding the raw rows put a 2^-9 error of that shared part against the small row-to-row
+// differences that dq is made of: 12-34 % in dq and dW_q on inputs whose v has a mean (tests/test_linear_attention_block_gpu.py).
+// cm: 128 floats of scratch LDS (free until the caller's next barrier).
+__device__ __forceinline__ void lc_stage_ctx_centred(unsigned char* lds, const float* __restrict__ src, float* cm, int tid) {
+    if (tid < 128) {
+        const float* col = src + (tid >> 5) * 1024 + (tid & 31);
+        float s = 0.0f;
+#pragma unroll 8
+        for (int r = 0; r < 32; ++r) s += col[r * 32];
+        cm[tid] = s * (1.0f / 32.0f);
+    }
+    __syncthreads();
+    for (int i = tid; i < 4096; i += 256) {
+        const int h = i >> 10, r = (i >> 5) & 31, c = i & 31;
+        *(bf16_t*)(lds + ((h * 32 + r) * 40 + c) * 2) = f2bf(src[i] - cm[h * 32 + c]);
+    }
+}
 __device__ __forceinline__ bf16x8 lc_afrag(const unsigned char* lds, int h, int s, int l31, int half) {
     return *(const bf16x8*)(lds + ((h * 32 + l31) * 40 + s * 16 + half * 8) * 2);
 }
@@ -398,7 +418,7 @@ __global__ void __launch_bounds__(256, 2) lc_bwd_apply_kernel(const bf16_t* __re
 #pragma unroll
                 for (int r = 0; r < 16; ++r) wacc[a][j][r] = 0.0f;
     }
-    lc_stage_matrix(cA, ctx + (size_t)b * 4096, false, tid);
+    lc_stage_ctx_centred(cA, ctx + (size_t)b * 4096, (float*)st, tid);      // (st: not written before the tile loop's first barrier)
     lc_stage_matrix(dA, dctx + (size_t)b * 4096, false, tid);
     lc_stage_matrix(dT, dctx + (size_t)b * 4096, true, tid);
     if (tid < 128) {
@@ -628,7 +648,7 @@ __global__ void __launch_bounds__(256) lc_bwd_combine_kernel(const float* __rest
             qd[i] = a;
         } else {
             dctx[(size_t)bh * 1024 + i] = a;
-            prod[i] = a * ctx[(size_t)bh * 1024 + i];
+            prod[i] = bf2f(f2bf(a)) * ctx[(size_t)bh * 1024 + i];      // (S from the ROUNDED dctx: see below)
         }
     }
     if (wo) {
@@ -649,7 +669,10 @@ __global__ void __launch_bounds__(256) lc_bwd_combine_kernel(const float* __rest
             float a = 0.0f;
             for (int c = 0; c < 64; ++c) a += qd[d * 64 + c] * bf2f(wo[((size_t)(e >> 3) * 64 + c) * 8 + (e & 7)]);
             dctx[(size_t)bh * 1024 + i] = a;
-            prod[i] = a * ctx[(size_t)bh * 1024 + i];
+            // S[d] = sum_n k (dctx . v / n) = <dctx[d], ctx[d]> with the dctx the apply kernel MULTIPLIES by, i.e. rounded to bf16 as its A
+            // operand is: dk_raw = k (dctx . v / n - S) then sums to zero over the pixels as it must.  With S from the fp32 dctx the part of
+            // dctx . v / n that is common to all pixels (v has a mean) did not cancel: sum_n dk_raw != 0, 9-19 % in dW_k.
+            prod[i] = bf2f(f2bf(a)) * ctx[(size_t)bh * 1024 + i];
         }
     }
     __syncthreads();

@@ -283,6 +283,17 @@ __global__ void __launch_bounds__(256, 2) la_ctx_fused_kernel(const bf16_t* __re
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2)   // ctx^T[e][d] += sum_pix v[pix][e] p[pix][d]
                 ctxT[hd] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(acc_frag(va, s2), acc_frag(ka, s2), ctxT[hd], 0, 0, 0);
+            if constexpr (TRAIN) {
+                // the context kept for the BACKWARD must be the sum of v over the softmax the backward recomputes from the stored k (fp32
+                // p / l), not over p rounded to bf16: the backward's S = <dctx, ctx> and its dq lean on ctx cancelling against per-pixel
+                // terms, and the 2^-9 of the rounded p came through that cancellation 10x - 1000x amplified in dW_q / dW_k
+                // (tests/test_linear_attention_block_gpu.py test_backward).  Second MFMA pass over the part of p the first one dropped.
+#pragma unroll
+                for (int r = 0; r < 16; ++r) ka[r] -= (float)(__bf16)ka[r];
+#pragma unroll
+                for (int s2 = 0; s2 < 2; ++s2)
+                    ctxT[hd] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(acc_frag(va, s2), acc_frag(ka, s2), ctxT[hd], 0, 0, 0);
+            }
         }
     }
     __syncthreads();                          // every wave is done with the weight fragments: the LDS becomes the combine buffer

@@ -587,6 +587,13 @@ extern "C" int ofd_layernorm_c_backward(const void* x, const float* g, const voi
     OFD_CHECK_ARG(x && g && dy && dx && dg, "layernorm_c_backward: null argument");
     return k_layernorm_c_bwd((const bf16_t*)x, g, (const bf16_t*)dy, (bf16_t*)dx, dg, npix, C, eps, accumulate, (hipStream_t)stream, nullptr);
 }
+extern "C" int ofd_layernorm_c_backward_residual(const void* x, const float* g, const void* dy, const void* extra, void* dx, float* dg, size_t npix,
+                                                 int C, float eps, int accumulate, void* stream) {
+    OFD_CHECK_ARG(x && g && dy && dx && dg, "layernorm_c_backward_residual: null argument");
+    OFD_CHECK_ARG(C == 64 || C == 128 || C == 256 || C == 512, "layernorm_c_backward_residual: C=%d", C);
+    OFD_CHECK_ARG(npix > 0, "layernorm_c_backward_residual: npix=0");
+    return k_layernorm_c_bwd((const bf16_t*)x, g, (const bf16_t*)dy, (bf16_t*)dx, dg, npix, C, eps, accumulate, (hipStream_t)stream, (const bf16_t*)extra);
+}
 extern "C" int ofd_final_conv_backward(const void* x, const float* w, const float* dy, void* dx, float* dw, float* db, int B, int H, int W, int C,
                                        int out_dim, void* stream) {
     OFD_CHECK_ARG(x && w && dy && dx && dw && db, "final_conv_backward: null argument");

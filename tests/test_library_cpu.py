@@ -52,6 +52,31 @@ def test_argument_errors_without_gpu(libpath):
     assert L.ofd_conv_forward(ctypes.byref(args), None) == -1
     assert L.ofd_conv_gn_partial_count(2, 16, 64, 64) == 2 * 2 * 2 * 4 * 8 * 2
     assert L.ofd_conv_weight_elems(64, 16, 7) == 49 * 16 * 64
+    # the fused LinearAttention entry points: one null-pointer call and one bad-C call each (p: a real, 16-byte aligned host address --
+    # validation returns before anything could read it)
+    buf = ctypes.create_string_buffer(64)
+    p = ctypes.c_void_p((ctypes.addressof(buf) + 15) & ~15)
+    calls = {
+        "la_weight_prep": lambda a, C: L.ofd_la_weight_prep(a, p, p, p, p, p, C, None),
+        "linear_attention_block": lambda a, C: L.ofd_linear_attention_block(a, *[p] * 8, 1, 4, C, 1e-5, 1e-3, None),
+        "linear_attention_block_train": lambda a, C: L.ofd_linear_attention_block_train(a, *[p] * 14, 1, 4, C, 1e-5, 1e-3, None),
+        "linear_attention_core_proj": lambda a, C: L.ofd_linear_attention_core_proj(a, *[p] * 7, C, 1, 4, None),
+        "linear_attention_block_backward": lambda a, C: L.ofd_linear_attention_block_backward(a, *[p] * 13, C, 1, 4, None),
+        "layernorm_c_backward_residual": lambda a, C: L.ofd_layernorm_c_backward_residual(a, p, p, None, p, p, 4, C, 1e-5, 0, None),
+    }
+    good_c = {"linear_attention_core_proj": 128}
+    for name, call in calls.items():
+        assert call(None, good_c.get(name, 64)) == -1 and b"null" in L.ofd_last_error() and name.encode() in L.ofd_last_error(), name
+        assert call(p, 96) == -1 and b"C=96" in L.ofd_last_error() and name.encode() in L.ofd_last_error(), name
+    # widths the other forms take but these do not, sizes, alignment
+    assert calls["linear_attention_block_train"](p, 128) == -1 and calls["linear_attention_block_backward"](p, 128) == -1
+    assert calls["linear_attention_core_proj"](p, 64) == -1
+    assert L.ofd_linear_attention_block(*[p] * 9, 0, 4, 64, 1e-5, 1e-3, None) == -1 and b"B=0" in L.ofd_last_error()
+    assert L.ofd_linear_attention_block(*[p] * 9, 1, 0, 64, 1e-5, 1e-3, None) == -1 and b"n=0" in L.ofd_last_error()
+    odd = ctypes.c_void_p(p.value + 2)
+    assert L.ofd_linear_attention_block(odd, *[p] * 8, 1, 4, 64, 1e-5, 1e-3, None) == -1 and b"aligned" in L.ofd_last_error()
+    assert L.ofd_linear_attention_block(p, odd, *[p] * 7, 1, 4, 64, 1e-5, 1e-3, None) == -1 and b"aligned" in L.ofd_last_error()
+    assert L.ofd_version() >= 4                                            # the minor went up with the new symbols
 
 
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
