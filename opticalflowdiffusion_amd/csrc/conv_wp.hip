@@ -261,8 +261,20 @@ __global__ void __launch_bounds__(256, 2) conv3x3_wp16_kernel(const ConvParams P
     int pyx[C::XPT];
     unsigned okmask;
     stage_map<C>(P, tid, oy0, ox0, pyx, okmask);
+    // tile loads in two parts, so that the loads themselves can sit between the MFMAs of a chunk without a branch and without address
+    // registers: src_of(kc) walks the sources (scalar: the chunk's uniform base, width, stride, shift), load_x issues one load per unit
+    // at base + a 32-bit byte offset (launch_conv3x3_wp sends sources of 4 GB per sample or more to conv3x3_wp_kernel).  The shift
+    // enters both field extractions: nothing of the offset is invariant over the chunks, so nothing of it is held across them
     int src_i = 0, src_first = 0;
-    auto load_x = [&](int kc, u4 (&xs)[C::XPT]) { load_chunk<C>(P, b, kc, tid, pyx, src_i, src_first, xs); };
+    const unsigned oct_off = (tid % C::NC) * 16;
+    auto src_of = [&](int kc) { return chunk_src(P, b, kc, 0, src_i, src_first); };
+    auto load_x = [&](const ChunkSrc& S, u4 (&xs)[C::XPT]) {
+#pragma unroll
+        for (int i = 0; i < C::XPT; ++i) {
+            const unsigned sy = (unsigned)pyx[i] >> (16 + S.up), sx = __builtin_amdgcn_ubfe((unsigned)pyx[i], S.up, 16 - S.up);
+            xs[i] = *(const u4*)((const unsigned char*)S.base + ((sy * S.SW + sx) * (S.stride * 2) + oct_off));
+        }
+    };
     auto write_x = [&](int kc, const u4 (&xs)[C::XPT], unsigned char* xbuf) { write_chunk<C, PRO>(P, b, kc, tid, okmask, xs, xbuf); };
 
     f32x4 acc[8][2][2];                               // [row][pixel half][channel half]
@@ -274,23 +286,21 @@ __global__ void __launch_bounds__(256, 2) conv3x3_wp16_kernel(const ConvParams P
             for (int k = 0; k < 4; ++k) acc[r][q >> 1][q & 1][k] = 0.0f;
 
     u4 xs[C::XPT];
-    load_x(0, xs);
+    load_x(src_of(0), xs);
     write_x(0, xs, smem);
     u4 wa[6], wb[6];                                  // weight sets: kx iterations alternate between them (3 per chunk: the parity flips every chunk)
 #pragma unroll
     for (int i = 0; i < 6; ++i) wa[i] = load_w(0, 0, i);
 
     const int xrow_off = lg * C::US + l15 * 16;       // octet lg, pixel l15 of a 16-pixel group
-    // one kernel column of one chunk: 96 MFMAs with the weights in `cur`; `nxt` receives the next column's
-    auto column = [&](const unsigned char* xrow, const int kx, u4 (&cur)[6], u4 (&nxt)[6], const int nkc, const int nkx, const bool fetch) {
-        if (fetch) {
-#pragma unroll
-            for (int i = 0; i < 6; ++i) nxt[i] = load_w(nkc, nkx, i);
-        }
+    // kernel column kx with the weights in `cur`: four groups of 24 MFMAs (pixel half p, rows 4 hf .. 4 hf + 3, which need staged rows
+    // 4 hf .. 4 hf + 5); before(slot) issues the loads that belong in front of group `slot` of the chunk's twelve
+    auto mfma_column = [&](const unsigned char* xrow, const int kx, const u4 (&cur)[6], auto before) {
 #pragma unroll
         for (int p = 0; p < 2; ++p)
 #pragma unroll
-            for (int hf = 0; hf < 2; ++hf) {          // rows 4 hf .. 4 hf + 3 need staged rows 4 hf .. 4 hf + 5
+            for (int hf = 0; hf < 2; ++hf) {
+                before(kx * 4 + p * 2 + hf);
                 bf16x8 x[6];
 #pragma unroll
                 for (int j = 0; j < 6; ++j) x[j] = *(const bf16x8*)(xrow + ((4 * hf + j) * IW + kx + 16 * p) * 16);
@@ -303,25 +313,53 @@ __global__ void __launch_bounds__(256, 2) conv3x3_wp16_kernel(const ConvParams P
                             acc[4 * hf + r][p][h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(cur[ky * 2 + h]), x[r + ky], acc[4 * hf + r][p][h], 0, 0, 0);
             }
     };
-    // chunk kc; EVEN: its first column uses set A (chunks alternate: three columns each)
+    auto fetch_w = [&](u4 (&nxt)[6], const int kc, const int kx) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) nxt[i] = load_w(kc, kx, i);
+    };
+    // chunk kc; EVEN: its first column uses set A (chunks alternate: three columns each).  A wave's vector-memory results retire in issue
+    // order, so WHERE in the chunk a load is issued decides what it waits behind.  Slots = the twelve 24-MFMA groups of the chunk:
+    //   slot 2   W(kc, 1) -> the other set     half a column (48 MFMAs) ahead of its use, nothing from HBM outstanding
+    //   slot 6   W(kc, 2)                      likewise
+    //   slot 8   the next tile's HBM loads     (5-8 k cycles under load) behind both; written to LDS after column 2
+    //   slot 10  W(kn, 0)                      the one set requested behind the tile: first used after write_x, which waits for the tile anyway
+    //                                          (plain kernel: a counted wait, W(kn, 0) stays in flight across it and the barrier; the
+    //                                          prologue kernel loads its scale / shift behind the set and waits for all of it)
+    // The scheduling fences pin the slots: MFMAs and vector-memory instructions do not cross them, LDS reads and ALU do.  Left alone the
+    // scheduler sinks every fetch to the last MFMAs before its use and the tile loads in among the MFMAs of the column behind them.  The
+    // slots are the earliest the registers allow: the staging registers are live in column 2 only, a fetch at the start of a column or
+    // the tile in column 1 spills.  LDS: write_x(kn) targets the buffer chunk kc - 1 read, which every wave left before the
+    // barrier at the top of this chunk; its readers wait at the next barrier.
     auto chunk = [&](const int kc, auto even_tag, auto last_tag) {
         constexpr bool EVEN = decltype(even_tag)::value, LAST = decltype(last_tag)::value;
+        constexpr int FENCE = 0x386;                  // VALU, SALU and LDS instructions may cross
         const int kn = LAST ? kc : kc + 1;
-        if constexpr (!LAST) load_x(kn, xs);
+        ChunkSrc S = {};
+        if constexpr (!LAST) S = src_of(kn);          // (the walk's loop stays outside the MFMA block)
         __syncthreads();                              // tile kc complete; every wave is done reading the other buffer
         const unsigned char* xrow = smem + (kc & 1) * C::XB + xrow_off;
         unsigned char* xnext = smem + ((kc + 1) & 1) * C::XB;
-        if constexpr (EVEN) {
-            column(xrow, 0, wa, wb, kc, 1, true);
-            if constexpr (!LAST) write_x(kn, xs, xnext);
-            column(xrow, 1, wb, wa, kc, 2, true);
-            column(xrow, 2, wa, wb, kn, 0, !LAST);
-        } else {
-            column(xrow, 0, wb, wa, kc, 1, true);
-            if constexpr (!LAST) write_x(kn, xs, xnext);
-            column(xrow, 1, wa, wb, kc, 2, true);
-            column(xrow, 2, wb, wa, kn, 0, !LAST);
-        }
+        auto body = [&](u4 (&s0)[6], u4 (&s1)[6]) {
+            auto before = [&](const int slot) {
+                if (slot != 2 && slot != 6 && (LAST || (slot != 8 && slot != 10))) return;
+                __builtin_amdgcn_sched_barrier(FENCE);
+                if (slot == 2) fetch_w(s1, kc, 1);
+                if (slot == 6) fetch_w(s0, kc, 2);
+                if constexpr (!LAST) {
+                    if (slot == 8) load_x(S, xs);
+                    if (slot == 10) fetch_w(s1, kn, 0);
+                }
+                __builtin_amdgcn_sched_barrier(FENCE);
+            };
+            mfma_column(xrow, 0, s0, before);
+            mfma_column(xrow, 1, s1, before);
+            mfma_column(xrow, 2, s0, before);
+            if constexpr (!LAST) {
+                if constexpr (!PRO) __builtin_amdgcn_sched_barrier(0x384);    // (no VALU across: write_x's padding selects would rise to the tile loads and wait for them in column 2)
+                write_x(kn, xs, xnext);
+            }
+        };
+        if constexpr (EVEN) body(wa, wb); else body(wb, wa);
     };
     for (int kc = 0; kc < n32 - 2; kc += 2) {         // (n32 is even: 64-channel chunks of the descriptors)
         chunk(kc, std::true_type{}, std::false_type{});
@@ -430,7 +468,9 @@ int launch_conv3x3_wp(const ConvParams& P0, bool wide, hipStream_t s) {
     // that wave is matrix-pipe idle time, which two independent 4-wave workgroups per CU cover for each other.)
     using W = wp::Cfg<4, 1>;
     using N = wp::Cfg<2, 2>;
-    if (wide && plain_epilogue(P)) return P.in_scale ? wp::launch<W>(wp::conv3x3_wp16_kernel<true>, P, s) : wp::launch<W>(wp::conv3x3_wp16_kernel<false>, P, s);
+    bool off32 = true;                                // conv3x3_wp16_kernel addresses a sample of a source by 32-bit byte offsets
+    for (int i = 0; i < P.n_src; ++i) off32 = off32 && (size_t)P.src[i].SH * P.src[i].SW * P.src[i].src_channels * 2 < ((size_t)1 << 32);
+    if (wide && off32 && plain_epilogue(P)) return P.in_scale ? wp::launch<W>(wp::conv3x3_wp16_kernel<true>, P, s) : wp::launch<W>(wp::conv3x3_wp16_kernel<false>, P, s);
     // producer / consumer form for the 64 -> 64 layers with plain / prologue / statistics epilogues (OFD_CONV_PC=0: off, read per call)
     if (!wide && env_int("OFD_CONV_PC", 1)) {
         const int r = launch_conv3x3_pc(P, s);
