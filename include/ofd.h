@@ -25,6 +25,7 @@
  *   (not in the reference)            condition dropout (CFG training)  -> ofd_cond_drop
  *   (not in the reference)            dynamic thresholding              -> ofd_x0_abs_quantile, ofd_ddpm_update_thresh,
  *                                                                          ofd_ddim_update_thresh, ofd_dpmpp_update_thresh
+ *   (not in the reference)            photometric guidance of sampling  -> ofd_photo_pyramid, ofd_photo_guide
  *   denoising_diffusion.py:806-812    q_sample                          -> ofd_q_sample
  *   denoising_diffusion.py:844-879,985-993  p_losses noise / target     -> ofd_diffusion_prep
  *   denoising_diffusion.py:73-77      (un)normalize                     -> ofd_range_map
@@ -297,6 +298,42 @@ int ofd_dpmpp_update_thresh(int objective, int order, const float* x_t, const fl
                             const float* d_prev2, const float* cx, const float* w0, const float* w1, const float* w2, int last,
                             const float* known, const float* e0, const float* sqrt_ac_next, const float* sqrt_1mac_next, float* out,
                             float* d_out, int B, size_t n_per_sample, void* stream);
+/* Photometric guidance (an addition, not in the reference): one optional launch per reverse step that rewrites the model output so that
+ * the predicted flow moves one damped Gauss-Newton step (Lucas & Kanade 1981; Levenberg 1944 / Marquardt 1963 damping) towards
+ * photometric agreement of two frames, first(p) ~ second(p + f(p)).  It acts on the predicted x_start alone, as manifold-preserving
+ * guided diffusion does (He et al. 2024); nothing is differentiated through the network (cf. Chung et al. 2023).  Every reverse step,
+ * the quantile and the guided combination read the model output only, so they compose with it unchanged.
+ *
+ * The pyramid.  levels: HOST array of n_levels (1..4) positive integers L, each dividing H and W, read at call time.  Level k of a
+ * (B, Ci, H, W) fp32 frame is its L_k x L_k box average, a contiguous (B, Ci, H / L_k, W / L_k) fp32 block; the blocks are packed in
+ * the order of `levels`, ofd_photo_pyramid_floats(...) floats in all (0 for bad arguments).  ofd_photo_pyramid builds it, one launch
+ * per level; it is meant to run once per chain and frame.  The step gathers both frames from these packed pyramids; no full-resolution
+ * copy of the first frame's samples is kept.
+ *
+ * The step, per sample b and pixel p = (x, y), all in fp32:
+ *   x0     the unclamped x_start of the flow channels c0, c0 + 1 of the (B, C, H, W) diffused tensor, formed exactly as the reverse
+ *          steps form it: model_out (pred_x0) or xa*x_t - xb*model_out, with model_out replaced by the guided combination G1 when
+ *          model_out_uncond / guidance are given.  x_t, xa and xb are NULL for OFD_PRED_X0 and required otherwise.
+ *   f      = flow_max * clamp(x0, -1, 1), in pixels; channel c0 displaces x, channel c0 + 1 displaces y (the forward splat's order).
+ *   A full-resolution coordinate u is (u + 0.5) / L - 0.5 at level L.  a_{L,c}: the bilinear sample of first_L at p's own level
+ *   coordinate, clamped to the image.  b_{L,c}: the bilinear sample of second_L at the level coordinate of p + f; a level where that
+ *   coordinate lies outside [0, W/L - 1] x [0, H/L - 1] contributes nothing at p.  r = b - a; J = db/df, the derivative of the bilinear
+ *   interpolant inside its cell (the cell of floor(coordinate), the last cell at the far edge) over L.
+ *   A = sum J J^T + damping I,  g = sum J r  (sums over levels and the Ci channels),  delta = -A^-1 g  (closed 2x2 solve),
+ *   dx0 = step[b] * delta / flow_max.
+ * Written back: pred_x0: out = model_out + dx0; pred_noise / pred_v: out = model_out - dx0 / xb[b], unchanged where xb[b] == 0.  With
+ * the uncond pair the same increment goes to out and out_uncond (their guided combination moves by exactly that increment for any w).
+ * Bit for bit unchanged: a pixel whose x0 is non-finite in either flow channel, a sample whose step[b] == 0, every channel outside
+ * c0, c0 + 1.  out may be model_out and out_uncond may be model_out_uncond (a pixel reads and writes only itself); when they differ
+ * the untouched values are copied through.  model_out_uncond, guidance and out_uncond come together or not at all.  One pixel per
+ * thread in a grid-stride loop; no atomics, no host synchronisation: the same inputs give the same bits.  Ci 1..4, c0 + 2 <= C,
+ * flow_max and damping finite and > 0.  Argument errors return OFD_ERR_ARG and set ofd_last_error before any GPU work. */
+size_t ofd_photo_pyramid_floats(int B, int Ci, int H, int W, const int* levels, int n_levels);
+int ofd_photo_pyramid(const float* img, const int* levels, int n_levels, int B, int Ci, int H, int W, float* pyr, void* stream);
+int ofd_photo_guide(int objective, const float* x_t, const float* model_out, const float* model_out_uncond, const float* guidance,
+                    const float* xa, const float* xb, const float* step, const float* first_pyr, const float* second_pyr,
+                    const int* levels, int n_levels, int B, int C, int c0, int Ci, int H, int W, float flow_max, float damping,
+                    float* out, float* out_uncond, void* stream);
 /* Training prep, one launch (DD:844-848, 806-812, 874-879, 985-993), x0 / noise / outputs (B,C,hw):
  *   x0n = normalize ? 2*x0 - 1 : x0;  nz = noise + offset_strength*offset[b,c] (offset (B,C), or NULL: no offset noise);
  *   x_t = sqrt_ac*x0n + sqrt_1mac*nz;  target = nz (pred_noise), x0n (pred_x0), sqrt_ac*nz - sqrt_1mac*x0n (pred_v).

@@ -2,7 +2,7 @@
 `algorithms.diffusion_animation` plugin surface.  See DESIGN.md / INTEGRATION.md."""
 from .warp import warp, nan_mse, nan_mse_rows, scale, warp_forward_flow, warp_backward_flow  # noqa: F401
 from .softsplat import softsplat  # noqa: F401
-from .denoising_diffusion import Unet, ConditionalDiffusion  # noqa: F401,E402
+from .denoising_diffusion import Unet, ConditionalDiffusion, PhotoGuide  # noqa: F401,E402
 from .flow_diffuser import FlowDiffuser, UnetWithWarp  # noqa: F401,E402
 from .flow_learner import FlowLearner  # noqa: F401,E402
 from .flow_pred import FlowPred, Autoencoder  # noqa: F401,E402

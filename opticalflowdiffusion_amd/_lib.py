@@ -81,6 +81,9 @@ SIGNATURES = {
     "ofd_dpmpp_update_thresh": (c_int, [c_int, c_int] + [c_void_p] * 13 + [c_int] + [c_void_p] * 6 + [c_int, c_size_t, c_void_p]),
     "ofd_x0_abs_quantile_ws_bytes": (c_size_t, [c_int]),
     "ofd_x0_abs_quantile": (c_int, [c_int] + [c_void_p] * 6 + [c_int, c_size_t, c_size_t, c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "ofd_photo_pyramid_floats": (c_size_t, [c_int] * 4 + [c_void_p, c_int]),
+    "ofd_photo_pyramid": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p]),
+    "ofd_photo_guide": (c_int, [c_int] + [c_void_p] * 10 + [c_int] * 7 + [c_float, c_float] + [c_void_p] * 3),
     "ofd_cond_drop": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_size_t, c_void_p]),
     "ofd_diffusion_prep": (c_int, [c_int] + [c_void_p] * 3 + [c_float] + [c_void_p] * 2 + [c_int] + [c_void_p] * 3 + [c_int, c_int, c_size_t, c_void_p]),
     "ofd_range_map": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p]),

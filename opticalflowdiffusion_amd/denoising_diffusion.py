@@ -167,6 +167,40 @@ def _threshold_max_value(value, what="threshold_max"):
     return float(value)
 
 
+PHOTO_SCHEDULES = ("constant", "alpha")
+
+
+class PhotoGuide:
+    """What `ConditionalDiffusion.sample(photo=)` takes (photometric guidance; not in the reference; include/ofd.h, ofd_photo_guide): the
+    two frames and how the flow channels of the diffused tensor relate to them.  first / second: (B, Ci, H, W), Ci in 1..4, both in one
+    range (cond's), used as given; the model is first(p) ~ second(p + f(p)) with f = flow_max * clamp(x_start[:, c0:c0 + 2], -1, 1) in
+    pixels, channel c0 displacing x.  scale: the fraction of the damped Gauss-Newton step taken per reverse step; levels: the box
+    pyramid, 1 to 4 positive integers dividing H and W; damping: what is added to the diagonal of the 2x2 normal matrix; schedule: the
+    step is scale * lambda_t with lambda = 1 ("constant") or sqrt(alphas_cumprod[t]) ("alpha").  The defaults come from a synthetic
+    translation in float64 on the CPU and are untuned on real footage.  A plain record: the rules are checked where it is used."""
+
+    def __init__(self, first, second, flow_max, c0, scale=1.0, levels=(1, 2, 4), damping=1e-2, schedule="constant"):
+        self.first, self.second, self.flow_max, self.c0 = first, second, flow_max, c0
+        self.scale, self.levels, self.damping, self.schedule = scale, levels, damping, schedule
+
+
+def _positive_finite(value):
+    return not isinstance(value, bool) and isinstance(value, (int, float)) and math.isfinite(value) and value > 0
+
+
+def photo_levels_value(levels, H, W, what="levels"):
+    """the pyramid levels as a tuple of ints: 1 to 4 positive integers, each dividing H and W (ValueError otherwise)"""
+    try:
+        out = tuple(levels)
+    except TypeError:
+        raise ValueError(f"{what} must be a sequence of 1 to 4 positive integers, got {levels!r}")
+    if not 1 <= len(out) <= 4 or any(isinstance(v, bool) or not isinstance(v, int) or v < 1 for v in out):
+        raise ValueError(f"{what} must be a sequence of 1 to 4 positive integers, got {levels!r}")
+    if any(H % v or W % v for v in out):
+        raise ValueError(f"{what}: every level must divide H={H} and W={W}, got {levels!r}")
+    return out
+
+
 def normalize_to_neg_one_to_one(img):
     """DD:73-74"""
     return _range_map(img, 0)
@@ -933,6 +967,67 @@ class ConditionalDiffusion(nn.Module):
                                             img.numel() // img.shape[0], rank, cap, L.ptr(row), L.ptr(ws), ws.numel(), L.stream()))
         return row
 
+    def _check_photo(self, shape, photo, additional_tgt=None):
+        """the argument rules of photometric guidance, checked before any engine call (ValueError); returns None (off), or
+        (first, second as the kernels read them, flow_max, c0, scale, levels, damping, schedule)"""
+        if photo is None:
+            return None
+        if not isinstance(photo, PhotoGuide):
+            raise ValueError(f"photo must be None or a PhotoGuide, got {type(photo).__name__}")
+        if additional_tgt is not None:
+            raise ValueError("photo cannot be combined with additional_tgt (FlowDiffuser target='target'): there the flow is an extra "
+                             "model output, not part of the diffused tensor")
+        B, C, H, W = shape
+        for name, f in (("first", photo.first), ("second", photo.second)):
+            if not torch.is_tensor(f) or f.dim() != 4 or f.shape[0] != B or not 1 <= f.shape[1] <= 4 or tuple(f.shape[2:]) != (H, W):
+                raise ValueError(f"photo.{name} must be a (B, Ci, H, W) = ({B}, 1..4, {H}, {W}) tensor, got "
+                                 f"{tuple(f.shape) if torch.is_tensor(f) else type(f).__name__}")
+        if tuple(photo.first.shape) != tuple(photo.second.shape):
+            raise ValueError(f"photo.first and photo.second must have one shape, got {tuple(photo.first.shape)} and {tuple(photo.second.shape)}")
+        if not _positive_finite(photo.flow_max):
+            raise ValueError(f"photo.flow_max must be a finite number > 0, got {photo.flow_max!r}")
+        if not _positive_finite(photo.damping):
+            raise ValueError(f"photo.damping must be a finite number > 0, got {photo.damping!r}")
+        if isinstance(photo.scale, bool) or not isinstance(photo.scale, (int, float)) or not math.isfinite(photo.scale) or photo.scale < 0:
+            raise ValueError(f"photo.scale must be a finite number >= 0, got {photo.scale!r}")
+        if isinstance(photo.c0, bool) or not isinstance(photo.c0, int) or not 0 <= photo.c0 <= C - 2:
+            raise ValueError(f"photo.c0 must be an integer with c0 + 2 <= channels={C}, got {photo.c0!r}")
+        if photo.schedule not in PHOTO_SCHEDULES:
+            raise ValueError(f"unknown photo.schedule {photo.schedule!r}: expected one of {PHOTO_SCHEDULES}")
+        levels = photo_levels_value(photo.levels, H, W, "photo.levels")
+        L.require_gpu(photo.first, photo.second)
+        return (L.f32c(photo.first), L.f32c(photo.second), float(photo.flow_max), photo.c0, float(photo.scale), levels,
+                float(photo.damping), photo.schedule)
+
+    def _photo_plan(self, ph, img, guided):
+        """what the photometric launches of a chain on `img`-shaped tensors need, made once per chain: the two packed pyramids (one
+        ofd_photo_pyramid call per frame), the (T, B) step table scale * lambda_t of which a step reads a row, and the buffers the
+        rewritten model output(s) go to"""
+        first, second, flow_max, c0, scale, levels, damping, schedule = ph
+        B, Ci, H, W = first.shape
+        lib = L.lib()
+        lv = (ctypes.c_int * len(levels))(*levels)
+        floats = int(lib.ofd_photo_pyramid_floats(B, Ci, H, W, lv, len(levels)))
+        pyr = [torch.empty(floats, dtype=torch.float32, device=img.device) for _ in range(2)]
+        for frame, dst in zip((first, second), pyr):
+            L.check(lib.ofd_photo_pyramid(L.ptr(frame), lv, len(levels), B, Ci, H, W, L.ptr(dst), L.stream()))
+        lam = self.sqrt_alphas_cumprod.to(device=img.device, dtype=torch.float32)
+        if schedule == "constant":
+            lam = torch.ones_like(lam)
+        steps = (scale * lam).reshape(-1, 1).repeat(1, B).contiguous()
+        return dict(pyr=pyr, lv=lv, n=len(levels), Ci=Ci, c0=c0, flow_max=flow_max, damping=damping, steps=steps,
+                    out=torch.empty_like(img), out_uncond=torch.empty_like(img) if guided else None)
+
+    def _photo_guide(self, tab, t, img, out, guide, pg):
+        """the photometric launch of a step at level t (include/ofd.h, ofd_photo_guide) on the arguments the update launch gets;
+        returns (out, guide) rewritten into the chain's buffers, in stream order: no allocation, no host sync"""
+        B, C, H, W = img.shape
+        gd = (None, None) if guide is None else (L.ptr(guide[0]), L.ptr(guide[1]))
+        L.check(L.lib().ofd_photo_guide(self._obj, L.ptr(img), L.ptr(out), *gd, *self._xab(tab, t), L.ptr(pg["steps"][t]),
+                                        L.ptr(pg["pyr"][0]), L.ptr(pg["pyr"][1]), pg["lv"], pg["n"], B, C, pg["c0"], pg["Ci"], H, W,
+                                        pg["flow_max"], pg["damping"], L.ptr(pg["out"]), L.ptr(pg["out_uncond"]), L.stream()))
+        return pg["out"], (None if guide is None else (pg["out_uncond"], guide[1]))
+
     def _guidance_row(self, batch, device, w):
         """the per-sample guidance row of the guided entry points (include/ofd.h: guidance), built once per (batch, device, w) like a
         row of `_sampling_tables`: a step reads it, no fill launch per step"""
@@ -969,16 +1064,17 @@ class ConditionalDiffusion(nn.Module):
 
     @torch.no_grad()
     def p_sample_loop(self, shape, return_all_timesteps=False, external_cond=None, additional_tgt=None, verbose=False, x_T=None,
-                      known=None, resample=1, guidance_scale=UNSET, dynamic_threshold=UNSET, threshold_max=UNSET):
+                      known=None, resample=1, guidance_scale=UNSET, dynamic_threshold=UNSET, threshold_max=UNSET, photo=None):
         """DD:700-729 (no per-step print / host sync).  `x_T` (optional, not in the reference): the start of the chains (DD:705).
         A step is: one UNet call, one in-place normal_ into a reused buffer, one fused update kernel writing into the other of
         two ping-pong images -- no per-step allocation, no coefficient gathers (rows of `_sampling_tables`).
         `known` / `resample` (optional, not in the reference): constrained sampling, see `sample`; known is in the loop's own range
         ([-1, 1]), as external_cond and x_T are.  `guidance_scale`: classifier-free guidance, see `sample`.
-        `dynamic_threshold` / `threshold_max`: dynamic thresholding, see `sample`."""
+        `dynamic_threshold` / `threshold_max`: dynamic thresholding, see `sample`.  `photo`: photometric guidance, see `sample`."""
         known = self._check_known(shape, known, resample, additional_tgt)
         w = self._check_guidance(guidance_scale, additional_tgt, external_cond)
         th = self._check_threshold(dynamic_threshold, threshold_max)
+        ph = self._check_photo(shape, photo, additional_tgt)
         if additional_tgt is not None:                                                # target='target': the general step (DD:676-698)
             # kept on p_sample: this branch keeps every frame whatever trajectory_stride says, which the shared chain would not
             img = torch.randn(shape, device=self.device) if x_T is None else L.f32c(x_T)
@@ -1009,9 +1105,10 @@ class ConditionalDiffusion(nn.Module):
 
             return [(t, resample if t > 0 else 1) for t in reversed(range(0, self.num_timesteps))], step, renoise
 
-        return self._run_chain(shape, x_T, plan, return_all_timesteps, external_cond, guidance=w, threshold=th)   # DD:725-726
+        return self._run_chain(shape, x_T, plan, return_all_timesteps, external_cond, guidance=w, threshold=th, photo=ph)   # DD:725-726
 
-    def _run_chain(self, shape, x_T, plan, return_all_timesteps, external_cond, additional_tgt=None, guidance=None, threshold=None):
+    def _run_chain(self, shape, x_T, plan, return_all_timesteps, external_cond, additional_tgt=None, guidance=None, threshold=None,
+                   photo=None):
         """The reverse chain p_sample_loop, ddim_sample and dpmpp_sample share.  It owns the start image (x_T or a fresh draw, made before
         any table is built), the two ping-pong images, the model call on a row of `_sampling_tables`, the additional_tgt split, the
         trajectory (x_T, every trajectory_stride-th schedule entry and the last) and the return form.  `plan(x_T, tab)` is the sampler:
@@ -1023,7 +1120,10 @@ class ConditionalDiffusion(nn.Module):
         once here), and hands step() guide = (the second output, the guidance row) for the guided entry point.  `threshold` (what
         _check_threshold returns, or None): the threshold row and the quantile workspace are made once here; every step runs the
         quantile launches on the diffused channels of the model output(s), after the additional_tgt split, and hands step() the row
-        as its last argument for the thresholded entry point.  Without it step() is called as before."""
+        as its last argument for the thresholded entry point.  Without it step() is called as before.  `photo` (what _check_photo
+        returns, or None): the pyramids, the step table and the output buffers are made once here (_photo_plan); every model
+        evaluation, RePaint's repeated runs included, is followed by one ofd_photo_guide launch that rewrites the model output(s)
+        into those buffers, before the quantile launches and the update launch, which both read the rewritten output(s)."""
         img = torch.randn(shape, device=self.device) if x_T is None else L.f32c(x_T)
         assert tuple(img.shape) == tuple(shape)
         tab = self._sampling_tables(shape[0], img.device)
@@ -1031,6 +1131,7 @@ class ConditionalDiffusion(nn.Module):
         if guidance is not None:
             null_cond, row = torch.zeros_like(external_cond), self._guidance_row(shape[0], img.device, guidance)
         qplan = None if threshold is None else self._threshold_plan(threshold, img)
+        pplan = None if photo is None else self._photo_plan(photo, img, guidance is not None)
         schedule, step, renoise = plan(img, tab)                                      # img is x_T: never written, the loop writes to pong
         pong = [torch.empty_like(img), torch.empty_like(img)]
         imgs, additionals, stride = [img], [None], self.trajectory_stride
@@ -1048,6 +1149,8 @@ class ConditionalDiffusion(nn.Module):
                 if guidance is not None:
                     guide = (self._same_shape(L.f32c(self.model_with_condition(img, tab["t"][t], None, external_cond=null_cond)), img), row)
                 out = self._same_shape(L.f32c(out), img)
+                if pplan is not None:
+                    out, guide = self._photo_guide(tab, t, img, out, guide, pplan)
                 if qplan is None:
                     step(i, t, img, out, pong[writes & 1], guide)
                 else:
@@ -1061,13 +1164,14 @@ class ConditionalDiffusion(nn.Module):
     # -- DDIM --------------------------------------------------------------------------------
     @torch.no_grad()
     def ddim_sample(self, shape, return_all_timesteps=False, external_cond=None, additional_tgt=None, x_T=None, known=None, resample=1,
-                    guidance_scale=UNSET, dynamic_threshold=UNSET, threshold_max=UNSET):
+                    guidance_scale=UNSET, dynamic_threshold=UNSET, threshold_max=UNSET, photo=None):
         """DD:731-774; accepts (and ignores) additional_tgt so that sample() can reach it.  `x_T` (optional, not in
         the reference) starts the chains from a given tensor instead of a fresh draw (DD:741).  `known` (optional, not in the
         reference): constrained sampling, see `sample`; in the loop's own range ([-1, 1]).  resample > 1 is DDPM's: ValueError."""
         known = self._check_known(shape, known, resample, additional_tgt, ddpm=False)
         w = self._check_guidance(guidance_scale, additional_tgt, external_cond)
         th = self._check_threshold(dynamic_threshold, threshold_max)
+        ph = self._check_photo(shape, photo)                                    # additional_tgt is ignored here, so it cannot clash
         batch, T, S, eta = shape[0], self.num_timesteps, self.sampling_timesteps, self.ddim_sampling_eta
         times = torch.linspace(-1, T - 1, steps=S + 1)
         times = list(reversed(times.int().tolist()))
@@ -1094,7 +1198,7 @@ class ConditionalDiffusion(nn.Module):
 
             return [(time, 1) for time, _ in time_pairs], step, None
 
-        return self._run_chain(shape, x_T, plan, return_all_timesteps, external_cond, guidance=w, threshold=th)  # DD:772-773
+        return self._run_chain(shape, x_T, plan, return_all_timesteps, external_cond, guidance=w, threshold=th, photo=ph)  # DD:772-773
 
     # -- DPM-Solver++ (not in the reference) --------------------------------------------------
     def _dpmpp_tables(self, batch, device):
@@ -1116,7 +1220,7 @@ class ConditionalDiffusion(nn.Module):
 
     @torch.no_grad()
     def dpmpp_sample(self, shape, return_all_timesteps=False, external_cond=None, additional_tgt=None, x_T=None, known=None, resample=1,
-                     guidance_scale=UNSET, dynamic_threshold=UNSET, threshold_max=UNSET):
+                     guidance_scale=UNSET, dynamic_threshold=UNSET, threshold_max=UNSET, photo=None):
         """DPM-Solver++ multistep sampling (include/ofd.h, ofd_dpmpp_update): one UNet call per grid point, S - 1 solver steps and a
         final evaluation that returns the clamped prediction.  Signature, x_T, trajectory_stride and the (B, S + 1, C, H, W)
         trajectory are ddim_sample's.  With additional_tgt (FlowDiffuser's target='target') the model's extra output channels are
@@ -1127,6 +1231,7 @@ class ConditionalDiffusion(nn.Module):
         known = self._check_known(shape, known, resample, additional_tgt, ddpm=False)
         w = self._check_guidance(guidance_scale, additional_tgt, external_cond)
         th = self._check_threshold(dynamic_threshold, threshold_max)
+        ph = self._check_photo(shape, photo, additional_tgt)
 
         def plan(x_T, tab):
             grid, orders, coef = self._dpmpp_tables(shape[0], x_T.device)
@@ -1141,11 +1246,11 @@ class ConditionalDiffusion(nn.Module):
 
             return [(t, 1) for t in grid], step, None
 
-        return self._run_chain(shape, x_T, plan, return_all_timesteps, external_cond, additional_tgt, guidance=w, threshold=th)
+        return self._run_chain(shape, x_T, plan, return_all_timesteps, external_cond, additional_tgt, guidance=w, threshold=th, photo=ph)
 
     @torch.no_grad()
     def sample(self, batch_size=16, return_all_timesteps=False, external_cond=None, additional_tgt=None, known=None, resample=1,
-               guidance_scale=UNSET, dynamic_threshold=UNSET, threshold_max=UNSET):
+               guidance_scale=UNSET, dynamic_threshold=UNSET, threshold_max=UNSET, photo=None):
         """DD:776-784, with image_size allowed to be (H, W).  external_cond is normalised once per call (DD:778-779); the loops
         unnormalise what they return.
 
@@ -1169,18 +1274,28 @@ class ConditionalDiffusion(nn.Module):
         back rather than saturated.  A step is the UNet call(s), the quantile launches and one fused update launch; the row and the
         workspace are allocated once per chain.  None is the static clamp: the entry points called today, launch for launch.  It
         composes with every sampler and objective, `known` / `resample` (held elements stay clamp(known)), `guidance_scale` and
-        `additional_tgt` (the statistic is over the diffused channels)."""
+        `additional_tgt` (the statistic is over the diffused channels).
+
+        Photometric guidance (not in the reference): `photo` = a `PhotoGuide` with two frames makes every model
+        evaluation be followed by one ofd_photo_guide launch, which moves the predicted flow (channels c0, c0 + 1 of x_start) one damped
+        Gauss-Newton step towards first(p) ~ second(p + f(p)) by rewriting the model output(s); the quantile launches and the update
+        launch read the rewritten output(s), so it composes with every sampler and objective, `known` / `resample`, `guidance_scale`
+        and `dynamic_threshold`.  The frames are used as given (not normalised here).  It guides x_start only and does not
+        differentiate through the model.  Not combinable with `additional_tgt`.  None is the present path, launch for launch."""
         H, W = self._hw()
         shape = (batch_size, self.channels, H, W)
         ddpm = self.sampler != "dpmpp" and not self.is_ddim_sampling
         known = self._check_known(shape, known, resample, additional_tgt, ddpm=ddpm)
         self._check_guidance(guidance_scale, additional_tgt, external_cond)
         self._check_threshold(dynamic_threshold, threshold_max)
+        self._check_photo(shape, photo, additional_tgt)
         per_call = {} if guidance_scale is UNSET else dict(guidance_scale=guidance_scale)      # the optional arguments only when given
         if dynamic_threshold is not UNSET:
             per_call["dynamic_threshold"] = dynamic_threshold
         if threshold_max is not UNSET:
             per_call["threshold_max"] = threshold_max
+        if photo is not None:
+            per_call["photo"] = photo
         if external_cond is not None:
             external_cond = self.normalize(external_cond)
         if self.sampler == "dpmpp":

@@ -9,13 +9,14 @@ with the keys of configurations/algorithm/flow_diffuser.yaml (+ optional `image_
 `sampling_timesteps`, `precision`, `ae_checkpoint`, the sampler keys `sampler`, `solver_order`,
 `sampler_spacing` of ConditionalDiffusion, its classifier-free guidance keys `cond_drop_prob`, `guidance_scale` (target 'flow'
 only), its dynamic thresholding keys `dynamic_threshold`, `threshold_max`, its training-loss keys `loss_weighting`,
-`min_snr_loss_weight`, `min_snr_gamma`, `loss_by_timestep`, `log_animation` (N > 0: validation_step also logs an N-frame `animate` strip), and the `ema_*` keys and `sample_with_ema` of ema.EMA_DEFAULTS, which are not in the reference).
+`min_snr_loss_weight`, `min_snr_gamma`, `loss_by_timestep`, its photometric guidance keys `photo_scale`, `photo_levels`, `photo_damping`,
+`photo_schedule` (what `sample(target_frame=)` / `estimate_flow` use), `log_animation` (N > 0: validation_step also logs an N-frame `animate` strip), and the `ema_*` keys and `sample_with_ema` of ema.EMA_DEFAULTS, which are not in the reference).
 """
 import os
 
 import torch
 
-from .denoising_diffusion import UNSET, Unet, ConditionalDiffusion, loss_by_timestep
+from .denoising_diffusion import UNSET, PhotoGuide, Unet, ConditionalDiffusion, loss_by_timestep
 from .ema import EMA_DEFAULTS, EmaMixin, ema_optimizer_kwargs
 from .warp import warp
 from . import _lib as L
@@ -47,6 +48,7 @@ class _Cfg:
                      sampling_timesteps=None, precision="bf16", augment=True, sampler=None, solver_order=2, sampler_spacing="logsnr",
                      cond_drop_prob=0.0, guidance_scale=None, dynamic_threshold=None, threshold_max=None,
                      loss_weighting=None, min_snr_loss_weight=True, min_snr_gamma=5, loss_by_timestep=False, log_animation=0,
+                     photo_scale=1.0, photo_levels=(1, 2, 4), photo_damping=1e-2, photo_schedule="constant",
                      **EMA_DEFAULTS)
 
     def __init__(self, cfg):
@@ -296,27 +298,61 @@ class FlowDiffuser(EmaMixin, _Base):
             known = torch.cat((torch.full((b, self.dim, h, w), float("nan"), dtype=known.dtype, device=known.device), known), dim=1)
         return known
 
+    def photo_guide(self, cond, target_frame, photo_scale=UNSET, photo_levels=UNSET, photo_damping=UNSET, photo_schedule=UNSET):
+        """the `PhotoGuide` of ConditionalDiffusion.sample for `sample(cond, ..., target_frame=)`: first = cond's three image channels,
+        second = target_frame (both in cond's range, 2 * img - 1), the flow in channels c0 = 0 (target 'flow') or c0 = dim (target
+        'joint') of the diffused tensor, in units of flow_max; scale / levels / damping / schedule from the photo_* cfg keys unless
+        given.  The rules that need no engine are checked here (ValueError): any device, no engine call."""
+        if not self.is_diffusion:
+            raise ValueError("target_frame needs a diffusion model: is_diffusion=False is a plain regression, there is no chain to guide")
+        if self.latent:
+            raise ValueError("target_frame is not supported with latent=True: the diffused flow lives beside latents, and the frames "
+                             "would have to be compared in pixel space")
+        if self.target not in ("flow", "joint"):
+            raise ValueError(f"target_frame is not supported for target={self.target!r}: there the flow is an extra model output, not "
+                             "part of the diffused tensor")
+        if not torch.is_tensor(cond) or cond.dim() != 4 or cond.shape[1] < 3:
+            raise ValueError(f"cond must be (B, 3, H, W), got {tuple(cond.shape) if torch.is_tensor(cond) else type(cond).__name__}")
+        want = (cond.shape[0], 3) + tuple(cond.shape[2:])
+        if not torch.is_tensor(target_frame) or tuple(target_frame.shape) != want:
+            raise ValueError(f"target_frame must be a (B, 3, H, W) = {want} tensor in cond's range, got "
+                             f"{tuple(target_frame.shape) if torch.is_tensor(target_frame) else type(target_frame).__name__}")
+        pick = lambda v, key: getattr(self.cfg, key) if v is UNSET else v
+        return PhotoGuide(cond[:, :3], target_frame, float(self.flow_max), 0 if self.target == "flow" else self.dim,
+                          scale=pick(photo_scale, "photo_scale"), levels=tuple(pick(photo_levels, "photo_levels")),
+                          damping=pick(photo_damping, "photo_damping"), schedule=pick(photo_schedule, "photo_schedule"))
+
     def sample(self, cond, flow, known_flow=None, resample=1, guidance_scale=UNSET, dynamic_threshold=UNSET,
-               threshold_max=UNSET):                                                              # FD:189-215
+               threshold_max=UNSET, target_frame=None, photo_scale=UNSET, photo_levels=UNSET, photo_damping=UNSET,
+               photo_schedule=UNSET):                                                             # FD:189-215
         """`known_flow` (optional, not in the reference): (B, 2, H, W) in pixels, NaN = free; the returned flow has
         clamp(known_flow / flow_max) at the other elements and the sampler fills in the rest consistently (constrained sampling,
         ConditionalDiffusion.sample).  target 'flow' or 'joint' only.  `resample` as there: DDPM only, `resample` UNet calls per step.
         `guidance_scale` (optional, not in the reference): classifier-free guidance for this call instead of cfg.guidance_scale
         (ConditionalDiffusion.sample); target 'flow' only; composes with known_flow.
         `dynamic_threshold`, `threshold_max` (optional, not in the reference): dynamic thresholding for this call instead of the cfg
-        keys (ConditionalDiffusion.sample); every target; composes with known_flow and guidance_scale."""
+        keys (ConditionalDiffusion.sample); every target; composes with known_flow and guidance_scale.
+        `target_frame` (optional, not in the reference): (B, 3, H, W) in cond's range, the second frame; the chain is then guided
+        photometrically towards cond(p) ~ target_frame(p + flow(p)) (photometric guidance, ConditionalDiffusion.sample(photo=)), with
+        `photo_scale`, `photo_levels`, `photo_damping`, `photo_schedule` instead of the cfg keys of those names.  target 'flow' or
+        'joint', not latent; composes with all of the above and every sampler."""
         thresh = {k: v for k, v in (("dynamic_threshold", dynamic_threshold), ("threshold_max", threshold_max)) if v is not UNSET}
+        photo_kw = {k: v for k, v in (("photo_scale", photo_scale), ("photo_levels", photo_levels), ("photo_damping", photo_damping),
+                                      ("photo_schedule", photo_schedule)) if v is not UNSET}
+        if target_frame is None and photo_kw:
+            raise ValueError(f"{sorted(photo_kw)} configure photometric guidance: they need a target_frame")
+        photo = None if target_frame is None else self.photo_guide(cond, target_frame, **photo_kw)
         # a regression model called with autograd on runs the training forward, which has no EMA weights to run on
         if self.is_diffusion or not torch.is_grad_enabled():
             with self._sampling_scope():
-                return self._sample(cond, flow, known_flow, resample, guidance_scale, thresh)
-        return self._sample(cond, flow, known_flow, resample, guidance_scale, thresh)
+                return self._sample(cond, flow, known_flow, resample, guidance_scale, thresh, photo)
+        return self._sample(cond, flow, known_flow, resample, guidance_scale, thresh, photo)
 
-    def _sample(self, cond, flow, known_flow, resample, guidance_scale=UNSET, thresh=None):
+    def _sample(self, cond, flow, known_flow, resample, guidance_scale=UNSET, thresh=None, photo=None):
         bsz = flow.shape[0]
-        kw = {}
+        kw = {} if photo is None else dict(photo=photo)
         if known_flow is not None:
-            kw = dict(known=self.known_from_flow(known_flow), resample=resample)
+            kw.update(known=self.known_from_flow(known_flow), resample=resample)
         elif resample != 1:
             raise ValueError("resample needs a known_flow to harmonise with")
         if guidance_scale is not UNSET:
@@ -345,6 +381,22 @@ class FlowDiffuser(EmaMixin, _Base):
             img = cond[:, :self.dim]
             samples = warp(img, None, flow[:, -1], mode="forward")
         return samples, flow
+
+    def estimate_flow(self, frame1, frame2, **sample_kw):
+        """The flow from frame1 to frame2 in pixels, (B, 2, H, W): frame1(p) ~ frame2(p + flow(p)) (not in the reference, whose diffusion
+        model never sees a second frame when sampling).  Frames are (B, 3, H, W) in cond's range (2 * img - 1).  It is the last
+        trajectory frame of `self.sample(frame1, ., target_frame=frame2, **sample_kw)` times flow_max, the conversion `animate` uses:
+        the trained prior proposes, the photometric step pulls every prediction towards agreement with frame2.  sample_kw: known_flow,
+        guidance_scale, dynamic_threshold, photo_scale, ...; the EMA scope applies as in `sample`."""
+        if not torch.is_tensor(frame1) or frame1.dim() != 4:
+            raise ValueError(f"estimate_flow: frame1 must be (B, 3, H, W), got "
+                             f"{tuple(frame1.shape) if torch.is_tensor(frame1) else type(frame1).__name__}")
+        if frame2 is None:
+            raise ValueError("estimate_flow: frame2 is needed (the target_frame of sample)")
+        B, _, H, W = frame1.shape
+        with torch.no_grad():
+            _samples, fl = self.sample(frame1, frame1.new_zeros(B, 2, H, W), target_frame=frame2, **sample_kw)
+        return fl[:, -1] * float(self.flow_max)
 
     def animate(self, cond, flow=None, frames=8, times=None, fill_holes=True, fill_gain=1.0, **sample_kw):
         """A short clip from a still (not in the reference, which stops at one raw splat): (video, flow).
