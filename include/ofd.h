@@ -26,6 +26,7 @@
  *   (not in the reference)            dynamic thresholding              -> ofd_x0_abs_quantile, ofd_ddpm_update_thresh,
  *                                                                          ofd_ddim_update_thresh, ofd_dpmpp_update_thresh
  *   (not in the reference)            photometric guidance of sampling  -> ofd_photo_pyramid, ofd_photo_guide
+ *   (not in the reference)            two-frame interpolation (softmax splatting) -> ofd_interp_prep, ofd_interp_merge
  *   denoising_diffusion.py:806-812    q_sample                          -> ofd_q_sample
  *   denoising_diffusion.py:844-879,985-993  p_losses noise / target     -> ofd_diffusion_prep
  *   denoising_diffusion.py:73-77      (un)normalize                     -> ofd_range_map
@@ -120,6 +121,36 @@ int ofd_warp_holes(const float* splat, float* img, int B, int C, int Ho, int Wo,
 size_t ofd_pushpull_workspace(int B, int C, int H, int W);
 int ofd_pushpull_fill(const float* x, const float* weight, float* out, void* workspace, size_t workspace_bytes,
                       int B, int C, int H, int W, int premultiplied, float gain, void* stream);
+
+/* Frame interpolation by softmax splatting (Niklaus & Liu, "Softmax Splatting for Video Frame Interpolation", CVPR 2020), extended by a
+ * forward-backward flow term.  An addition: the reference's softsplat(strMode="soft") leaves the importance metric to the caller and
+ * merges nothing.  Both frames are splatted to every time t_k with ofd_splat_fwd and blended; ofd_pushpull_fill closes what both leave
+ * open.  These two calls are the passes before and after the splat.  All arithmetic fp32.
+ * frame1, frame2: (B,C,H,W); flow12, flow21: (B,2,H,W) in pixels, channel 0 = x, frame1(p) ~ frame2(p + flow12(p)) -- the convention of
+ * ofd_splat_fwd and ofd_photo_guide, not the flipped one of ofd_grid_warp_fwd.  times: n floats on the DEVICE, each in [0, 1] (the caller
+ * checks the range: no call reads device memory on the host).
+ *   metric   for direction a -> b ((1, 2) and (2, 1)) at pixel p = (x, y), q = p + flow_ab(p) (one fp32 addition per axis):
+ *            inside = 0 <= q.x <= W-1 and 0 <= q.y <= H-1 (false for a non-finite q).  Bilinear reads at q: x0 = floor(q.x),
+ *            x1 = min(x0 + 1, W-1), tx = q.x - x0, likewise in y; value = (1-ty) * ((1-tx) * g00 + tx * g01) + ty * ((1-tx) * g10 + tx * g11).
+ *            d = (sum over c, ascending, of |a_c(p) - b_c(q)|) / C;  r = flow_ab(p) + flow_ba(q);  |r| = sqrt(r.x^2 + r.y^2);
+ *            z = -alpha * d - beta * |r| where inside, z = -alpha * oob elsewhere;  Z = clamp(z, -zmax, 0), and Z = -zmax where z is NaN
+ *            (a NaN of b or flow_ba under q: the worst match).  Z <= 0: exp(Z) cannot overflow.
+ *            v = 1 if every channel of a(p) and both components of flow_ab(p) are finite, else 0.
+ *   sources  for time t = times[k]: s = 1 - t for frame 1, t for frame 2;  m = s * exp(Z) where v = 1, else 0;
+ *            ten_in[dir, b, k] = (a_c * m for the C channels [0 where v = 0], m, v): C + 2 planes;
+ *            flows[dir, b, k] = t * flow12 (dir 0), (1 - t) * flow21 (dir 1): one fp32 multiply (1 - t is one fp32 subtraction).
+ *            ten_in: (2,B,n,C+2,H,W), flows: (2,B,n,2,H,W): the input and flow of ONE ofd_splat_fwd call on 2*B*n samples of C+2 channels,
+ *            whose result is `acc` below.  (A sample whose flow is non-finite at p is skipped by the splat and has v = 0 anyway.)
+ *   merge    acc: (2,Bn,C+2,H,W), Bn = B*n.  S_c, M, K = acc[0] + acc[1] of the colour, m and v planes (one fp32 addition each).
+ *            colour (Bn,C,H,W) = S_c / M where M > 0 (C divisions per pixel, no reciprocal: M may be tiny), NaN elsewhere (M = 0 or NaN);
+ *            weight (Bn,1,H,W) = K where M > 0, else 0: the UNSCALED coverage, so that a pixel one frame covers fully has confidence 1 in
+ *            ofd_pushpull_fill(colour, weight, premultiplied = 0) and keeps its colour however small exp(Z) is.
+ * One launch each, both directions in the prep's; no atomics, no host sync, the same input gives the same bits.  Loads and stores are
+ * 16 bytes wide where W % 4 == 0 (merge: H*W % 4 == 0) and the pointers are 16-byte aligned.  1 <= n <= 64, 1 <= C <= 8;
+ * alpha, beta, oob, zmax finite and >= 0.  Outputs must not alias inputs. */
+int ofd_interp_prep(const float* frame1, const float* frame2, const float* flow12, const float* flow21, const float* times, int n,
+                    float alpha, float beta, float oob, float zmax, float* ten_in, float* flows, int B, int C, int H, int W, void* stream);
+int ofd_interp_merge(const float* acc, float* colour, float* weight, int Bn, int C, int H, int W, void* stream);
 
 /* ------------------------------------------------------------ grid_sample warp (WP:95-119) -
  * second: (B,C,H,W), flow: (B,2,H,W) exactly as handed to the reference's warp(mode='backward'):

@@ -18,7 +18,7 @@ import torch
 
 from .denoising_diffusion import UNSET, PhotoGuide, Unet, ConditionalDiffusion, loss_by_timestep
 from .ema import EMA_DEFAULTS, EmaMixin, ema_optimizer_kwargs
-from .warp import warp
+from .warp import interpolate_frames, warp
 from . import _lib as L
 
 try:                                                   # pragma: no cover - not installed in this image
@@ -435,6 +435,43 @@ class FlowDiffuser(EmaMixin, _Base):
             parts = [warp(imgs[i:i + per], None, flows[i:i + per], mode="forward", **kw) for i in range(0, B * n, per)]
             video = parts[0] if len(parts) == 1 else torch.cat(parts)
         return video.view(B, n, 3, H, W), flow
+
+    def interpolate(self, frame1, frame2, frames=7, times=None, flow12=None, flow21=None, alpha=10.0, beta=0.0, fill_holes=True,
+                    fill_gain=1.0, **sample_kw):
+        """The frames between two real frames (not in the reference): (video, flow12, flow21), by softmax splatting both frames to every
+        time and blending them (`warp.interpolate_frames`, which has the method and the meaning of alpha and beta).
+        frame1, frame2: (B, 3, H, W) in cond's range (2 * img - 1).  times: numbers in [0, 1], default k / (frames + 1) for
+        k = 1..frames (the frames strictly in between).  flow12, flow21: (B, 2, H, W) IN PIXELS as `estimate_flow` returns them
+        (frame1(p) ~ frame2(p + flow12(p))), both or neither.  Neither: both come from ONE call
+        estimate_flow(cat(frame1, frame2), cat(frame2, frame1), **sample_kw) on a batch of 2B.  Both: no UNet call is made, and
+        sample_kw is an error.  video: (B, n, 3, H, W) in cond's range; fill_holes=False leaves NaN where neither frame lands.
+        Forward only."""
+        if self.latent:
+            raise ValueError("interpolate: latent=True is not supported (every frame would have to be decoded by the Autoencoder)")
+        if times is None:
+            if isinstance(frames, bool) or not isinstance(frames, int) or frames < 1:
+                raise ValueError(f"interpolate: frames must be a positive integer, got {frames!r}")
+            times = [k / (frames + 1) for k in range(1, frames + 1)]
+        for name, fr in (("frame1", frame1), ("frame2", frame2)):
+            if not torch.is_tensor(fr) or fr.dim() != 4 or fr.shape[1] != 3:
+                raise ValueError(f"interpolate: {name} must be (B, 3, H, W), got {tuple(fr.shape) if torch.is_tensor(fr) else type(fr).__name__}")
+        if frame1.shape != frame2.shape:
+            raise ValueError(f"interpolate: frame2 must have frame1's shape {tuple(frame1.shape)}, got {tuple(frame2.shape)}")
+        if (flow12 is None) != (flow21 is None):
+            raise ValueError("interpolate: flow12 and flow21 come together: give both, or neither to have both estimated")
+        if flow12 is not None and sample_kw:
+            raise ValueError(f"interpolate: {sorted(sample_kw)} are sampling arguments; with the flows given nothing is sampled")
+        B = frame1.shape[0]
+        with torch.no_grad():
+            if flow12 is None:
+                L.require_gpu(frame1, frame2)
+                if not self.is_diffusion:
+                    raise ValueError("interpolate: estimating the flows needs a diffusion model (estimate_flow); pass flow12 and flow21")
+                both = self.estimate_flow(torch.cat((frame1, frame2)), torch.cat((frame2, frame1)), **sample_kw)
+                flow12, flow21 = both[:B], both[B:]
+            video = interpolate_frames(frame1, frame2, flow12, flow21, times, alpha=alpha, beta=beta, fill_holes=fill_holes,
+                                       fill_gain=fill_gain)
+        return (video if fill_holes else video[0]), flow12, flow21
 
     @staticmethod
     def _batch_stats(x):

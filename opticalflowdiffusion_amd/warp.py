@@ -139,6 +139,133 @@ def warp_forward_flow(first, second, flow, scale=1, set_nans=True, get_variance=
     return img
 
 
+# ---- two-frame interpolation by softmax splatting (not in the reference; semantics: include/ofd.h, `ofd_interp_prep`) ------------------
+def _interp_times(times):
+    """`times` as a list of floats in [0, 1]"""
+    try:
+        ts = [float(t) for t in (times.tolist() if torch.is_tensor(times) else times)]
+    except TypeError:
+        raise ValueError(f"interpolate: times must be a sequence of numbers, got {times!r}")
+    if not ts or not all(0.0 <= t <= 1.0 for t in ts):                      # false for NaN
+        raise ValueError(f"interpolate: times must be a non-empty sequence of numbers in [0, 1], got {times!r}")
+    if len(ts) > 64:
+        raise ValueError(f"interpolate: at most 64 times per call, got {len(ts)}")
+    return ts
+
+
+def _interp_check(frame1, frame2, flow12, flow21):
+    if not torch.is_tensor(frame1) or frame1.dim() != 4 or frame1.numel() == 0:
+        raise ValueError(f"interpolate: frame1 must be a non-empty (B, C, H, W) tensor, got "
+                         f"{tuple(frame1.shape) if torch.is_tensor(frame1) else type(frame1).__name__}")
+    B, C, H, W = frame1.shape
+    if not torch.is_tensor(frame2) or frame2.shape != frame1.shape:
+        raise ValueError(f"interpolate: frame2 must have frame1's shape {tuple(frame1.shape)}, got "
+                         f"{tuple(frame2.shape) if torch.is_tensor(frame2) else type(frame2).__name__}")
+    if not 1 <= C <= 8:
+        raise ValueError(f"interpolate: 1 to 8 channels, got {C}")
+    for name, fl in (("flow12", flow12), ("flow21", flow21)):
+        if not torch.is_tensor(fl) or tuple(fl.shape) != (B, 2, H, W):
+            raise ValueError(f"interpolate: {name} must be (B, 2, H, W) = {(B, 2, H, W)}, got "
+                             f"{tuple(fl.shape) if torch.is_tensor(fl) else type(fl).__name__}")
+    return B, C, H, W
+
+
+def _interp_params(alpha, beta, oob, zmax):
+    vals = dict(alpha=alpha, beta=beta, oob=oob, zmax=zmax)
+    for k, v in vals.items():
+        if not 0.0 <= float(v) < float("inf"):                              # false for NaN
+            raise ValueError(f"interpolate: {k} must be finite and >= 0, got {v!r}")
+    return [float(v) for v in vals.values()]
+
+
+def _interp_prep(frame1, frame2, flow12, flow21, tdev, params, B, C, H, W):
+    n = tdev.numel()
+    ten_in = torch.empty(2, B, n, C + 2, H, W, dtype=torch.float32, device=frame1.device)
+    flows = torch.empty(2, B, n, 2, H, W, dtype=torch.float32, device=frame1.device)
+    L.check(L.lib().ofd_interp_prep(L.ptr(frame1), L.ptr(frame2), L.ptr(flow12), L.ptr(flow21), L.ptr(tdev), n, *params,
+                                    L.ptr(ten_in), L.ptr(flows), B, C, H, W, L.stream()))
+    return ten_in, flows
+
+
+def interp_prep(frame1, frame2, flow12, flow21, times, alpha=10.0, beta=0.0, oob=0.5, zmax=20.0):
+    """First stage of `interpolate_frames` (`ofd_interp_prep`): (ten_in (2, B, n, C+2, H, W), flows (2, B, n, 2, H, W)), the sources and
+    flows of both directions for every time: the input of one splat of 2*B*n samples."""
+    B, C, H, W = _interp_check(frame1, frame2, flow12, flow21)
+    ts = _interp_times(times)
+    params = _interp_params(alpha, beta, oob, zmax)
+    L.require_gpu(frame1, frame2, flow12, flow21)
+    with torch.no_grad():
+        tdev = torch.tensor(ts, dtype=torch.float32, device=frame1.device)
+        return _interp_prep(*(L.f32c(t.detach()) for t in (frame1, frame2, flow12, flow21)), tdev, params, B, C, H, W)
+
+
+def interp_merge(acc):
+    """Last stage before the fill (`ofd_interp_merge`): acc (2, Bn, C+2, H, W), the splat of `interp_prep`'s sources -> (colour
+    (Bn, C, H, W) with NaN where nothing landed, weight (Bn, 1, H, W), the unscaled coverage)."""
+    if not torch.is_tensor(acc) or acc.dim() != 5 or acc.shape[0] != 2 or not 3 <= acc.shape[2] <= 10 or acc.numel() == 0:
+        raise ValueError(f"interp_merge: acc must be a non-empty (2, Bn, C+2, H, W) tensor with 1 <= C <= 8, got "
+                         f"{tuple(acc.shape) if torch.is_tensor(acc) else type(acc).__name__}")
+    L.require_gpu(acc)
+    _, Bn, C2, H, W = acc.shape
+    with torch.no_grad():
+        acc = L.f32c(acc.detach())
+        colour = torch.empty(Bn, C2 - 2, H, W, dtype=torch.float32, device=acc.device)
+        weight = torch.empty(Bn, 1, H, W, dtype=torch.float32, device=acc.device)
+        L.check(L.lib().ofd_interp_merge(L.ptr(acc), L.ptr(colour), L.ptr(weight), Bn, C2 - 2, H, W, L.stream()))
+    return colour, weight
+
+
+def interpolate_frames(frame1, frame2, flow12, flow21, times, alpha=10.0, beta=0.0, oob=0.5, zmax=20.0, fill_holes=True, fill_gain=1.0):
+    """The frames between two frames by softmax splatting (Niklaus & Liu 2020; not in the reference): (B, n, C, H, W) at `times`.
+    frame1, frame2: (B, C, H, W) in cond's range (2 * img - 1), C <= 8.  flow12, flow21: (B, 2, H, W) IN PIXELS, channel 0 = x, with
+    frame1(p) ~ frame2(p + flow12(p)): what `FlowDiffuser.estimate_flow` returns (not `animate`'s units of flow_max, not the flipped
+    channels of warp(mode="backward")).  times: 1 to 64 numbers in [0, 1]; 0 gives frame1, 1 gives frame2.
+    Each frame is splatted to time t by its share of its flow, weighted by its temporal distance and by exp(Z), Z = clamp(-alpha *
+    mean_c |a(p) - b(q)| - beta * |flow_ab(p) + flow_ba(q)|, -zmax, 0) at q = p + flow_ab(p), -alpha * oob where q leaves the frame
+    (brightness constancy and forward-backward consistency: where two sources collide, the one that matches the other frame wins).
+    fill_holes=True: what neither frame reaches is filled by the push-pull fill (`fill_holes(colour, weight, gain=fill_gain)`), no NaN.
+    fill_holes=False: (frames with NaN there, weight (B, n, 1, H, W)), the weight being the unscaled coverage the fill takes as confidence.
+    One prep, one splat, one merge and one fill for all directions and times, in chunks of at most
+    flow_diffuser.ANIMATE_MAX_PIXELS pixels; no model, forward only, the same input gives the same bits.  Semantics: include/ofd.h."""
+    from .flow_diffuser import ANIMATE_MAX_PIXELS
+    B, C, H, W = _interp_check(frame1, frame2, flow12, flow21)
+    ts = _interp_times(times)
+    params = _interp_params(alpha, beta, oob, zmax)
+    if fill_holes and (not fill_gain >= 1.0 or fill_gain == float("inf")):
+        raise ValueError(f"interpolate: fill_gain must be finite and >= 1, got {fill_gain}")
+    if any(t.requires_grad for t in (frame1, frame2, flow12, flow21)):
+        raise L.OfdError("interpolate: forward only (neither the merge nor the push-pull fill has a backward pass): detach the inputs")
+    L.require_gpu(frame1, frame2, flow12, flow21)
+    n = len(ts)
+    with torch.no_grad():
+        frame1, frame2, flow12, flow21 = (L.f32c(t) for t in (frame1, frame2, flow12, flow21))
+        per = max(1, ANIMATE_MAX_PIXELS // (2 * H * W))                     # frames per chunk: each is two samples of the splat
+        nk, nb = min(n, per), max(1, per // n)
+        video = cover = None
+        for b0 in range(0, B, nb):
+            bs = slice(b0, min(b0 + nb, B))
+            cb = bs.stop - bs.start
+            for k0 in range(0, n, nk):
+                tdev = torch.tensor(ts[k0:k0 + nk], dtype=torch.float32, device=frame1.device)
+                ck = tdev.numel()
+                ten_in, flows = _interp_prep(frame1[bs], frame2[bs], flow12[bs], flow21[bs], tdev, params, cb, C, H, W)
+                acc = splat_forward(ten_in.view(2 * cb * ck, C + 2, H, W), flows.view(2 * cb * ck, 2, H, W))
+                del ten_in, flows
+                colour, weight = interp_merge(acc.view(2, cb * ck, C + 2, H, W))
+                del acc
+                if fill_holes:
+                    colour = _pushpull(colour, weight, cb * ck, C, H, W, False, fill_gain)
+                if cb == B and ck == n:                                     # one chunk: its tensors are the result
+                    video, cover = colour.view(B, n, C, H, W), weight.view(B, n, 1, H, W)
+                    break
+                if video is None:
+                    video = torch.empty(B, n, C, H, W, dtype=torch.float32, device=frame1.device)
+                    cover = torch.empty(B, n, 1, H, W, dtype=torch.float32, device=frame1.device)
+                video[bs, k0:k0 + ck] = colour.view(cb, ck, C, H, W)
+                cover[bs, k0:k0 + ck] = weight.view(cb, ck, 1, H, W)
+    return video if fill_holes else (video, cover)
+
+
 class _GridWarp(torch.autograd.Function):
     """warp_backward_flow (WP:95-119) with the gradients autograd derives for it: d/d second is the bilinear scatter of the
     incoming gradient (the splat kernel on grid_sample's coordinates), d/d flow ATen's grid gradient; the thresholded mask
