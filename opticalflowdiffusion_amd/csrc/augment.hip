@@ -4,6 +4,7 @@
 // crop's zoom.  HBM-bound: every output element is written once; a sample that takes no transform is a copy.
 // The per-sample decisions are drawn on the host side of the boundary (augmentation.py of this package) and arrive as a table.
 #include "common.h"
+#include "reduce.h"
 
 namespace ofd {
 
@@ -23,12 +24,9 @@ __global__ void __launch_bounds__(256) aug_gray_mean_kernel(const float* __restr
     const float* p = (frame ? tgt : img) + (size_t)b * 3 * plane;
     double s = 0.0;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < plane; i += gridDim.x * 256) s += (double)aug_gray(p[i], p[plane + i], p[2 * plane + i]);
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    __shared__ double ws[4];
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
-    __syncthreads();
+    s = block_sum_waves(s);
     if (threadIdx.x == 0)
-        atomicAdd((unsigned long long*)(means + blockIdx.y), (unsigned long long)__double2ll_rn(((ws[0] + ws[1]) + (ws[2] + ws[3])) / (double)plane * AUG_MEAN_SCALE));
+        atomicAdd((unsigned long long*)(means + blockIdx.y), (unsigned long long)__double2ll_rn(s / (double)plane * AUG_MEAN_SCALE));
 }
 
 __global__ void __launch_bounds__(256) augment_kernel(const float* __restrict__ img, const float* __restrict__ tgt, const float* __restrict__ flow,
@@ -156,7 +154,8 @@ __global__ void __launch_bounds__(64) augment_table_kernel(const float* __restri
 
 // min, max, mean and mean over the elements of the (unbiased) standard deviation ACROSS the batch of x (B, n): the statistics training_step logs
 // for cond and flow (flow_diffuser.py:218-235 of the reference: torch.min / max / mean / mean(std(x, dim = 0))) in one pass over x.
-// Per-workgroup partials (ws: 4 doubles per workgroup), added in a fixed order by the second kernel.
+// Per-workgroup partials (ws: 4 doubles per workgroup), added in a fixed order by the second kernel: both run reduce.h's 256-slot
+// tree over slots of their own, which carry the min and the max beside the two sums.
 constexpr int BS_BLOCKS = 1024;
 __global__ void __launch_bounds__(256) batch_stats_kernel(const float* __restrict__ x, int B, size_t n, double* __restrict__ ws) {
     float mn = 3.0e38f, mx = -3.0e38f;
@@ -177,14 +176,10 @@ __global__ void __launch_bounds__(256) batch_stats_kernel(const float* __restric
     __shared__ double r0[256], r1[256];
     __shared__ float r2[256], r3[256];
     r0[threadIdx.x] = sum; r1[threadIdx.x] = sd; r2[threadIdx.x] = mn; r3[threadIdx.x] = mx;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if ((int)threadIdx.x < k) {
-            r0[threadIdx.x] += r0[threadIdx.x + k]; r1[threadIdx.x] += r1[threadIdx.x + k];
-            r2[threadIdx.x] = fminf(r2[threadIdx.x], r2[threadIdx.x + k]); r3[threadIdx.x] = fmaxf(r3[threadIdx.x], r3[threadIdx.x + k]);
-        }
-        __syncthreads();
-    }
+    block_tree([&](int i, int j) {
+        r0[i] += r0[j]; r1[i] += r1[j];
+        r2[i] = fminf(r2[i], r2[j]); r3[i] = fmaxf(r3[i], r3[j]);
+    });
     if (threadIdx.x == 0) {
         double* o = ws + 4 * (size_t)blockIdx.x;
         o[0] = r0[0]; o[1] = r1[0]; o[2] = (double)r2[0]; o[3] = (double)r3[0];
@@ -198,14 +193,10 @@ __global__ void __launch_bounds__(256) batch_stats_total_kernel(const double* __
         mn = fmin(mn, ws[4 * i + 2]); mx = fmax(mx, ws[4 * i + 3]);
     }
     r0[threadIdx.x] = sum; r1[threadIdx.x] = sd; r2[threadIdx.x] = mn; r3[threadIdx.x] = mx;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if ((int)threadIdx.x < k) {
-            r0[threadIdx.x] += r0[threadIdx.x + k]; r1[threadIdx.x] += r1[threadIdx.x + k];
-            r2[threadIdx.x] = fmin(r2[threadIdx.x], r2[threadIdx.x + k]); r3[threadIdx.x] = fmax(r3[threadIdx.x], r3[threadIdx.x + k]);
-        }
-        __syncthreads();
-    }
+    block_tree([&](int i, int j) {
+        r0[i] += r0[j]; r1[i] += r1[j];
+        r2[i] = fmin(r2[i], r2[j]); r3[i] = fmax(r3[i], r3[j]);
+    });
     if (threadIdx.x == 0) {
         out[0] = (float)r2[0];                                // min
         out[1] = (float)r3[0];                                // max

@@ -1,6 +1,7 @@
 // FlowCompleter (algorithms/diffusion_animation/diffusion_animation.py:127-246, "DA") on the device: the sparse-flow sampler, the
 // magnitude-weighted flow loss and the null-embedding gradient.  No host sync, no float atomics: every reduction runs through
-// per-workgroup partials that one workgroup adds up in a fixed order, so every output is the same bits for the same inputs.
+// per-workgroup partials that one workgroup adds up in a fixed order (reduce.h; the totals are diffusion_common.h's
+// ordered_total_kernel), so every output is the same bits for the same inputs.
 //
 // Sampler (DA:159-175).  m = |flow| per pixel, s = batch mean of m, w = m + s (w = 1 everywhere when s = 0: the all-zero batch samples
 // uniformly).  Frame b keeps the k_b largest keys log(u) / w (Efraimidis-Spirakis: the distribution of sequential weighted sampling
@@ -10,7 +11,8 @@
 //   launch 3  sampler_cand_kernel    one workgroup per (frame, chunk): keys of the chunk and its top 8 (per-thread top 8 in registers,
 //                                    then a tree of merges in LDS); writes the null embedding over the chunk of the sparse tensor
 //   launch 4  sampler_merge_kernel   one workgroup per frame: top k_b of the frame's nblk x 8 candidates, dense flow at the picks, amax
-#include "common.h"
+#include "diffusion_common.h"
+#include "reduce.h"
 
 #include <cfloat>
 #include <climits>
@@ -91,34 +93,26 @@ __global__ void __launch_bounds__(CMP_THREADS) sampler_stats_kernel(const float*
         s += (double)m;
         mx = fmaxf(mx, m);
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        s += __shfl_down(s, o, 64);
-        mx = fmaxf(mx, __shfl_down(mx, o, 64));
-    }
+    // block_sum_waves spelled out, to carry the max (a float, exact in any order) under the sum's one barrier
+    wave_tree([&](auto from) { s += from(s); mx = fmaxf(mx, from(mx)); });
     __shared__ double ss[CMP_THREADS / 64];
     __shared__ float sm[CMP_THREADS / 64];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     if (lane == 0) { ss[wid] = s; sm[wid] = mx; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        psum[blockIdx.x] = (ss[0] + ss[1]) + (ss[2] + ss[3]);
-        pmax[blockIdx.x] = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
+        psum[blockIdx.x] = four_slots(ss);
+        pmax[blockIdx.x] = four_slots(sm, [](float a, float b) { return fmaxf(a, b); });
     }
 }
 
 // mean[0] = sum of the n partials / count, in a fixed order
 __global__ void __launch_bounds__(CMP_THREADS) sampler_mean_kernel(const double* __restrict__ psum, int n, double count,
                                                                   double* __restrict__ mean) {
-    __shared__ double red[CMP_THREADS];
     double a = 0.0;
     for (int i = threadIdx.x; i < n; i += CMP_THREADS) a += psum[i];
-    red[threadIdx.x] = a;
-    __syncthreads();
-    for (int k = CMP_THREADS / 2; k > 0; k >>= 1) {
-        if ((int)threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) mean[0] = red[0] / count;
+    a = block_sum_tree(a);
+    if (threadIdx.x == 0) mean[0] = a / count;
 }
 
 __global__ void __launch_bounds__(CMP_THREADS) sampler_cand_kernel(const float* __restrict__ dense, const float* __restrict__ u,
@@ -214,39 +208,8 @@ __global__ void __launch_bounds__(256) loss_partial_kernel(const float* __restri
         const float wgt = loss_weight(sqrtf(d0 * d0 + d1 * d1), amax[b], lmbd);
         acc += (double)(wgt * sqrtf(r0 * r0 + r1 * r1));
     }
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
-    __shared__ double sa[4];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    if (lane == 0) sa[wid] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = (sa[0] + sa[1]) + (sa[2] + sa[3]);
-}
-
-// fixed-order sum of the partials of `nblocks` workgroups (stride `stride` doubles, `nv` values each) -> res[0..nv), and res[v] / div as
-// float into outf[v]
-template <int NV>
-__global__ void __launch_bounds__(256) ordered_total_kernel(const double* __restrict__ part, int nblocks, double div,
-                                                           double* __restrict__ res, float* __restrict__ outf) {
-    __shared__ double sh[NV][256];
-    double a[NV];
-#pragma unroll
-    for (int v = 0; v < NV; ++v) a[v] = 0.0;
-    for (int i = threadIdx.x; i < nblocks; i += 256)
-#pragma unroll
-        for (int v = 0; v < NV; ++v) a[v] += part[(size_t)i * NV + v];
-#pragma unroll
-    for (int v = 0; v < NV; ++v) sh[v][threadIdx.x] = a[v];
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if ((int)threadIdx.x < k)
-#pragma unroll
-            for (int v = 0; v < NV; ++v) sh[v][threadIdx.x] += sh[v][threadIdx.x + k];
-        __syncthreads();
-    }
-    if (threadIdx.x < NV) {
-        if (res) res[threadIdx.x] = sh[threadIdx.x][0];
-        outf[threadIdx.x] = (float)(sh[threadIdx.x][0] / div);
-    }
+    acc = block_sum_waves(acc);
+    if (threadIdx.x == 0) part[blockIdx.x] = acc;
 }
 
 __global__ void __launch_bounds__(256) loss_grad_kernel(const float* __restrict__ out, const float* __restrict__ dense,
@@ -268,7 +231,7 @@ __global__ void __launch_bounds__(256) loss_grad_kernel(const float* __restrict_
 // per-workgroup (sum of dx[:, 0], sum of dx[:, 1]) over the pixels that are not picks of their frame
 __global__ void __launch_bounds__(256) null_grad_partial_kernel(const float* __restrict__ dx, const int* __restrict__ picks, int hw,
                                                                size_t n, double* __restrict__ part) {
-    double a0 = 0.0, a1 = 0.0;
+    double a[2] = {0.0, 0.0};
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const unsigned b = (unsigned)i / (unsigned)hw;
         const int p = (int)((unsigned)i - b * (unsigned)hw);
@@ -278,22 +241,12 @@ __global__ void __launch_bounds__(256) null_grad_partial_kernel(const float* __r
         for (int j = 0; j < CMP_TOPK; ++j) picked |= pk[j] == p;
         if (!picked) {
             const size_t o = b * 2 * hw + p;
-            a0 += (double)dx[o];
-            a1 += (double)dx[o + hw];
+            a[0] += (double)dx[o];
+            a[1] += (double)dx[o + hw];
         }
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        a0 += __shfl_down(a0, o, 64);
-        a1 += __shfl_down(a1, o, 64);
-    }
-    __shared__ double s0[4], s1[4];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    if (lane == 0) { s0[wid] = a0; s1[wid] = a1; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        part[2 * blockIdx.x] = (s0[0] + s0[1]) + (s0[2] + s0[3]);
-        part[2 * blockIdx.x + 1] = (s1[0] + s1[1]) + (s1[2] + s1[3]);
-    }
+    block_sum_waves(a);
+    if (threadIdx.x == 0) { part[2 * blockIdx.x] = a[0]; part[2 * blockIdx.x + 1] = a[1]; }
 }
 
 __global__ void __launch_bounds__(256) fill_nan_kernel(const float* __restrict__ sparse, const float* __restrict__ null_emb, int hw, size_t n,

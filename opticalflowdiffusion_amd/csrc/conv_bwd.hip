@@ -8,6 +8,7 @@
 //     (denoising_diffusion.py:109-112).
 // Nothing here adds across workgroups: no gacc_add, no deterministic-mode setter.
 #include "blocks.h"
+#include "reduce.h"
 
 namespace ofd {
 
@@ -51,15 +52,6 @@ __global__ void __launch_bounds__(256) wt_transpose_batched_kernel(const ofd_wei
 __global__ void __launch_bounds__(256) wgrad_finish_kernel(const float* __restrict__ acc, const float* __restrict__ w_raw, float* __restrict__ dst,
                                                            int Cout, int Cin, int Cin_pad, int ksize, float ws_eps, int unshuffle, int accumulate) {
     const int o = blockIdx.x, tid = threadIdx.x, taps = ksize * ksize, n = Cin * taps;
-    __shared__ double sh[256];
-    auto block_sum = [&](double v) {
-        sh[tid] = v;
-        __syncthreads();
-        for (int k = 128; k > 0; k >>= 1) { if (tid < k) sh[tid] += sh[tid + k]; __syncthreads(); }
-        const double r = sh[0];
-        __syncthreads();
-        return r;
-    };
     auto gval = [&](int i) {          // i over the reference's (ci, tap) order
         const int ci = i / taps, tap = i % taps;
         int cp = ci;
@@ -71,10 +63,10 @@ __global__ void __launch_bounds__(256) wgrad_finish_kernel(const float* __restri
     if (ws_eps >= 0.0f) {
         double s = 0.0;
         for (int i = tid; i < n; i += 256) s += (double)wo[i];
-        const double m = block_sum(s) / n;
+        const double m = block_sum_tree(s, true) / n;           // reduce.h's 256-slot tree; the four calls share its slots
         double v = 0.0;
         for (int i = tid; i < n; i += 256) { const double d = (double)wo[i] - m; v += d * d; }
-        const double var = block_sum(v) / n;
+        const double var = block_sum_tree(v, true) / n;
         mean = (float)m;
         rstd = rsqrtf((float)var + ws_eps);
         // (the accumulator reads are one 4-byte element every Cout floats: eight of them in flight per thread)
@@ -95,8 +87,8 @@ __global__ void __launch_bounds__(256) wgrad_finish_kernel(const float* __restri
                     b2 += g * (double)((wv[u] - mean) * rstd);
                 }
         }
-        mg = (float)(block_sum(a) / n);
-        mgw = (float)(block_sum(b2) / n);
+        mg = (float)(block_sum_tree(a, true) / n);
+        mgw = (float)(block_sum_tree(b2, true) / n);
     }
     for (int i0 = tid; i0 < n; i0 += 256 * 8) {
         float gv[8];

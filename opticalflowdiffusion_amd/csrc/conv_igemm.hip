@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include "conv_common.h"
 #include "blocks.h"
+#include "reduce.h"
 
 namespace ofd {
 
@@ -419,23 +420,15 @@ __device__ __forceinline__ void conv_weight_prep_body(const float* __restrict__ 
     const int tid = threadIdx.x;
     const int taps = ksize * ksize, n = Cin * taps;
     const float* wo = w + (size_t)o * n;
-    __shared__ double sh[256];
     float mean = 0.0f, rstd = 1.0f;
-    if (ws_eps >= 0.0f) {       // DD:109-112: biased variance over (Cin, kh, kw), fp32 result
+    if (ws_eps >= 0.0f) {       // DD:109-112: biased variance over (Cin, kh, kw), fp32 result; both moments in reduce.h's fixed order
         double s = 0.0;
         for (int i = tid; i < n; i += 256) s += (double)wo[i];
-        sh[tid] = s;
-        __syncthreads();
-        for (int k = 128; k > 0; k >>= 1) { if (tid < k) sh[tid] += sh[tid + k]; __syncthreads(); }
-        const double m = sh[0] / n;
-        __syncthreads();
+        const double m = block_sum_tree(s, true) / n;
         double v = 0.0;
         for (int i = tid; i < n; i += 256) { const double d = (double)wo[i] - m; v += d * d; }
-        sh[tid] = v;
-        __syncthreads();
-        for (int k = 128; k > 0; k >>= 1) { if (tid < k) sh[tid] += sh[tid + k]; __syncthreads(); }
         mean = (float)m;
-        rstd = rsqrtf((float)(sh[0] / n) + ws_eps);
+        rstd = rsqrtf((float)(block_sum_tree(v) / n) + ws_eps);
     }
     const int c8n = Cin_pad / 8;
     for (int i = tid; i < Cin_pad * taps; i += 256) {

@@ -2,6 +2,7 @@
 // NaN-masked squared-error reduction (warp.py:260-271 + torch.nanmean, DD:908,973).
 // HBM-bound streaming kernels: float4 accesses, per-sample scalar coefficients.
 #include "diffusion_common.h"
+#include "reduce.h"
 
 namespace ofd {
 
@@ -282,44 +283,22 @@ __global__ void __launch_bounds__(256) cond_drop_kernel(const float* __restrict_
     }
 }
 
-// per-workgroup (sum, count) -> part[2 * block]; nan_mse_total_kernel adds the workgroups up in a fixed order (no atomics: the loss is
-// the same number, bit for bit, for the same inputs)
+// per-workgroup (sum, count) -> part[2 * block]; ordered_total_kernel<2> adds the workgroups up in a fixed order (no atomics: the loss is
+// the same number, bit for bit, for the same inputs; the order is reduce.h's)
 constexpr int NAN_MSE_BLOCKS = 2048;
 __global__ void __launch_bounds__(256) nan_mse_kernel(const float* __restrict__ pred, const float* __restrict__ target,
                                                       size_t n, double* __restrict__ part) {
-    double sum = 0.0, cnt = 0.0;
+    double v[2] = {0.0, 0.0};      // sum, count
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const float p = pred[i], t = target[i];
         if (!(isnan(p) || isnan(t))) {
             const float d = p - t;
-            sum += (double)(d * d);
-            cnt += 1.0;
+            v[0] += (double)(d * d);
+            v[1] += 1.0;
         }
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        sum += __shfl_down(sum, o, 64);
-        cnt += __shfl_down(cnt, o, 64);
-    }
-    __shared__ double ssum[4], scnt[4];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    if (lane == 0) { ssum[wid] = sum; scnt[wid] = cnt; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        part[2 * blockIdx.x] = (ssum[0] + ssum[1]) + (ssum[2] + ssum[3]);
-        part[2 * blockIdx.x + 1] = (scnt[0] + scnt[1]) + (scnt[2] + scnt[3]);
-    }
-}
-__global__ void __launch_bounds__(256) nan_mse_total_kernel(double* __restrict__ result, int nblocks) {
-    __shared__ double s1[256], s2[256];
-    double a = 0.0, c = 0.0;
-    for (int i = threadIdx.x; i < nblocks; i += 256) { a += result[2 + 2 * i]; c += result[3 + 2 * i]; }
-    s1[threadIdx.x] = a; s2[threadIdx.x] = c;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if ((int)threadIdx.x < k) { s1[threadIdx.x] += s1[threadIdx.x + k]; s2[threadIdx.x] += s2[threadIdx.x + k]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { result[0] = s1[0]; result[1] = s2[0]; }
+    block_sum_waves(v);
+    if (threadIdx.x == 0) { part[2 * blockIdx.x] = v[0]; part[2 * blockIdx.x + 1] = v[1]; }
 }
 
 // backward of mean over the non-NaN entries: dpred = 2 (pred - target) * gout / count where both are finite
@@ -667,7 +646,7 @@ extern "C" int ofd_nan_mse_sum(const float* pred, const float* target, size_t n,
     size_t b = (n + 255) / 256;
     if (b > NAN_MSE_BLOCKS) b = NAN_MSE_BLOCKS;
     nan_mse_kernel<<<(unsigned)b, 256, 0, s>>>(pred, target, n, result + 2);
-    nan_mse_total_kernel<<<1, 256, 0, s>>>(result, (int)b);
+    ordered_total_kernel<2><<<1, 256, 0, s>>>(result + 2, (int)b, 1.0, result, nullptr);
     OFD_LAUNCH_CHECK();
     return OFD_OK;
 }

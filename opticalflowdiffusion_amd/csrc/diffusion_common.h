@@ -1,10 +1,12 @@
 // What the reverse-step kernels (diffusion.hip) and the x_start quantile (x0_quantile.hip) share: the element groups, the unclamped x_start of
 // an objective, the guided combination, and the float4 / scalar launch choice.  Both files are built with -ffp-contract=off, so the value one
-// of them ranks is, bit for bit, the value the other clamps.
+// of them ranks is, bit for bit, the value the other clamps.  Also ordered_total_kernel, the fixed-order total that the losses of diffusion.hip
+// and completer.hip launch after their per-workgroup partials.
 #pragma once
 #include <type_traits>
 
 #include "common.h"
+#include "reduce.h"
 
 namespace ofd {
 
@@ -72,6 +74,27 @@ template <typename F> static void obj_dispatch(int obj, F&& f) {
     if (obj == PRED_NOISE) f(std::integral_constant<int, PRED_NOISE>{});
     else if (obj == PRED_V) f(std::integral_constant<int, PRED_V>{});
     else f(std::integral_constant<int, PRED_X0>{});
+}
+
+// The second launch of every two-launch loss (diffusion.hip, completer.hip): one workgroup adds the partials of `nblocks` workgroups
+// (`NV` doubles each, partial i at part[i * NV]) in reduce.h's fixed order -> res[0..NV) (null: not stored), and res[v] / div as float
+// -> outf[v] (null: not stored).  part may lie behind res in the same buffer.
+template <int NV>
+__global__ void __launch_bounds__(256) ordered_total_kernel(const double* part, int nblocks, double div, double* res, float* outf) {
+    double a[NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) a[v] = 0.0;
+    for (int i = threadIdx.x; i < nblocks; i += 256)
+#pragma unroll
+        for (int v = 0; v < NV; ++v) a[v] += part[(size_t)i * NV + v];
+    block_sum_tree(a);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            if (res) res[v] = a[v];
+            if (outf) outf[v] = (float)(a[v] / div);
+        }
+    }
 }
 
 }  // namespace ofd

@@ -1,8 +1,9 @@
 // Per-sample NaN-masked squared-error sums and their gradient (rules R1-R4 of include/ofd.h): what an SNR-weighted training loss needs
-// from the reduction.  The structure is nan_mse_kernel / nan_mse_total_kernel's (diffusion.hip): per-workgroup partials, then a
-// fixed-order total, no float atomics; here the workgroups are assigned per sample and the loads are 16 bytes wide.
+// from the reduction.  Per-workgroup partials in the fixed order of reduce.h (waves, then four slots), then a fixed-order total of its
+// own (nan_mse_rows_total_kernel), no float atomics; the workgroups are assigned per sample and the loads are 16 bytes wide.
 // HBM-bound: the forward streams two arrays once, the backward three.
 #include "diffusion_common.h"
+#include "reduce.h"
 
 namespace ofd {
 
@@ -39,8 +40,6 @@ __device__ __forceinline__ void rows_accumulate(const EwVec<VEC>& p, const EwVec
 template <int VEC>
 __global__ void __launch_bounds__(256) nan_mse_rows_kernel(const float* __restrict__ pred, const float* __restrict__ target,
                                                            size_t n_per_sample, unsigned wps, size_t nslots, double* __restrict__ part) {
-    __shared__ double ssum[4], scnt[4];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const size_t nv = n_per_sample / VEC, step = (size_t)wps * 256;
     for (size_t slot = blockIdx.x; slot < nslots; slot += gridDim.x) {
         const size_t b = slot / wps, w = slot % wps;
@@ -56,18 +55,9 @@ __global__ void __launch_bounds__(256) nan_mse_rows_kernel(const float* __restri
             rows_accumulate<VEC>(p1, t1, sum, cnt);
         }
         if (i < nv) rows_accumulate<VEC>(ew_load<VEC>(p + i * VEC), ew_load<VEC>(t + i * VEC), sum, cnt);
-        double c = (double)cnt;                                    // exact: a count is far below 2^53
-        for (int o = 32; o > 0; o >>= 1) {
-            sum += __shfl_down(sum, o, 64);
-            c += __shfl_down(c, o, 64);
-        }
-        if (lane == 0) { ssum[wid] = sum; scnt[wid] = c; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            part[2 * slot] = (ssum[0] + ssum[1]) + (ssum[2] + ssum[3]);
-            part[2 * slot + 1] = (scnt[0] + scnt[1]) + (scnt[2] + scnt[3]);
-        }
-        __syncthreads();                                           // the next slot reuses ssum / scnt
+        double v[2] = {sum, (double)cnt};                          // exact: a count is far below 2^53
+        block_sum_waves(v, true);                                  // reuse: the next slot comes back to it
+        if (threadIdx.x == 0) { part[2 * slot] = v[0]; part[2 * slot + 1] = v[1]; }
     }
 }
 

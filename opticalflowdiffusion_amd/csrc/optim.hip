@@ -5,6 +5,7 @@
 // host synchronisation (the clip coefficient stays on the device).  ofd_adam_step_ema is the same step with an exponential moving
 // average of the parameters kept in the same pass (the weights a diffusion model is sampled from).
 #include "common.h"
+#include "reduce.h"
 
 namespace ofd {
 
@@ -47,28 +48,19 @@ __global__ void __launch_bounds__(256) grad_sqnorm_kernel(const Row* __restrict_
         const float g = t.g[i];
         s += (double)g * (double)g;
     }
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-    __shared__ double sh[4];
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+    s = block_sum_waves(s);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
 // clip_grad_norm_: coef = min(1, max_norm / (sqrt(sum) + 1e-6)); max_norm <= 0 disables clipping
-// acc[0] <- sum of acc[1 .. n_tasks] (thread t adds tasks t, t + 256, ...; then a fixed tree)
+// acc[0] <- sum of acc[1 .. n_tasks] (thread t adds tasks t, t + 256, ...; then reduce.h's 256-slot tree)
 __global__ void __launch_bounds__(256) clip_coef_kernel(double* __restrict__ acc, int n_tasks, float max_norm, float* __restrict__ coef, float* __restrict__ total_norm) {
-    __shared__ double sh[256];
     double s = 0.0;
     for (int i = threadIdx.x; i < n_tasks; i += 256) s += acc[1 + i];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if ((int)threadIdx.x < k) sh[threadIdx.x] += sh[threadIdx.x + k];
-        __syncthreads();
-    }
+    s = block_sum_tree(s);
     if (threadIdx.x != 0) return;
-    acc[0] = sh[0];
-    const float norm = (float)sqrt(sh[0]);
+    acc[0] = s;
+    const float norm = (float)sqrt(s);
     if (total_norm) *total_norm = norm;
     float c = 1.0f;
     if (max_norm > 0.0f) c = fminf(1.0f, max_norm / (norm + 1e-6f));

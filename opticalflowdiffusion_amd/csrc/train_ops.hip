@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include "blocks.h"
 #include "det.h"
+#include "reduce.h"
 
 namespace ofd {
 
@@ -109,7 +110,6 @@ __global__ void __launch_bounds__(256) gnbwd_finalize_kernel(const float* __rest
                                                              const float* __restrict__ a_aff, const float* __restrict__ ss, int ss_stride, int ss_offset,
                                                              float* __restrict__ c2c3, float* __restrict__ dgamma, float* __restrict__ dbeta,
                                                              float* __restrict__ dss, float* __restrict__ dconv_bias) {
-    __shared__ double g1s[256], g2s[256];
     const int b = blockIdx.x, g = blockIdx.y, tid = threadIdx.x, gs = C / 8;     // gs <= 64: at most one channel per thread
     const float mu = stats[((size_t)b * 8 + g) * 2], r = stats[((size_t)b * 8 + g) * 2 + 1];
     double G1 = 0.0, G2 = 0.0, A1 = 0.0, A3 = 0.0;
@@ -147,15 +147,10 @@ __global__ void __launch_bounds__(256) gnbwd_finalize_kernel(const float* __rest
         G1 = (double)gamma[c] * scp * A1;
         G2 = (double)gamma[c] * scp * S;
     }
-    g1s[tid] = G1;
-    g2s[tid] = G2;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if (tid < k) { g1s[tid] += g1s[tid + k]; g2s[tid] += g2s[tid + k]; }
-        __syncthreads();
-    }
+    double G[2] = {G1, G2};
+    block_sum_tree(G);                                  // the group sums, in reduce.h's fixed order
     const double rr = (double)r, N = count;
-    const double c2 = -rr * rr * g2s[0] / N, c3 = -rr * g1s[0] / N + rr * rr * (double)mu * g2s[0] / N;
+    const double c2 = -rr * rr * G[1] / N, c3 = -rr * G[0] / N + rr * rr * (double)mu * G[1] / N;
     if (tid == 0) {
         c2c3[((size_t)b * 8 + g) * 2] = (float)c2;
         c2c3[((size_t)b * 8 + g) * 2 + 1] = (float)c3;
