@@ -583,7 +583,7 @@ int ofd_conv_weight_prep(const float* w_oihw, void* w_out, int Cout, int Cin, in
                          float ws_eps, int unshuffle, void* stream);
 
 /* ---------------------------------------------------------------- conv backward (training) --
- * (conv_wgrad.hip: ofd_conv_wgrad, ofd_conv7_wgrad, ofd_conv7_wgrad_c, ofd_channel_sum; conv_bwd.hip: the layout kernels around them)
+ * (conv_wgrad.hip: ofd_conv_wgrad, ofd_conv7_wgrad, ofd_conv7_wgrad_c, their _bias forms, ofd_channel_sum; conv_bwd.hip: the layout kernels around them)
  * data gradient  : run ofd_conv_forward on dY (source, Cout channels) with the weights produced by
  *                  ofd_conv_dgrad_weight_prep (tap-flipped, in/out transposed); output has Cin channels;
  *                  ofd_grad_scatter applies the adjoint of concat / up-sample (mode 1) / unshuffle (mode 2).
@@ -598,6 +598,11 @@ int ofd_conv_wgrad(const ofd_conv_args* fwd, const void* dy, float* dw_acc, void
 int ofd_conv7_wgrad(const void* x16, const void* dy, float* dw_acc, int B, int H, int W, void* stream);
 /* the same for an input packed to `channels` = 8, 16, 32 or 48 (pixel stride); dw_acc is [49][channels][64] */
 int ofd_conv7_wgrad_c(const void* x, const void* dy, float* dw_acc, int B, int H, int W, int channels, void* stream);
+/* ofd_conv_wgrad / ofd_conv7_wgrad_c as the training executor calls them: the same launch also ADDS the column sums of dY (the bias
+ * gradient) to dbias [Cout] fp32 (64 for the 7x7 conv); dbias must not be NULL.  With dbias a 1x1 conv of Cout = 384 over one plain source
+ * runs the 64 x 64 block kernel, not the to_qkv kernel (which sums no bias). */
+int ofd_conv_wgrad_bias(const ofd_conv_args* fwd, const void* dy, float* dw_acc, float* dbias, void* stream);
+int ofd_conv7_wgrad_bias(const void* x, const void* dy, float* dw_acc, float* dbias, int B, int H, int W, int channels, void* stream);
 /* data gradient of the 7x7 init conv w.r.t. its first cx <= 16 input channels: dy NHWC bf16 [B][H][W][64], w_t the tap-flipped transposed
  * weights of ofd_conv_dgrad_weight_prep (Cin = cin_pad = 16, 32 or 48) -> dx NCHW fp32 [B][cx][H][W] = scale * conv_transpose(dy)
  * (written, not added; deterministic: a gather, no atomics) */

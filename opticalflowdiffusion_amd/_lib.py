@@ -131,6 +131,8 @@ SIGNATURES = {
     "ofd_conv_wgrad": (c_int, [ctypes.POINTER(ConvArgs), c_void_p, c_void_p, c_void_p]),
     "ofd_conv7_wgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "ofd_conv7_wgrad_c": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "ofd_conv_wgrad_bias": (c_int, [ctypes.POINTER(ConvArgs), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ofd_conv7_wgrad_bias": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ofd_conv_wgrad_finish": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_float, c_int, c_int, c_void_p]),
     "ofd_grad_scatter": (c_int, [c_void_p, c_int, c_int, c_void_p] + [c_int] * 8 + [c_void_p]),
     "ofd_channel_sum": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p]),

@@ -943,6 +943,15 @@ extern "C" int ofd_conv7_wgrad_c(const void* x, const void* dy, float* dw_acc, i
     OFD_CHECK_ARG(x && dy && dw_acc, "conv7_wgrad_c: null argument");
     return k_conv7_wgrad((const bf16_t*)x, (const bf16_t*)dy, dw_acc, B, H, W, (hipStream_t)stream, nullptr, channels);
 }
+// the forms the training executor calls: the column sums of dY are added to dbias [Cout] by the same kernels (their do_bias / dbias paths)
+extern "C" int ofd_conv_wgrad_bias(const ofd_conv_args* fwd, const void* dy, float* dw_acc, float* dbias, void* stream) {
+    OFD_CHECK_ARG(dbias, "conv_wgrad_bias: null argument");
+    return k_conv_wgrad(fwd, (const bf16_t*)dy, dw_acc, (hipStream_t)stream, dbias);
+}
+extern "C" int ofd_conv7_wgrad_bias(const void* x, const void* dy, float* dw_acc, float* dbias, int B, int H, int W, int channels, void* stream) {
+    OFD_CHECK_ARG(x && dy && dw_acc && dbias, "conv7_wgrad_bias: null argument");
+    return k_conv7_wgrad((const bf16_t*)x, (const bf16_t*)dy, dw_acc, B, H, W, (hipStream_t)stream, dbias, channels);
+}
 extern "C" int ofd_channel_sum(const void* dy, float* out, size_t npix, int C, void* stream) {
     OFD_CHECK_ARG(dy && out, "channel_sum: null argument");
     return k_channel_sum((const bf16_t*)dy, out, npix, C, (hipStream_t)stream);

@@ -100,7 +100,8 @@ def test_conv3x3_weight_gradient_with_input_prologue(L, B, H, W, Cin, Cout):
 @pytest.mark.parametrize("Cin,B,H,W", [(128, 2, 13, 21), (64, 3, 40, 56)])
 def test_conv1x1_weight_gradient_qkv_kernel(L, Cin, B, H, W):
     """to_qkv shapes (DD:222, DD:252): Cout = 384 over one plain source (conv_wgrad1_qkv_kernel, a ci block and all 384 output channels
-    per workgroup); 546 pixels are no multiple of its 64-pixel tile, (3, 40, 56) gives a workgroup several tiles; against autograd."""
+    per workgroup); 546 pixels are no multiple of its 64-pixel tile; against autograd.  At both shapes a workgroup has ONE tile (9 tiles
+    against 256 workgroups wanted, 105 against 512): the walk over several tiles is test_conv_wgrad_walk_gpu.py's."""
     torch.manual_seed(17)
     x = q(torch.randn(B, Cin, H, W))
     w = (torch.randn(384, Cin, 1, 1) / math.sqrt(Cin)).requires_grad_(True)
@@ -117,8 +118,9 @@ def test_conv1x1_weight_gradient_qkv_kernel(L, Cin, B, H, W):
 def test_conv1x1_weight_gradient_wide_kernel(L, Cout, cins, B, H, W, monkeypatch):
     """res_conv / to_out.0 shapes (DD:212, DD:226): the kernel that owns a ci block and ALL output channels (conv_wgrad1_wide_kernel), over
     one or two concatenated sources and a pixel count that is not a multiple of its 64-pixel tile; Cout = 512 (ups.0's res_conv, the mid
-    attention's to_out) as two 256-channel column blocks; (3, 40, 56): several tiles per workgroup, so the register prefetch of the next
-    tile runs; against autograd."""
+    attention's to_out) as two 256-channel column blocks; against autograd.  At every shape here a workgroup has ONE tile ((3, 40, 56) is
+    105 tiles against 171 workgroups wanted), so the register prefetch of a next tile never runs: the walk over several tiles and the fused
+    bias sums are test_conv_wgrad_walk_gpu.py's."""
     torch.manual_seed(7)
     xs = [q(torch.randn(B, c, H, W)).requires_grad_(True) for c in cins]
     cin = sum(cins)

@@ -77,6 +77,11 @@ def test_argument_errors_without_gpu(libpath):
     assert L.ofd_linear_attention_block(odd, *[p] * 8, 1, 4, 64, 1e-5, 1e-3, None) == -1 and b"aligned" in L.ofd_last_error()
     assert L.ofd_linear_attention_block(p, odd, *[p] * 7, 1, 4, 64, 1e-5, 1e-3, None) == -1 and b"aligned" in L.ofd_last_error()
     assert L.ofd_version() >= 4                                            # the minor went up with the new symbols
+    # the weight-gradient entry points that take a bias accumulator: it is not optional there
+    assert L.ofd_conv_wgrad_bias(ctypes.byref(args), p, p, None, None) == -1 and b"conv_wgrad_bias: null" in L.ofd_last_error()
+    assert L.ofd_conv7_wgrad_bias(p, p, p, None, 1, 8, 32, 8, None) == -1 and b"conv7_wgrad_bias: null" in L.ofd_last_error()
+    assert L.ofd_conv7_wgrad_bias(p, p, p, p, 1, 8, 32, 24, None) == -1 and b"packed to 24 channels" in L.ofd_last_error()
+    assert L.ofd_version() >= 7
 
 
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
