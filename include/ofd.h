@@ -27,6 +27,7 @@
  *                                                                          ofd_ddim_update_thresh, ofd_dpmpp_update_thresh
  *   (not in the reference)            photometric guidance of sampling  -> ofd_photo_pyramid, ofd_photo_guide
  *   (not in the reference)            two-frame interpolation (softmax splatting) -> ofd_interp_prep, ofd_interp_merge
+ *   (not in the reference)            joint bilateral upsampling (reduced-size sampling) -> ofd_joint_upsample
  *   denoising_diffusion.py:806-812    q_sample                          -> ofd_q_sample
  *   denoising_diffusion.py:844-879,985-993  p_losses noise / target     -> ofd_diffusion_prep
  *   denoising_diffusion.py:73-77      (un)normalize                     -> ofd_range_map
@@ -151,6 +152,38 @@ int ofd_pushpull_fill(const float* x, const float* weight, float* out, void* wor
 int ofd_interp_prep(const float* frame1, const float* frame2, const float* flow12, const float* flow21, const float* times, int n,
                     float alpha, float beta, float oob, float zmax, float* ten_in, float* flows, int B, int C, int H, int W, void* stream);
 int ofd_interp_merge(const float* acc, float* colour, float* weight, int Bn, int C, int H, int W, void* stream);
+
+/* Joint bilateral upsampling (Kopf, Cohen, Lischinski & Uyttendaele, "Joint Bilateral Upsampling", SIGGRAPH 2007).  An addition: the
+ * reference samples at the frame's own size only.  A field computed on a frame box-reduced by s is carried back to the frame's size;
+ * each output pixel takes its value from the low-resolution neighbours whose guide colour matches its own, so an edge of the field
+ * snaps to the edge of the full-resolution guide instead of being smeared across it.  All arithmetic fp32.
+ * lo: (B,C,h,w), guide_lo: (B,Cg,h,w) (the guide at low resolution, e.g. its s x s box average), guide: (B,Cg,H,W), out: (B,C,H,W) with
+ * H = h*s, W = w*s.  Per sample and output pixel (x, y):
+ *   window   nx = 2x + 1 - s and i0 = floor(nx / (2s)) in integers (the low-resolution cell whose centre lies at or left of the pixel's
+ *            centre; -1 at the left border), fx = (nx - 2s*i0) / (2s) in [0, 1): one fp32 division of two exact integers.  The taps
+ *            are the columns i = i0 - radius + 1 ... i0 + radius; j0, fy and the rows j likewise from y.  Rows run j ascending, and
+ *            within a row i ascending.
+ *   skipped  a tap outside [0, w-1] x [0, h-1]; a tap where any of the C values of lo is non-finite.
+ *   score    dx = (i - i0) - fx, dy = (j - j0) - fy;  d2 = (sum over c, ascending, of (guide_c(x,y) - guide_lo_c(i,j))^2) / Cg;
+ *            z = -(dx*dx + dy*dy) / (2 sigma_s^2) - d2 / (2 sigma_r^2), the denominators 2 * (sigma * sigma) in fp32.  sigma_r = +inf
+ *            switches the guide off (d2 / inf = 0).  A tap whose z is NaN (a NaN of either guide, inf / inf) is skipped.  The second
+ *            term is evaluated as (the sum over c) * k with k = 1 / (Cg * 2 sigma_r^2) rounded to fp32 once (0 for sigma_r = +inf): two
+ *            roundings, as the two divisions have.
+ *   output   m = the largest z over the kept taps;  out_c = gain * ((sum of exp(z - m) * lo_c) / (sum of exp(z - m))), one division per
+ *            channel, then one multiply.  NaN in all C channels when no tap is kept, or when every kept z is -inf.  The maximum is
+ *            formed online: a tap with a larger z rescales both running sums by exp(m_old - z) first.  The quotient is evaluated as
+ *            r_c + (sum of exp(z - m) * (lo_c - r_c)) / (sum of exp(z - m)) with r the lo of the pixel's own cell (max(i0, 0),
+ *            max(j0, 0)), 0 where that tap is skipped as non-finite: the same number, with a rounding error that scales with the
+ *            spread of the taps instead of their size (a constant lo comes back exactly).  A tap whose z is -inf has weight 0
+ *            under any maximum and is left out of the sums like a skipped one; the output is the same.
+ * gain turns the units of lo into those of out: s for a flow in low-resolution pixels that is wanted in full-resolution pixels.
+ * One launch; no atomics, no host sync, the same input gives the same bits.  A workgroup stages the low-resolution window of its 64 x 16
+ * output tile in LDS and reads the taps from there, the first term of z from a table of its (s * 2 radius)^2 possible values; guide loads and out stores are 16 bytes wide where W % 4 == 0 and guide and out
+ * are 16-byte aligned, scalar otherwise.  1 <= C <= 8, 1 <= Cg <= 4, 2 <= s <= 8, 1 <= radius <= 3; sigma_s finite and > 0; sigma_r > 0,
+ * +inf allowed; gain finite; H, W < 2^30 and B*(C+Cg)*H*W < 2^40.  Outputs must not alias inputs.  Argument errors return OFD_ERR_ARG and
+ * set ofd_last_error before any GPU work.  Compulsory traffic: 4 * B * (H*W*(Cg + C) + h*w*(Cg + C)) bytes. */
+int ofd_joint_upsample(const float* lo, const float* guide_lo, const float* guide, float* out, int B, int C, int Cg, int h, int w, int s,
+                       int radius, float sigma_s, float sigma_r, float gain, void* stream);
 
 /* ------------------------------------------------------------ grid_sample warp (WP:95-119) -
  * second: (B,C,H,W), flow: (B,2,H,W) exactly as handed to the reference's warp(mode='backward'):

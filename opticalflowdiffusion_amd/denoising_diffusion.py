@@ -723,6 +723,19 @@ class ConditionalDiffusion(nn.Module):
         s = self.image_size
         return (s, s) if isinstance(s, int) else tuple(s)
 
+    @staticmethod
+    def _call_hw(image_size, external_cond=None):
+        """the per-call (H, W) of sample(image_size=): two positive integers, which external_cond must match (ValueError)"""
+        try:
+            hw = tuple(image_size)
+        except TypeError:
+            raise ValueError(f"image_size must be None or (H, W), two positive integers, got {image_size!r}")
+        if len(hw) != 2 or any(isinstance(v, bool) or not isinstance(v, int) or v < 1 for v in hw):
+            raise ValueError(f"image_size must be None or (H, W), two positive integers, got {image_size!r}")
+        if torch.is_tensor(external_cond) and tuple(external_cond.shape[-2:]) != hw:
+            raise ValueError(f"external_cond must have the call's image_size {hw}, got {tuple(external_cond.shape)}")
+        return hw
+
     # -- network call ------------------------------------------------------------------------
     def model_with_condition(self, x, t, x_self_cond, external_cond=None, additional_tgt=None):
         assert self.conditioned == torch.is_tensor(external_cond)                      # DD:627
@@ -1250,7 +1263,7 @@ class ConditionalDiffusion(nn.Module):
 
     @torch.no_grad()
     def sample(self, batch_size=16, return_all_timesteps=False, external_cond=None, additional_tgt=None, known=None, resample=1,
-               guidance_scale=UNSET, dynamic_threshold=UNSET, threshold_max=UNSET, photo=None):
+               guidance_scale=UNSET, dynamic_threshold=UNSET, threshold_max=UNSET, photo=None, image_size=None):
         """DD:776-784, with image_size allowed to be (H, W).  external_cond is normalised once per call (DD:778-779); the loops
         unnormalise what they return.
 
@@ -1281,8 +1294,12 @@ class ConditionalDiffusion(nn.Module):
         Gauss-Newton step towards first(p) ~ second(p + f(p)) by rewriting the model output(s); the quantile launches and the update
         launch read the rewritten output(s), so it composes with every sampler and objective, `known` / `resample`, `guidance_scale`
         and `dynamic_threshold`.  The frames are used as given (not normalised here).  It guides x_start only and does not
-        differentiate through the model.  Not combinable with `additional_tgt`.  None is the present path, launch for launch."""
-        H, W = self._hw()
+        differentiate through the model.  Not combinable with `additional_tgt`.  None is the present path, launch for launch.
+
+        `image_size` (not in the reference): an (H, W) that replaces the constructor's for this call only -- the Unet takes any size
+        its levels divide, so a chain may run on a reduced frame (FlowDiffuser's `sample_scale`).  `known`, `photo` and
+        `external_cond` must have that size.  None is the constructor's size: the present path, bit for bit under one seed."""
+        H, W = self._hw() if image_size is None else self._call_hw(image_size, external_cond)
         shape = (batch_size, self.channels, H, W)
         ddpm = self.sampler != "dpmpp" and not self.is_ddim_sampling
         known = self._check_known(shape, known, resample, additional_tgt, ddpm=ddpm)

@@ -10,7 +10,9 @@ with the keys of configurations/algorithm/flow_diffuser.yaml (+ optional `image_
 `sampler_spacing` of ConditionalDiffusion, its classifier-free guidance keys `cond_drop_prob`, `guidance_scale` (target 'flow'
 only), its dynamic thresholding keys `dynamic_threshold`, `threshold_max`, its training-loss keys `loss_weighting`,
 `min_snr_loss_weight`, `min_snr_gamma`, `loss_by_timestep`, its photometric guidance keys `photo_scale`, `photo_levels`, `photo_damping`,
-`photo_schedule` (what `sample(target_frame=)` / `estimate_flow` use), `log_animation` (N > 0: validation_step also logs an N-frame `animate` strip), and the `ema_*` keys and `sample_with_ema` of ema.EMA_DEFAULTS, which are not in the reference).
+`photo_schedule` (what `sample(target_frame=)` / `estimate_flow` use), the reduced-size sampling keys `sample_scale`, `upsample_radius`,
+`upsample_sigma_s`, `upsample_sigma_r` (`sample` runs the chain on the frame box-reduced by `sample_scale` and carries the flow back with
+`warp.upsample_flow`), `log_animation` (N > 0: validation_step also logs an N-frame `animate` strip), and the `ema_*` keys and `sample_with_ema` of ema.EMA_DEFAULTS, which are not in the reference).
 """
 import os
 
@@ -18,7 +20,7 @@ import torch
 
 from .denoising_diffusion import UNSET, PhotoGuide, Unet, ConditionalDiffusion, loss_by_timestep
 from .ema import EMA_DEFAULTS, EmaMixin, ema_optimizer_kwargs
-from .warp import interpolate_frames, warp
+from .warp import box_reduce, interpolate_frames, upsample_flow, upsample_params, warp
 from . import _lib as L
 
 try:                                                   # pragma: no cover - not installed in this image
@@ -49,6 +51,7 @@ class _Cfg:
                      cond_drop_prob=0.0, guidance_scale=None, dynamic_threshold=None, threshold_max=None,
                      loss_weighting=None, min_snr_loss_weight=True, min_snr_gamma=5, loss_by_timestep=False, log_animation=0,
                      photo_scale=1.0, photo_levels=(1, 2, 4), photo_damping=1e-2, photo_schedule="constant",
+                     sample_scale=1, upsample_radius=2, upsample_sigma_s=1.0, upsample_sigma_r=0.1,
                      **EMA_DEFAULTS)
 
     def __init__(self, cfg):
@@ -322,9 +325,41 @@ class FlowDiffuser(EmaMixin, _Base):
                           scale=pick(photo_scale, "photo_scale"), levels=tuple(pick(photo_levels, "photo_levels")),
                           damping=pick(photo_damping, "photo_damping"), schedule=pick(photo_schedule, "photo_schedule"))
 
+    def reduced_sampling(self, cond, known_flow=None, sample_scale=UNSET, upsample_radius=UNSET, upsample_sigma_s=UNSET,
+                         upsample_sigma_r=UNSET):
+        """(s, the window and widths of `warp.upsample_flow`) of a `sample` call: `sample_scale` and the `upsample_*` values from the
+        cfg keys of those names unless given.  s = 1 is full-size sampling; the rules of s > 1 are checked here (ValueError): host
+        logic, any device, no engine call."""
+        pick = lambda v, key: getattr(self.cfg, key) if v is UNSET else v
+        s = pick(sample_scale, "sample_scale")
+        if isinstance(s, bool) or not isinstance(s, int) or not 1 <= s <= 8:
+            raise ValueError(f"sample_scale must be an integer in 1..8, got {s!r}")
+        if s == 1:
+            return 1, None
+        up = upsample_params(pick(upsample_radius, "upsample_radius"), pick(upsample_sigma_s, "upsample_sigma_s"),
+                             pick(upsample_sigma_r, "upsample_sigma_r"))
+        if not self.is_diffusion:
+            raise ValueError("sample_scale > 1 needs a diffusion model: is_diffusion=False is a plain regression, there is no chain to "
+                             "run at a reduced size")
+        if self.latent:
+            raise ValueError("sample_scale > 1 is not supported with latent=True: the chain already runs on the Autoencoder's reduced "
+                             "grid, and the flow would have to be upsampled along latents, not a frame")
+        if self.target not in ("flow", "joint"):
+            raise ValueError(f"sample_scale > 1 is not supported for target={self.target!r}: there the flow is an extra model output, "
+                             "not part of the diffused tensor")
+        if known_flow is not None:
+            raise ValueError("sample_scale > 1 cannot be combined with known_flow: the constraints would need a NaN-aware reduction")
+        if not torch.is_tensor(cond) or cond.dim() != 4 or cond.shape[1] < 3:
+            raise ValueError(f"cond must be (B, 3, H, W), got {tuple(cond.shape) if torch.is_tensor(cond) else type(cond).__name__}")
+        H, W = cond.shape[-2:]
+        if H % s or W % s:
+            raise ValueError(f"sample_scale={s} must divide H={H} and W={W}")
+        return s, up
+
     def sample(self, cond, flow, known_flow=None, resample=1, guidance_scale=UNSET, dynamic_threshold=UNSET,
                threshold_max=UNSET, target_frame=None, photo_scale=UNSET, photo_levels=UNSET, photo_damping=UNSET,
-               photo_schedule=UNSET):                                                             # FD:189-215
+               photo_schedule=UNSET, sample_scale=UNSET, upsample_radius=UNSET, upsample_sigma_s=UNSET,
+               upsample_sigma_r=UNSET):                                                           # FD:189-215
         """`known_flow` (optional, not in the reference): (B, 2, H, W) in pixels, NaN = free; the returned flow has
         clamp(known_flow / flow_max) at the other elements and the sampler fills in the rest consistently (constrained sampling,
         ConditionalDiffusion.sample).  target 'flow' or 'joint' only.  `resample` as there: DDPM only, `resample` UNet calls per step.
@@ -335,13 +370,32 @@ class FlowDiffuser(EmaMixin, _Base):
         `target_frame` (optional, not in the reference): (B, 3, H, W) in cond's range, the second frame; the chain is then guided
         photometrically towards cond(p) ~ target_frame(p + flow(p)) (photometric guidance, ConditionalDiffusion.sample(photo=)), with
         `photo_scale`, `photo_levels`, `photo_damping`, `photo_schedule` instead of the cfg keys of those names.  target 'flow' or
-        'joint', not latent; composes with all of the above and every sampler."""
+        'joint', not latent; composes with all of the above and every sampler.
+        `sample_scale` = s (optional, not in the reference; an integer in 1..8 dividing H and W) instead of cfg.sample_scale: with s > 1
+        the chain runs on cond[:, :3] (and target_frame) box-reduced by s -- padded at the bottom and right by edge replication to
+        the next multiples of 8, the Unet's granularity, and cropped back afterwards -- at about 1 / s^2 of the cost, and the final
+        flow is carried to (H, W) by `warp.upsample_flow(flow_lo, cond[:, :3], s, gain=s)` with `upsample_radius`,
+        `upsample_sigma_s`, `upsample_sigma_r` instead of the cfg keys of those names (read only when s > 1): joint bilateral
+        upsampling, which puts the motion boundaries where the full-size frame has its edges.  The photometric guide then compares
+        the reduced frames.  Returned: (samples (B, 3, H, W), flow (B, 1, 2, H, W)): the flow is the final frame only (the
+        low-resolution trajectory is dropped), still in units of flow_max -- it may exceed 1: a reduced chain represents motions up
+        to s * flow_max pixels -- and samples is the forward warp of cond[:, :dim] by it, formed as target 'flow' forms it at full
+        size.  target 'flow' or 'joint', a diffusion model, not latent, not with known_flow (ValueError before any engine call);
+        composes with every sampler and objective, guidance_scale, dynamic_threshold and target_frame.  How well a model trained at
+        full size predicts the flow of a reduced frame has not been measured with trained weights.  s = 1 is the present path, launch
+        for launch."""
+        s, up = self.reduced_sampling(cond, known_flow, sample_scale, upsample_radius, upsample_sigma_s, upsample_sigma_r)
         thresh = {k: v for k, v in (("dynamic_threshold", dynamic_threshold), ("threshold_max", threshold_max)) if v is not UNSET}
         photo_kw = {k: v for k, v in (("photo_scale", photo_scale), ("photo_levels", photo_levels), ("photo_damping", photo_damping),
                                       ("photo_schedule", photo_schedule)) if v is not UNSET}
         if target_frame is None and photo_kw:
             raise ValueError(f"{sorted(photo_kw)} configure photometric guidance: they need a target_frame")
         photo = None if target_frame is None else self.photo_guide(cond, target_frame, **photo_kw)
+        if s > 1:
+            if resample != 1:
+                raise ValueError("resample needs a known_flow to harmonise with")
+            with self._sampling_scope():
+                return self._sample_reduced(cond, s, up, guidance_scale, thresh, target_frame, photo_kw)
         # a regression model called with autograd on runs the training forward, which has no EMA weights to run on
         if self.is_diffusion or not torch.is_grad_enabled():
             with self._sampling_scope():
@@ -381,6 +435,30 @@ class FlowDiffuser(EmaMixin, _Base):
             img = cond[:, :self.dim]
             samples = warp(img, None, flow[:, -1], mode="forward")
         return samples, flow
+
+    def _sample_reduced(self, cond, s, up, guidance_scale, thresh, target_frame, photo_kw):
+        """`sample` with sample_scale = s > 1, after `reduced_sampling` has checked the rules"""
+        L.require_gpu(cond, target_frame)
+        B, _, H, W = cond.shape
+        h, w = H // s, W // s
+        ph, pw = (-h) % 8, (-w) % 8                                         # the Unet halves three times
+
+        def padded(lo):
+            return torch.nn.functional.pad(lo, (0, pw, 0, ph), mode="replicate") if ph or pw else lo
+        with torch.no_grad():
+            guide = L.f32c(cond[:, :3].detach())
+            guide_lo = box_reduce(guide, s)
+            cond_lo = padded(guide_lo)
+            kw = {}
+            if target_frame is not None:
+                kw["photo"] = self.photo_guide(cond_lo, padded(box_reduce(L.f32c(target_frame.detach()), s)), **photo_kw)
+            if guidance_scale is not UNSET:
+                kw["guidance_scale"] = guidance_scale
+            kw.update(thresh)
+            out = self.model.sample(batch_size=B, external_cond=cond_lo, image_size=(h + ph, w + pw), **kw)
+            flow = upsample_flow(out[:, -2:, :h, :w], guide, s, gain=s, guide_lo=guide_lo, **up)
+            samples = warp(cond[:, :self.dim], None, flow, mode="forward")
+        return samples, flow[:, None]
 
     def estimate_flow(self, frame1, frame2, **sample_kw):
         """The flow from frame1 to frame2 in pixels, (B, 2, H, W): frame1(p) ~ frame2(p + flow(p)) (not in the reference, whose diffusion
@@ -525,7 +603,7 @@ class FlowDiffuser(EmaMixin, _Base):
 
         with torch.no_grad():
             loss = self.loss(tgt_, cond, flow_)
-            samples, p_flows = self.sample(cond, flow_)
+            samples, p_flows = self.sample(cond, flow_, sample_scale=1)      # full size: the strips below show the trajectory
             mid_samples = mid_flows = None
             if self.is_diffusion and warped_target:
                 mid_samples = samples[:, ::50]                               # FD:246

@@ -5,6 +5,8 @@
   backward -> warp_backward_flow (WP:95-119) : bilinear grid_sample gather + validity mask
 rep='filter' (FlowLearner / MatrixFlow only) is outside the FlowDiffuser path and raises.
 """
+import ctypes
+
 import torch
 
 from . import _lib as L
@@ -264,6 +266,79 @@ def interpolate_frames(frame1, frame2, flow12, flow21, times, alpha=10.0, beta=0
                 video[bs, k0:k0 + ck] = colour.view(cb, ck, C, H, W)
                 cover[bs, k0:k0 + ck] = weight.view(cb, ck, 1, H, W)
     return video if fill_holes else (video, cover)
+
+
+# ---- joint bilateral upsampling (not in the reference; semantics: include/ofd.h, `ofd_joint_upsample`) --------------------------------
+def _shape_of(t):
+    return tuple(t.shape) if torch.is_tensor(t) else type(t).__name__
+
+
+def box_reduce(img, scale):
+    """the scale x scale box average of a (B, Ci, H, W) GPU tensor, Ci <= 4, scale dividing H and W: one `ofd_photo_pyramid` launch"""
+    B, Ci, H, W = img.shape
+    lv = (ctypes.c_int * 1)(scale)
+    lib = L.lib()
+    floats = int(lib.ofd_photo_pyramid_floats(B, Ci, H, W, lv, 1))
+    if floats != B * Ci * (H // scale) * (W // scale):
+        raise ValueError(f"box_reduce: scale {scale} must divide H={H} and W={W} of a (B, 1..4, H, W) tensor, got {tuple(img.shape)}")
+    out = torch.empty(B, Ci, H // scale, W // scale, dtype=torch.float32, device=img.device)
+    L.check(lib.ofd_photo_pyramid(L.ptr(img), lv, 1, B, Ci, H, W, L.ptr(out), L.stream()))
+    return out
+
+
+def upsample_params(radius=2, sigma_s=1.0, sigma_r=0.1):
+    """the rules of `upsample_flow`'s window and widths (ValueError); host logic, no engine call"""
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 1 <= radius <= 3:
+        raise ValueError(f"upsample_flow: radius must be an integer in 1..3, got {radius!r}")
+    real = lambda v: not isinstance(v, bool) and isinstance(v, (int, float))
+    if not real(sigma_s) or not 0.0 < sigma_s < float("inf"):               # false for NaN
+        raise ValueError(f"upsample_flow: sigma_s must be finite and > 0, got {sigma_s!r}")
+    if not real(sigma_r) or not sigma_r > 0.0:
+        raise ValueError(f"upsample_flow: sigma_r must be > 0 (inf switches the guide off), got {sigma_r!r}")
+    return dict(radius=radius, sigma_s=float(sigma_s), sigma_r=float(sigma_r))
+
+
+def upsample_flow(lo, guide, scale, radius=2, sigma_s=1.0, sigma_r=0.1, gain=None, guide_lo=None):
+    """Joint bilateral upsampling (Kopf et al. 2007; not in the reference): a low-resolution field carried to the size of `guide`, a new
+    fp32 (B, C, h * scale, w * scale) tensor.  lo: (B, C, h, w), C <= 8, e.g. a flow sampled on a frame box-reduced by `scale`; guide:
+    (B, Cg, h * scale, w * scale), Cg <= 4, the full-resolution frame; guide_lo: (B, Cg, h, w), the guide at lo's size, None = its box
+    average (one `ofd_photo_pyramid` launch).  Every output pixel is the average of the (2 radius)^2 low-resolution neighbours of its
+    position, weighted by exp(-distance^2 / (2 sigma_s^2) - mean_c (guide - guide_lo)^2 / (2 sigma_r^2)): where the guide has an edge
+    the field gets one too.  sigma_r = inf switches the guide off.  gain multiplies the result; None means `scale`, which keeps a flow in
+    pixels a flow in pixels.  Neighbours with a non-finite lo are left out; a pixel with none left is NaN.  scale = 1 returns lo * gain
+    without an engine call.  radius 1..3, scale 1..8.  The defaults suit frames in [-1, 1]; they come from a synthetic edge and are
+    untuned on real footage.  Forward only; inputs are not modified; the same input gives the same bits.  Semantics: include/ofd.h."""
+    if not torch.is_tensor(lo) or lo.dim() != 4 or lo.numel() == 0 or not 1 <= lo.shape[1] <= 8:
+        raise ValueError(f"upsample_flow: lo must be a non-empty (B, C, h, w) tensor with 1 <= C <= 8, got {_shape_of(lo)}")
+    if isinstance(scale, bool) or not isinstance(scale, int) or not 1 <= scale <= 8:
+        raise ValueError(f"upsample_flow: scale must be an integer in 1..8, got {scale!r}")
+    upsample_params(radius, sigma_s, sigma_r)
+    B, C, h, w = lo.shape
+    if not torch.is_tensor(guide) or guide.dim() != 4 or not 1 <= guide.shape[1] <= 4 or \
+            (guide.shape[0], guide.shape[2], guide.shape[3]) != (B, h * scale, w * scale):
+        raise ValueError(f"upsample_flow: guide must be (B, 1..4, h * scale, w * scale) = ({B}, 1..4, {h * scale}, {w * scale}), "
+                         f"got {_shape_of(guide)}")
+    Cg = guide.shape[1]
+    if guide_lo is not None and (not torch.is_tensor(guide_lo) or tuple(guide_lo.shape) != (B, Cg, h, w)):
+        raise ValueError(f"upsample_flow: guide_lo must be (B, Cg, h, w) = {(B, Cg, h, w)}, got {_shape_of(guide_lo)}")
+    gain = float(scale if gain is None else gain)
+    if not abs(gain) < float("inf"):
+        raise ValueError(f"upsample_flow: gain must be finite, got {gain!r}")
+    given = [t for t in (lo, guide, guide_lo) if t is not None]
+    if any(t.requires_grad for t in given):
+        raise L.OfdError("upsample_flow: forward only (the upsampling has no backward pass): detach the inputs")
+    L.require_gpu(*given)
+    if any(t.device != lo.device for t in given):
+        raise ValueError(f"upsample_flow: lo, guide and guide_lo must be on one device, got {[str(t.device) for t in given]}")
+    with torch.no_grad():
+        if scale == 1:
+            return L.f32c(lo) * gain
+        lo, guide = L.f32c(lo), L.f32c(guide)
+        guide_lo = box_reduce(guide, scale) if guide_lo is None else L.f32c(guide_lo)
+        out = torch.empty(B, C, h * scale, w * scale, dtype=torch.float32, device=lo.device)
+        L.check(L.lib().ofd_joint_upsample(L.ptr(lo), L.ptr(guide_lo), L.ptr(guide), L.ptr(out), B, C, Cg, h, w, scale, radius,
+                                           float(sigma_s), float(sigma_r), gain, L.stream()))
+    return out
 
 
 class _GridWarp(torch.autograd.Function):
