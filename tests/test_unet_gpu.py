@@ -61,7 +61,8 @@ def gn_octet_sums(gn, B, tiles, Cout):
 
 
 def run_conv(L, B, H, W, ksize, srcs, Cout, weight, bias=None, in_scale=None, in_shift=None, residual=None,
-             res_act=None, res_scale=None, res_shift=None, want_gn=False):
+             res_act=None, res_scale=None, res_shift=None, want_gn=False, out=None, gn=None, out2=None, residual2=None, split=0, up2_phase=0):
+    """out / gn / out2: buffers of the caller's instead of fresh ones (test_conv_forward_exact_gpu.py puts fences around them)"""
     a = L.ConvArgs()
     a.B, a.H, a.W, a.ksize, a.n_src, a.Cout = B, H, W, ksize, len(srcs), Cout
     keep = []
@@ -75,11 +76,11 @@ def run_conv(L, B, H, W, ksize, srcs, Cout, weight, bias=None, in_scale=None, in
         a.src[i].upsample = s.get("upsample", 0)
         a.src[i].unshuffle = s.get("unshuffle", 0)
         a.src[i].p1, a.src[i].p2 = s.get("p1", 0), s.get("p2", 0)
-    out = torch.empty(B, H, W, Cout, dtype=torch.bfloat16, device="cuda")
+    if out is None:
+        out = torch.empty(B, H, W, Cout, dtype=torch.bfloat16, device="cuda")
     dev = lambda v: None if v is None else v.contiguous().cuda()
     bias, in_scale, in_shift, res_scale, res_shift = map(dev, (bias, in_scale, in_shift, res_scale, res_shift))
-    gn = None
-    if want_gn:
+    if want_gn and gn is None:
         gn = torch.full((L.lib().ofd_conv_gn_partial_count(B, H, W, Cout),), float("nan"), device="cuda")
     a.weight, a.bias = weight.data_ptr(), (bias.data_ptr() if bias is not None else None)
     a.in_scale = in_scale.data_ptr() if in_scale is not None else None
@@ -90,6 +91,9 @@ def run_conv(L, B, H, W, ksize, srcs, Cout, weight, bias=None, in_scale=None, in
     a.res_shift = res_shift.data_ptr() if res_shift is not None else None
     a.out = out.data_ptr()
     a.gn_partial = gn.data_ptr() if gn is not None else None
+    a.split, a.up2_phase = split, up2_phase
+    a.out2 = out2.data_ptr() if out2 is not None else None
+    a.residual2 = residual2.data_ptr() if residual2 is not None else None
     L.check(L.lib().ofd_conv_forward(ctypes.byref(a), L.stream()))
     torch.cuda.synchronize()
     return out, gn
@@ -128,8 +132,10 @@ def test_conv3x3_plain_and_ws(L, B, H, W, Cin, Cout):
 def test_conv3x3_producer_consumer_kernel_forms(L, B, H, W, cins, Cout, pro, up):
     """conv3x3_pc_kernel (conv_pc.hip, r04: the 64-channel-block 3x3 as a persistent producer / consumer workgroup) over the forms it serves:
     one or two concatenated sources, a nearest-x2 source, the GroupNorm + SiLU prologue, several channel blocks per pixel tile (Cout 128 /
-    192 on grids too small for the 128-channel-block kernel), partial tiles on both axes, more tiles than workgroups (200 x 352: every
-    workgroup walks several items).  Against F.conv2d on the bf16-rounded operands AND against conv3x3_wp_kernel<2,2> (OFD_CONV_PC=0) on the
+    192 on grids too small for the 128-channel-block kernel), partial tiles on both axes.  The largest shape, 200 x 352, has 11 x 13 tiles
+    of 16 x 32 = 144 items: a device of more than 144 CUs (the MI355X has 256) gives every workgroup ONE item, so the persistent walk over
+    several items does not run here -- it is test_conv_forward_exact_gpu.py's (pc_walk_64, pc_walk_192, pc_concat_up: 2 to 3 items per
+    workgroup on 256 CUs, checked for equality).  Against F.conv2d on the bf16-rounded operands AND against conv3x3_wp_kernel<2,2> (OFD_CONV_PC=0) on the
     same inputs: values within the per-op tolerance, GroupNorm partial sums within 1e-4 of each other per (sample, 8-channel group)."""
     import os
     torch.manual_seed(17 + H)
