@@ -28,6 +28,7 @@
  *   (not in the reference)            photometric guidance of sampling  -> ofd_photo_pyramid, ofd_photo_guide
  *   (not in the reference)            two-frame interpolation (softmax splatting) -> ofd_interp_prep, ofd_interp_merge
  *   (not in the reference)            joint bilateral upsampling (reduced-size sampling) -> ofd_joint_upsample
+ *   (not in the reference)            looping clips from a steady motion field -> ofd_flow_integrate, ofd_loop_render
  *   denoising_diffusion.py:806-812    q_sample                          -> ofd_q_sample
  *   denoising_diffusion.py:844-879,985-993  p_losses noise / target     -> ofd_diffusion_prep
  *   denoising_diffusion.py:73-77      (un)normalize                     -> ofd_range_map
@@ -184,6 +185,43 @@ int ofd_interp_merge(const float* acc, float* colour, float* weight, int Bn, int
  * set ofd_last_error before any GPU work.  Compulsory traffic: 4 * B * (H*W*(Cg + C) + h*w*(Cg + C)) bytes. */
 int ofd_joint_upsample(const float* lo, const float* guide_lo, const float* guide, float* out, int B, int C, int Cg, int h, int w, int s,
                        int radius, float sigma_s, float sigma_r, float gain, void* stream);
+
+/* Looping clips from a still and a steady motion field (Chuang et al., "Animating Pictures with Stochastic Motion Textures", SIGGRAPH
+ * 2005; Holynski et al., "Animating Pictures with Eulerian Motion Fields", CVPR 2021).  An addition: the reference stops at one raw splat
+ * of the still by its flow.  For a field that does not change with time the colour of pixel p in frame k is the still read at the
+ * point reached by tracing p BACK through the field for k frames: a gather, no holes, no atomics, no fill.  Cross-fading it with the
+ * still traced FORWARD for N - k frames makes frame N equal frame 0: the clip repeats without a jump.  All arithmetic fp32, in the
+ * order written here.
+ * motion: (B,2,H,W) in pixels per frame, channel 0 = x; the content at p moves to p + motion(p) -- the convention of ofd_splat_fwd and
+ * ofd_interp_prep.  A non-finite component of motion is read as 0 ("does not move") wherever it is read.
+ *   sample   sample(F, qx, qy) is a bilinear read with edge clamp: sx = min(max(qx, 0), W-1), x0 = floor(sx), x1 = min(x0 + 1, W-1),
+ *            tx = sx - x0, likewise in y; value = (1-ty) * ((1-tx) * g00 + tx * g01) + ty * ((1-tx) * g10 + tx * g11).  (A NaN
+ *            coordinate -- inf - inf after a displacement overflowed -- is read at 0.)  A point traced past the frame's border reads
+ *            the border: its colour is stretched, not lost.
+ *   trace    a trace with frame step dt keeps a displacement D per pixel p = (x, y), D = 0 at the start.  One frame is `substeps`
+ *            sub-steps of h = dt / substeps (one fp32 division); hh = 0.5f * h.  A sub-step reads at q = ((float)x + D.x, (float)y + D.y):
+ *            order 1 (Euler)     v = sample(motion, q);  D = D + h * v;
+ *            order 2 (midpoint)  v = sample(motion, q);  Dm = D + hh * v;  vm = sample(motion, p + Dm);  D = D + h * vm.
+ *            D_j is D after j frames.
+ * ofd_flow_integrate: disp (B, steps+1, 2, H, W), disp[:, j] = D_j, disp[:, 0] = 0.  dt: any finite float, negative traces back; it
+ * carries the caller's speed, so the field is never rescaled in a pass of its own.  0 <= steps <= 4096.
+ * ofd_loop_render: img (B,C,H,W), finite; video (B, nk, C, H, W): the frames k = k0 .. k0 + nk - 1 of the N-frame loop.  For frame k:
+ *            t = (float)k / (float)N;  a = sample(img, p + Db_k), Db the trace with dt = -speed;  b = sample(img, p + Df_{N-k}), Df the
+ *            trace with dt = +speed;  out = (1 - t) * a + t * b.  Frame 0 is img (1 * a + 0 * b).  The call keeps no state: every call
+ *            traces from D = 0, so the frames of a loop split over several calls have the bits of one call.
+ *            workspace: ofd_loop_workspace(B, H, W, nk) bytes (0 for a bad shape), the forward displacements of the call's frames,
+ *            8 bytes per pixel and frame; a smaller one is an error (OFD_ERR_WORKSPACE).
+ *            1 <= C <= 8, 1 <= N <= 4096, 0 <= k0, 1 <= nk, k0 + nk <= N; speed finite.
+ * Both: 1 <= substeps <= 16, order 1 or 2, H, W <= 32768.  One launch (integrate) or two (render: the forward trace into the workspace,
+ * then back-trace, gathers and blend); no atomics, no host sync, the same input gives the same bits.  A workgroup owns a 64 x 16 tile, a
+ * thread one column of four neighbouring rows: every load and store of a wave covers 64 neighbouring pixels of a row, and no pointer
+ * needs more than a float's alignment.  Outputs must not alias inputs.  Argument errors return OFD_ERR_ARG and set ofd_last_error
+ * before any GPU work.  B * ceil(H / 16) * ceil(W / 64) < 2^30.  Compulsory traffic of ofd_loop_render: 4 * B * (nk*C*H*W + (C+2)*H*W)
+ * bytes. */
+int ofd_flow_integrate(const float* motion, float* disp, int B, int H, int W, int steps, int substeps, int order, float dt, void* stream);
+size_t ofd_loop_workspace(int B, int H, int W, int nk);
+int ofd_loop_render(const float* img, const float* motion, float* video, int B, int C, int H, int W, int N, int k0, int nk, int substeps,
+                    int order, float speed, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------ grid_sample warp (WP:95-119) -
  * second: (B,C,H,W), flow: (B,2,H,W) exactly as handed to the reference's warp(mode='backward'):

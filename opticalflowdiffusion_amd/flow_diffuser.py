@@ -20,7 +20,7 @@ import torch
 
 from .denoising_diffusion import UNSET, PhotoGuide, Unet, ConditionalDiffusion, loss_by_timestep
 from .ema import EMA_DEFAULTS, EmaMixin, ema_optimizer_kwargs
-from .warp import box_reduce, interpolate_frames, upsample_flow, upsample_params, warp
+from .warp import box_reduce, interpolate_frames, loop_frames, loop_params, upsample_flow, upsample_params, warp
 from . import _lib as L
 
 try:                                                   # pragma: no cover - not installed in this image
@@ -513,6 +513,41 @@ class FlowDiffuser(EmaMixin, _Base):
             parts = [warp(imgs[i:i + per], None, flows[i:i + per], mode="forward", **kw) for i in range(0, B * n, per)]
             video = parts[0] if len(parts) == 1 else torch.cat(parts)
         return video.view(B, n, 3, H, W), flow
+
+    def animate_loop(self, cond, flow=None, frames=24, speed=1.0, substeps=1, order=2, **sample_kw):
+        """A clip that repeats without a jump, from a still (not in the reference): (video, flow).  Where `animate` moves every pixel
+        along a straight line for one flow length, this follows the field: the flow is taken as a velocity field that does not change
+        with time -- a sampled frame-to-frame flow used as a steady field -- and every frame is gathered from cond where a trace through
+        that field ends (`warp.loop_frames`, which has the method).  cond, flow and sample_kw as for `animate`: flow (B, 2, H, W) in
+        units of flow_max; None samples it (a diffusion model only, the EMA scope applies as in `sample`); with a flow given no UNet call
+        is made and sample_kw is an error.  The field handed down is flow * flow_max, pixels per frame; speed scales the step of the
+        traces, substeps and order choose the integrator.  The defaults (order=2, substeps=1, speed=1) come from a synthetic rotation
+        and are untuned on real footage.  video: (B, frames, 3, H, W) in cond's range, frame 0 = cond[:, :3], and the frame after the
+        last is frame 0 again; no NaN, no holes: a trace that leaves the frame repeats the border's colour.  Forward only."""
+        if self.latent:
+            raise ValueError("animate_loop: latent=True is not supported (every frame would have to be decoded by the Autoencoder)")
+        if isinstance(frames, bool) or not isinstance(frames, int) or not 1 <= frames <= 4096:
+            raise ValueError(f"animate_loop: frames must be an integer in 1..4096, got {frames!r}")
+        par = loop_params(substeps, order, speed, name="animate_loop")
+        if not torch.is_tensor(cond) or cond.dim() != 4 or cond.shape[1] < 3:
+            raise ValueError(f"animate_loop: cond must be (B, 3, H, W), got {tuple(cond.shape) if torch.is_tensor(cond) else type(cond).__name__}")
+        B, _, H, W = cond.shape
+        if flow is not None:
+            if sample_kw:
+                raise ValueError(f"animate_loop: {sorted(sample_kw)} are sampling arguments; with a flow given nothing is sampled")
+            if not torch.is_tensor(flow) or tuple(flow.shape) != (B, 2, H, W):
+                raise ValueError(f"animate_loop: flow must be (B, 2, H, W) = {(B, 2, H, W)}, got "
+                                 f"{tuple(flow.shape) if torch.is_tensor(flow) else type(flow).__name__}")
+        L.require_gpu(cond, flow)
+        with torch.no_grad():
+            if flow is None:
+                if not self.is_diffusion:
+                    raise ValueError("animate_loop: flow=None needs a diffusion model to sample the flow from; pass the flow")
+                _samples, fl = self.sample(cond, cond.new_zeros(B, 2, H, W), **sample_kw)
+                flow = fl[-1] if isinstance(fl, (list, tuple)) else fl[:, -1]
+            flow = flow.detach().float()
+            video = loop_frames(cond[:, :3].detach(), flow * float(self.flow_max), frames, **par)
+        return video, flow
 
     def interpolate(self, frame1, frame2, frames=7, times=None, flow12=None, flow21=None, alpha=10.0, beta=0.0, fill_holes=True,
                     fill_gain=1.0, **sample_kw):

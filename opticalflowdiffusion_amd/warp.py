@@ -341,6 +341,116 @@ def upsample_flow(lo, guide, scale, radius=2, sigma_s=1.0, sigma_r=0.1, gain=Non
     return out
 
 
+# ---- looping clips from a steady motion field (not in the reference; semantics: include/ofd.h, `ofd_loop_render`) ---------------------
+_loop_ws = {}                                          # device index -> the forward displacements of a call (grown on demand)
+
+
+def _loop_int(name, what, v, lo, hi):
+    if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+        raise ValueError(f"{name}: {what} must be an integer in {lo}..{hi}, got {v!r}")
+    return v
+
+
+def _loop_real(name, what, v):
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not abs(v) < float("inf"):       # false for NaN
+        raise ValueError(f"{name}: {what} must be a finite number, got {v!r}")
+    return float(v)
+
+
+def _loop_motion(name, motion, B=None, H=None, W=None):
+    ok = torch.is_tensor(motion) and motion.dim() == 4 and motion.shape[1] == 2 and motion.numel() > 0
+    if ok and B is not None:
+        ok = tuple(motion.shape) == (B, 2, H, W)
+    if not ok:
+        want = "a non-empty (B, 2, H, W) tensor" if B is None else f"(B, 2, H, W) = {(B, 2, H, W)}"
+        raise ValueError(f"{name}: motion must be {want}, got {_shape_of(motion)}")
+    if max(motion.shape[2:]) > 32768:
+        raise ValueError(f"{name}: H and W must be at most 32768, got {tuple(motion.shape)}")
+
+
+def loop_params(substeps=1, order=2, speed=1.0, name="loop_frames"):
+    """the rules of the traces' integrator and step (ValueError); host logic, no engine call"""
+    return dict(substeps=_loop_int(name, "substeps", substeps, 1, 16), order=_loop_int(name, "order", order, 1, 2),
+                speed=_loop_real(name, "speed", speed))
+
+
+def integrate_flow(motion, steps, substeps=1, order=2, dt=1.0):
+    """The displacements of every pixel traced through a steady field (not in the reference): a new fp32 (B, steps + 1, 2, H, W) tensor,
+    [:, j] = where the content of a pixel is after j frames, minus where it started; [:, 0] = 0.  motion: (B, 2, H, W) in pixels per
+    frame, channel 0 = x, content at p moves to p + motion(p) (the convention of the forward splat); non-finite entries count as 0.
+    Each frame is `substeps` (1..16) sub-steps of Euler (order=1) or the midpoint rule (order=2); dt scales the frame step and may be
+    negative (a trace back).  The field is read bilinearly with the coordinates clamped to the frame.  steps 0..4096.  Forward only;
+    inputs are not modified; the same input gives the same bits.  Semantics: include/ofd.h (`ofd_flow_integrate`)."""
+    _loop_motion("integrate_flow", motion)
+    steps = _loop_int("integrate_flow", "steps", steps, 0, 4096)
+    substeps = _loop_int("integrate_flow", "substeps", substeps, 1, 16)
+    order = _loop_int("integrate_flow", "order", order, 1, 2)
+    dt = _loop_real("integrate_flow", "dt", dt)
+    if motion.requires_grad:
+        raise L.OfdError("integrate_flow: forward only (the trace has no backward pass): detach the input")
+    L.require_gpu(motion)
+    B, _, H, W = motion.shape
+    with torch.no_grad():
+        motion = L.f32c(motion)
+        disp = torch.empty(B, steps + 1, 2, H, W, dtype=torch.float32, device=motion.device)
+        L.check(L.lib().ofd_flow_integrate(L.ptr(motion), L.ptr(disp), B, H, W, steps, substeps, order, dt, L.stream()))
+    return disp
+
+
+def _loop_render(img, motion, video, N, k0, substeps, order, speed):
+    """`ofd_loop_render` into `video` (cb, nk, C, H, W), contiguous: the frames k0 .. k0 + nk - 1 of the N-frame loop"""
+    cb, nk, C, H, W = video.shape
+    lib = L.lib()
+    nbytes = lib.ofd_loop_workspace(cb, H, W, nk)
+    ws = _loop_ws.get(img.device.index)
+    if ws is None or ws.numel() < nbytes:
+        _loop_ws.pop(img.device.index, None)
+        ws = _loop_ws[img.device.index] = torch.empty(nbytes, dtype=torch.uint8, device=img.device)
+    L.check(lib.ofd_loop_render(L.ptr(img), L.ptr(motion), L.ptr(video), cb, C, H, W, N, k0, nk, substeps, order, speed, L.ptr(ws),
+                                ws.numel(), L.stream()))
+
+
+def loop_frames(img, motion, frames, substeps=1, order=2, speed=1.0):
+    """A clip that repeats without a jump, from a still and a steady motion field (Chuang et al. 2005, Holynski et al. 2021; not in the
+    reference): a new fp32 (B, frames, C, H, W) tensor, to be played round and round.  img: (B, C, H, W), finite, C <= 8; motion:
+    (B, 2, H, W) IN PIXELS per frame, channel 0 = x, content at p moves to p + motion(p); non-finite entries count as 0.  A sampled
+    frame-to-frame flow is used here as a velocity field that does not change with time.  Frame k is img read where tracing the pixel
+    back for k frames ends, cross-faded (weight k / frames) with img read where tracing it forward for frames - k frames ends: frame 0
+    is img, and the frame after the last one would be img again.  A gather: no holes, nothing to fill; a trace that leaves the frame
+    reads the border's colour (a stretch, not a hole).  The traces are `integrate_flow`'s (substeps, order), speed scales the step.
+    The defaults (order=2, substeps=1, speed=1) come from a synthetic rotation and are untuned on real footage.  frames 1..4096.  One
+    `ofd_loop_render` call per at most flow_diffuser.ANIMATE_MAX_PIXELS pixels of output, over samples first and then over frames;
+    chunked or not, the bits are the same.  Forward only; inputs are not modified.  Semantics: include/ofd.h."""
+    from .flow_diffuser import ANIMATE_MAX_PIXELS
+    if not torch.is_tensor(img) or img.dim() != 4 or img.numel() == 0:
+        raise ValueError(f"loop_frames: img must be a non-empty (B, C, H, W) tensor, got {_shape_of(img)}")
+    B, C, H, W = img.shape
+    if not 1 <= C <= 8:
+        raise ValueError(f"loop_frames: 1 to 8 channels, got {C}")
+    _loop_motion("loop_frames", motion, B, H, W)
+    N = _loop_int("loop_frames", "frames", frames, 1, 4096)
+    par = loop_params(substeps, order, speed)
+    if img.requires_grad or motion.requires_grad:
+        raise L.OfdError("loop_frames: forward only (neither the trace nor the gather has a backward pass): detach the inputs")
+    L.require_gpu(img, motion)
+    if img.device != motion.device:
+        raise ValueError(f"loop_frames: img and motion must be on one device, got {img.device} and {motion.device}")
+    with torch.no_grad():
+        img, motion = L.f32c(img), L.f32c(motion)
+        per = max(1, ANIMATE_MAX_PIXELS // (H * W))                          # frames per call
+        nk, nb = min(N, per), max(1, per // N)
+        video = torch.empty(B, N, C, H, W, dtype=torch.float32, device=img.device)
+        for b0 in range(0, B, nb):
+            cb = min(nb, B - b0)
+            for k0 in range(0, N, nk):
+                ck = min(nk, N - k0)
+                if ck == N:                                                  # whole samples: their frames are contiguous in the result
+                    _loop_render(img[b0:b0 + cb], motion[b0:b0 + cb], video[b0:b0 + cb], N, 0, **par)
+                else:                                                        # nb == 1: one sample's frames k0 .. k0 + ck - 1
+                    _loop_render(img[b0:b0 + 1], motion[b0:b0 + 1], video[b0:b0 + 1, k0:k0 + ck], N, k0, **par)
+    return video
+
+
 class _GridWarp(torch.autograd.Function):
     """warp_backward_flow (WP:95-119) with the gradients autograd derives for it: d/d second is the bilinear scatter of the
     incoming gradient (the splat kernel on grid_sample's coordinates), d/d flow ATen's grid gradient; the thresholded mask
