@@ -292,9 +292,9 @@ extern "C" int ofd_linear_attention_block_backward(const void* qkv, const void* 
     OFD_CHECK_ARG(B > 0 && n > 0, "linear_attention_block_backward: B=%d n=%d", B, n);
     OFD_CHECK_ARG(al16(qkv) && al16(do2) && al16(xn) && al16(dxn) && al16(wqkv_t) && al16(wo_fwd) && al16(wo_t) && al16(wq_fwd),
                   "linear_attention_block_backward: qkv, do2, xn, dxn and the weights must be 16-byte aligned");
-    return k_linear_attention_core_bwd((const bf16_t*)qkv, (const bf16_t*)do2, ctx, ml, nullptr, workspace, B, n, (hipStream_t)stream, (const bf16_t*)xn,
-                                       (const bf16_t*)wqkv_t, dw_acc, (bf16_t*)dxn, (const bf16_t*)wo_fwd, (const bf16_t*)wo_t, dwo_acc, dbo,
-                                       (const bf16_t*)wq_fwd);
+    return k_linear_attention_block_bwd((const bf16_t*)qkv, (const bf16_t*)do2, ctx, ml, workspace, B, n, (hipStream_t)stream, (const bf16_t*)xn,
+                                        (const bf16_t*)wqkv_t, dw_acc, (bf16_t*)dxn, (const bf16_t*)wo_fwd, (const bf16_t*)wo_t, dwo_acc, dbo,
+                                        (const bf16_t*)wq_fwd);
 }
 extern "C" int ofd_flash_attention(const void* qkv, void* out, float* lse, int B, int n, void* stream) {
     OFD_CHECK_ARG(qkv && out && B > 0 && n > 0, "flash_attention: bad argument");

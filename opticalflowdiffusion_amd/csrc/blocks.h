@@ -13,8 +13,7 @@ struct MlpDesc {            // one ResnetBlock's time-embedding Linear (DD:193-1
 
 struct FcFuse { const float* w; const float* b; float* out; };      // ConvParams::fc_* (the UNet's final 1x1 conv on the final res_conv's tile)
 bool conv_fc_fuse_supported(const ofd_conv_args* a, int out_dim);
-int conv_forward_impl(const ofd_conv_args* a, hipStream_t s, int cout0 = 0, int pool2 = 0, const bf16_t* residual_b = nullptr, const FcFuse* fc = nullptr);      // cout0: see ConvParams::cout0 (honoured by the streaming 1x1 kernel only
-                                                                                   // for 64 -> 384 with cout0 = 128; everything else computes all channels)
+int conv_forward_impl(const ofd_conv_args* a, hipStream_t s, int pool2 = 0, const bf16_t* residual_b = nullptr, const FcFuse* fc = nullptr);
 bool conv_pool2_supported(const ofd_conv_args* a);
 bool conv_residual_b_supported(const ofd_conv_args* a);                            // residual_b: ConvParams::residual_b (3x3 through conv_wp.hip only)                                 // pool2: ConvParams::pool2 (3x3 through conv_wp.hip only)
 // conv backward (conv_bwd.hip; k_conv_wgrad, k_conv7_wgrad, k_channel_sum: conv_wgrad.hip)
@@ -47,8 +46,7 @@ int k_resblock_out(const bf16_t* h, const float* a, const float* sft, const bf16
 int k_layernorm_c(const bf16_t* x, const float* g, const bf16_t* res, bf16_t* out, size_t npix, int C, float eps, hipStream_t s);
 int la_parts(int B, int n);
 int k_linear_attention_core(const bf16_t* qkv, float* partial, float* ctx, bf16_t* out, int B, int n, hipStream_t s, float* ml_out = nullptr,
-                            const bf16_t* wo = nullptr, const float* bo = nullptr, bf16_t* o2 = nullptr, int C = 0, const bf16_t* xn = nullptr,
-                            const bf16_t* wq = nullptr);
+                            const bf16_t* wo = nullptr, const float* bo = nullptr, bf16_t* o2 = nullptr, int C = 0);
 int la_fused_blocks(int n, int B);
 int la_fwd_parts(int B, int n);
 int k_linear_attention_fused_train(const bf16_t* x, const bf16_t* wq, const bf16_t* wkv, const bf16_t* woutp, const float* bias, const float* g_pre,
@@ -85,9 +83,10 @@ int k_grad_add(bf16_t* dst, const bf16_t* src, size_t elems, int accumulate, hip
 // attention backward (attn_bwd.hip)
 size_t la_bwd_workspace_floats(int B, int n);
 int k_linear_attention_core_bwd(const bf16_t* qkv, const bf16_t* dout, const float* ctx, const float* ml, bf16_t* dqkv, float* workspace, int B, int n,
-                                hipStream_t s, const bf16_t* xn = nullptr, const bf16_t* wt = nullptr, float* dw = nullptr, bf16_t* dxn = nullptr,
-                                const bf16_t* wo_fwd = nullptr, const bf16_t* wo_t = nullptr, float* dwo = nullptr, float* dbo = nullptr,
-                                const bf16_t* wq = nullptr);
+                                hipStream_t s);
+int k_linear_attention_block_bwd(const bf16_t* qkv, const bf16_t* do2, const float* ctx, const float* ml, float* workspace, int B, int n, hipStream_t s,
+                                 const bf16_t* xn, const bf16_t* wt, float* dw, bf16_t* dxn, const bf16_t* wo_fwd, const bf16_t* wo_t, float* dwo,
+                                 float* dbo, const bf16_t* wq);
 int k_flash_attention_bwd(const bf16_t* qkv, const bf16_t* o, const bf16_t* dout, const float* lse, bf16_t* dqkv, float* delta, int B, int n,
                           hipStream_t s);
 

@@ -215,67 +215,6 @@ __global__ void __launch_bounds__(256) layernorm_c_kernel(const bf16_t* __restri
     }
 }
 
-// combine the partials: ctx[bh][d][e] = sum_c exp(m_c - M) ctx_c / (sum_c exp(m_c - M) l_c) / n
-__global__ void __launch_bounds__(256) la_ctx_combine_kernel(const float* __restrict__ partial, float* __restrict__ ctx, int nparts, float inv_n, float* __restrict__ ml_out) {
-    // all 256 threads on the maxima / normalisers (thread -> d = tid & 31, parts tid >> 5, + 8, ...), the per-part weights exp(m_c - M)
-    // once into LDS, eight loads in flight in the accumulation: one thread per d and one load at a time made this 57 us per launch
-    __shared__ float M[32], Linv[32], red[8][32];
-    extern __shared__ float w_s[];                      // [nparts][32]
-    const int tid = threadIdx.x, bh = blockIdx.x, dd = tid & 31, grp = tid >> 5;
-    const float* base = partial + (size_t)bh * nparts * 1088;
-    float mx = -3.0e38f;
-    for (int c = grp; c < nparts; c += 8) mx = fmaxf(mx, base[(size_t)c * 1088 + dd]);
-    red[grp][dd] = mx;
-    __syncthreads();
-    if (tid < 32) {
-        float m = red[0][tid];
-#pragma unroll
-        for (int g = 1; g < 8; ++g) m = fmaxf(m, red[g][tid]);
-        M[tid] = m;
-    }
-    __syncthreads();
-    const bool use_ws = nparts <= 256;               // (the launcher sizes w_s for at most 256 parts; beyond that the weights are recomputed)
-    float l = 0.0f;
-    for (int c = grp; c < nparts; c += 8) {
-        const float w = __expf(base[(size_t)c * 1088 + dd] - M[dd]);
-        if (use_ws) w_s[c * 32 + dd] = w;
-        l += base[(size_t)c * 1088 + 32 + dd] * w;
-    }
-    __syncthreads();
-    red[grp][dd] = l;
-    __syncthreads();
-    if (tid < 32) {
-        float t = red[0][tid];
-#pragma unroll
-        for (int g = 1; g < 8; ++g) t += red[g][tid];
-        Linv[tid] = 1.0f / t;
-        if (ml_out && blockIdx.y == 0) {  // softmax-over-pixels normalisers, kept for the backward
-            ml_out[(size_t)bh * 64 + tid] = M[tid];
-            ml_out[(size_t)bh * 64 + 32 + tid] = 1.0f / t;
-        }
-    }
-    __syncthreads();
-    {   // grid (B * 4, 4): this workgroup's quarter of the 32 x 32 context (the normalisers above are recomputed by each of the four)
-        const int i = blockIdx.y * 256 + tid, d = i >> 5;
-        float a = 0.0f;
-        for (int c0 = 0; c0 < nparts; c0 += 8) {
-            float v[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) v[k] = base[(size_t)min(c0 + k, nparts - 1) * 1088 + 64 + i];
-            if (use_ws) {
-#pragma unroll
-                for (int k = 0; k < 8; ++k)
-                    if (c0 + k < nparts) a += v[k] * w_s[(c0 + k) * 32 + d];
-            } else {
-#pragma unroll
-                for (int k = 0; k < 8; ++k)
-                    if (c0 + k < nparts) a += v[k] * __expf(base[(size_t)(c0 + k) * 1088 + d] - M[d]);
-            }
-        }
-        ctx[(size_t)bh * 1024 + i] = a * Linv[d] * inv_n;
-    }
-}
-
 // ---- mid-block attention (DD:256-268), flash style, d = 32, 4 heads, MFMA 32x32x16 bf16 -----------
 // workgroup = 4 waves x 32 queries of one (sample, head); K/V tiles of 64 keys shared through LDS.
 // S^T = K.Q^T puts the query on the lane, so row max / sum are lane-local (+1 cross-half shuffle)
@@ -512,10 +451,6 @@ int k_layernorm_c(const bf16_t* x, const float* g, const bf16_t* res, bf16_t* ou
     layernorm_c_kernel<<<sgrid(waves * 64, 256, 0), 256, 0, s>>>(x, g, res, out, C, eps, npix);
     OFD_LAUNCH_CHECK();
     return OFD_OK;
-}
-void launch_la_ctx_combine(const float* partial, float* ctx, int B, int nparts, float inv_n, float* ml_out, hipStream_t s) {
-    const size_t lds = (size_t)(nparts <= 256 ? nparts : 1) * 32 * sizeof(float);
-    la_ctx_combine_kernel<<<dim3(B * 4, 4), 256, lds, s>>>(partial, ctx, nparts, inv_n, ml_out);
 }
 int k_flash_attention(const bf16_t* qkv, bf16_t* out, int B, int n, hipStream_t s, float* lse) {
     flash_attn_d32_kernel<<<dim3(cdiv(n, 128), B * 4), 256, 0, s>>>(qkv, out, n, 0.17677669529663687f, lse);

@@ -393,7 +393,7 @@ int launch_conv1x1_wp(const ConvParams& C, hipStream_t s) {
     const bool no_pl = env_int("OFD_CONV1_NO_PL", 0);     // (read per call) 1: these go to the shared-slab kernel, the tests' reference
     const bool pl = (C.residual || C.residual2 || C.split > 0) && !C.res_act;
     if (!pl && (C.residual || C.residual2 || C.split || C.out2)) return 1;
-    if (pl && (no_pl || C.fc_out || C.residual_b || C.pool2 || C.cout0 || (C.split > 0 && (!C.out2 || C.split % 32 != 0 || C.split >= C.Cout)))) return 1;
+    if (pl && (no_pl || C.fc_out || C.residual_b || C.pool2 || (C.split > 0 && (!C.out2 || C.split % 32 != 0 || C.split >= C.Cout)))) return 1;
     if (C.res_act && !(C.res_scale && C.res_shift)) return 1;
     const int cin = C.Cin_total, plane = C.H * C.W;
     const bool ra = C.res_act != nullptr;
@@ -443,7 +443,6 @@ int launch_conv1x1_wp(const ConvParams& C, hipStream_t s) {
         if (cin == 256) return launch<4, 256, 64, true, 1, false, true>(P, s);
         return launch<4, 512, 32, true, 1, false, true>(P, s);
     }
-    if (cin == 64 && C.cout0 == 128) { P.cout0 = 128; return launch<4, 64, 128, false, 2>(P, s); }      // ... its k and v blocks only (q recomputed downstream)
     if (cin == 64) return launch<4, 64, 128, false, 3>(P, s);                 // to_qkv of the 64-channel LinearAttention (training)
     if (cin == 128 && C.Cout == 384 && !ra && !C.bias) return launch<4, 128, 128, false, 3>(P, s);
     if (cin == 128) {

@@ -531,7 +531,7 @@ bool conv_residual_b_supported(const ofd_conv_args* a) {
     return true;
 }
 
-int conv_forward_impl(const ofd_conv_args* a, hipStream_t s, int cout0, int pool2, const bf16_t* residual_b, const FcFuse* fc) {
+int conv_forward_impl(const ofd_conv_args* a, hipStream_t s, int pool2, const bf16_t* residual_b, const FcFuse* fc) {
     OFD_CHECK_ARG(a && a->out && a->weight, "conv: null out/weight");
     OFD_CHECK_ARG(a->B > 0 && a->H > 0 && a->W > 0, "conv: bad shape");
     OFD_CHECK_ARG(a->ksize == 1 || a->ksize == 2 || a->ksize == 3 || a->ksize == 7, "conv: ksize %d unsupported", a->ksize);
@@ -579,7 +579,6 @@ int conv_forward_impl(const ofd_conv_args* a, hipStream_t s, int cout0, int pool
         P.pad_y = 1 - py; P.pad_x = 1 - px; P.out_oy = py; P.out_ox = px;
         P.phase_all = a->up2_phase == 5;
     }
-    P.cout0 = cout0;
     P.pool2 = pool2;
     P.residual_b = residual_b;
     if (fc) { P.fc_w = fc->w; P.fc_b = fc->b; P.fc_out = fc->out; }
@@ -618,10 +617,10 @@ int conv_forward_impl(const ofd_conv_args* a, hipStream_t s, int cout0, int pool
 }  // namespace ofd
 using namespace ofd;
 
-extern "C" int ofd_conv_forward(const ofd_conv_args* a, void* stream) { return conv_forward_impl(a, (hipStream_t)stream, 0); }
+extern "C" int ofd_conv_forward(const ofd_conv_args* a, void* stream) { return conv_forward_impl(a, (hipStream_t)stream); }
 extern "C" int ofd_conv_forward_pool2(const ofd_conv_args* a, void* stream) {
     OFD_CHECK_ARG(conv_pool2_supported(a), "conv_forward_pool2: 3x3, even H and W, Cout a multiple of 64 (not 64 -> 64), no split / GroupNorm statistics / activation residual");
-    return conv_forward_impl(a, (hipStream_t)stream, 0, 1);
+    return conv_forward_impl(a, (hipStream_t)stream, 1);
 }
 
 extern "C" size_t ofd_conv_gn_partial_count(int B, int H, int W, int Cout) {

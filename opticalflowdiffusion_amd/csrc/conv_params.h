@@ -36,7 +36,6 @@ struct ConvParams {
     int out_oy, out_ox; // KS == 2: the output is (2H, 2W) and this launch writes pixels (2y + out_oy, 2x + out_ox)
     int phase_all;      // KS == 2: one launch computes the four phases; block j -> XCD j % 8, phase (j / 8) % 4, tile slot j / 32 (the phases of a
                         // tile run on one XCD at the same time: its input tile comes from that L2 three times out of four)
-    int cout0;          // 1x1 streaming kernel: output channels below cout0 are not computed (training to_qkv with q recomputed downstream); 0 = all
     int cy_fast;        // conv_wp: 1-D grid, the channel blocks of a pixel tile adjacent in dispatch order and on one XCD
     const bf16_t* residual_b;   // conv_wp 3x3: a second plain residual (same shape as `residual`; training: gradient already in the buffer + the identity-residual gradient)
     int pool2;          // conv_wp 3x3: the epilogue sums every 2x2 block of output pixels and writes the (H/2, W/2) tensor (+ residual there): the

@@ -11,27 +11,12 @@
 //           -> LN -> + x   (each stage's accumulator tile is the next MFMA's B operand)
 // The PreNorm gain g is folded into Wq / Wkv (W.diag(g)) when the weights are prepared.
 #include <cstdlib>
+#include <type_traits>
 #include "blocks.h"
+#include "la_common.h"
 
 namespace ofd {
 
-int la_fused_blocks(int n, int B);
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-__device__ __forceinline__ uint32_t la_pack2(float a, float b) { return f2bf2(a, b); }
-__device__ __forceinline__ int acc_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-
-// registers 8*s2 .. 8*s2+7 of an accumulator tile as an MFMA operand fragment (k = tile row)
-__device__ __forceinline__ bf16x8 acc_frag(const f32x16& a, int s2) {
-    bf16x8 f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) f[j] = (__bf16)a[8 * s2 + j];
-    return f;
-}
-
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 template <int C>
 struct XRaw {
     u32x4 v[C / 16];
@@ -44,18 +29,17 @@ __device__ __forceinline__ void load_raw_x(const bf16_t* __restrict__ xrow, XRaw
     for (int s = 0; s < C / 16; ++s) r.v[s] = *(const u32x4*)(xrow + 16 * s + 8 * half);
 }
 
-// raw tile -> normalised (no gain) bf16 fragments (LayerNorm over channels, DD:121-125).  r03: the two sums run on the PACKED words
+// LayerNorm over channels (DD:121-125) of a raw tile: x^ = x * rstd + off.  r03: the two sums run on the PACKED words
 // (v_dot2_f32_bf16: x . (1, 1) and x . x, two channels per instruction, fp32 accumulate) and the variance is E[x^2] - mean^2 -- the
 // inputs are bf16 activations, |mean| / std stays far below the 2^12 at which fp32 cancellation would reach bf16 resolution -- so an
 // element costs unpack + one fma + convert instead of unpack + add + subtract + fma + multiply + convert.
 typedef __bf16 la_bf16x2 __attribute__((ext_vector_type(2)));
 template <int C>
-__device__ __forceinline__ void norm_x(const XRaw<C>& r, float eps, bf16x8 (&xs)[C / 16]) {
-    constexpr int KS = C / 16;
+__device__ __forceinline__ void norm_stats(const XRaw<C>& r, float eps, float& rstd, float& off) {
     const la_bf16x2 one = __builtin_bit_cast(la_bf16x2, 0x3f803f80u);
     float s1 = 0.0f, s2 = 0.0f;
 #pragma unroll
-    for (int s = 0; s < KS; ++s)
+    for (int s = 0; s < C / 16; ++s)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const la_bf16x2 w = __builtin_bit_cast(la_bf16x2, (uint32_t)r.v[s][j]);
@@ -66,9 +50,16 @@ __device__ __forceinline__ void norm_x(const XRaw<C>& r, float eps, bf16x8 (&xs)
     s2 += __shfl_xor(s2, 32, 64);
     const float mean = s1 * (1.0f / C);
     const float var = fmaxf(__builtin_fmaf(-mean, mean, s2 * (1.0f / C)), 0.0f);
-    const float rstd = rsqrtf(var + eps), off = -mean * rstd;
+    rstd = rsqrtf(var + eps);
+    off = -mean * rstd;
+}
+// raw tile -> normalised (no gain) bf16 fragments
+template <int C>
+__device__ __forceinline__ void norm_x(const XRaw<C>& r, float eps, bf16x8 (&xs)[C / 16]) {
+    float rstd, off;
+    norm_stats<C>(r, eps, rstd, off);
 #pragma unroll
-    for (int s = 0; s < KS; ++s)
+    for (int s = 0; s < C / 16; ++s)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const uint32_t w = r.v[s][j];
@@ -81,24 +72,10 @@ __device__ __forceinline__ void norm_x(const XRaw<C>& r, float eps, bf16x8 (&xs)
 // plain weights, and what the backward's q recompute / to_qkv weight gradient read) -- g: the PreNorm gain, fp32 [C] in LDS.
 template <int C>
 __device__ __forceinline__ void norm_x_gain(const XRaw<C>& r, float eps, const float* __restrict__ g, int half, bf16x8 (&xs)[C / 16]) {
-    constexpr int KS = C / 16;
-    const la_bf16x2 one = __builtin_bit_cast(la_bf16x2, 0x3f803f80u);
-    float s1 = 0.0f, s2 = 0.0f;
+    float rstd, off;
+    norm_stats<C>(r, eps, rstd, off);
 #pragma unroll
-    for (int s = 0; s < KS; ++s)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const la_bf16x2 w = __builtin_bit_cast(la_bf16x2, (uint32_t)r.v[s][j]);
-            s1 = __builtin_amdgcn_fdot2_f32_bf16(w, one, s1, false);
-            s2 = __builtin_amdgcn_fdot2_f32_bf16(w, w, s2, false);
-        }
-    s1 += __shfl_xor(s1, 32, 64);
-    s2 += __shfl_xor(s2, 32, 64);
-    const float mean = s1 * (1.0f / C);
-    const float var = fmaxf(__builtin_fmaf(-mean, mean, s2 * (1.0f / C)), 0.0f);
-    const float rstd = rsqrtf(var + eps), off = -mean * rstd;
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
+    for (int s = 0; s < C / 16; ++s) {
         const float4 g0 = *(const float4*)(g + 16 * s + 8 * half), g1 = *(const float4*)(g + 16 * s + 8 * half + 4);
         const float gg[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
 #pragma unroll
@@ -110,24 +87,10 @@ __device__ __forceinline__ void norm_x_gain(const XRaw<C>& r, float eps, const f
     }
 }
 
-// accumulator tile [rows = 32 channels][col = this lane's pixel] -> bf16, 16-byte stores: pairs of register quads are exchanged between the
-// half-waves (v_permlane32_swap) so that a lane stores 8 consecutive channels of its pixel; `row` = that pixel's first channel of the tile
-__device__ __forceinline__ void store_acc_rows(const f32x16& a, bf16_t* __restrict__ row, int half, bool ok) {
-#pragma unroll
-    for (int g = 0; g < 4; g += 2) {
-        const uint2 q0 = make_uint2(la_pack2(a[4 * g], a[4 * g + 1]), la_pack2(a[4 * g + 2], a[4 * g + 3]));
-        const uint2 q1 = make_uint2(la_pack2(a[4 * g + 4], a[4 * g + 5]), la_pack2(a[4 * g + 6], a[4 * g + 7]));
-        const auto rx = __builtin_amdgcn_permlane32_swap(q0.x, q1.x, false, false);
-        const auto ry = __builtin_amdgcn_permlane32_swap(q0.y, q1.y, false, false);
-        if (ok) *(uint4*)(row + 8 * g + 8 * half) = make_uint4(rx[0], ry[0], rx[1], ry[1]);
-    }
-}
-
 // ---- end of pass 1: the workgroup's four waves merge their online-softmax states (m, l, ctx relative to m) of one head through LDS and
 // write ONE part: a quarter of the partial traffic, and a grid of 256+ workgroups (small batches) stays within the combine's 256 parts.
 // Part format unchanged: [m 32 | l 32 | ctx[d][e] 32 x 32].  LDS: 4 x LA_PART_PITCH floats (rows padded to 36 floats).
 constexpr int LA_PART_PITCH = 64 + 32 * 36;
-constexpr float LOG2E = 1.4426950408889634f;
 __device__ __forceinline__ void la_store_part(float* lds, float* __restrict__ o, float m, float l, const f32x16& ctxT, int tid, int wave, int l31,
                                               int half) {
     float* mine = lds + wave * LA_PART_PITCH;
@@ -168,6 +131,39 @@ __device__ __forceinline__ void la_store_part(float* lds, float* __restrict__ o,
 }
 
 // ---- pass 1 ---------------------------------------------------------------------------------------
+// What the two first-pass kernels share.  The online-softmax state of a wave: per head, the reference point m, the normaliser l and ctx^T
+// relative to m.  How m moves and what p is (rescale and exp policies) stay in each kernel.
+__device__ __forceinline__ void ctx_state_init(f32x16 (&ctxT)[4], float (&m)[4], float (&l)[4]) {
+#pragma unroll
+    for (int hd = 0; hd < 4; ++hd) {
+        m[hd] = -3.0e38f;
+        l[hd] = 0.0f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) ctxT[hd][r] = 0.0f;
+    }
+}
+// the k tile [rows = pixels][col = d]: rows past the sample's end are taken out of the softmax
+__device__ __forceinline__ f32x16 ctx_mask_rows(f32x16 ka, int tile, int n, int half) {
+    if (tile * 32 + 32 > n) {            // (only a sample's last tile has rows past its end: 32 compares + selects per head otherwise)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            if (tile * 32 + acc_row(r, half) >= n) ka[r] = -3.0e38f;
+    }
+    return ka;
+}
+// maximum over the tile's pixels of every column d
+__device__ __forceinline__ float ctx_tile_max(const f32x16& ka) {
+    float mt = -3.0e38f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) mt = fmaxf(mt, ka[r]);
+    return fmaxf(mt, __shfl_xor(mt, 32, 64));
+}
+// ctx^T[e][d] += sum_pix v[pix][e] p[pix][d]: the accumulator tiles are the operands (rows = pixels = the contraction index)
+__device__ __forceinline__ void ctx_update(f32x16& ctxT, const f32x16& va, const f32x16& p) {
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2) ctxT = __builtin_amdgcn_mfma_f32_32x32x16_bf16(acc_frag(va, s2), acc_frag(p, s2), ctxT, 0, 0, 0);
+}
+
 // TRAIN (the training forward, C = 64): the pass also WRITES what the backward reads -- xn (LayerNorm output with the gain, bf16) and k | v
 // (channels 128 .. 383 of the [pixel][384] qkv tensor) -- so the LayerNorm kernel, the to_qkv conv and the read of k, v by la_ctx_stored_kernel
 // disappear (11 -> 6 tensor passes of 64 channels).  Its operands are those of the unfused path: xn rounded to bf16 times the PLAIN weights
@@ -189,13 +185,7 @@ __global__ void __launch_bounds__(256, 2) la_ctx_fused_kernel(const bf16_t* __re
 
     f32x16 ctxT[4];
     float m[4], l[4];
-#pragma unroll
-    for (int hd = 0; hd < 4; ++hd) {
-        m[hd] = -3.0e38f;
-        l[hd] = 0.0f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) ctxT[hd][r] = 0.0f;
-    }
+    ctx_state_init(ctxT, m, l);
     const bf16_t* xb = x + (size_t)b * n * C;
     XRaw<C> raw_next;
     load_raw_x<C>(xb + (size_t)min(wave_id * 32 + l31, n - 1) * C, raw_next, half);
@@ -248,15 +238,8 @@ __global__ void __launch_bounds__(256, 2) la_ctx_fused_kernel(const bf16_t* __re
 #pragma unroll
                 for (int r = 0; r < 16; ++r) ka[r] = bf2f(f2bf(ka[r]));      // the softmax sees the stored (bf16) k, as the backward will
             }
-            float mt = -3.0e38f;
-            if (tile * 32 + 32 > n) {            // (only a sample's last tile has rows past its end: 32 compares + selects per head otherwise)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    if (tile * 32 + acc_row(r, half) >= n) ka[r] = -3.0e38f;
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) mt = fmaxf(mt, ka[r]);
-            mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
+            ka = ctx_mask_rows(ka, tile, n, half);
+            const float mt = ctx_tile_max(ka);
             // deferred running maximum: the reference point m moves only when a tile's maximum exceeds it by more than `defer`
             // (natural-log units; 0 = always): p = exp(k - m) then stays below e^defer (2^8 by default: exact range for fp32 sums and
             // bf16 operands alike) and the rescaling of l and ctx^T -- 16 multiplies + an exp per head and tile -- runs only in the
@@ -272,17 +255,15 @@ __global__ void __launch_bounds__(256, 2) la_ctx_fused_kernel(const bf16_t* __re
                 for (int r = 0; r < 16; ++r) ctxT[hd][r] *= f;
             }
             float ps = 0.0f;
-            const float m2 = m[hd] * LOG2E;      // exp(k - m) as exp2(k log2e - m log2e): one fma + v_exp per element instead of sub, mul, v_exp
+            const float m2 = m[hd] * LA_LOG2E;      // exp(k - m) as exp2(k log2e - m log2e): one fma + v_exp per element instead of sub, mul, v_exp
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(ka[r], LOG2E, -m2));
+                const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(ka[r], LA_LOG2E, -m2));
                 ka[r] = p;
                 ps += p;
             }
             l[hd] += ps;
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2)   // ctx^T[e][d] += sum_pix v[pix][e] p[pix][d]
-                ctxT[hd] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(acc_frag(va, s2), acc_frag(ka, s2), ctxT[hd], 0, 0, 0);
+            ctx_update(ctxT[hd], va, ka);
             if constexpr (TRAIN) {
                 // the context kept for the BACKWARD must be the sum of v over the softmax the backward recomputes from the stored k (fp32
                 // p / l), not over p rounded to bf16: the backward's S = <dctx, ctx> and its dq lean on ctx cancelling against per-pixel
@@ -290,9 +271,7 @@ __global__ void __launch_bounds__(256, 2) la_ctx_fused_kernel(const bf16_t* __re
                 // (tests/test_linear_attention_block_gpu.py test_backward).  Second MFMA pass over the part of p the first one dropped.
 #pragma unroll
                 for (int r = 0; r < 16; ++r) ka[r] -= (float)(__bf16)ka[r];
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2)
-                    ctxT[hd] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(acc_frag(va, s2), acc_frag(ka, s2), ctxT[hd], 0, 0, 0);
+                ctx_update(ctxT[hd], va, ka);
             }
         }
     }
@@ -317,13 +296,7 @@ __global__ void __launch_bounds__(256, 2) la_ctx_stored_kernel(const bf16_t* __r
         for (int j = 0; j < 8; ++j) ident[s2][j] = (__bf16)((16 * s2 + 8 * half + j == l31) ? 1.0f : 0.0f);
     f32x16 ctxT[4];
     float m[4], l[4];
-#pragma unroll
-    for (int hd = 0; hd < 4; ++hd) {
-        m[hd] = -3.0e38f;
-        l[hd] = 0.0f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) ctxT[hd][r] = 0.0f;
-    }
+    ctx_state_init(ctxT, m, l);
     const bf16_t* qb = qkv + (size_t)b * n * 384;
     // this lane's k (v) units of a tile: head hd, k-step s2 -> channels 128 (256) + 32 hd + 16 s2 + 8 half .. + 7 of pixel tile * 32 + l31.
     // No cross-tile prefetch: with it the kernel needs 265 registers (9 spilled); the second resident workgroup covers the load latency.
@@ -346,32 +319,23 @@ __global__ void __launch_bounds__(256, 2) la_ctx_stored_kernel(const bf16_t* __r
                 ka = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kr[hd * 2 + s2]), ident[s2], ka, 0, 0, 0);   // rows = pixels, col = d
                 va = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vr[hd * 2 + s2]), ident[s2], va, 0, 0, 0);   // rows = pixels, col = e
             }
-            float mt = -3.0e38f;
-            if (tile * 32 + 32 > n) {            // (only a sample's last tile has rows past its end: 32 compares + selects per head otherwise)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    if (tile * 32 + acc_row(r, half) >= n) ka[r] = -3.0e38f;
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) mt = fmaxf(mt, ka[r]);
-            mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
+            ka = ctx_mask_rows(ka, tile, n, half);
+            const float mt = ctx_tile_max(ka);
             const float m_new = fmaxf(m[hd], mt);
             const float f = __expf(m[hd] - m_new);
             m[hd] = m_new;
             float ps = 0.0f;
-            const float m2 = m_new * LOG2E;
+            const float m2 = m_new * LA_LOG2E;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const float p = bf2f(f2bf(__builtin_amdgcn_exp2f(__builtin_fmaf(ka[r], LOG2E, -m2))));      // the value the context MFMA multiplies by: the normaliser sums the same
+                const float p = bf2f(f2bf(__builtin_amdgcn_exp2f(__builtin_fmaf(ka[r], LA_LOG2E, -m2))));      // the value the context MFMA multiplies by: the normaliser sums the same
                 ka[r] = p;
                 ps += p;
             }
             l[hd] = l[hd] * f + ps;
 #pragma unroll
             for (int r = 0; r < 16; ++r) ctxT[hd][r] *= f;
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2)   // ctx^T[e][d] += sum_pix v[pix][e] p[pix][d]
-                ctxT[hd] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(acc_frag(va, s2), acc_frag(ka, s2), ctxT[hd], 0, 0, 0);
+            ctx_update(ctxT[hd], va, ka);
         }
     }
     __shared__ __attribute__((aligned(16))) float part_s[4 * LA_PART_PITCH];
@@ -387,13 +351,16 @@ int launch_la_ctx_stored(const bf16_t* qkv, float* partial, int B, int n, hipStr
     return gx;
 }
 
-// combine partials -> context as pass 2's A fragments:
-// ctxfrag[bh][s2][lane][j] = ctx[d = 16 s2 + 8 (j>>2) + 4 (lane>>5) + (j&3)][e = lane & 31]
-// grid (B*4, 4): each workgroup produces 256 of the 1024 fragment elements of one (sample, head);
-// the per-part rescale weights exp(m_c - M) are computed once into LDS.
+// combine the partials: ctx[bh][d][e] = sum_c exp(m_c - M) ctx_c / (sum_c exp(m_c - M) l_c) / n, written
+//   FRAG:  as pass 2's A fragments, bf16: ctxfrag[bh][s2][lane][j] = ctx[d = 16 s2 + 8 (j>>2) + 4 (lane>>5) + (j&3)][e = lane & 31]
+//   !FRAG: as fp32 ctx[bh][d][e], with the softmax-over-pixels statistics ml[bh] = [M 32 | 1 / L 32] (kept for the backward) if ml_out
+// grid (B*4, 4): each workgroup produces 256 of the 1024 elements of one (sample, head) (the normalisers are recomputed by each of the
+// four); the per-part rescale weights exp(m_c - M) are computed once into LDS.
 constexpr int LA_MAX_PARTS = 256;
-__global__ void __launch_bounds__(256) la_ctx_combine_frag_kernel(const float* __restrict__ partial, bf16_t* __restrict__ ctxfrag,
-                                                                  int nparts, float inv_n) {
+template <class Out>      // bf16_t: FRAG, float: !FRAG
+__global__ void __launch_bounds__(256) la_ctx_combine_kernel(const float* __restrict__ partial, Out* __restrict__ out, int nparts, float inv_n,
+                                                             float* __restrict__ ml_out) {
+    constexpr bool FRAG = std::is_same<Out, bf16_t>::value;
     __shared__ float red[8][32], M[32], Linv[32], w_s[LA_MAX_PARTS][32];
     const int tid = threadIdx.x, bh = blockIdx.x, dd = tid & 31, grp = tid >> 5;
     const float* base = partial + (size_t)bh * nparts * 1088;
@@ -441,11 +408,22 @@ __global__ void __launch_bounds__(256) la_ctx_combine_frag_kernel(const float* _
 #pragma unroll
         for (int g = 1; g < 8; ++g) t += red[g][tid];
         Linv[tid] = 1.0f / t;
+        if (!FRAG && ml_out && blockIdx.y == 0) {
+            ml_out[(size_t)bh * 64 + tid] = M[tid];
+            ml_out[(size_t)bh * 64 + 32 + tid] = 1.0f / t;
+        }
     }
     __syncthreads();
-    const int i = blockIdx.y * 256 + tid;
-    const int j = i & 7, lane = (i >> 3) & 63, s2 = i >> 9;
-    const int d = 16 * s2 + 8 * (j >> 2) + 4 * (lane >> 5) + (j & 3), e = lane & 31;
+    const int i = blockIdx.y * 256 + tid;      // this thread's element of the output, and its (d, e)
+    int d, e;
+    if constexpr (FRAG) {
+        const int j = i & 7, lane = (i >> 3) & 63, s2 = i >> 9;
+        d = 16 * s2 + 8 * (j >> 2) + 4 * (lane >> 5) + (j & 3);
+        e = lane & 31;
+    } else {
+        d = i >> 5;
+        e = i & 31;
+    }
     // eight loads in flight per thread (one at a time this loop was a chain of nparts memory latencies: 54 us per launch); the
     // products are still added in part order
     float a = 0.0f;
@@ -466,7 +444,13 @@ __global__ void __launch_bounds__(256) la_ctx_combine_frag_kernel(const float* _
                 if (c0 + k < nparts) a += v[k] * __expf(mc[k] - M[d]);
         }
     }
-    ctxfrag[(size_t)bh * 1024 + i] = f2bf(a * Linv[d] * inv_n);
+    const float c = a * Linv[d] * inv_n;
+    if constexpr (FRAG) out[(size_t)bh * 1024 + i] = f2bf(c);
+    else out[(size_t)bh * 1024 + i] = c;
+}
+// the fp32 form: the forward of the unfused path (la_core.hip) and the tape of the fused training forward
+void launch_la_ctx_combine(const float* partial, float* ctx, int B, int nparts, float inv_n, float* ml_out, hipStream_t s) {
+    la_ctx_combine_kernel<<<dim3(B * 4, 4), 256, 0, s>>>(partial, ctx, nparts, inv_n, ml_out);
 }
 
 // ---- pass 2 ---------------------------------------------------------------------------------------
@@ -531,15 +515,7 @@ __global__ void __launch_bounds__(256, C == 64 ? 4 : 2) la_out_fused_kernel(cons
 #pragma unroll
                 for (int r = 0; r < 16; ++r) qa[r] = bf2f(f2bf(qa[r]));
             }
-            float mx = qa[0];                 // softmax over d (DD:234) then * scale (DD:237)
-#pragma unroll
-            for (int r = 1; r < 16; ++r) mx = fmaxf(mx, qa[r]);
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            float sum = 0.0f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { qa[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(qa[r], LOG2E, -mx * LOG2E)); sum += qa[r]; }
-            sum += __shfl_xor(sum, 32, 64);
-            const float k = scale / sum;
+            const float k = scale / softmax_d(qa, 32);      // softmax over d (DD:234) then * scale (DD:237)
 #pragma unroll
             for (int r = 0; r < 16; ++r) qa[r] *= k;
             f32x16 oa;                        // out[e][pixel] = sum_d ctx[d][e] q~[d][pixel]   (DD:242)
@@ -589,8 +565,7 @@ __global__ void __launch_bounds__(256, C == 64 ? 4 : 2) la_out_fused_kernel(cons
         q += __shfl_xor(q, 32, 64);
         const float rstd = rsqrtf(q * (1.0f / C) + eps_post);
         {
-            // 16-byte accesses: pairs of register quads are exchanged between the half-waves (v_permlane32_swap) so that a
-            // lane loads / stores 8 consecutive channels; every lane takes part, out-of-range pixels use a clamped row
+            // 16-byte stores (store_quad_pair); every lane takes part, out-of-range pixels use a clamped row
             const bool ok = pix < n;
             bf16_t* yrow = y + ((size_t)b * n + min(pix, n - 1)) * C;
 #pragma unroll
@@ -613,11 +588,9 @@ __global__ void __launch_bounds__(256, C == 64 ? 4 : 2) la_out_fused_kernel(cons
                         const float o1 = acc_o[rt][4 * (g + k) + 1] * rstd * gv.y + bf2f((bf16_t)(xq[k][0] >> 16));
                         const float o2 = acc_o[rt][4 * (g + k) + 2] * rstd * gv.z + bf2f((bf16_t)(xq[k][1] & 0xffffu));
                         const float o3 = acc_o[rt][4 * (g + k) + 3] * rstd * gv.w + bf2f((bf16_t)(xq[k][1] >> 16));
-                        qo[k] = make_uint2(la_pack2(o0, o1), la_pack2(o2, o3));
+                        qo[k] = pack_quad(o0, o1, o2, o3);
                     }
-                    const auto rx = __builtin_amdgcn_permlane32_swap(qo[0].x, qo[1].x, false, false);
-                    const auto ry = __builtin_amdgcn_permlane32_swap(qo[0].y, qo[1].y, false, false);
-                    if (ok) *(uint4*)(yrow + rt * 32 + 8 * g + 8 * half) = make_uint4(rx[0], ry[0], rx[1], ry[1]);
+                    store_quad_pair(yrow + rt * 32 + 8 * g, qo[0], qo[1], half, ok);
                 }
         }
     }
@@ -652,6 +625,13 @@ __global__ void __launch_bounds__(256) la_weight_prep_kernel(const float* __rest
 constexpr float LA_DEFER = 5.545177f;
 // second-pass workgroups per sample (at least 1024 over the batch: small batches need enough workgroups for the chip)
 constexpr int LA_GX2_CAP = 128;
+static int la_out_blocks(int n, int B) {
+    int gx2 = cdiv(cdiv(n, 32), 4 * 4);     // >= 4 tiles per wave amortise the weight staging
+    if (gx2 < 1) gx2 = 1;
+    const int cap2 = (LA_GX2_CAP * B < 1024) ? 1024 / B : LA_GX2_CAP;
+    if (gx2 > cap2) gx2 = cap2;
+    return gx2;
+}
 
 template <int C>
 static int launch_la(const bf16_t* x, const bf16_t* wq, const bf16_t* wkv, const bf16_t* woutp, const float* bias, const float* g2,
@@ -666,17 +646,11 @@ static int launch_la(const bf16_t* x, const bf16_t* wq, const bf16_t* wkv, const
     }
     const int gx = la_fused_blocks(n, B);
     la_ctx_fused_kernel<C, false><<<dim3(gx, B), 256, LDS1, s>>>(x, wkv, partial, n, eps_pre, LA_DEFER, nullptr, nullptr, nullptr);
-    la_ctx_combine_frag_kernel<<<dim3(B * 4, 4), 256, 0, s>>>(partial, ctxfrag, gx, 1.0f / (float)n);
-    int gx2 = cdiv(cdiv(n, 32), 4 * 4);     // >= 4 tiles per wave amortise the weight staging
-    if (gx2 < 1) gx2 = 1;
-    const int cap2 = (LA_GX2_CAP * B < 1024) ? 1024 / B : LA_GX2_CAP;
-    if (gx2 > cap2) gx2 = cap2;
-    la_out_fused_kernel<C, false><<<dim3(gx2, B), 256, LDS2, s>>>(x, wq, woutp, ctxfrag, bias, g2, y, n, eps_pre, eps_post, 0.17677669529663687f, nullptr, nullptr);
+    la_ctx_combine_kernel<<<dim3(B * 4, 4), 256, 0, s>>>(partial, ctxfrag, gx, 1.0f / (float)n, nullptr);
+    la_out_fused_kernel<C, false><<<dim3(la_out_blocks(n, B), B), 256, LDS2, s>>>(x, wq, woutp, ctxfrag, bias, g2, y, n, eps_pre, eps_post, LA_SCALE, nullptr, nullptr);
     OFD_LAUNCH_CHECK();
     return OFD_OK;
 }
-
-void launch_la_ctx_combine(const float* partial, float* ctx, int B, int nparts, float inv_n, float* ml_out, hipStream_t s);   // blocks.hip
 
 // The training forward of a 64-channel block: the two fused passes, which also leave the tape (xn, k | v inside qkv, o2) and the fp32 context + softmax
 // statistics (ctx, ml) of the unfused path for the backward (unet_train.hip linattn_backward).  wq / wkv: the PLAIN to_qkv weights in fragment layout.
@@ -694,13 +668,9 @@ int k_linear_attention_fused_train(const bf16_t* x, const bf16_t* wq, const bf16
     }
     const int gx = la_fused_blocks(n, B);
     la_ctx_fused_kernel<64, true><<<dim3(gx, B), 256, LDS1, s>>>(x, wkv, partial, n, eps_pre, LA_DEFER, g_pre, xn, qkv);
-    la_ctx_combine_frag_kernel<<<dim3(B * 4, 4), 256, 0, s>>>(partial, ctxfrag, gx, 1.0f / (float)n);
+    la_ctx_combine_kernel<<<dim3(B * 4, 4), 256, 0, s>>>(partial, ctxfrag, gx, 1.0f / (float)n, nullptr);
     launch_la_ctx_combine(partial, ctx, B, gx, 1.0f / (float)n, ml, s);
-    int gx2 = cdiv(cdiv(n, 32), 4 * 4);
-    if (gx2 < 1) gx2 = 1;
-    const int cap2 = (LA_GX2_CAP * B < 1024) ? 1024 / B : LA_GX2_CAP;
-    if (gx2 > cap2) gx2 = cap2;
-    la_out_fused_kernel<64, true><<<dim3(gx2, B), 256, LDS2, s>>>(x, wq, woutp, ctxfrag, bias, g2, y, n, eps_pre, eps_post, 0.17677669529663687f, g_pre, o2);
+    la_out_fused_kernel<64, true><<<dim3(la_out_blocks(n, B), B), 256, LDS2, s>>>(x, wq, woutp, ctxfrag, bias, g2, y, n, eps_pre, eps_post, LA_SCALE, g_pre, o2);
     OFD_LAUNCH_CHECK();
     return OFD_OK;
 }

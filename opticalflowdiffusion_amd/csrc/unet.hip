@@ -125,7 +125,7 @@ static void build_registry(ofd_unet* u) {
 
 void conv(Ctx& c, const std::string& prefix, const std::vector<SrcSpec>& srcs, Tensor out, const float* in_scale,
                  const float* in_shift, const bf16_t* residual, const bf16_t* res_act, const float* res_scale,
-                 const float* res_shift, float* gn_partial, int cout0, const FcFuse* fc) {
+                 const float* res_shift, float* gn_partial, const FcFuse* fc) {
     if (c.rc != OFD_OK) return;
     const ConvDesc& d = c.u->convs[c.u->cindex.at(prefix)];
     ofd_conv_args a{};
@@ -155,7 +155,7 @@ void conv(Ctx& c, const std::string& prefix, const std::vector<SrcSpec>& srcs, T
     const int cls3 = pp ? PC_CONV3_PP : (d.Cout % 128 == 0 ? PC_CONV3 : PC_CONV3_64);
     c.begin(d.ksize == 3 ? cls3 : (d.ksize == 1 ? PC_CONV1 : PC_CONV7), flops, bytes,
             prefix + " " + std::to_string(d.Cin) + "->" + std::to_string(d.Cout) + " @" + std::to_string(out.H) + "x" + std::to_string(out.W));
-    RUN(conv_forward_impl(&a, c.s, cout0, 0, nullptr, fc));
+    RUN(conv_forward_impl(&a, c.s, 0, nullptr, fc));
     c.end();
 }
 
@@ -206,7 +206,7 @@ static Tensor resblock(Ctx& c, const std::string& name, const std::vector<Tensor
     RUN(k_gn_finalize(p2, B, H, W, Cout, u->P(name + ".block2.norm.weight"), u->P(name + ".block2.norm.bias"), nullptr, 0, 0, a2, s2, c.s, st2));
     c.end();
     if (cin != Cout) {
-        conv(c, name + ".res_conv", srcs, out, nullptr, nullptr, nullptr, h2.p, a2, s2, nullptr, 0, fc);   // DD:214 fused into the 1x1 (fc: + the final 1x1 conv, `out` not written)
+        conv(c, name + ".res_conv", srcs, out, nullptr, nullptr, nullptr, h2.p, a2, s2, nullptr, fc);   // DD:214 fused into the 1x1 (fc: + the final 1x1 conv, `out` not written)
     } else {
         c.begin(PC_RESOUT, 0, (double)B * H * W * Cout * 6.0);
         RUN(k_resblock_out(h2.p, a2, s2, in[0].p, out.p, B, H, W, Cout, c.s));
@@ -227,7 +227,7 @@ static Tensor linattn(Ctx& c, const std::string& name, Tensor x) {
     const size_t npix = (size_t)B * n;
     auto fit = u->la_fused.find(name);
     if (fit != u->la_fused.end() && !c.train) {
-        // fused two-pass block (la_fused.hip): no LayerNorm / qkv / head-output tensors in HBM
+        // inference, C <= 128: fused two-pass block (la_fused.hip): no LayerNorm / qkv / head-output tensors in HBM
         const int nparts = la_fused_blocks(n, B);
         float* partial = c.tmpf((size_t)B * 4 * nparts * 1088);
         bf16_t* ctxfrag = (bf16_t*)c.tmpf((size_t)B * 2048);
@@ -245,7 +245,7 @@ static Tensor linattn(Ctx& c, const std::string& name, Tensor x) {
     Tensor xn = c.tmp(C, H, W), qkv = c.tmp(384, H, W), ao = c.tmp(128, H, W), o2 = c.tmp(C, H, W);
     const int nparts = la_fwd_parts(B, n);
     if (c.train && fit != u->la_fused.end() && la_train_fused(C)) {
-        // training, 64 channels: the two fused passes leave the tape themselves (xn, k | v, o2, ctx, ml): no LayerNorm kernels, no to_qkv conv
+        // training, C = 64: the two fused passes leave the tape themselves (xn, k | v, o2, ctx, ml): no LayerNorm kernels, no to_qkv conv
         float* partial = c.tmpf((size_t)B * 4 * nparts * 1088);
         bf16_t* ctxfrag = (bf16_t*)c.tmpf((size_t)B * 2048);
         float* ctx = c.keepf((size_t)B * 4 * 1024);
@@ -264,6 +264,7 @@ static Tensor linattn(Ctx& c, const std::string& name, Tensor x) {
         u->tape.push_back(r);
         return y;
     }
+    // unfused: training at C = 128, and the wider blocks (C >= 256) in inference and training
     float* partial = c.tmpf((size_t)B * 4 * nparts * 1088);
     float* ctx = c.train ? c.keepf((size_t)B * 4 * 1024) : c.tmpf((size_t)B * 4 * 1024);
     float* ml = c.train ? c.keepf((size_t)B * 4 * 64) : nullptr;
@@ -273,19 +274,13 @@ static Tensor linattn(Ctx& c, const std::string& name, Tensor x) {
     RUN(k_layernorm_c(x.p, u->P(name + ".fn.norm.g"), nullptr, xn.p, npix, C, site_eps(u, name + ".fn.norm"), c.s));
     c.end();
     SrcSpec s; s.t = xn;
-    // training, 64 channels: the passes that need q re-derive it from xn -- only k and v are computed
-    const bool rq = c.train && la_train_fused(C);
-    conv(c, name + ".fn.fn.to_qkv", {s}, qkv, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, rq ? 128 : 0);
+    conv(c, name + ".fn.fn.to_qkv", {s}, qkv, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
     c.begin(PC_LINATTN, 4.0 * npix * 4 * 32 * 32, (double)npix * (384 + 128 + 128) * 2);
-    if (C <= 128) {     // to_out.0 rides on the head-output tile of the core's second pass (la_core.hip lc_out_kernel)
+    if (C == 128) {     // to_out.0 rides on the head-output tile of the core's second pass (la_core.hip lc_out_kernel)
         const ConvDesc& d = u->convs[u->cindex.at(name + ".fn.fn.to_out.0")];
-        // training, 64 channels: nothing reads the head outputs again (the backward derives what it needs from ctx and q)
-        bf16_t* ao_out = rq ? nullptr : ao.p;
-        const ConvDesc& dq = u->convs[u->cindex.at(name + ".fn.fn.to_qkv")];
-        RUN(k_linear_attention_core(qkv.p, partial, ctx, ao_out, B, n, c.s, ml, u->d_wbuf + d.w_off, u->P(name + ".fn.fn.to_out.0.bias"), o2.p, C,
-                                    rq ? xn.p : nullptr, rq ? u->d_wbuf + dq.w_off : nullptr));
+        RUN(k_linear_attention_core(qkv.p, partial, ctx, ao.p, B, n, c.s, ml, u->d_wbuf + d.w_off, u->P(name + ".fn.fn.to_out.0.bias"), o2.p, C));
         c.end();
-    } else {
+    } else {            // C >= 256: the plain core, then the to_out.0 conv
         RUN(k_linear_attention_core(qkv.p, partial, ctx, ao.p, B, n, c.s, ml));
         c.end();
         SrcSpec s2; s2.t = ao;

@@ -277,7 +277,7 @@ static inline bool la_train_fused(int C) { return C == 64; }
 
 float site_eps(const ofd_unet* u, const std::string& site);
 void conv(Ctx& c, const std::string& prefix, const std::vector<SrcSpec>& srcs, Tensor out, const float* in_scale, const float* in_shift,
-          const bf16_t* residual, const bf16_t* res_act, const float* res_scale, const float* res_shift, float* gn_partial, int cout0 = 0,
+          const bf16_t* residual, const bf16_t* res_act, const float* res_scale, const float* res_shift, float* gn_partial,
           const FcFuse* fc = nullptr);
 size_t persist_bytes(const ofd_unet* u, int B, int H, int W);
 size_t scratch_bytes(const ofd_unet* u, int B, int H, int W);

@@ -158,7 +158,7 @@ static Tensor conv_backward(Bwd& b, const std::string& prefix, const std::vector
         a.out = t.g;
         if (conv_pool2_supported(&a)) {
             c.begin(PC_DGRAD3, 2.0 * px * d.Cout * (double)d.Cin * taps, px * 2.0 * d.Cout + px * 0.5 * cin, prefix + " dgrad (pooled)");
-            RUN(conv_forward_impl(&a, c.s, 0, 1));
+            RUN(conv_forward_impl(&a, c.s, 1));
             c.end();
             b.mark(t);
             D = t; D.p = t.g;
@@ -195,7 +195,7 @@ static Tensor conv_backward(Bwd& b, const std::string& prefix, const std::vector
     a.residual = add;
     a.out = D.p;
     c.begin(d.ksize == 3 ? PC_DGRAD3 : PC_DGRAD1, 2.0 * px * d.Cout * (double)d.Cin * taps, px * 2.0 * (d.Cout + cin), prefix + " dgrad");
-    RUN(conv_forward_impl(&a, c.s, 0, 0, res_b));
+    RUN(conv_forward_impl(&a, c.s, 0, res_b));
     c.end();
     return D;
 }
@@ -326,9 +326,9 @@ static void linattn_backward(Bwd& b, const TapeRec& r) {
         if (c.rc != OFD_OK) return;
         c.begin(PC_LABWD, npix * (4.0 * 4 * 32 * 32 * 2 + 4.0 * 384 * 64), (double)npix * (384 + 128 + 64 + 64) * 2, name + " core + to_qkv bwd");
         const ConvDesc& dto = u->convs[u->cindex.at(name + ".fn.fn.to_out.0")];
-        RUN(k_linear_attention_core_bwd(r.qkv.p, r.o2.g, r.ctx, r.ml, nullptr, ws, B, n, c.s, r.xn.p, u->d_wtbuf + d.w_off, acc, Dx.p,
-                                        u->d_wbuf + dto.w_off, u->d_wtbuf + dto.w_off, u->d_wacc + dto.w_off, u->G(name + ".fn.fn.to_out.0.bias"),
-                                        u->d_wbuf + d.w_off));
+        RUN(k_linear_attention_block_bwd(r.qkv.p, r.o2.g, r.ctx, r.ml, ws, B, n, c.s, r.xn.p, u->d_wtbuf + d.w_off, acc, Dx.p,
+                                         u->d_wbuf + dto.w_off, u->d_wtbuf + dto.w_off, u->d_wacc + dto.w_off, u->G(name + ".fn.fn.to_out.0.bias"),
+                                         u->d_wbuf + d.w_off));
         RUN(det_flush_wacc(c, dto));
         RUN(k_wgrad_finish(u->d_wacc + dto.w_off, u->P(dto.wname), u->G(dto.wname), dto.Cout, dto.Cin, dto.Cin_pad, dto.ksize, dto.ws_eps, dto.unshuffle, 0, c.s));
         RUN(det_flush_wacc(c, d));
