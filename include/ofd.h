@@ -29,6 +29,7 @@
  *   (not in the reference)            two-frame interpolation (softmax splatting) -> ofd_interp_prep, ofd_interp_merge
  *   (not in the reference)            joint bilateral upsampling (reduced-size sampling) -> ofd_joint_upsample
  *   (not in the reference)            looping clips from a steady motion field -> ofd_flow_integrate, ofd_loop_render
+ *   (not in the reference)            forward-backward check of a flow pair -> ofd_flow_consistency
  *   denoising_diffusion.py:806-812    q_sample                          -> ofd_q_sample
  *   denoising_diffusion.py:844-879,985-993  p_losses noise / target     -> ofd_diffusion_prep
  *   denoising_diffusion.py:73-77      (un)normalize                     -> ofd_range_map
@@ -222,6 +223,39 @@ int ofd_flow_integrate(const float* motion, float* disp, int B, int H, int W, in
 size_t ofd_loop_workspace(int B, int H, int W, int nk);
 int ofd_loop_render(const float* img, const float* motion, float* video, int B, int C, int H, int W, int N, int k0, int nk, int substeps,
                     int order, float speed, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Forward-backward consistency check of a flow pair (Sundaram, Brox & Keutzer, "Dense Point Trajectories by GPU-accelerated Large
+ * Displacement Optical Flow", ECCV 2010; the bound of Meister, Hur & Roth, "UnFlow", AAAI 2018).  An addition: nothing in the reference
+ * holds the two directions of a flow against each other.  Following a pixel by flow_ab and coming back by flow_ba should end where it
+ * started; where it does not, the pixel is occluded in the other frame or one of the flows is wrong.  All arithmetic fp32, in the order
+ * written here.
+ * flow12, flow21: (B,2,H,W) in pixels, channel 0 = x, frame1(p) ~ frame2(p + flow12(p)): the convention of ofd_splat_fwd and
+ * ofd_interp_prep.  For direction a -> b ((1, 2), then (2, 1)) at pixel p = (x, y), with f = flow_ab(p), the first rule that applies:
+ *   5 invalid       a component of f is non-finite.
+ *   3 leaves        q = p + f (one fp32 addition per axis) is not inside: inside = 0 <= q.x <= W-1 and 0 <= q.y <= H-1, the test of
+ *                   ofd_interp_prep (false for a non-finite q).
+ *   4 unmatched     g = the bilinear read of flow_ba at q, by ofd_interp_prep's formula (x0 = floor(q.x), x1 = min(x0 + 1, W-1),
+ *                   tx = q.x - x0, likewise in y; value = (1-ty) * ((1-tx) * g00 + tx * g01) + ty * ((1-tx) * g10 + tx * g11)), has a
+ *                   non-finite component (a non-finite corner makes it so even under weight 0).
+ *   2 inconsistent  r = f + g;  e2 = r.x*r.x + r.y*r.y;  m = (f.x*f.x + f.y*f.y) + (g.x*g.x + g.y*g.y);  bound = a1*m + a2;
+ *                   `e2 <= bound` is false.  (A finite g so large that its square overflows gives e2 = m = inf: inf <= inf holds for
+ *                   a1 > 0, and bound is NaN for a1 = 0.)
+ *   1 released      consistent, but dilate > 0 and some pixel of the frame within Chebyshev distance dilate has a state in {2,3,4,5}.
+ *   0 held          every other consistent pixel.
+ * known (2,B,2,H,W): flow_ab(p) bit for bit in state 0, NaN in both components otherwise: the `known` of the constrained reverse steps
+ * once scaled, i.e. what the samplers hold fixed.  err (2,B,1,H,W): sqrtf(e2) in states 0, 1, 2, NaN otherwise.  state (2,B,1,H,W):
+ * uint8.  counts (2,B,6), int32: the number of pixels per state; the call zeroes it with a memset on `stream` and fills it with integer
+ * atomics, one instruction per wave and tile.  Index 0 of the leading dimension is direction 1 -> 2.
+ * One launch for both directions and all samples; no float atomics, no host sync, the same input gives the same bits.  A workgroup owns
+ * a 64 x 16 tile of one direction and sample, a thread 4 neighbouring pixels of a row.  For dilate > 0 it also classifies the ring of
+ * dilate pixels around its tile, keeps a byte per position in LDS and takes the (2 dilate + 1)^2 maximum there: no plane in between
+ * goes through memory.  dilate == 0 has no ring, LDS or barrier.  Loads and stores are 16 bytes wide (state: 4) where W % 4 == 0 and
+ * flow12, flow21, known, err are 16-byte and state 4-byte aligned, one element wide otherwise, with the same bits.  a1, a2 finite and
+ * >= 0; 0 <= dilate <= 4; H, W <= 32768; 2 * B * ceil(H / 16) * ceil(W / 64) < 2^30.  Outputs must not alias inputs.  Argument errors
+ * return OFD_ERR_ARG and set ofd_last_error before any GPU work.  Compulsory traffic per direction and pixel: 8 B read, 8 + 4 + 1 B
+ * written: 42 * B * H * W bytes in all.  The pass is bound by the latency of its gathers (8 corner loads per pixel), not by that. */
+int ofd_flow_consistency(const float* flow12, const float* flow21, float a1, float a2, int dilate, float* known, float* err,
+                         uint8_t* state, int32_t* counts, int B, int H, int W, void* stream);
 
 /* ------------------------------------------------------------ grid_sample warp (WP:95-119) -
  * second: (B,C,H,W), flow: (B,2,H,W) exactly as handed to the reference's warp(mode='backward'):

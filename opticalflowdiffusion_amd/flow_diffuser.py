@@ -20,7 +20,8 @@ import torch
 
 from .denoising_diffusion import UNSET, PhotoGuide, Unet, ConditionalDiffusion, loss_by_timestep
 from .ema import EMA_DEFAULTS, EmaMixin, ema_optimizer_kwargs
-from .warp import box_reduce, interpolate_frames, loop_frames, loop_params, upsample_flow, upsample_params, warp
+from .warp import (box_reduce, consistency_params, flow_consistency, interpolate_frames, loop_frames, loop_params, upsample_flow,
+                   upsample_params, warp)
 from . import _lib as L
 
 try:                                                   # pragma: no cover - not installed in this image
@@ -476,6 +477,60 @@ class FlowDiffuser(EmaMixin, _Base):
             _samples, fl = self.sample(frame1, frame1.new_zeros(B, 2, H, W), target_frame=frame2, **sample_kw)
         return fl[:, -1] * float(self.flow_max)
 
+    def estimate_flow_pair(self, frame1, frame2, refine=1, a1=0.01, a2=0.5, dilate=2, refine_photo=False, **sample_kw):
+        """Both flows between two frames, made to agree with each other (not in the reference): (flow12, flow21, check), the flows
+        (B, 2, H, W) in pixels as `estimate_flow` returns them, check the `warp.FlowConsistency` of the returned pair (states, round
+        trip miss, counts).  Frames are (B, 3, H, W) in cond's range (2 * img - 1).
+        Round 0 is ONE `estimate_flow(cat(frame1, frame2), cat(frame2, frame1), **sample_kw)` call on 2B samples, as `interpolate`
+        makes it.  Each of the `refine` (0..16) rounds runs the forward-backward check `warp.flow_consistency(flow12, flow21, a1, a2,
+        dilate)` and one `self.sample` on the 2B batch with known_flow = cat(known12, known21): the part of each flow that passes is
+        held bit for bit, the part that fails -- occluded, leaving the frame, mismatched, or within `dilate` pixels of such a pixel -- is
+        sampled again given the rest (RePaint-style inpainting, no retraining).  By default these calls get no target_frame and no
+        photo_* key of sample_kw: where a pixel is occluded there is nothing in the other frame for a photometric pull to match, so
+        the prior alone completes it; refine_photo=True passes both.  refine=0 returns the bits of the `estimate_flow` call.
+        With refine > 0 everything known_flow rejects is a ValueError before any UNet call: a non-diffusion model, target 'target',
+        latent=True, sample_scale > 1.  Cost: 1 + refine chains on 2B samples; no host sync beyond `sample`'s.  a1, a2 are UnFlow's
+        (Meister et al. 2018) and untuned with trained weights; how well the prior completes occluded regions has not been
+        measured."""
+        if isinstance(refine, bool) or not isinstance(refine, int) or not 0 <= refine <= 16:
+            raise ValueError(f"estimate_flow_pair: refine must be an integer in 0..16, got {refine!r}")
+        par = consistency_params(a1, a2, dilate, name="estimate_flow_pair")
+        for name, fr in (("frame1", frame1), ("frame2", frame2)):
+            if not torch.is_tensor(fr) or fr.dim() != 4 or fr.shape[1] != 3:
+                raise ValueError(f"estimate_flow_pair: {name} must be (B, 3, H, W), got "
+                                 f"{tuple(fr.shape) if torch.is_tensor(fr) else type(fr).__name__}")
+        if frame1.shape != frame2.shape:
+            raise ValueError(f"estimate_flow_pair: frame2 must have frame1's shape {tuple(frame1.shape)}, got {tuple(frame2.shape)}")
+        if "known_flow" in sample_kw or "target_frame" in sample_kw:
+            raise ValueError("estimate_flow_pair: known_flow and target_frame are its own to set; use estimate_flow to pass them")
+        B, _, H, W = frame1.shape
+        cond, other = torch.cat((frame1, frame2)), torch.cat((frame2, frame1))
+        if refine > 0:
+            if not self.is_diffusion:
+                raise ValueError("estimate_flow_pair: refine > 0 needs a diffusion model: is_diffusion=False is a plain regression, there "
+                                 "is no chain to constrain")
+            if self.latent:
+                raise ValueError("estimate_flow_pair: refine > 0 is not supported with latent=True (the photometric estimate it starts "
+                                 "from compares frames in pixel space)")
+            if self.target not in ("flow", "joint"):
+                raise ValueError(f"estimate_flow_pair: refine > 0 is not supported for target={self.target!r}: there the flow is an "
+                                 "extra model output, not part of the diffused tensor")
+            reduced = {k: v for k, v in sample_kw.items() if k in ("sample_scale", "upsample_radius", "upsample_sigma_s", "upsample_sigma_r")}
+            if self.reduced_sampling(cond, None, **reduced)[0] > 1:
+                raise ValueError("estimate_flow_pair: refine > 0 cannot be combined with sample_scale > 1: known_flow has no reduced form")
+        refine_kw = sample_kw if refine_photo else {k: v for k, v in sample_kw.items() if not k.startswith("photo_")}
+        scale = float(self.flow_max)
+        with torch.no_grad():
+            both = self.estimate_flow(cond, other, **sample_kw)
+            for _ in range(refine):
+                check = flow_consistency(both[:B], both[B:], **par)
+                known = torch.cat((check.known12, check.known21))
+                extra = dict(target_frame=other) if refine_photo else {}
+                _samples, fl = self.sample(cond, cond.new_zeros(2 * B, 2, H, W), known_flow=known, **extra, **refine_kw)
+                both = torch.where(torch.isnan(known), fl[:, -1] * scale, both)     # held pixels keep their bits through every round
+            check = flow_consistency(both[:B], both[B:], **par)
+        return both[:B], both[B:], check
+
     def animate(self, cond, flow=None, frames=8, times=None, fill_holes=True, fill_gain=1.0, **sample_kw):
         """A short clip from a still (not in the reference, which stops at one raw splat): (video, flow).
         cond: (B, 3, H, W) as for `sample` (2 * img - 1).  flow: (B, 2, H, W) in units of flow_max, i.e. the last trajectory frame of
@@ -550,15 +605,17 @@ class FlowDiffuser(EmaMixin, _Base):
         return video, flow
 
     def interpolate(self, frame1, frame2, frames=7, times=None, flow12=None, flow21=None, alpha=10.0, beta=0.0, fill_holes=True,
-                    fill_gain=1.0, **sample_kw):
+                    fill_gain=1.0, refine=0, **sample_kw):
         """The frames between two real frames (not in the reference): (video, flow12, flow21), by softmax splatting both frames to every
         time and blending them (`warp.interpolate_frames`, which has the method and the meaning of alpha and beta).
         frame1, frame2: (B, 3, H, W) in cond's range (2 * img - 1).  times: numbers in [0, 1], default k / (frames + 1) for
         k = 1..frames (the frames strictly in between).  flow12, flow21: (B, 2, H, W) IN PIXELS as `estimate_flow` returns them
         (frame1(p) ~ frame2(p + flow12(p))), both or neither.  Neither: both come from ONE call
         estimate_flow(cat(frame1, frame2), cat(frame2, frame1), **sample_kw) on a batch of 2B.  Both: no UNet call is made, and
-        sample_kw is an error.  video: (B, n, 3, H, W) in cond's range; fill_holes=False leaves NaN where neither frame lands.
-        Forward only."""
+        sample_kw is an error.  refine > 0 (with neither flow given; with flows it is an error): the flows come from
+        `estimate_flow_pair(frame1, frame2, refine=refine, **sample_kw)` instead, which re-samples the part of each flow that fails the
+        forward-backward check; sample_kw may then carry its a1, a2, dilate and refine_photo.  refine=0 is the call above, unchanged.
+        video: (B, n, 3, H, W) in cond's range; fill_holes=False leaves NaN where neither frame lands.  Forward only."""
         if self.latent:
             raise ValueError("interpolate: latent=True is not supported (every frame would have to be decoded by the Autoencoder)")
         if times is None:
@@ -574,14 +631,21 @@ class FlowDiffuser(EmaMixin, _Base):
             raise ValueError("interpolate: flow12 and flow21 come together: give both, or neither to have both estimated")
         if flow12 is not None and sample_kw:
             raise ValueError(f"interpolate: {sorted(sample_kw)} are sampling arguments; with the flows given nothing is sampled")
+        if isinstance(refine, bool) or not isinstance(refine, int) or not 0 <= refine <= 16:
+            raise ValueError(f"interpolate: refine must be an integer in 0..16, got {refine!r}")
+        if refine > 0 and flow12 is not None:
+            raise ValueError("interpolate: refine > 0 refines estimated flows; with the flows given nothing is estimated")
         B = frame1.shape[0]
         with torch.no_grad():
             if flow12 is None:
                 L.require_gpu(frame1, frame2)
                 if not self.is_diffusion:
                     raise ValueError("interpolate: estimating the flows needs a diffusion model (estimate_flow); pass flow12 and flow21")
-                both = self.estimate_flow(torch.cat((frame1, frame2)), torch.cat((frame2, frame1)), **sample_kw)
-                flow12, flow21 = both[:B], both[B:]
+                if refine > 0:
+                    flow12, flow21, _check = self.estimate_flow_pair(frame1, frame2, refine=refine, **sample_kw)
+                else:
+                    both = self.estimate_flow(torch.cat((frame1, frame2)), torch.cat((frame2, frame1)), **sample_kw)
+                    flow12, flow21 = both[:B], both[B:]
             video = interpolate_frames(frame1, frame2, flow12, flow21, times, alpha=alpha, beta=beta, fill_holes=fill_holes,
                                        fill_gain=fill_gain)
         return (video if fill_holes else video[0]), flow12, flow21

@@ -5,6 +5,7 @@
   backward -> warp_backward_flow (WP:95-119) : bilinear grid_sample gather + validity mask
 rep='filter' (FlowLearner / MatrixFlow only) is outside the FlowDiffuser path and raises.
 """
+import collections
 import ctypes
 
 import torch
@@ -449,6 +450,60 @@ def loop_frames(img, motion, frames, substeps=1, order=2, speed=1.0):
                 else:                                                        # nb == 1: one sample's frames k0 .. k0 + ck - 1
                     _loop_render(img[b0:b0 + 1], motion[b0:b0 + 1], video[b0:b0 + 1, k0:k0 + ck], N, k0, **par)
     return video
+
+
+# ---- forward-backward check of a flow pair (not in the reference; semantics: include/ofd.h, `ofd_flow_consistency`) -------------------
+STATE_HELD, STATE_RELEASED, STATE_INCONSISTENT, STATE_LEAVES_FRAME, STATE_UNMATCHED, STATE_INVALID = range(6)
+
+FlowConsistency = collections.namedtuple("FlowConsistency", "known12 known21 err12 err21 state12 state21 counts")
+
+
+def consistency_params(a1=0.01, a2=0.5, dilate=0, name="flow_consistency"):
+    """the rules of the check's bound and dilation (ValueError); host logic, no engine call"""
+    real = lambda v: not isinstance(v, bool) and isinstance(v, (int, float)) and 0.0 <= v < float("inf")      # false for NaN
+    if not real(a1) or not real(a2):
+        raise ValueError(f"{name}: a1 and a2 must be finite numbers >= 0, got {a1!r} and {a2!r}")
+    return dict(a1=float(a1), a2=float(a2), dilate=_loop_int(name, "dilate", dilate, 0, 4))
+
+
+def flow_consistency(flow12, flow21, a1=0.01, a2=0.5, dilate=0):
+    """The forward-backward check of a flow pair (Sundaram et al. 2010, with UnFlow's bound, Meister et al. 2018; not in the reference):
+    a `FlowConsistency` (known12, known21, err12, err21, state12, state21, counts).  flow12, flow21: (B, 2, H, W) IN PIXELS, channel
+    0 = x, frame1(p) ~ frame2(p + flow12(p)): what `FlowDiffuser.estimate_flow` returns.  A pixel p of direction 1 -> 2 is followed to
+    q = p + flow12(p) and back by flow21 read bilinearly at q; it is consistent when the squared length of flow12(p) + flow21(q) is
+    at most a1 * (|flow12(p)|^2 + |flow21(q)|^2) + a2; direction 2 -> 1 likewise.  state12, state21 ((B, 1, H, W), uint8) hold one of
+    STATE_HELD (consistent), STATE_RELEASED (consistent, but within `dilate` pixels, 0..4, of one that is not), STATE_INCONSISTENT,
+    STATE_LEAVES_FRAME (q outside the frame), STATE_UNMATCHED (a non-finite flow under q), STATE_INVALID (a non-finite flow at p).
+    known12, known21 ((B, 2, H, W)): the flow's own bits where held, NaN elsewhere: ready to pass as `known_flow`, which re-samples
+    exactly the rest.  err12, err21 ((B, 1, H, W)): the length of the round trip's miss in pixels where it exists (states 0..2), NaN
+    elsewhere.  counts ((2, B, 6), int32): pixels per direction, sample and state.  The defaults are UnFlow's and untuned with
+    trained weights.  One launch; forward only; inputs are not modified; the same input gives the same bits.  Semantics:
+    include/ofd.h."""
+    if not torch.is_tensor(flow12) or flow12.dim() != 4 or flow12.shape[1] != 2 or flow12.numel() == 0:
+        raise ValueError(f"flow_consistency: flow12 must be a non-empty (B, 2, H, W) tensor, got {_shape_of(flow12)}")
+    if not torch.is_tensor(flow21) or flow21.shape != flow12.shape:
+        raise ValueError(f"flow_consistency: flow21 must have flow12's shape {tuple(flow12.shape)}, got {_shape_of(flow21)}")
+    if max(flow12.shape[2:]) > 32768:
+        raise ValueError(f"flow_consistency: H and W must be at most 32768, got {tuple(flow12.shape)}")
+    if not flow12.is_floating_point() or not flow21.is_floating_point():
+        raise ValueError(f"flow_consistency: the flows must be floating-point tensors, got {flow12.dtype} and {flow21.dtype}")
+    par = consistency_params(a1, a2, dilate)
+    if flow12.requires_grad or flow21.requires_grad:
+        raise L.OfdError("flow_consistency: forward only (the check has no backward pass): detach the inputs")
+    L.require_gpu(flow12, flow21)
+    if flow12.device != flow21.device:
+        raise ValueError(f"flow_consistency: flow12 and flow21 must be on one device, got {flow12.device} and {flow21.device}")
+    B, _, H, W = flow12.shape
+    with torch.no_grad():
+        flow12, flow21 = L.f32c(flow12), L.f32c(flow21)
+        dev = flow12.device
+        known = torch.empty(2, B, 2, H, W, dtype=torch.float32, device=dev)
+        err = torch.empty(2, B, 1, H, W, dtype=torch.float32, device=dev)
+        state = torch.empty(2, B, 1, H, W, dtype=torch.uint8, device=dev)
+        counts = torch.empty(2, B, 6, dtype=torch.int32, device=dev)
+        L.check(L.lib().ofd_flow_consistency(L.ptr(flow12), L.ptr(flow21), par["a1"], par["a2"], par["dilate"], L.ptr(known),
+                                             L.ptr(err), L.ptr(state), L.ptr(counts), B, H, W, L.stream()))
+    return FlowConsistency(known[0], known[1], err[0], err[1], state[0], state[1], counts)
 
 
 class _GridWarp(torch.autograd.Function):
