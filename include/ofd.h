@@ -762,7 +762,9 @@ int ofd_linear_attention_core_backward(const void* qkv, const void* dout, const 
                                        float* workspace, int B, int n, void* stream);
 /* --------------------------------------------------- fused LinearAttention block, one call at a time ------
  * The executor's own launches of a Residual(PreNorm(LinearAttention)) block (DD:81-87, DD:127-135, DD:216-244), exported so that one
- * block can be run and checked alone.  x / y / xn / o2 / dy / dx: [B][n][C] bf16 (pixel-major), C = 64 or 128 as stated per call.
+ * block can be run and checked alone.  x / y / xn / o2 / dy / dx: [B][n][C] bf16 (pixel-major), C = 64 or 128 as stated per call
+ * (ofd_la_weight_prep and ofd_linear_attention_block: also 256 and 512; at 512 the block uses the first 128 channels of each row of y
+ * as its own intermediate before it writes the row, so y must not alias x).
  * Any n >= 1 is legal in every call below (rows are whole 16-byte units for every C; pixels past the end of a partial 32-pixel tile
  * are read from a clamped row and masked).  Pointers named x, y and every weight pointer must be 16-byte aligned.
  *

@@ -249,14 +249,14 @@ extern "C" int ofd_linear_attention_core_backward(const void* qkv, const void* d
 static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 extern "C" int ofd_la_weight_prep(const float* wqkv, const float* g, const float* wout, void* wq, void* wkv, void* woutp, int C, void* stream) {
     OFD_CHECK_ARG(wqkv && wq && wkv && (woutp == nullptr) == (wout == nullptr), "la_weight_prep: null argument (wout and woutp go together)");
-    OFD_CHECK_ARG(C == 64 || C == 128, "la_weight_prep: C=%d (64 or 128)", C);
+    OFD_CHECK_ARG(C == 64 || C == 128 || C == 256 || C == 512, "la_weight_prep: C=%d (64, 128, 256 or 512)", C);
     OFD_CHECK_ARG(al16(wq) && al16(wkv) && al16(woutp), "la_weight_prep: weight buffers must be 16-byte aligned");
     return k_la_weight_prep(wqkv, g, wout, (bf16_t*)wq, (bf16_t*)wkv, (bf16_t*)woutp, C, (hipStream_t)stream);
 }
 extern "C" int ofd_linear_attention_block(const void* x, const void* wq, const void* wkv, const void* woutp, const float* bias, const float* g2,
                                           float* partial, void* ctxfrag, void* y, int B, int n, int C, float eps_pre, float eps_post, void* stream) {
     OFD_CHECK_ARG(x && wq && wkv && woutp && bias && g2 && partial && ctxfrag && y, "linear_attention_block: null argument");
-    OFD_CHECK_ARG(C == 64 || C == 128, "linear_attention_block: C=%d (64 or 128)", C);
+    OFD_CHECK_ARG(C == 64 || C == 128 || C == 256 || C == 512, "linear_attention_block: C=%d (64, 128, 256 or 512)", C);
     OFD_CHECK_ARG(B > 0 && n > 0, "linear_attention_block: B=%d n=%d", B, n);
     OFD_CHECK_ARG(al16(x) && al16(y) && al16(wq) && al16(wkv) && al16(woutp) && al16(ctxfrag), "linear_attention_block: x, y, ctxfrag and the weights must be 16-byte aligned");
     return k_linear_attention_fused((const bf16_t*)x, (const bf16_t*)wq, (const bf16_t*)wkv, (const bf16_t*)woutp, bias, g2, partial, (bf16_t*)ctxfrag,

@@ -1,5 +1,5 @@
 // Fused LinearAttention block for gfx950 (denoising_diffusion.py:216-244 inside
-// Residual(PreNorm(.)), DD:81-87, DD:127-135), C in {64, 128}.
+// Residual(PreNorm(.)), DD:81-87, DD:127-135), C in {64, 128, 256, 512}.
 //
 // The reference materialises LayerNorm(x), qkv (6x the activation), the head outputs and the
 // to_out result: ~2.9 KB of HBM traffic per pixel.  Here the block is two streaming passes over x
@@ -10,6 +10,12 @@
 //   pass 2  x -> LN -> q = Wq x^ -> softmax over d -> out = ctx^T q -> o = Wout out + b
 //           -> LN -> + x   (each stage's accumulator tile is the next MFMA's B operand)
 // The PreNorm gain g is folded into Wq / Wkv (W.diag(g)) when the weights are prepared.
+// The wide blocks (C >= 256; inference only) run the same kernels with ONE workgroup per CU: the weights of a pass fill most of the LDS (128 KB) and
+// a wave has the whole 512-register file (__launch_bounds__(256, 1)) for its pixel rows.  At C = 512 the weights of a pass are 256 KB, so
+//   pass 1  splits the heads over two workgroups (the partials are per (sample, head, part) anyway), each with its two heads' k | v rows,
+//   pass 2  is two kernels, la_heads_kernel (x -> LN -> q -> softmax -> ctx^T q, Wq in LDS) and la_tail_kernel (to_out.0 + bias -> LN -> + x, Wout
+//           in LDS); the head outputs between them (128 channels, bf16) lie in the first 256 bytes of the pixel's own row of y, which the wave
+//           that reads them overwrites afterwards: 4C + 256 channel values per pixel and no scratch tensor.
 #include <cstdlib>
 #include <type_traits>
 #include "blocks.h"
@@ -27,6 +33,25 @@ template <int C>
 __device__ __forceinline__ void load_raw_x(const bf16_t* __restrict__ xrow, XRaw<C>& r, int half) {
 #pragma unroll
     for (int s = 0; s < C / 16; ++s) r.v[s] = *(const u32x4*)(xrow + 16 * s + 8 * half);
+}
+
+// Weight staging of the wide blocks (C >= 256): N16 16-byte units global -> LDS by the workgroup's 256 threads, unit i from src[at(i)], eight loads
+// in flight per thread.  (The plain loop of the narrow kernels compiles to one load, one wait, one ds_write per turn: 32 serial L2 round trips per
+// thread for the 128 KB of a wide pass, 20 us of a 44 us kernel.)
+template <int N16, class At>
+__device__ __forceinline__ void la_stage(unsigned char* dst, const bf16_t* __restrict__ src, int tid, At at) {
+    static_assert(N16 % (8 * 256) == 0, "whole turns of eight units per thread");
+    for (int i0 = tid; i0 < N16; i0 += 8 * 256) {
+        uint4 v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = ((const uint4*)src)[at(i0 + k * 256)];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) ((uint4*)dst)[i0 + k * 256] = v[k];
+    }
+}
+template <int N16>
+__device__ __forceinline__ void la_stage(unsigned char* dst, const bf16_t* __restrict__ src, int tid) {
+    la_stage<N16>(dst, src, tid, [](int i) { return i; });
 }
 
 // LayerNorm over channels (DD:121-125) of a raw tile: x^ = x * rstd + off.  r03: the two sums run on the PACKED words
@@ -133,9 +158,10 @@ __device__ __forceinline__ void la_store_part(float* lds, float* __restrict__ o,
 // ---- pass 1 ---------------------------------------------------------------------------------------
 // What the two first-pass kernels share.  The online-softmax state of a wave: per head, the reference point m, the normaliser l and ctx^T
 // relative to m.  How m moves and what p is (rescale and exp policies) stay in each kernel.
-__device__ __forceinline__ void ctx_state_init(f32x16 (&ctxT)[4], float (&m)[4], float (&l)[4]) {
+template <int NH>
+__device__ __forceinline__ void ctx_state_init(f32x16 (&ctxT)[NH], float (&m)[NH], float (&l)[NH]) {
 #pragma unroll
-    for (int hd = 0; hd < 4; ++hd) {
+    for (int hd = 0; hd < NH; ++hd) {
         m[hd] = -3.0e38f;
         l[hd] = 0.0f;
 #pragma unroll
@@ -169,23 +195,33 @@ __device__ __forceinline__ void ctx_update(f32x16& ctxT, const f32x16& va, const
 // disappear (11 -> 6 tensor passes of 64 channels).  Its operands are those of the unfused path: xn rounded to bf16 times the PLAIN weights
 // (wkv: not folded with the gain), k rounded to bf16 before the softmax.  k, v leave through a second projection with the operands swapped
 // (rows = channel, col = pixel: a lane owns whole 8-channel units of its pixel and stores 16 bytes); the MFMA pipe has the room.
-template <int C, bool TRAIN>
-__global__ void __launch_bounds__(256, 2) la_ctx_fused_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ wkv,
+// HPW: heads per workgroup.  4, or 2 at C = 512: blockIdx.z picks the pair, whose k | v rows (128 KB) are what the LDS holds.
+template <int C, bool TRAIN, int HPW = 4>
+__global__ void __launch_bounds__(256, C >= 256 ? 1 : 2) la_ctx_fused_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ wkv,
                                                            float* __restrict__ partial, int n, float eps, float defer,
                                                            const float* __restrict__ g, bf16_t* __restrict__ xn_out, bf16_t* __restrict__ qkv_out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int KS = C / 16;
+    static_assert(HPW == 4 || (HPW == 2 && !TRAIN), "the training form writes all four heads' k | v");
+    constexpr int KS = C / 16, WR = 64 * HPW;      // WR: weight rows in LDS per 8-channel unit, k rows then v rows
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, half = lane >> 5;
-    for (int i = tid; i < (C / 8) * 256; i += 256) ((uint4*)smem)[i] = ((const uint4*)wkv)[i];
-    float* s_g = (float*)(smem + (C / 8) * 256 * 16);
+    const int h0 = HPW == 4 ? 0 : blockIdx.z * HPW;
+    if constexpr (C < 256) {
+        for (int i = tid; i < (C / 8) * 256; i += 256) ((uint4*)smem)[i] = ((const uint4*)wkv)[i];
+    } else {       // row r of the WR staged per channel unit: k | v row r % (32 HPW) of the workgroup's heads
+        la_stage<(C / 8) * WR>(smem, wkv, tid, [&](int i) {
+            const int r = i % WR, kv = r / (32 * HPW);
+            return (i / WR) * 256 + kv * 128 + h0 * 32 + (r - kv * 32 * HPW);
+        });
+    }
+    float* s_g = (float*)(smem + (C / 8) * WR * 16);
     if constexpr (TRAIN)
         for (int i = tid; i < C; i += 256) s_g[i] = g[i];
     __syncthreads();
     const int b = blockIdx.y, wave_id = blockIdx.x * 4 + wave, nw = gridDim.x * 4, ntiles = (n + 31) / 32;
 
-    f32x16 ctxT[4];
-    float m[4], l[4];
-    ctx_state_init(ctxT, m, l);
+    f32x16 ctxT[HPW];
+    float m[HPW], l[HPW];
+    ctx_state_init<HPW>(ctxT, m, l);
     const bf16_t* xb = x + (size_t)b * n * C;
     XRaw<C> raw_next;
     load_raw_x<C>(xb + (size_t)min(wave_id * 32 + l31, n - 1) * C, raw_next, half);
@@ -223,14 +259,14 @@ __global__ void __launch_bounds__(256, 2) la_ctx_fused_kernel(const bf16_t* __re
             }
         }
 #pragma unroll
-        for (int hd = 0; hd < 4; ++hd) {
+        for (int hd = 0; hd < HPW; ++hd) {
             f32x16 ka, va;
 #pragma unroll
             for (int r = 0; r < 16; ++r) { ka[r] = 0.0f; va[r] = 0.0f; }
 #pragma unroll
             for (int s = 0; s < KS; ++s) {
-                const bf16x8 wk = *(const bf16x8*)(smem + ((size_t)(2 * s + half) * 256 + hd * 32 + l31) * 16);
-                const bf16x8 wv = *(const bf16x8*)(smem + ((size_t)(2 * s + half) * 256 + 128 + hd * 32 + l31) * 16);
+                const bf16x8 wk = *(const bf16x8*)(smem + ((size_t)(2 * s + half) * WR + hd * 32 + l31) * 16);
+                const bf16x8 wv = *(const bf16x8*)(smem + ((size_t)(2 * s + half) * WR + 32 * HPW + hd * 32 + l31) * 16);
                 ka = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xs[s], wk, ka, 0, 0, 0);   // rows = pixels, col = d
                 va = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xs[s], wv, va, 0, 0, 0);   // rows = pixels, col = e
             }
@@ -277,8 +313,8 @@ __global__ void __launch_bounds__(256, 2) la_ctx_fused_kernel(const bf16_t* __re
     }
     __syncthreads();                          // every wave is done with the weight fragments: the LDS becomes the combine buffer
 #pragma unroll
-    for (int hd = 0; hd < 4; ++hd)
-        la_store_part((float*)smem, partial + ((size_t)(b * 4 + hd) * gridDim.x + blockIdx.x) * 1088, m[hd], l[hd], ctxT[hd], tid, wave, l31, half);
+    for (int hd = 0; hd < HPW; ++hd)
+        la_store_part((float*)smem, partial + ((size_t)(b * 4 + h0 + hd) * gridDim.x + blockIdx.x) * 1088, m[hd], l[hd], ctxT[hd], tid, wave, l31, half);
 }
 
 // ---- pass 1 on STORED k, v (the training forward: qkv is materialised for the backward): the online-softmax body of the kernel above,
@@ -454,11 +490,110 @@ void launch_la_ctx_combine(const float* partial, float* ctx, int B, int nparts, 
 }
 
 // ---- pass 2 ---------------------------------------------------------------------------------------
+// The three stages of a tile, shared by the whole-block kernel and the two kernels of the C = 512 split.
+// One head: q = Wq x^ (rows = d, col = pixel) -> softmax over d (DD:234), * scale (DD:237) -> out[e][pixel] = sum_d ctx[d][e] q~[d][pixel] (DD:242)
+template <int C, bool TRAIN>
+__device__ __forceinline__ f32x16 la_head_out(const bf16x8 (&xs)[C / 16], const unsigned char* s_wq, const unsigned char* s_cf, int hd, float scale,
+                                              int lane) {
+    const int l31 = lane & 31, half = lane >> 5;
+    f32x16 qa;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) qa[r] = 0.0f;
+#pragma unroll
+    for (int s = 0; s < C / 16; ++s) {
+        const bf16x8 wf = *(const bf16x8*)(s_wq + ((size_t)(2 * s + half) * 128 + hd * 32 + l31) * 16);
+        qa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf, xs[s], qa, 0, 0, 0);
+    }
+    if constexpr (TRAIN) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) qa[r] = bf2f(f2bf(qa[r]));
+    }
+    const float k = scale / softmax_d(qa, 32);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) qa[r] *= k;
+    f32x16 oa;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) oa[r] = 0.0f;
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2) {
+        const bf16x8 cf = *(const bf16x8*)(s_cf + ((size_t)(hd * 2 + s2) * 64 + lane) * 16);
+        oa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cf, acc_frag(qa, s2), oa, 0, 0, 0);
+    }
+    return oa;
+}
+// to_out.0, one k-step: o[c][pixel] += sum_e Wout[c][e] out[e][pixel] over the 16 e of unit u = hd * 2 + s2; of = acc_frag(out tile of head hd, s2)
+template <int C>
+__device__ __forceinline__ void la_to_out(f32x16 (&acc_o)[C / 32], const bf16x8 of, const unsigned char* s_wo, int u, int l31, int half) {
+#pragma unroll
+    for (int rt = 0; rt < C / 32; ++rt) {
+        const bf16x8 wf = *(const bf16x8*)(s_wo + ((size_t)(u * 2 + half) * C + rt * 32 + l31) * 16);
+        acc_o[rt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf, of, acc_o[rt], 0, 0, 0);
+    }
+}
+// + bias, LayerNorm over channels (to_out.1, DD:226), + x (Residual), stored.  xres(s): the residual's words of channels 16 s + 8 half .. + 7 of
+// this lane's pixel (the layout of XRaw).  yrow / orow: the pixel's (clamped) rows of y and, TRAIN, of o2.
+template <int C, bool TRAIN, class XRes>
+__device__ __forceinline__ void la_out_tail(f32x16 (&acc_o)[C / 32], XRes xres, const float* s_bias, const float* s_g2, bf16_t* yrow, bf16_t* orow, bool ok,
+                                            int half, float eps_post) {
+    constexpr int RT = C / 32;
+    float sum = 0.0f;
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const float4 bv = *(const float4*)(s_bias + rt * 32 + 8 * g + 4 * half);
+            acc_o[rt][4 * g] += bv.x; acc_o[rt][4 * g + 1] += bv.y; acc_o[rt][4 * g + 2] += bv.z; acc_o[rt][4 * g + 3] += bv.w;
+            if constexpr (TRAIN) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) acc_o[rt][4 * g + k] = bf2f(f2bf(acc_o[rt][4 * g + k]));       // o2 as stored
+            }
+            sum += (acc_o[rt][4 * g] + acc_o[rt][4 * g + 1]) + (acc_o[rt][4 * g + 2] + acc_o[rt][4 * g + 3]);
+        }
+    if constexpr (TRAIN) {
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) store_acc_rows(acc_o[rt], orow + rt * 32, half, ok);
+    }
+    sum += __shfl_xor(sum, 32, 64);
+    const float mean = sum * (1.0f / C);
+    float q = 0.0f;
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { acc_o[rt][r] -= mean; q += acc_o[rt][r] * acc_o[rt][r]; }
+    q += __shfl_xor(q, 32, 64);
+    const float rstd = rsqrtf(q * (1.0f / C) + eps_post);
+    // 16-byte stores (store_quad_pair); every lane takes part, out-of-range pixels use a clamped row
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int g = 0; g < 4; g += 2) {
+            // the residual x: in the whole-block kernel the very words this lane loaded for the LayerNorm (channels 16 s + 8 half .. + 7 with
+            // s = 2 rt + g / 2) -- kept in registers (r03; was a second global load per tile: 922 MB more through L2 at full resolution)
+            const u32x4 xw = xres(rt * 2 + (g >> 1));
+            const uint4 xv = make_uint4(xw[0], xw[1], xw[2], xw[3]);
+            const auto sx = __builtin_amdgcn_permlane32_swap(xv.x, xv.z, false, false);
+            const auto sy = __builtin_amdgcn_permlane32_swap(xv.y, xv.w, false, false);
+            const unsigned xq[2][2] = {{sx[0], sy[0]}, {sx[1], sy[1]}};      // residual of quad g, quad g+1
+            uint2 qo[2];
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const int c0 = rt * 32 + 8 * (g + k) + 4 * half;
+                const float4 gv = *(const float4*)(s_g2 + c0);
+                const float o0 = acc_o[rt][4 * (g + k)] * rstd * gv.x + bf2f((bf16_t)(xq[k][0] & 0xffffu));
+                const float o1 = acc_o[rt][4 * (g + k) + 1] * rstd * gv.y + bf2f((bf16_t)(xq[k][0] >> 16));
+                const float o2 = acc_o[rt][4 * (g + k) + 2] * rstd * gv.z + bf2f((bf16_t)(xq[k][1] & 0xffffu));
+                const float o3 = acc_o[rt][4 * (g + k) + 3] * rstd * gv.w + bf2f((bf16_t)(xq[k][1] >> 16));
+                qo[k] = pack_quad(o0, o1, o2, o3);
+            }
+            store_quad_pair(yrow + rt * 32 + 8 * g, qo[0], qo[1], half, ok);
+        }
+}
+
 // TRAIN (the training forward, C = 64): operands as the unfused path has them (xn with the gain rounded to bf16 times the plain Wq, q rounded
 // to bf16 before its softmax -- what the backward recomputes), and o2 = to_out.0's output is WRITTEN (bf16; the to_out.1 LayerNorm backward
 // reads it) and the LayerNorm runs on those rounded values: lc_out_kernel + the LayerNorm kernel (5 tensor passes) become 3.
 template <int C, bool TRAIN>
-__global__ void __launch_bounds__(256, C == 64 ? 4 : 2) la_out_fused_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ wq,
+__global__ void __launch_bounds__(256, C == 64 ? 4 : C == 128 ? 2 : 1) la_out_fused_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ wq,
                                                            const bf16_t* __restrict__ woutp, const bf16_t* __restrict__ ctxfrag,
                                                            const float* __restrict__ bias, const float* __restrict__ g2,
                                                            bf16_t* __restrict__ y, int n, float eps_pre, float eps_post, float scale,
@@ -476,8 +611,13 @@ __global__ void __launch_bounds__(256, C == 64 ? 4 : 2) la_out_fused_kernel(cons
     const int b = blockIdx.y;
     if constexpr (TRAIN)
         for (int i = tid; i < C; i += 256) s_g[i] = g[i];
-    for (int i = tid; i < WQ_B / 16; i += 256) ((uint4*)s_wq)[i] = ((const uint4*)wq)[i];
-    for (int i = tid; i < WO_B / 16; i += 256) ((uint4*)s_wo)[i] = ((const uint4*)woutp)[i];
+    if constexpr (C < 256) {
+        for (int i = tid; i < WQ_B / 16; i += 256) ((uint4*)s_wq)[i] = ((const uint4*)wq)[i];
+        for (int i = tid; i < WO_B / 16; i += 256) ((uint4*)s_wo)[i] = ((const uint4*)woutp)[i];
+    } else {
+        la_stage<WQ_B / 16>(s_wq, wq, tid);
+        la_stage<WO_B / 16>(s_wo, woutp, tid);
+    }
     for (int i = tid; i < CF_B / 16; i += 256) ((uint4*)s_cf)[i] = ((const uint4*)(ctxfrag + (size_t)b * 4096))[i];
     for (int i = tid; i < C; i += 256) { s_bias[i] = bias[i]; s_g2[i] = g2[i]; }
     __syncthreads();
@@ -489,8 +629,7 @@ __global__ void __launch_bounds__(256, C == 64 ? 4 : 2) la_out_fused_kernel(cons
     for (int tile = wave_id; tile < ntiles; tile += nw) {
         asm volatile("" ::: "memory");   // keep the LDS weight reads inside the loop (see pass 1)
         const int pix = tile * 32 + l31;
-        const int pid = min(pix, n - 1);
-        const bf16_t* xrow = xb + (size_t)pid * C;
+        const size_t row = (size_t)b * n + min(pix, n - 1);
         const XRaw<C> raw = raw_next;
         load_raw_x<C>(xb + (size_t)min((tile + nw) * 32 + l31, n - 1) * C, raw_next, half);
         bf16x8 xs[KS];
@@ -503,96 +642,97 @@ __global__ void __launch_bounds__(256, C == 64 ? 4 : 2) la_out_fused_kernel(cons
             for (int r = 0; r < 16; ++r) acc_o[rt][r] = 0.0f;
 #pragma unroll
         for (int hd = 0; hd < 4; ++hd) {
-            f32x16 qa;
+            const f32x16 oa = la_head_out<C, TRAIN>(xs, s_wq, s_cf, hd, scale, lane);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) qa[r] = 0.0f;
-#pragma unroll
-            for (int s = 0; s < KS; ++s) {   // rows = d, col = pixel
-                const bf16x8 wf = *(const bf16x8*)(s_wq + ((size_t)(2 * s + half) * 128 + hd * 32 + l31) * 16);
-                qa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf, xs[s], qa, 0, 0, 0);
-            }
-            if constexpr (TRAIN) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) qa[r] = bf2f(f2bf(qa[r]));
-            }
-            const float k = scale / softmax_d(qa, 32);      // softmax over d (DD:234) then * scale (DD:237)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) qa[r] *= k;
-            f32x16 oa;                        // out[e][pixel] = sum_d ctx[d][e] q~[d][pixel]   (DD:242)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) oa[r] = 0.0f;
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                const bf16x8 cf = *(const bf16x8*)(s_cf + ((size_t)(hd * 2 + s2) * 64 + lane) * 16);
-                oa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cf, acc_frag(qa, s2), oa, 0, 0, 0);
-            }
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {  // o[c][pixel] += sum_e Wout[c][hd*32+e] out[e][pixel]  (to_out.0)
-                const bf16x8 of = acc_frag(oa, s2);
-#pragma unroll
-                for (int rt = 0; rt < RT; ++rt) {
-                    const bf16x8 wf = *(const bf16x8*)(s_wo + ((size_t)((hd * 2 + s2) * 2 + half) * C + rt * 32 + l31) * 16);
-                    acc_o[rt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf, of, acc_o[rt], 0, 0, 0);
-                }
-            }
+            for (int s2 = 0; s2 < 2; ++s2) la_to_out<C>(acc_o, acc_frag(oa, s2), s_wo, hd * 2 + s2, l31, half);
         }
-        // bias, LayerNorm over channels (to_out.1, DD:226), + x (Residual)
-        float sum = 0.0f;
+        la_out_tail<C, TRAIN>(acc_o, [&](int s) { return raw.v[s]; }, s_bias, s_g2, y + row * C, TRAIN ? o2_out + row * C : nullptr, pix < n, half, eps_post);
+    }
+}
+
+// ---- pass 2 at C = 512, where Wq and Wout (128 KB each) do not share the LDS: the two halves of the kernel above.  The head outputs travel
+// as the very fragments la_to_out multiplies by -- unit (hd * 2 + s2) * 2 + half of 8 channels, 16 bytes per lane -- in the first 128 channels
+// of the pixel's row of y.
+template <int C>
+__global__ void __launch_bounds__(256, 1) la_heads_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ wq, const bf16_t* __restrict__ ctxfrag,
+                                                          bf16_t* __restrict__ y, int n, float eps_pre, float scale) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int WQ_B = (C / 8) * 128 * 16, CF_B = 4 * 2 * 64 * 16;
+    unsigned char* s_wq = smem;
+    unsigned char* s_cf = smem + WQ_B;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, half = lane >> 5;
+    const int b = blockIdx.y;
+    la_stage<WQ_B / 16>(s_wq, wq, tid);
+    for (int i = tid; i < CF_B / 16; i += 256) ((uint4*)s_cf)[i] = ((const uint4*)(ctxfrag + (size_t)b * 4096))[i];
+    __syncthreads();
+    const int wave_id = blockIdx.x * 4 + wave, nw = gridDim.x * 4, ntiles = (n + 31) / 32;
+    const bf16_t* xb = x + (size_t)b * n * C;
+    XRaw<C> raw_next;
+    load_raw_x<C>(xb + (size_t)min(wave_id * 32 + l31, n - 1) * C, raw_next, half);
+    for (int tile = wave_id; tile < ntiles; tile += nw) {
+        asm volatile("" ::: "memory");   // keep the LDS weight reads inside the loop (see pass 1)
+        const int pix = tile * 32 + l31;
+        const XRaw<C> raw = raw_next;
+        load_raw_x<C>(xb + (size_t)min((tile + nw) * 32 + l31, n - 1) * C, raw_next, half);
+        bf16x8 xs[C / 16];
+        norm_x<C>(raw, eps_pre, xs);
+        bf16_t* arow = y + ((size_t)b * n + min(pix, n - 1)) * C + 8 * half;
 #pragma unroll
-        for (int rt = 0; rt < RT; ++rt)
+        for (int hd = 0; hd < 4; ++hd) {
+            const f32x16 oa = la_head_out<C, false>(xs, s_wq, s_cf, hd, scale, lane);
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const float4 bv = *(const float4*)(s_bias + rt * 32 + 8 * g + 4 * half);
-                acc_o[rt][4 * g] += bv.x; acc_o[rt][4 * g + 1] += bv.y; acc_o[rt][4 * g + 2] += bv.z; acc_o[rt][4 * g + 3] += bv.w;
-                if constexpr (TRAIN) {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) acc_o[rt][4 * g + k] = bf2f(f2bf(acc_o[rt][4 * g + k]));       // o2 as stored
-                }
-                sum += (acc_o[rt][4 * g] + acc_o[rt][4 * g + 1]) + (acc_o[rt][4 * g + 2] + acc_o[rt][4 * g + 3]);
-            }
-        if constexpr (TRAIN) {
-            bf16_t* orow = o2_out + ((size_t)b * n + min(pix, n - 1)) * C;
-#pragma unroll
-            for (int rt = 0; rt < RT; ++rt) store_acc_rows(acc_o[rt], orow + rt * 32, half, pix < n);
+            for (int s2 = 0; s2 < 2; ++s2)
+                if (pix < n) *(bf16x8*)(arow + (hd * 2 + s2) * 16) = acc_frag(oa, s2);
         }
-        sum += __shfl_xor(sum, 32, 64);
-        const float mean = sum * (1.0f / C);
-        float q = 0.0f;
+    }
+}
+
+// NOT __restrict__: y holds this wave's head outputs until the wave has read them, then its result.  A wave reads only rows of its own tiles
+// before it writes them (the prefetch past its last tile re-reads the sample's last row, whatever that holds by then, and drops it).
+template <int C>
+__global__ void __launch_bounds__(256, 1) la_tail_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ woutp, const float* __restrict__ bias,
+                                                         const float* __restrict__ g2, bf16_t* y, int n, float eps_post) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int RT = C / 32, WO_B = 16 * C * 16;
+    unsigned char* s_wo = smem;
+    float* s_bias = (float*)(smem + WO_B);
+    float* s_g2 = s_bias + C;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, half = lane >> 5;
+    const int b = blockIdx.y;
+    la_stage<WO_B / 16>(s_wo, woutp, tid);
+    for (int i = tid; i < C; i += 256) { s_bias[i] = bias[i]; s_g2[i] = g2[i]; }
+    __syncthreads();
+    const int wave_id = blockIdx.x * 4 + wave, nw = gridDim.x * 4, ntiles = (n + 31) / 32;
+    const bf16_t* xb = x + (size_t)b * n * C;
+    bf16_t* yb = y + (size_t)b * n * C;
+    bf16x8 of_next[8];
+    {
+        const bf16_t* arow = yb + (size_t)min(wave_id * 32 + l31, n - 1) * C + 8 * half;
 #pragma unroll
-        for (int rt = 0; rt < RT; ++rt)
+        for (int u = 0; u < 8; ++u) of_next[u] = *(const bf16x8*)(arow + u * 16);
+    }
+    for (int tile = wave_id; tile < ntiles; tile += nw) {
+        asm volatile("" ::: "memory");   // keep the LDS weight reads inside the loop (see pass 1)
+        const int pix = tile * 32 + l31;
+        const size_t pid = min(pix, n - 1);
+        bf16x8 of[8];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) { acc_o[rt][r] -= mean; q += acc_o[rt][r] * acc_o[rt][r]; }
-        q += __shfl_xor(q, 32, 64);
-        const float rstd = rsqrtf(q * (1.0f / C) + eps_post);
+        for (int u = 0; u < 8; ++u) of[u] = of_next[u];
         {
-            // 16-byte stores (store_quad_pair); every lane takes part, out-of-range pixels use a clamped row
-            const bool ok = pix < n;
-            bf16_t* yrow = y + ((size_t)b * n + min(pix, n - 1)) * C;
+            const bf16_t* arow = yb + (size_t)min((tile + nw) * 32 + l31, n - 1) * C + 8 * half;
 #pragma unroll
-            for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-                for (int g = 0; g < 4; g += 2) {
-                    // the residual x: the very words this lane loaded for the LayerNorm (channels 16 s + 8 half .. + 7 with s = 2 rt + g / 2) --
-                    // kept in registers (r03; was a second global load per tile: 922 MB more through L2 at full resolution)
-                    const u32x4 xw = raw.v[rt * 2 + (g >> 1)];
-                    const uint4 xv = make_uint4(xw[0], xw[1], xw[2], xw[3]);
-                    const auto sx = __builtin_amdgcn_permlane32_swap(xv.x, xv.z, false, false);
-                    const auto sy = __builtin_amdgcn_permlane32_swap(xv.y, xv.w, false, false);
-                    const unsigned xq[2][2] = {{sx[0], sy[0]}, {sx[1], sy[1]}};      // residual of quad g, quad g+1
-                    uint2 qo[2];
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-                        const int c0 = rt * 32 + 8 * (g + k) + 4 * half;
-                        const float4 gv = *(const float4*)(s_g2 + c0);
-                        const float o0 = acc_o[rt][4 * (g + k)] * rstd * gv.x + bf2f((bf16_t)(xq[k][0] & 0xffffu));
-                        const float o1 = acc_o[rt][4 * (g + k) + 1] * rstd * gv.y + bf2f((bf16_t)(xq[k][0] >> 16));
-                        const float o2 = acc_o[rt][4 * (g + k) + 2] * rstd * gv.z + bf2f((bf16_t)(xq[k][1] & 0xffffu));
-                        const float o3 = acc_o[rt][4 * (g + k) + 3] * rstd * gv.w + bf2f((bf16_t)(xq[k][1] >> 16));
-                        qo[k] = pack_quad(o0, o1, o2, o3);
-                    }
-                    store_quad_pair(yrow + rt * 32 + 8 * g, qo[0], qo[1], half, ok);
-                }
+            for (int u = 0; u < 8; ++u) of_next[u] = *(const bf16x8*)(arow + u * 16);
         }
+        f32x16 acc_o[RT];
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc_o[rt][r] = 0.0f;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) la_to_out<C>(acc_o, of[u], s_wo, u, l31, half);
+        // the residual x is read here, a 16-byte unit at a time (a whole row in registers next to the 16 accumulator tiles does not fit)
+        const bf16_t* xrow = xb + pid * C + 8 * half;
+        la_out_tail<C, false>(acc_o, [&](int s) { return *(const u32x4*)(xrow + 16 * s); }, s_bias, s_g2, yb + pid * C, nullptr, pix < n, half, eps_post);
     }
 }
 
@@ -625,7 +765,11 @@ __global__ void __launch_bounds__(256) la_weight_prep_kernel(const float* __rest
 constexpr float LA_DEFER = 5.545177f;
 // second-pass workgroups per sample (at least 1024 over the batch: small batches need enough workgroups for the chip)
 constexpr int LA_GX2_CAP = 128;
-static int la_out_blocks(int n, int B) {
+static int la_out_blocks(int n, int B, int C) {
+    if (C >= 256) {                         // one workgroup per CU stages 128+ KB of weights: no more workgroups than CUs, a tile per wave at least
+        const int gx2 = cdiv(cdiv(n, 32), 4), cap2 = 256 / B;
+        return gx2 < cap2 ? gx2 : (cap2 < 1 ? 1 : cap2);
+    }
     int gx2 = cdiv(cdiv(n, 32), 4 * 4);     // >= 4 tiles per wave amortise the weight staging
     if (gx2 < 1) gx2 = 1;
     const int cap2 = (LA_GX2_CAP * B < 1024) ? 1024 / B : LA_GX2_CAP;
@@ -636,18 +780,32 @@ static int la_out_blocks(int n, int B) {
 template <int C>
 static int launch_la(const bf16_t* x, const bf16_t* wq, const bf16_t* wkv, const bf16_t* woutp, const float* bias, const float* g2,
                      float* partial, bf16_t* ctxfrag, bf16_t* y, int B, int n, float eps_pre, float eps_post, hipStream_t s) {
-    constexpr int LDS1 = (C / 8) * 256 * 16;
+    constexpr int HPW = C == 512 ? 2 : 4;   // heads per first-pass workgroup
+    constexpr bool SPLIT2 = C == 512;       // second pass as la_heads_kernel + la_tail_kernel
+    constexpr int LDS1 = (C / 8) * 64 * HPW * 16;
     constexpr int LDS2 = (C / 8) * 128 * 16 + 16 * C * 16 + 4 * 2 * 64 * 16 + 2 * C * 4;
+    constexpr int LDS2H = (C / 8) * 128 * 16 + 4 * 2 * 64 * 16, LDS2T = 16 * C * 16 + 2 * C * 4;
+    static_assert(LDS1 <= 160 * 1024 && (SPLIT2 ? LDS2H <= 160 * 1024 && LDS2T <= 160 * 1024 : LDS2 <= 160 * 1024), "the weights of a pass must fit the LDS");
     static bool attr = false;
     if (!attr) {
-        OFD_HIP(hipFuncSetAttribute((const void*)la_ctx_fused_kernel<C, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS1));
-        OFD_HIP(hipFuncSetAttribute((const void*)la_out_fused_kernel<C, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS2));
+        OFD_HIP(hipFuncSetAttribute((const void*)la_ctx_fused_kernel<C, false, HPW>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS1));
+        if constexpr (SPLIT2) {
+            OFD_HIP(hipFuncSetAttribute((const void*)la_heads_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS2H));
+            OFD_HIP(hipFuncSetAttribute((const void*)la_tail_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS2T));
+        } else {
+            OFD_HIP(hipFuncSetAttribute((const void*)la_out_fused_kernel<C, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS2));
+        }
         attr = true;
     }
-    const int gx = la_fused_blocks(n, B);
-    la_ctx_fused_kernel<C, false><<<dim3(gx, B), 256, LDS1, s>>>(x, wkv, partial, n, eps_pre, LA_DEFER, nullptr, nullptr, nullptr);
+    const int gx = la_fused_blocks(n, B, C), gx2 = la_out_blocks(n, B, C);
+    la_ctx_fused_kernel<C, false, HPW><<<dim3(gx, B, 4 / HPW), 256, LDS1, s>>>(x, wkv, partial, n, eps_pre, LA_DEFER, nullptr, nullptr, nullptr);
     la_ctx_combine_kernel<<<dim3(B * 4, 4), 256, 0, s>>>(partial, ctxfrag, gx, 1.0f / (float)n, nullptr);
-    la_out_fused_kernel<C, false><<<dim3(la_out_blocks(n, B), B), 256, LDS2, s>>>(x, wq, woutp, ctxfrag, bias, g2, y, n, eps_pre, eps_post, LA_SCALE, nullptr, nullptr);
+    if constexpr (SPLIT2) {
+        la_heads_kernel<C><<<dim3(gx2, B), 256, LDS2H, s>>>(x, wq, ctxfrag, y, n, eps_pre, LA_SCALE);
+        la_tail_kernel<C><<<dim3(gx2, B), 256, LDS2T, s>>>(x, woutp, bias, g2, y, n, eps_post);
+    } else {
+        la_out_fused_kernel<C, false><<<dim3(gx2, B), 256, LDS2, s>>>(x, wq, woutp, ctxfrag, bias, g2, y, n, eps_pre, eps_post, LA_SCALE, nullptr, nullptr);
+    }
     OFD_LAUNCH_CHECK();
     return OFD_OK;
 }
@@ -670,7 +828,7 @@ int k_linear_attention_fused_train(const bf16_t* x, const bf16_t* wq, const bf16
     la_ctx_fused_kernel<64, true><<<dim3(gx, B), 256, LDS1, s>>>(x, wkv, partial, n, eps_pre, LA_DEFER, g_pre, xn, qkv);
     la_ctx_combine_kernel<<<dim3(B * 4, 4), 256, 0, s>>>(partial, ctxfrag, gx, 1.0f / (float)n, nullptr);
     launch_la_ctx_combine(partial, ctx, B, gx, 1.0f / (float)n, ml, s);
-    la_out_fused_kernel<64, true><<<dim3(la_out_blocks(n, B), B), 256, LDS2, s>>>(x, wq, woutp, ctxfrag, bias, g2, y, n, eps_pre, eps_post, LA_SCALE, g_pre, o2);
+    la_out_fused_kernel<64, true><<<dim3(la_out_blocks(n, B, 64), B), 256, LDS2, s>>>(x, wq, woutp, ctxfrag, bias, g2, y, n, eps_pre, eps_post, LA_SCALE, g_pre, o2);
     OFD_LAUNCH_CHECK();
     return OFD_OK;
 }
@@ -679,11 +837,17 @@ int k_linear_attention_fused_train(const bf16_t* x, const bf16_t* wq, const bf16
 // themselves, up to 256 over the batch (one per CU; 128 / 192 / 384 / 512 measured slower at B = 1 1080p --
 // beyond 256 the combine's chain over the parts costs more than the first pass gains) over the batch for small ones -- at B = 1 (1080p: BASELINE configs[4] per
 // GPU) 64 workgroups were a quarter of the CUs
-int la_fused_blocks(int n, int B) {
+// C >= 256 (one resident workgroup per CU, 128 KB of weights staged by each): one workgroup per CU over the batch and the head split, and as for the
+// narrow form the same count for every batch of 8 or more -- the parts fix the order of a sample's sums, and the two half-batches of the two-stream
+// forward must give the whole batch's bits (tests/test_full_size_parity_gpu.py).  Never more parts than the narrow form has (la_fwd_parts sizes the
+// partial buffer by that)
+int la_fused_blocks(int n, int B, int C) {
     constexpr int total = 256;
     int gx = cdiv(cdiv(n, 32), 8);
     int cap = total / (B < 1 ? 1 : B);
-    if (cap < 64) cap = 64;
+    if (C >= 256) cap = (cap < 32 ? 32 : cap) / (C / 256);
+    else if (cap < 64) cap = 64;
+    if (cap < 1) cap = 1;
     if (gx < 1) gx = 1;
     if (gx > cap) gx = cap;
     return gx;
@@ -699,6 +863,8 @@ int k_linear_attention_fused(const bf16_t* x, const bf16_t* wq, const bf16_t* wk
                              float* partial, bf16_t* ctxfrag, bf16_t* y, int B, int n, int C, float eps_pre, float eps_post, hipStream_t s) {
     if (C == 64) return launch_la<64>(x, wq, wkv, woutp, bias, g2, partial, ctxfrag, y, B, n, eps_pre, eps_post, s);
     if (C == 128) return launch_la<128>(x, wq, wkv, woutp, bias, g2, partial, ctxfrag, y, B, n, eps_pre, eps_post, s);
+    if (C == 256) return launch_la<256>(x, wq, wkv, woutp, bias, g2, partial, ctxfrag, y, B, n, eps_pre, eps_post, s);
+    if (C == 512) return launch_la<512>(x, wq, wkv, woutp, bias, g2, partial, ctxfrag, y, B, n, eps_pre, eps_post, s);
     set_error("linear_attention_fused: C=%d unsupported", C);
     return OFD_ERR_ARG;
 }

@@ -67,11 +67,9 @@ static void add_linattn(ofd_unet* u, const std::string& name, int c) {
     add_conv(u, name + ".fn.fn.to_out.0", c, 128, 1, true, -1.0f);
     add_param(u, name + ".fn.fn.to_out.1.g", {1, c, 1, 1});
     add_param(u, name + ".fn.norm.g", {1, c, 1, 1});
-    if (c <= 128) {
-        u->la_fused[name] = {u->n_labuf, c};
-        u->n_labuf += (size_t)512 * c;
-        if (c == 64) u->n_labuf += (size_t)384 * c;      // + the plain (gain not folded in) wq | wkv of the fused TRAINING forward
-    }
+    u->la_fused[name] = {u->n_labuf, c};
+    u->n_labuf += (size_t)512 * c;
+    if (c == 64) u->n_labuf += (size_t)384 * c;      // + the plain (gain not folded in) wq | wkv of the fused TRAINING forward
 }
 
 static void build_registry(ofd_unet* u) {
@@ -226,9 +224,10 @@ static Tensor linattn(Ctx& c, const std::string& name, Tensor x) {
     const int H = x.H, W = x.W, B = c.B, C = x.C, n = H * W;
     const size_t npix = (size_t)B * n;
     auto fit = u->la_fused.find(name);
-    if (fit != u->la_fused.end() && !c.train) {
-        // inference, C <= 128: fused two-pass block (la_fused.hip): no LayerNorm / qkv / head-output tensors in HBM
-        const int nparts = la_fused_blocks(n, B);
+    // OFD_LA_FUSED_WIDE=0 (read per call): the blocks of 256 and 512 channels on the unfused chain below, the reference of their fused form
+    if (fit != u->la_fused.end() && !c.train && (C <= 128 || env_int("OFD_LA_FUSED_WIDE", 1))) {
+        // inference: fused two-pass block (la_fused.hip): no LayerNorm / qkv / to_out tensors in HBM
+        const int nparts = la_fused_blocks(n, B, C);
         float* partial = c.tmpf((size_t)B * 4 * nparts * 1088);
         bf16_t* ctxfrag = (bf16_t*)c.tmpf((size_t)B * 2048);
         Tensor y = c.keep(C, H, W);
@@ -264,7 +263,7 @@ static Tensor linattn(Ctx& c, const std::string& name, Tensor x) {
         u->tape.push_back(r);
         return y;
     }
-    // unfused: training at C = 128, and the wider blocks (C >= 256) in inference and training
+    // unfused: training at C >= 128, and the blocks of 256 / 512 channels under OFD_LA_FUSED_WIDE=0
     float* partial = c.tmpf((size_t)B * 4 * nparts * 1088);
     float* ctx = c.train ? c.keepf((size_t)B * 4 * 1024) : c.tmpf((size_t)B * 4 * 1024);
     float* ml = c.train ? c.keepf((size_t)B * 4 * 64) : nullptr;

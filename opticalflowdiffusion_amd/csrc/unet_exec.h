@@ -105,7 +105,7 @@ struct ofd_unet {
     bf16_t* d_wbuf = nullptr;
     size_t n_wbuf = 0;
     MlpDesc* d_mlp = nullptr;
-    bf16_t* d_labuf = nullptr;                // fused LinearAttention weights (C <= 128): wq | wkv | wout per block
+    bf16_t* d_labuf = nullptr;                // fused LinearAttention weights: wq | wkv | wout per block
     size_t n_labuf = 0;
     std::map<std::string, std::pair<size_t, int>> la_fused;   // block name -> (offset, C)
     bool prepared = false;
