@@ -30,6 +30,7 @@
  *   (not in the reference)            joint bilateral upsampling (reduced-size sampling) -> ofd_joint_upsample
  *   (not in the reference)            looping clips from a steady motion field -> ofd_flow_integrate, ofd_loop_render
  *   (not in the reference)            forward-backward check of a flow pair -> ofd_flow_consistency
+ *   (not in the reference)            guided weighted median of a flow  -> ofd_flow_median
  *   denoising_diffusion.py:806-812    q_sample                          -> ofd_q_sample
  *   denoising_diffusion.py:844-879,985-993  p_losses noise / target     -> ofd_diffusion_prep
  *   denoising_diffusion.py:73-77      (un)normalize                     -> ofd_range_map
@@ -256,6 +257,44 @@ int ofd_loop_render(const float* img, const float* motion, float* video, int B, 
  * written: 42 * B * H * W bytes in all.  The pass is bound by the latency of its gathers (8 corner loads per pixel), not by that. */
 int ofd_flow_consistency(const float* flow12, const float* flow21, float a1, float a2, int dilate, float* known, float* err,
                          uint8_t* state, int32_t* counts, int B, int H, int W, void* stream);
+
+/* Guided weighted median of a flow (Sun, Roth & Black, "Secrets of optical flow estimation and their principles", CVPR 2010, in its
+ * weighted, image-guided form).  An addition: nothing in the reference cleans a flow.  Every vector is replaced, plane by plane, by the
+ * lower weighted median of its (2 radius + 1)^2 window; a neighbour counts by how near it is and by how much its guide colour
+ * resembles the centre's, so that isolated wild vectors are voted away while a motion boundary stays on the guide's edge.  Scores are
+ * fp32 in the order written here; from the weights on everything is integer arithmetic.
+ * flow, out: (B,C,H,W), 1 <= C <= 4; guide: (B,Cg,H,W), 0 <= Cg <= 4, NULL exactly when Cg == 0; conf: (B,1,H,W) or NULL.  For the
+ * output pixel p = (x, y) and tap j = (dy + radius) * (2 radius + 1) + (dx + radius), dy outer, dx inner, both ascending from -radius,
+ * let q = p + (dx, dy):
+ *   confidence  cf = conf(q) clamped to [0, 1], a NaN counting as 0; 1 when conf is NULL.
+ *   score       d2 = sum over c, ascending, of (guide_c(p) - guide_c(q))^2;  z = -(dx*dx + dy*dy) / (2 sigma_s^2) - d2 * k_r with
+ *               k_r = 1 / (Cg * 2 sigma_r^2): the denominators 2 * (sigma * sigma) in fp32, k_r rounded to fp32 once, the formulas and
+ *               operation order of ofd_joint_upsample.  +inf is allowed for either sigma and switches that term off: the first
+ *               term is then -0 and k_r is 0.  With Cg == 0 there is no second term: z is the first.  With both terms off every tap
+ *               has z = -0.
+ *   valid       q is inside the image, all C values of flow at q are finite, and z is not NaN (a NaN of the guide at p or q,
+ *               inf * 0).
+ *   weight      w_j = (uint32) floorf(expf(z) * cf * 65536 + 0.5), the products from left to right; 0 for a tap that is not valid.
+ *               T = the sum of the w_j, at most 49 * 65536.  Integer sums do not depend on their order (the idea of csrc/det.h,
+ *               applied to a rank).
+ *   result      for each plane c by itself: order the taps by (flow_c(q) ascending, j ascending) under the float <, so that -0.0 and
+ *               +0.0 tie and j decides; below_k = the sum of w over the taps before k.  out_c(p) = the BITS of flow_c at the one
+ *               tap with w_k > 0 and 2 below_k < T <= 2 (below_k + w_k): the lower weighted median, always one of the window's own
+ *               values.  T == 0: the quiet NaN 0x7fc00000 in every plane.
+ *   fill        0: a pixel whose own flow is non-finite in some plane is that NaN in every plane, so that a NaN mask such as a
+ *               `known` plane passes through.  1: such a pixel gets the weighted median of its valid neighbours (its own tap is
+ *               not valid): holes up to radius wide close.
+ * One launch; no atomics, no host sync, no branch on data, no float becomes an index; the same input gives the same bits.  A workgroup
+ * stages the (64 + 2 radius) x (16 + 2 radius) window of its 64 x 16 tile in LDS, C + Cg + 1 planes, the last being cf with 0 for
+ * every position that cannot vote; a thread owns 4 neighbouring pixels of a row, keeps a pixel's weights in registers and finds each
+ * plane's median by counting, without a sort.  out stores are 16 bytes wide where W % 4 == 0 and out is 16-byte aligned, one float
+ * wide otherwise, with the same bits.  1 <= radius <= 3; sigma_s, sigma_r > 0; fill 0 or 1; H, W <= 32768;
+ * B * ceil(H / 16) * ceil(W / 64) < 2^30; B*(C+Cg+1)*H*W < 2^40.  out must not overlap flow, guide or conf: the filter is not in place.
+ * Argument errors return OFD_ERR_ARG and set ofd_last_error before any GPU work.  Compulsory traffic: 4 * B * H * W * (2 C + Cg + 1)
+ * bytes (+1: conf, where given).  The pass is bound by its vector ALU work -- about 5 operations per pair of taps and plane, 300
+ * pairs at radius 2 -- not by that. */
+int ofd_flow_median(const float* flow, const float* guide, const float* conf, float* out, int B, int C, int Cg, int H, int W, int radius,
+                    float sigma_s, float sigma_r, int fill, void* stream);
 
 /* ------------------------------------------------------------ grid_sample warp (WP:95-119) -
  * second: (B,C,H,W), flow: (B,2,H,W) exactly as handed to the reference's warp(mode='backward'):

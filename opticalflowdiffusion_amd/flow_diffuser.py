@@ -12,7 +12,8 @@ only), its dynamic thresholding keys `dynamic_threshold`, `threshold_max`, its t
 `min_snr_loss_weight`, `min_snr_gamma`, `loss_by_timestep`, its photometric guidance keys `photo_scale`, `photo_levels`, `photo_damping`,
 `photo_schedule` (what `sample(target_frame=)` / `estimate_flow` use), the reduced-size sampling keys `sample_scale`, `upsample_radius`,
 `upsample_sigma_s`, `upsample_sigma_r` (`sample` runs the chain on the frame box-reduced by `sample_scale` and carries the flow back with
-`warp.upsample_flow`), `log_animation` (N > 0: validation_step also logs an N-frame `animate` strip), and the `ema_*` keys and `sample_with_ema` of ema.EMA_DEFAULTS, which are not in the reference).
+`warp.upsample_flow`), the flow-cleaning keys `median_radius` (0 = off), `median_sigma_s`, `median_sigma_r`, `median_iterations`
+(`estimate_flow` and `estimate_flow_pair` pass the pixel flow through `warp.median_filter_flow`, guided by the first frame), `log_animation` (N > 0: validation_step also logs an N-frame `animate` strip), and the `ema_*` keys and `sample_with_ema` of ema.EMA_DEFAULTS, which are not in the reference).
 """
 import os
 
@@ -20,8 +21,8 @@ import torch
 
 from .denoising_diffusion import UNSET, PhotoGuide, Unet, ConditionalDiffusion, loss_by_timestep
 from .ema import EMA_DEFAULTS, EmaMixin, ema_optimizer_kwargs
-from .warp import (box_reduce, consistency_params, flow_consistency, interpolate_frames, loop_frames, loop_params, upsample_flow,
-                   upsample_params, warp)
+from .warp import (box_reduce, consistency_params, flow_consistency, interpolate_frames, loop_frames, loop_params, median_filter_flow,
+                   median_params, upsample_flow, upsample_params, warp)
 from . import _lib as L
 
 try:                                                   # pragma: no cover - not installed in this image
@@ -53,6 +54,7 @@ class _Cfg:
                      loss_weighting=None, min_snr_loss_weight=True, min_snr_gamma=5, loss_by_timestep=False, log_animation=0,
                      photo_scale=1.0, photo_levels=(1, 2, 4), photo_damping=1e-2, photo_schedule="constant",
                      sample_scale=1, upsample_radius=2, upsample_sigma_s=1.0, upsample_sigma_r=0.1,
+                     median_radius=0, median_sigma_s=2.0, median_sigma_r=0.1, median_iterations=1,
                      **EMA_DEFAULTS)
 
     def __init__(self, cfg):
@@ -137,6 +139,9 @@ def ae_checkpoint_path(cfg):
     p = cfg.ae_checkpoint if "ae_checkpoint" in cfg else None
     return p if p else os.path.join("outputs", "loaded_checkpoints", "diffusion_control", str(cfg.ae), "model.ckpt")
 
+
+# the keys of `FlowDiffuser.median_filtering`: cfg keys that a call of estimate_flow / estimate_flow_pair may override
+MEDIAN_KEYS = ("median_radius", "median_sigma_s", "median_sigma_r", "median_iterations")
 
 # `FlowDiffuser.animate` hands the engine at most this many pixels (samples x H x W) per warp call: a quarter of the splat's
 # B*H*W < 2^31 limit, 4.3 GB of fp32 accumulators, frames and pyramid at three channels
@@ -461,21 +466,44 @@ class FlowDiffuser(EmaMixin, _Base):
             samples = warp(cond[:, :self.dim], None, flow, mode="forward")
         return samples, flow[:, None]
 
+    def median_filtering(self, sample_kw, name="estimate_flow"):
+        """(sample_kw without the `median_*` keys, the arguments of `warp.median_filter_flow` or None = off) of an `estimate_flow` call:
+        `median_radius`, `median_sigma_s`, `median_sigma_r`, `median_iterations` from sample_kw, else from the cfg keys of those names.
+        median_radius = 0 is off, and the other three are then not read.  The rules are checked here (ValueError): host logic, any
+        device, no engine call."""
+        rest = {k: v for k, v in sample_kw.items() if k not in MEDIAN_KEYS}
+        pick = lambda key: sample_kw[key] if key in sample_kw else getattr(self.cfg, key)
+        radius = pick("median_radius")
+        if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= 3:
+            raise ValueError(f"{name}: median_radius must be an integer in 0..3 (0 = no median filter), got {radius!r}")
+        if radius == 0:
+            return rest, None
+        par = median_params(radius, pick("median_sigma_s"), pick("median_sigma_r"), pick("median_iterations"), name=name)
+        del par["fill"]                                                     # a sampled flow has no holes to close
+        return rest, par
+
     def estimate_flow(self, frame1, frame2, **sample_kw):
         """The flow from frame1 to frame2 in pixels, (B, 2, H, W): frame1(p) ~ frame2(p + flow(p)) (not in the reference, whose diffusion
         model never sees a second frame when sampling).  Frames are (B, 3, H, W) in cond's range (2 * img - 1).  It is the last
         trajectory frame of `self.sample(frame1, ., target_frame=frame2, **sample_kw)` times flow_max, the conversion `animate` uses:
         the trained prior proposes, the photometric step pulls every prediction towards agreement with frame2.  sample_kw: known_flow,
-        guidance_scale, dynamic_threshold, photo_scale, ...; the EMA scope applies as in `sample`."""
+        guidance_scale, dynamic_threshold, photo_scale, ...; the EMA scope applies as in `sample`.
+        `median_radius` = r > 0 (1..3; with `median_sigma_s`, `median_sigma_r`, `median_iterations`; instead of the cfg keys of those
+        names, which default to off) returns `warp.median_filter_flow(flow, frame1, r, ...)` of that flow -- with sample_scale > 1 of
+        the upsampled one: the guided weighted median votes isolated wild vectors away and keeps motion boundaries on frame1's
+        edges.  The keys are checked before any model call and never reach `sample`.  Their defaults come from a synthetic thin bar
+        and are untuned on real footage.  median_radius = 0 or unset is the call without them, launch for launch."""
         if not torch.is_tensor(frame1) or frame1.dim() != 4:
             raise ValueError(f"estimate_flow: frame1 must be (B, 3, H, W), got "
                              f"{tuple(frame1.shape) if torch.is_tensor(frame1) else type(frame1).__name__}")
         if frame2 is None:
             raise ValueError("estimate_flow: frame2 is needed (the target_frame of sample)")
+        sample_kw, median = self.median_filtering(sample_kw)
         B, _, H, W = frame1.shape
         with torch.no_grad():
             _samples, fl = self.sample(frame1, frame1.new_zeros(B, 2, H, W), target_frame=frame2, **sample_kw)
-        return fl[:, -1] * float(self.flow_max)
+            flow = fl[:, -1] * float(self.flow_max)
+            return flow if median is None else median_filter_flow(flow, frame1, **median)
 
     def estimate_flow_pair(self, frame1, frame2, refine=1, a1=0.01, a2=0.5, dilate=2, refine_photo=False, **sample_kw):
         """Both flows between two frames, made to agree with each other (not in the reference): (flow12, flow21, check), the flows
@@ -491,7 +519,10 @@ class FlowDiffuser(EmaMixin, _Base):
         With refine > 0 everything known_flow rejects is a ValueError before any UNet call: a non-diffusion model, target 'target',
         latent=True, sample_scale > 1.  Cost: 1 + refine chains on 2B samples; no host sync beyond `sample`'s.  a1, a2 are UnFlow's
         (Meister et al. 2018) and untuned with trained weights; how well the prior completes occluded regions has not been
-        measured."""
+        measured.
+        The `median_*` keys of `estimate_flow` (sample_kw or cfg; checked before any model call) clean round 0 inside that call,
+        each direction guided by its own first frame, and in every refine round the freshly sampled flow the same way BEFORE it is
+        merged: held pixels keep their bits, and the keys never reach the round's `sample`."""
         if isinstance(refine, bool) or not isinstance(refine, int) or not 0 <= refine <= 16:
             raise ValueError(f"estimate_flow_pair: refine must be an integer in 0..16, got {refine!r}")
         par = consistency_params(a1, a2, dilate, name="estimate_flow_pair")
@@ -518,7 +549,9 @@ class FlowDiffuser(EmaMixin, _Base):
             reduced = {k: v for k, v in sample_kw.items() if k in ("sample_scale", "upsample_radius", "upsample_sigma_s", "upsample_sigma_r")}
             if self.reduced_sampling(cond, None, **reduced)[0] > 1:
                 raise ValueError("estimate_flow_pair: refine > 0 cannot be combined with sample_scale > 1: known_flow has no reduced form")
-        refine_kw = sample_kw if refine_photo else {k: v for k, v in sample_kw.items() if not k.startswith("photo_")}
+        refine_kw, median = self.median_filtering(sample_kw, name="estimate_flow_pair")
+        if not refine_photo:
+            refine_kw = {k: v for k, v in refine_kw.items() if not k.startswith("photo_")}
         scale = float(self.flow_max)
         with torch.no_grad():
             both = self.estimate_flow(cond, other, **sample_kw)
@@ -527,7 +560,10 @@ class FlowDiffuser(EmaMixin, _Base):
                 known = torch.cat((check.known12, check.known21))
                 extra = dict(target_frame=other) if refine_photo else {}
                 _samples, fl = self.sample(cond, cond.new_zeros(2 * B, 2, H, W), known_flow=known, **extra, **refine_kw)
-                both = torch.where(torch.isnan(known), fl[:, -1] * scale, both)     # held pixels keep their bits through every round
+                fresh = fl[:, -1] * scale
+                if median is not None:
+                    fresh = median_filter_flow(fresh, cond, **median)
+                both = torch.where(torch.isnan(known), fresh, both)         # held pixels keep their bits through every round
             check = flow_consistency(both[:B], both[B:], **par)
         return both[:B], both[B:], check
 

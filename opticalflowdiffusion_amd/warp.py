@@ -506,6 +506,62 @@ def flow_consistency(flow12, flow21, a1=0.01, a2=0.5, dilate=0):
     return FlowConsistency(known[0], known[1], err[0], err[1], state[0], state[1], counts)
 
 
+# ---- guided weighted median of a flow (not in the reference; semantics: include/ofd.h, `ofd_flow_median`) ----------------------------
+def median_params(radius=2, sigma_s=2.0, sigma_r=0.1, iterations=1, fill=False, name="median_filter_flow"):
+    """the rules of the median's window, widths and passes (ValueError); host logic, no engine call"""
+    real = lambda v: not isinstance(v, bool) and isinstance(v, (int, float)) and v > 0.0                      # false for NaN
+    if not real(sigma_s) or not real(sigma_r):
+        raise ValueError(f"{name}: sigma_s and sigma_r must be numbers > 0 (inf switches a term off), got {sigma_s!r} and {sigma_r!r}")
+    if not isinstance(fill, bool):
+        raise ValueError(f"{name}: fill must be True or False, got {fill!r}")
+    return dict(radius=_loop_int(name, "radius", radius, 1, 3), sigma_s=float(sigma_s), sigma_r=float(sigma_r),
+                iterations=_loop_int(name, "iterations", iterations, 1, 8), fill=fill)
+
+
+def median_filter_flow(flow, guide=None, radius=2, sigma_s=2.0, sigma_r=0.1, conf=None, iterations=1, fill=False):
+    """The guided weighted median of a flow (Sun, Roth & Black 2010; not in the reference): a new fp32 (B, C, H, W) tensor in which every
+    vector is, plane by plane, the weighted median of its (2 radius + 1)^2 window.  flow: (B, C, H, W), C <= 4; guide: (B, Cg, H, W),
+    Cg <= 4, e.g. the first frame, or None; conf: (B, 1, H, W), a confidence per vector that is clamped to [0, 1], or None.  A
+    neighbour votes with the weight exp(-distance^2 / (2 sigma_s^2) - sum_c (guide - guide at the centre)^2 / (Cg * 2 sigma_r^2)) * conf:
+    isolated wild vectors are voted away, a motion boundary stays on the guide's edge and a thin structure is not erased by the
+    background around it, which the plain median (sigma_s = sigma_r = inf, no conf) does.  The result at a pixel is always one of
+    its window's own values.  Neighbours outside the frame or with a non-finite flow do not vote; a pixel left with no vote is NaN.
+    fill=False: a pixel whose own flow is not finite stays NaN in every plane, so a NaN mask passes through; True: it gets the
+    median of its neighbours, which closes holes up to `radius` wide.  `iterations` (1..8) passes, each on the result of the one
+    before, between two buffers.  radius 1..3.  The defaults suit frames in [-1, 1]; they come from a synthetic thin bar and are
+    untuned on real footage.  One launch per pass; forward only; inputs are not modified; the same input gives the same bits.
+    Semantics: include/ofd.h."""
+    if not torch.is_tensor(flow) or flow.dim() != 4 or flow.numel() == 0 or not 1 <= flow.shape[1] <= 4:
+        raise ValueError(f"median_filter_flow: flow must be a non-empty (B, C, H, W) tensor with 1 <= C <= 4, got {_shape_of(flow)}")
+    B, C, H, W = flow.shape
+    if max(H, W) > 32768:
+        raise ValueError(f"median_filter_flow: H and W must be at most 32768, got {tuple(flow.shape)}")
+    if guide is not None and (not torch.is_tensor(guide) or guide.dim() != 4 or not 1 <= guide.shape[1] <= 4 or
+                              (guide.shape[0], guide.shape[2], guide.shape[3]) != (B, H, W)):
+        raise ValueError(f"median_filter_flow: guide must be (B, 1..4, H, W) = ({B}, 1..4, {H}, {W}) or None, got {_shape_of(guide)}")
+    if conf is not None and (not torch.is_tensor(conf) or tuple(conf.shape) != (B, 1, H, W)):
+        raise ValueError(f"median_filter_flow: conf must be (B, 1, H, W) = {(B, 1, H, W)} or None, got {_shape_of(conf)}")
+    given = [t for t in (flow, guide, conf) if t is not None]
+    if not all(t.is_floating_point() for t in given):
+        raise ValueError(f"median_filter_flow: flow, guide and conf must be floating-point tensors, got {[t.dtype for t in given]}")
+    par = median_params(radius, sigma_s, sigma_r, iterations, fill)
+    if any(t.requires_grad for t in given):
+        raise L.OfdError("median_filter_flow: forward only (the selection has no backward pass): detach the inputs")
+    L.require_gpu(*given)
+    if any(t.device != flow.device for t in given):
+        raise ValueError(f"median_filter_flow: flow, guide and conf must be on one device, got {[str(t.device) for t in given]}")
+    Cg = 0 if guide is None else guide.shape[1]
+    with torch.no_grad():
+        src, guide, conf = L.f32c(flow), None if guide is None else L.f32c(guide), None if conf is None else L.f32c(conf)
+        bufs = [torch.empty(B, C, H, W, dtype=torch.float32, device=flow.device) for _ in range(min(par["iterations"], 2))]
+        for i in range(par["iterations"]):
+            dst = bufs[i % 2]
+            L.check(L.lib().ofd_flow_median(L.ptr(src), L.ptr(guide), L.ptr(conf), L.ptr(dst), B, C, Cg, H, W, par["radius"],
+                                            par["sigma_s"], par["sigma_r"], int(par["fill"]), L.stream()))
+            src = dst
+    return src
+
+
 class _GridWarp(torch.autograd.Function):
     """warp_backward_flow (WP:95-119) with the gradients autograd derives for it: d/d second is the bilinear scatter of the
     incoming gradient (the splat kernel on grid_sample's coordinates), d/d flow ATen's grid gradient; the thresholded mask
