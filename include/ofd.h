@@ -30,6 +30,7 @@
  *   (not in the reference)            joint bilateral upsampling (reduced-size sampling) -> ofd_joint_upsample
  *   (not in the reference)            looping clips from a steady motion field -> ofd_flow_integrate, ofd_loop_render
  *   (not in the reference)            forward-backward check of a flow pair -> ofd_flow_consistency
+ *   (not in the reference)            tracks through a clip's flows, layer propagation -> ofd_flow_chain, ofd_flow_chain_to, ofd_layer_composite
  *   (not in the reference)            guided weighted median of a flow  -> ofd_flow_median
  *   denoising_diffusion.py:806-812    q_sample                          -> ofd_q_sample
  *   denoising_diffusion.py:844-879,985-993  p_losses noise / target     -> ofd_diffusion_prep
@@ -295,6 +296,65 @@ int ofd_flow_consistency(const float* flow12, const float* flow21, float a1, flo
  * pairs at radius 2 -- not by that. */
 int ofd_flow_median(const float* flow, const float* guide, const float* conf, float* out, int B, int C, int Cg, int H, int W, int radius,
                     float sigma_s, float sigma_r, int fill, void* stream);
+
+/* Flow chaining: dense tracks through a clip, and a painted layer carried along them (the subject of Sundaram, Brox & Keutzer, ECCV
+ * 2010, cited above, with UnFlow's bound).  An addition: nothing in the reference looks at more than two frames.  Every pixel of one
+ * frame is followed through the consecutive flows of the clip by COMPOSING them -- each flow is read where the track has got to, not
+ * at the pixel it started from -- and a track ends where the round trip of a step fails (occlusion), where it leaves the frame, or
+ * where a flow is not finite.  This is not ofd_flow_integrate, which walks ONE steady field, clamps at the border and reads NaN as 0.
+ * All arithmetic fp32, in the order written here.
+ * fwd, bwd: (B,T,2,H,W) in pixels, channel 0 = x.  fwd[:, j] carries frame j to frame j + 1: frame_j(p) ~ frame_{j+1}(p + fwd_j(p)),
+ * the convention of ofd_flow_consistency's flow12; bwd[:, j] carries frame j + 1 to frame j.  A clip of T + 1 frames has T of each.
+ * One step of a track from frame a to a neighbouring frame uses S, the field that carries a to the neighbour (fwd[:, a] ahead,
+ * bwd[:, a - 1] back), and, with the check on, K, the field that carries the neighbour back to a (bwd[:, a] ahead, fwd[:, a - 1] back).
+ * A track of the pixel p = (x, y) keeps a displacement D, 0 at the start, and a state, 0 at the start.  A step of a living track:
+ *   q = ((float)x + D.x, (float)y + D.y);  v = the bilinear read of S at q by ofd_flow_consistency's formula (x0 = floor(q.x),
+ *   x1 = min(x0 + 1, W-1), tx = q.x - x0, likewise in y; value = (1-ty) * ((1-tx) * g00 + tx * g01) + ty * ((1-tx) * g10 + tx * g11); a
+ *   non-finite corner makes v non-finite even under weight 0).  q is inside: it is the q' that the step before accepted, or p.
+ *   5 invalid       a component of v is non-finite.
+ *   D' = D + v;  q' = ((float)x + D'.x, (float)y + D'.y).
+ *   3 leaves        q' is not inside: inside = 0 <= q'.x <= W-1 and 0 <= q'.y <= H-1 (false for a non-finite q').
+ *   with the check on: g = the bilinear read of K at q'.
+ *   4 unmatched     g has a non-finite component.
+ *   2 inconsistent  r = v + g;  e2 = r.x*r.x + r.y*r.y;  m = (v.x*v.x + v.y*v.y) + (g.x*g.x + g.y*g.y);  bound = a1*m + a2, exactly as
+ *                   in ofd_flow_consistency; `e2 <= bound` is false.  (As there: a finite g so large that its square overflows, such
+ *                   as 1e30, gives e2 = m = inf; inf <= inf holds for a1 > 0, so the track lives on, and bound is NaN for a1 = 0, so
+ *                   it dies here.  Under weight 0 such a corner is 0 * 1e30 = 0.)
+ *   0 tracked       otherwise, and D = D'.
+ * The first rule that applies ends the track: it is dead, keeps that state, and its D is the quiet NaN at this and every later frame.
+ * The numbers are those of ofd_flow_consistency's states; 1 is not used.
+ * ofd_flow_chain: tracks every pixel of frame `start` to frame `stop`, n = |stop - start| steps, ahead (stop >= start: steps by fwd,
+ *   checks by bwd) or back (steps by bwd, checks by fwd).  disp (B, n+1, 2, H, W), state (B, n+1, 1, H, W) uint8: slot i holds the
+ *   track on arrival at the i-th frame of the walk, slot 0 is D = 0 with state 0.  life (B, 1, H, W) int32: the number of steps
+ *   completed alive, 0..n.  all_steps = 0 stores only the last slot: disp (B, 1, 2, H, W), state (B, 1, 1, H, W).  n = 0 is allowed.
+ *   The stepping array must be non-null (fwd for stop >= start), the checking array may be null only with use_check = 0.
+ * ofd_flow_chain_to: the lookup form.  For every frame t in [t0, t0 + nt) it gives, for each pixel of frame t, its displacement into
+ *   frame `anchor` and the final state of that walk of |t - anchor| steps towards the anchor: disp (B, nt, 2, H, W), state
+ *   (B, nt, 1, H, W), slot t - t0 with the bits of the last slot of ofd_flow_chain(start = t, stop = anchor).  One launch; all threads
+ *   of a workgroup share t.  A frame's result does not depend on how the frames are split over calls.  0 <= t0, 1 <= nt,
+ *   t0 + nt <= T + 1; fwd and bwd both non-null.
+ * ofd_layer_composite: frames, out (B, n, C, H, W); layer (B, C+1, H, W), premultiplied colour with alpha last; disp (B, n, 2, H, W),
+ *   e.g. ofd_flow_chain_to's; 1 <= C <= 8, 1 <= n <= 4097.  With d = disp(p) and q = ((float)x + d.x, (float)y + d.y): where d is finite
+ *   and q is inside, out_c = frame_c * (1 - A) + L_c (one subtraction, one product, one sum), A and L_c the bilinear reads of the
+ *   layer's planes at q, one cell formed for all C + 1 planes; elsewhere out = frame, bit for bit.  A gather: no holes.
+ * All three: one launch; no atomics, no LDS, no host sync; a thread writes only its own pixels; the same input gives the same bits.  A
+ * workgroup owns a 64 x 16 tile of one walk (or frame) and sample, a thread one column of four neighbouring rows, so that every load
+ * and store of a wave covers 64 neighbouring pixels of a row and no pointer needs more than its element's alignment; the step loop
+ * runs in registers.  A float becomes a gather index only after the inside test, which a non-finite or huge value fails; a dead
+ * track, and a pixel the composite leaves alone, read at offset 0 of the plane and drop what they read: whatever the fields hold,
+ * every read is inside its plane.  H, W <= 32768; 1 <= T <= 4096; 0 <= start, stop, anchor <= T; a1, a2 finite and >= 0; use_check
+ * and all_steps 0 or 1; the number of tiles (B, nt * B, B * n times ceil(H / 16) * ceil(W / 64)) < 2^30; every array < 2^40 elements.
+ * Outputs must not alias inputs: a thread gathers other pixels' inputs, so an output that shares a byte with an input array is a race,
+ * and is rejected.  Argument errors return OFD_ERR_ARG and set ofd_last_error before any GPU work.  Per step and pixel
+ * a walk makes 8 corner loads, 16 with the check, each step's behind the one before: it is taken to be bound by the latency of these gathers,
+ * like ofd_flow_integrate, whose time it matches, not by its compulsory traffic (ofd_flow_chain: 4 * B * H * W * (2 n [4 n with the check] read + 2 (n+1) written)
+ * + B * H * W * (n + 1 + 4) bytes; ofd_layer_composite: 4 * B * H * W * (n * (2 C + 2) + C + 1)). */
+int ofd_flow_chain(const float* fwd, const float* bwd, float* disp, uint8_t* state, int32_t* life, int B, int T, int H, int W, int start,
+                   int stop, int use_check, float a1, float a2, int all_steps, void* stream);
+int ofd_flow_chain_to(const float* fwd, const float* bwd, float* disp, uint8_t* state, int B, int T, int H, int W, int anchor, int t0, int nt,
+                      int use_check, float a1, float a2, void* stream);
+int ofd_layer_composite(const float* frames, const float* layer, const float* disp, float* out, int B, int n, int C, int H, int W,
+                        void* stream);
 
 /* ------------------------------------------------------------ grid_sample warp (WP:95-119) -
  * second: (B,C,H,W), flow: (B,2,H,W) exactly as handed to the reference's warp(mode='backward'):

@@ -4,6 +4,7 @@ from .warp import warp, nan_mse, nan_mse_rows, scale, warp_forward_flow, warp_ba
 from .warp import (flow_consistency, FlowConsistency, STATE_HELD, STATE_RELEASED, STATE_INCONSISTENT, STATE_LEAVES_FRAME,  # noqa: F401
                    STATE_UNMATCHED, STATE_INVALID)
 from .warp import median_filter_flow, median_params  # noqa: F401
+from .warp import chain_flows, chain_flows_to, composite_layer, FlowChain  # noqa: F401
 from .softsplat import softsplat  # noqa: F401
 from .denoising_diffusion import Unet, ConditionalDiffusion, PhotoGuide  # noqa: F401,E402
 from .flow_diffuser import FlowDiffuser, UnetWithWarp  # noqa: F401,E402

@@ -64,6 +64,9 @@ SIGNATURES = {
     "ofd_loop_render": (c_int, [c_void_p] * 3 + [c_int] * 9 + [c_float, c_void_p, c_size_t, c_void_p]),
     "ofd_flow_consistency": (c_int, [c_void_p] * 2 + [c_float] * 2 + [c_int] + [c_void_p] * 4 + [c_int] * 3 + [c_void_p]),
     "ofd_flow_median": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_float] * 2 + [c_int, c_void_p]),
+    "ofd_flow_chain": (c_int, [c_void_p] * 5 + [c_int] * 7 + [c_float] * 2 + [c_int, c_void_p]),
+    "ofd_flow_chain_to": (c_int, [c_void_p] * 4 + [c_int] * 8 + [c_float] * 2 + [c_void_p]),
+    "ofd_layer_composite": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p]),
     "ofd_grid_warp_fwd": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p]),
     "ofd_splat_pyramid_workspace_bytes": (c_size_t, [c_int] * 4),
     "ofd_splat_pyramid_fwd": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_void_p, c_size_t, c_void_p]),

@@ -21,8 +21,8 @@ import torch
 
 from .denoising_diffusion import UNSET, PhotoGuide, Unet, ConditionalDiffusion, loss_by_timestep
 from .ema import EMA_DEFAULTS, EmaMixin, ema_optimizer_kwargs
-from .warp import (box_reduce, consistency_params, flow_consistency, interpolate_frames, loop_frames, loop_params, median_filter_flow,
-                   median_params, upsample_flow, upsample_params, warp)
+from .warp import (box_reduce, chain_flows, chain_flows_to, composite_layer, consistency_params, flow_consistency, interpolate_frames,
+                   loop_frames, loop_params, median_filter_flow, median_params, upsample_flow, upsample_params, warp)
 from . import _lib as L
 
 try:                                                   # pragma: no cover - not installed in this image
@@ -685,6 +685,102 @@ class FlowDiffuser(EmaMixin, _Base):
             video = interpolate_frames(frame1, frame2, flow12, flow21, times, alpha=alpha, beta=beta, fill_holes=fill_holes,
                                        fill_gain=fill_gain)
         return (video if fill_holes else video[0]), flow12, flow21
+
+    def estimate_flow_clip(self, clip, refine=0, pairs_per_call=None, **sample_kw):
+        """The flows between the consecutive frames of a clip, in both directions (not in the reference): (fwd, bwd), both
+        (B, T, 2, H, W) in pixels; fwd[:, j] carries frame j to frame j + 1 as `estimate_flow` defines it, bwd[:, j] carries frame j + 1
+        to frame j: what `warp.chain_flows` takes.  clip: (B, T + 1, 3, H, W) in cond's range (2 * img - 1), T <= 4096.  The T
+        consecutive pairs of every sample, in the order (sample, pair), go through `estimate_flow_pair(first, second, refine=refine,
+        **sample_kw)` as one batch, or at most `pairs_per_call` (default: all B * T) of them per call; that call's own a1, a2, dilate,
+        refine_photo and median_* keys pass through, and its rules apply.  The noise a pair is sampled from depends on its place in
+        its call: another pairs_per_call gives other flows under the same seed, the same split gives the same bits."""
+        if self.latent:
+            raise ValueError("estimate_flow_clip: latent=True is not supported (the photometric estimate compares frames in pixel space)")
+        if not torch.is_tensor(clip) or clip.dim() != 5 or clip.shape[2] != 3 or clip.shape[1] < 2 or clip.numel() == 0:
+            raise ValueError(f"estimate_flow_clip: clip must be (B, T + 1, 3, H, W) with at least two frames, got "
+                             f"{tuple(clip.shape) if torch.is_tensor(clip) else type(clip).__name__}")
+        B, N, _, H, W = clip.shape
+        T = N - 1
+        if T > 4096:
+            raise ValueError(f"estimate_flow_clip: at most 4097 frames, got {N}")
+        if pairs_per_call is None:
+            pairs_per_call = B * T
+        if isinstance(pairs_per_call, bool) or not isinstance(pairs_per_call, int) or pairs_per_call < 1:
+            raise ValueError(f"estimate_flow_clip: pairs_per_call must be a positive integer or None, got {pairs_per_call!r}")
+        with torch.no_grad():
+            first, second = clip[:, :-1].reshape(B * T, 3, H, W), clip[:, 1:].reshape(B * T, 3, H, W)
+            parts = [self.estimate_flow_pair(first[i:i + pairs_per_call], second[i:i + pairs_per_call], refine=refine, **sample_kw)[:2]
+                     for i in range(0, B * T, pairs_per_call)]
+            fwd, bwd = (parts[0][k] if len(parts) == 1 else torch.cat([p[k] for p in parts]) for k in range(2))
+        return fwd.reshape(B, T, 2, H, W), bwd.reshape(B, T, 2, H, W)
+
+    def _clip_flows(self, name, clip, fwd, bwd, sample_kw):
+        """the rules `track` and `propagate` share, all before any model or engine call -> T.  The flows come both or neither."""
+        if self.latent:
+            raise ValueError(f"{name}: latent=True is not supported (the flows are estimated and chained in pixel space)")
+        if not torch.is_tensor(clip) or clip.dim() != 5 or clip.shape[2] != 3 or clip.shape[1] < 2 or clip.numel() == 0:
+            raise ValueError(f"{name}: clip must be (B, T + 1, 3, H, W) with at least two frames, got "
+                             f"{tuple(clip.shape) if torch.is_tensor(clip) else type(clip).__name__}")
+        B, N, _, H, W = clip.shape
+        if (fwd is None) != (bwd is None):
+            raise ValueError(f"{name}: fwd and bwd come together: give both, or neither to have both estimated")
+        if fwd is not None:
+            if sample_kw:
+                raise ValueError(f"{name}: {sorted(sample_kw)} are sampling arguments; with the flows given nothing is sampled")
+            for key, fl in (("fwd", fwd), ("bwd", bwd)):
+                if not torch.is_tensor(fl) or tuple(fl.shape) != (B, N - 1, 2, H, W):
+                    raise ValueError(f"{name}: {key} must be (B, T, 2, H, W) = {(B, N - 1, 2, H, W)}, got "
+                                     f"{tuple(fl.shape) if torch.is_tensor(fl) else type(fl).__name__}")
+        elif not self.is_diffusion:
+            raise ValueError(f"{name}: estimating the flows needs a diffusion model (estimate_flow_clip); pass fwd and bwd")
+        if any(t is not None and t.requires_grad for t in (clip, fwd, bwd)):
+            raise L.OfdError(f"{name}: forward only (the walk has no backward pass): detach the inputs")
+        return N - 1
+
+    def track(self, clip, start=0, stop=None, fwd=None, bwd=None, check=True, a1=0.01, a2=0.5, **sample_kw):
+        """Where every pixel of one frame of a clip is in the frames after (or before) it, and until when it is visible (not in the
+        reference): (chain, fwd, bwd), chain the `warp.FlowChain` (disp, state, life) of `warp.chain_flows(fwd, bwd, start, stop,
+        check, a1, a2)`, which has the method.  clip: (B, T + 1, 3, H, W) in cond's range; start, stop: frames in 0..T, stop None = T.
+        fwd, bwd: (B, T, 2, H, W) IN PIXELS as `estimate_flow_clip` returns them, both or neither.  Neither: they come from
+        `estimate_flow_clip(clip, **sample_kw)`, whose refine, pairs_per_call and sampling keys sample_kw may carry.  Both: no UNet call
+        is made, and sample_kw is an error.  a1, a2 are UnFlow's and untuned with trained weights; drift over long clips with real
+        estimated flows is unmeasured.  Forward only."""
+        T = self._clip_flows("track", clip, fwd, bwd, sample_kw)
+        for key, v in (("start", start), ("stop", T if stop is None else stop)):
+            if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= T:
+                raise ValueError(f"track: {key} must be an integer in 0..{T}, got {v!r}")
+        if not isinstance(check, bool):
+            raise ValueError(f"track: check must be True or False, got {check!r}")
+        par = consistency_params(a1, a2, name="track")
+        if fwd is None:
+            fwd, bwd = self.estimate_flow_clip(clip, **sample_kw)
+        return chain_flows(fwd, bwd, start=start, stop=stop, check=check, a1=par["a1"], a2=par["a2"]), fwd, bwd
+
+    def propagate(self, clip, layer, anchor=0, fwd=None, bwd=None, premultiplied=True, check=True, a1=0.01, a2=0.5, **sample_kw):
+        """Something painted on one frame of a clip, shown on all of them (not in the reference): (video, fwd, bwd), video
+        (B, T + 1, 3, H, W) = `warp.composite_layer(clip, layer, warp.chain_flows_to(fwd, bwd, anchor, check, a1, a2)[0],
+        premultiplied)`, which have the method.  clip: (B, T + 1, 3, H, W) in cond's range; layer: (B, 4, H, W), colour in the clip's
+        range with alpha last, in the coordinates of frame `anchor` (0..T).  Every pixel of every frame is followed to the anchor
+        frame; where it arrives, the layer is read there and laid over the pixel; where its track dies -- it is occluded on the way or
+        leaves the frame -- the pixel stays the clip's.  fwd, bwd, sample_kw as for `track`.  a1, a2 are UnFlow's and untuned with
+        trained weights; drift over long clips with real estimated flows is unmeasured.  Forward only: a clip, layer or flow that
+        requires grad is an OfdError, as in `warp.composite_layer`; nothing is detached on the quiet."""
+        T = self._clip_flows("propagate", clip, fwd, bwd, sample_kw)
+        B, _, _, H, W = clip.shape
+        if not torch.is_tensor(layer) or tuple(layer.shape) != (B, 4, H, W):
+            raise ValueError(f"propagate: layer must be (B, 4, H, W) = {(B, 4, H, W)}, got "
+                             f"{tuple(layer.shape) if torch.is_tensor(layer) else type(layer).__name__}")
+        if isinstance(anchor, bool) or not isinstance(anchor, int) or not 0 <= anchor <= T:
+            raise ValueError(f"propagate: anchor must be an integer in 0..{T}, got {anchor!r}")
+        if not isinstance(check, bool) or not isinstance(premultiplied, bool):
+            raise ValueError(f"propagate: check and premultiplied must be True or False, got {check!r} and {premultiplied!r}")
+        if layer.requires_grad:
+            raise L.OfdError("propagate: forward only (the composite has no backward pass): detach the layer")
+        par = consistency_params(a1, a2, name="propagate")
+        if fwd is None:
+            fwd, bwd = self.estimate_flow_clip(clip, **sample_kw)
+        disp, _state = chain_flows_to(fwd, bwd, anchor=anchor, check=check, a1=par["a1"], a2=par["a2"])
+        return composite_layer(clip, layer, disp, premultiplied=premultiplied), fwd, bwd
 
     @staticmethod
     def _batch_stats(x):

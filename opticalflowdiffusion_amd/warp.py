@@ -506,6 +506,156 @@ def flow_consistency(flow12, flow21, a1=0.01, a2=0.5, dilate=0):
     return FlowConsistency(known[0], known[1], err[0], err[1], state[0], state[1], counts)
 
 
+# ---- flow chaining: tracks through a clip and layer propagation (not in the reference; semantics: include/ofd.h, `ofd_flow_chain`) ----
+FlowChain = collections.namedtuple("FlowChain", "disp state life")
+
+
+def _chain_flows(name, fwd, bwd, need_bwd=True):
+    """the shape, dtype, grad and device rules of a clip's flows -> (B, T, H, W); bwd may be None unless need_bwd"""
+    if not torch.is_tensor(fwd) or fwd.dim() != 5 or fwd.shape[2] != 2 or fwd.numel() == 0:
+        raise ValueError(f"{name}: fwd must be a non-empty (B, T, 2, H, W) tensor, got {_shape_of(fwd)}")
+    if bwd is None and need_bwd:
+        raise ValueError(f"{name}: bwd is needed (the flows from every frame to the one before it)")
+    if bwd is not None and (not torch.is_tensor(bwd) or bwd.shape != fwd.shape):
+        raise ValueError(f"{name}: bwd must have fwd's shape {tuple(fwd.shape)}, got {_shape_of(bwd)}")
+    B, T, _, H, W = fwd.shape
+    if max(H, W) > 32768 or T > 4096:
+        raise ValueError(f"{name}: H and W must be at most 32768 and T at most 4096, got {tuple(fwd.shape)}")
+    given = [t for t in (fwd, bwd) if t is not None]
+    if not all(t.is_floating_point() for t in given):
+        raise ValueError(f"{name}: the flows must be floating-point tensors, got {[t.dtype for t in given]}")
+    return B, T, H, W
+
+
+def _chain_ready(name, *tensors):
+    """forward only, GPU only, one device: the rules that come after the host-only ones"""
+    given = [t for t in tensors if t is not None]
+    if any(t.requires_grad for t in given):
+        raise L.OfdError(f"{name}: forward only (the walk has no backward pass): detach the inputs")
+    L.require_gpu(*given)
+    if any(t.device != given[0].device for t in given):
+        raise ValueError(f"{name}: all tensors must be on one device, got {[str(t.device) for t in given]}")
+
+
+def _chain_check(name, check, default):
+    if check is None:
+        return default
+    if not isinstance(check, bool):
+        raise ValueError(f"{name}: check must be True, False or None, got {check!r}")
+    return check
+
+
+def chain_flows(fwd, bwd=None, start=0, stop=None, check=None, a1=0.01, a2=0.5, all_steps=True):
+    """Dense tracks through the consecutive flows of a clip (Sundaram et al. 2010; not in the reference): a `FlowChain` (disp, state,
+    life).  fwd, bwd: (B, T, 2, H, W) IN PIXELS, channel 0 = x; fwd[:, j] carries frame j to frame j + 1 (frame_j(p) ~
+    frame_{j+1}(p + fwd_j(p)), what `estimate_flow` returns), bwd[:, j] carries frame j + 1 to frame j: what
+    `FlowDiffuser.estimate_flow_clip` returns.  Every pixel of frame `start` is followed to frame `stop` (None: T; smaller than start:
+    a walk back, which steps by bwd) by composing the flows: each is read bilinearly where the track has got to.  disp
+    (B, n + 1, 2, H, W) with n = |stop - start|: [:, i] is where the pixel is on arrival at the i-th frame of the walk, minus where it
+    started; [:, 0] = 0.  state (B, n + 1, 1, H, W), uint8: STATE_HELD (0, tracked) while the track lives; the step that ends it
+    leaves STATE_INVALID (a non-finite flow under the track), STATE_LEAVES_FRAME, and with the check on STATE_UNMATCHED (a non-finite
+    flow under the point reached) or STATE_INCONSISTENT (the step's round trip by the other direction misses by more than
+    a1 * (|v|^2 + |g|^2) + a2 allows, `flow_consistency`'s bound: the pixel is occluded in the next frame).  A dead track keeps its
+    state and has NaN in disp from then on.  life (B, 1, H, W), int32: the steps completed alive.  check: None checks if the other
+    direction was given; True needs it.  all_steps=False keeps only the last slot: disp (B, 1, 2, H, W).  This is not
+    `integrate_flow`, which walks one steady field.  The defaults a1, a2 are UnFlow's and untuned with trained weights; drift over
+    long clips with real estimated flows is unmeasured.  One launch; forward only; inputs are not modified; the same input gives the
+    same bits.  Semantics: include/ofd.h."""
+    B, T, H, W = _chain_flows("chain_flows", fwd, bwd, need_bwd=False)
+    start = _loop_int("chain_flows", "start", start, 0, T)
+    stop = T if stop is None else _loop_int("chain_flows", "stop", stop, 0, T)
+    ahead = stop >= start
+    other = bwd if ahead else fwd
+    check = _chain_check("chain_flows", check, bwd is not None)
+    if not isinstance(all_steps, bool):
+        raise ValueError(f"chain_flows: all_steps must be True or False, got {all_steps!r}")
+    if not ahead and bwd is None:
+        raise ValueError(f"chain_flows: a walk back from frame {start} to frame {stop} steps by bwd, which was not given")
+    if check and other is None:
+        raise ValueError("chain_flows: check=True needs the flows of the other direction (bwd)")
+    par = consistency_params(a1, a2, name="chain_flows")
+    _chain_ready("chain_flows", fwd, bwd)
+    n = abs(stop - start)
+    slots = n + 1 if all_steps else 1
+    with torch.no_grad():
+        fwd, bwd = L.f32c(fwd), None if bwd is None else L.f32c(bwd)
+        dev = fwd.device
+        disp = torch.empty(B, slots, 2, H, W, dtype=torch.float32, device=dev)
+        state = torch.empty(B, slots, 1, H, W, dtype=torch.uint8, device=dev)
+        life = torch.empty(B, 1, H, W, dtype=torch.int32, device=dev)
+        L.check(L.lib().ofd_flow_chain(L.ptr(fwd), L.ptr(bwd), L.ptr(disp), L.ptr(state), L.ptr(life), B, T, H, W, start, stop, int(check),
+                                       par["a1"], par["a2"], int(all_steps), L.stream()))
+    return FlowChain(disp, state, life)
+
+
+def chain_flows_to(fwd, bwd, anchor=0, check=True, a1=0.01, a2=0.5):
+    """Where every pixel of every frame of a clip lies in one anchor frame (not in the reference): (disp (B, T + 1, 2, H, W), state
+    (B, T + 1, 1, H, W) uint8).  fwd, bwd as for `chain_flows`.  [:, t] is, for each pixel of frame t, its displacement into frame
+    `anchor` after the |t - anchor| steps towards it and the state that walk ended in -- the last slot of
+    `chain_flows(fwd, bwd, start=t, stop=anchor, check=check, a1=a1, a2=a2)`, bit for bit; NaN where the track died (it is occluded
+    somewhere on the way, leaves the frame, or meets a non-finite flow).  [:, anchor] is 0.  It is what `composite_layer` takes.  One
+    `ofd_flow_chain_to` call per at most flow_diffuser.ANIMATE_MAX_PIXELS pixels of output, over samples first and then over frames;
+    chunked or not, the bits are the same.  The defaults a1, a2 are UnFlow's and untuned with trained weights; drift over long clips
+    with real estimated flows is unmeasured.  Forward only; inputs are not modified.  Semantics: include/ofd.h."""
+    from .flow_diffuser import ANIMATE_MAX_PIXELS
+    B, T, H, W = _chain_flows("chain_flows_to", fwd, bwd)
+    anchor = _loop_int("chain_flows_to", "anchor", anchor, 0, T)
+    if not isinstance(check, bool):
+        raise ValueError(f"chain_flows_to: check must be True or False, got {check!r}")
+    par = consistency_params(a1, a2, name="chain_flows_to")
+    _chain_ready("chain_flows_to", fwd, bwd)
+    N = T + 1
+    with torch.no_grad():
+        fwd, bwd = L.f32c(fwd), L.f32c(bwd)
+        per = max(1, ANIMATE_MAX_PIXELS // (H * W))                          # frames per call
+        nt, nb = min(N, per), max(1, per // N)
+        disp = torch.empty(B, N, 2, H, W, dtype=torch.float32, device=fwd.device)
+        state = torch.empty(B, N, 1, H, W, dtype=torch.uint8, device=fwd.device)
+        lib = L.lib()
+        for b0 in range(0, B, nb):
+            cb = min(nb, B - b0)
+            for t0 in range(0, N, nt):
+                ct = min(nt, N - t0)                                         # ct == N: whole samples, contiguous in the result
+                d = disp[b0:b0 + cb] if ct == N else disp[b0:b0 + 1, t0:t0 + ct]
+                s = state[b0:b0 + cb] if ct == N else state[b0:b0 + 1, t0:t0 + ct]
+                L.check(lib.ofd_flow_chain_to(L.ptr(fwd[b0:b0 + cb]), L.ptr(bwd[b0:b0 + cb]), L.ptr(d), L.ptr(s), cb, T, H, W, anchor, t0, ct,
+                                              int(check), par["a1"], par["a2"], L.stream()))
+    return disp, state
+
+
+def composite_layer(frames, layer, disp, premultiplied=True):
+    """A layer painted on one frame, laid over every frame of a clip where that frame's pixels come from (not in the reference): a new
+    fp32 (B, n, C, H, W) tensor.  frames: (B, n, C, H, W), C <= 8; layer: (B, C + 1, H, W), colour with alpha last, in the anchor
+    frame's coordinates; disp: (B, n, 2, H, W) in pixels, each pixel's displacement into the anchor frame, e.g. `chain_flows_to`'s.
+    Where disp is finite and p + disp is inside the frame, out = frame * (1 - A) + L with A and L the layer read bilinearly at
+    p + disp; elsewhere -- the track died, so the pixel is not known to be on the painted surface -- out is the frame, bit for bit.  A
+    gather: no holes.  premultiplied=True: the layer's colour is already multiplied by its alpha; False: that product is made here
+    first, in torch.  One launch; forward only; inputs are not modified; the same input gives the same bits.  Semantics:
+    include/ofd.h (`ofd_layer_composite`)."""
+    if not torch.is_tensor(frames) or frames.dim() != 5 or frames.numel() == 0 or not 1 <= frames.shape[2] <= 8:
+        raise ValueError(f"composite_layer: frames must be a non-empty (B, n, C, H, W) tensor with 1 <= C <= 8, got {_shape_of(frames)}")
+    B, n, C, H, W = frames.shape
+    if max(H, W) > 32768 or n > 4097:
+        raise ValueError(f"composite_layer: H and W must be at most 32768 and n at most 4097, got {tuple(frames.shape)}")
+    if not torch.is_tensor(layer) or tuple(layer.shape) != (B, C + 1, H, W):
+        raise ValueError(f"composite_layer: layer must be (B, C + 1, H, W) = {(B, C + 1, H, W)}, got {_shape_of(layer)}")
+    if not torch.is_tensor(disp) or tuple(disp.shape) != (B, n, 2, H, W):
+        raise ValueError(f"composite_layer: disp must be (B, n, 2, H, W) = {(B, n, 2, H, W)}, got {_shape_of(disp)}")
+    if not all(t.is_floating_point() for t in (frames, layer, disp)):
+        raise ValueError(f"composite_layer: frames, layer and disp must be floating-point tensors, got "
+                         f"{[t.dtype for t in (frames, layer, disp)]}")
+    if not isinstance(premultiplied, bool):
+        raise ValueError(f"composite_layer: premultiplied must be True or False, got {premultiplied!r}")
+    _chain_ready("composite_layer", frames, layer, disp)
+    with torch.no_grad():
+        frames, layer, disp = L.f32c(frames), L.f32c(layer), L.f32c(disp)
+        if not premultiplied:
+            layer = torch.cat((layer[:, :C] * layer[:, C:], layer[:, C:]), dim=1)
+        out = torch.empty_like(frames)
+        L.check(L.lib().ofd_layer_composite(L.ptr(frames), L.ptr(layer), L.ptr(disp), L.ptr(out), B, n, C, H, W, L.stream()))
+    return out
+
+
 # ---- guided weighted median of a flow (not in the reference; semantics: include/ofd.h, `ofd_flow_median`) ----------------------------
 def median_params(radius=2, sigma_s=2.0, sigma_r=0.1, iterations=1, fill=False, name="median_filter_flow"):
     """the rules of the median's window, widths and passes (ValueError); host logic, no engine call"""
