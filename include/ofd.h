@@ -32,6 +32,7 @@
  *   (not in the reference)            forward-backward check of a flow pair -> ofd_flow_consistency
  *   (not in the reference)            tracks through a clip's flows, layer propagation -> ofd_flow_chain, ofd_flow_chain_to, ofd_layer_composite
  *   (not in the reference)            guided weighted median of a flow  -> ofd_flow_median
+ *   (not in the reference)            global motion of a flow: robust fit, split, render -> ofd_motion_fit, ofd_motion_field, ofd_homography_warp
  *   denoising_diffusion.py:806-812    q_sample                          -> ofd_q_sample
  *   denoising_diffusion.py:844-879,985-993  p_losses noise / target     -> ofd_diffusion_prep
  *   denoising_diffusion.py:73-77      (un)normalize                     -> ofd_range_map
@@ -355,6 +356,83 @@ int ofd_flow_chain_to(const float* fwd, const float* bwd, float* disp, uint8_t* 
                       int use_check, float a1, float a2, void* stream);
 int ofd_layer_composite(const float* frames, const float* layer, const float* disp, float* out, int B, int n, int C, int H, int W,
                         void* stream);
+
+/* Global motion of a flow: a robust parametric fit of the motion most pixels share (the camera's), the split of a flow into that motion
+ * and the rest, and the render of a frame through a homography (Odobez & Bouthemy 1995; Black & Anandan 1996).  An addition: the
+ * reference treats a flow as one field.  flow: (B,2,H,W) in pixels, channel 0 = x, a pixel p of the frame moves to p + flow(p); conf:
+ * (B,1,H,W) or NULL (every confidence 1).  All arithmetic of the fit and the field is double, every operation rounded on its own (no
+ * contraction), in the order written here; brackets are as written and a chain without brackets runs left to right.
+ *   M1. Coordinates.  cx = (W-1)/2, cy = (H-1)/2, s = max(W-1, H-1, 1)/2.  For the pixel (x, y) with the flow (u, v):
+ *       xn = (x - cx)/s, yn = (y - cy)/s, un = u/s, vn = v/s.  The P = 2, 4, 6, 8 parameters p of model 0, 1, 2, 3 are in these
+ *       coordinates; all-zero parameters are zero flow.
+ *   M2. Model displacement (mu, mv) and denominator D at the parameters p:
+ *       0 translation  mu = p0, mv = p1, D = 1.
+ *       1 similarity   mu = (p0 + p2*xn) - p3*yn,  mv = (p1 + p3*xn) + p2*yn,  D = 1.
+ *       2 affine       mu = (p0 + p2*xn) + p3*yn,  mv = (p1 + p4*xn) + p5*yn,  D = 1.
+ *       3 homography   D = (1 + p6*xn) + p7*yn,  mu = (((xn + p0) + p2*xn) + p3*yn)/D - xn,  mv = (((yn + p1) + p4*xn) + p5*yn)/D - yn.
+ *   M3. Design rows of a pixel, against un (Jx) and vn (Jy), with x' = xn + un, y' = yn + vn:
+ *       homography  Jx = [1, 0, xn, yn, 0, 0, -(xn*x'), -(yn*x')],  Jy = [0, 1, 0, 0, xn, yn, -(xn*y'), -(yn*y')];
+ *       affine      their first six entries;  similarity  Jx = [1, 0, xn, -yn], Jy = [0, 1, yn, xn];  translation  Jx = [1, 0], Jy = [0, 1].
+ *       The 0 entries are static: a product with one of them is not formed.
+ *   M4. Weight.  A pixel is usable when u, v and its confidence c are finite and c > 0; any other pixel has weight 0, is not counted and
+ *       is not read further.  ex = (un - mu)*s, ey = (vn - mv)*s, r2 = ex*ex + ey*ey (pixels squared).  Solve 0: w = c.  Every later
+ *       solve, at the parameters the solve before left: g = 1 + r2/(sigma*sigma), rho = 1/(g*g) (Geman-McClure), w = (c*rho)/(D*D).
+ *       A usable pixel whose D is not > 0, or whose w or r2 is not finite, is counted and adds nothing else in that solve.
+ *   M5. Sums.  Per sample and solve, over the usable pixels: a_ij = sum of (w*Jx[i])*Jx[j] + (w*Jy[i])*Jy[j] for i <= j (one product
+ *       where the other is statically zero), b_i = sum of (w*Jx[i])*un + (w*Jy[i])*vn (likewise), sum w, sum w*r2, and the count
+ *       (sum of 1.0): P(P+1)/2 + P + 3 values, 47 at P = 8.  Each is a double sum of the per-pixel terms in a fixed order: a thread adds its
+ *       pixels' terms in ascending address from +0.0 (thread t of the sample's workgroup g takes the units g*256 + t, + wps*256, ...;
+ *       a unit is 4 neighbouring pixels where H*W % 4 == 0 and flow and conf are 16-byte aligned, one pixel otherwise; a sample has
+ *       wps = min(ceil(units / 256), 128) workgroups, a number that depends on the frame and the alignment and never on B), the workgroup's
+ *       256 values go through the waves-then-four-slots order of ofd_nan_mse_rows' partials, and the partials g = 0, 1, ... are added
+ *       in ascending order from +0.0.  No atomics, no float accumulation: the same input gives the same bits, run to run.  The order
+ *       depends on the alignment; where every sum is exact it cannot matter.  It does not depend on B or on the sample's place in
+ *       the call: a sample fitted alone, or in a chunk of a longer call, has the bits it has in the whole call, at the same alignment
+ *       (which slices of one array share when H*W % 4 == 0).
+ *   M6. Solve, of A p = b with A the symmetric matrix of the a_ij: the square-root-free Cholesky factorisation A = L diag(d) L^T (L unit
+ *       lower triangular) and two triangular solves.  amax = the largest a_ii.  For j = 0 .. P-1: t_k = L[j][k]*d_k and
+ *       d_j = a_jj - L[j][0]*t_0 - ... - L[j][j-1]*t_{j-1} (each product subtracted in turn, k ascending); the sample is DEGENERATE if
+ *       d_j <= 1e-12 * amax or d_j is not finite; for i = j+1 .. P-1: L[i][j] = (a_ji - L[i][0]*t_0 - ... - L[i][j-1]*t_{j-1}) / d_j.
+ *       Then z_i = b_i - L[i][0]*z_0 - ... - L[i][i-1]*z_{i-1} for i = 0 .. P-1; y_i = z_i / d_i; p_i = y_i - L[i+1][i]*p_{i+1} - ... -
+ *       L[P-1][i]*p_{P-1} for i = P-1 .. 0.  A p with a non-finite entry is degenerate too.  (No square root: an integer translation
+ *       on a frame whose s is a power of two is recovered exactly, whatever the weights sum to.)
+ *   M7. ofd_motion_fit solves iterations + 1 times.  A degenerate solve leaves the sample's parameters what they were (zeros, the
+ *       identity, if it is solve 0), and the sample stays degenerate for the remaining solves.  params (B,8): p, the unused tail 0.
+ *       stats (B,4): sum w, sum w*r2 and the count of the LAST solve's sums (they describe the parameters that solve started from;
+ *       with iterations = 0: zero parameters and w = c), and the status, 0 ok / 1 degenerate.
+ *   M8. matrix (B,9), row-major 3x3, written after the last solve: M = N^-1 Hn N scaled to M[2][2] = 1, which maps [x, y, 1] to
+ *       ~[x + u, y + v, 1] in pixels.  Hn = [[a, b, c], [d, e, f], [g, h, 1]] with c = p0, f = p1 and (a, b, d, e, g, h) =
+ *       (1, 0, 0, 1, 0, 0) translation, (1 + p2, -p3, p3, 1 + p2, 0, 0) similarity, (1 + p2, p3, p4, 1 + p5, 0, 0) affine,
+ *       (1 + p2, p3, p4, 1 + p5, p6, p7) homography.  gs = g/s, hs = h/s, k = 1 - (g*cx + h*cy)/s;
+ *       M = [[a + cx*gs, b + cx*hs, (s*c - (a*cx + b*cy)) + cx*k], [d + cy*gs, e + cy*hs, (s*f - (d*cx + e*cy)) + cy*k], [gs, hs, k]],
+ *       every entry then divided by k.  Zero parameters give the identity exactly.  If k is 0 or an entry is not finite, the matrix
+ *       is the identity and the status 1.
+ *   M9. A matrix M at the pixel (x, y): D = (M6*x + M7*y) + M8, X = ((M0*x + M1*y) + M2)/D, Y = ((M3*x + M4*y) + M5)/D, in double; the
+ *       position is valid when D is finite and > 0.
+ *       ofd_motion_field: model_flow = ((float)(X - x), (float)(Y - y)), NaN in both where the position is not valid.  residual =
+ *       flow - model_flow, one fp32 subtraction; NaN propagates.  weight = (float)(c * rho) with rho of M4 from r2 = rx*rx + ry*ry of the
+ *       fp32 residual taken in double; 0 where the residual or c is not finite or c <= 0.  flow == NULL (then conf, residual and
+ *       weight must be NULL too) only synthesises the flow of the matrix.  One elementwise launch.
+ *       ofd_homography_warp: img, out (B,C,H,W), 1 <= C <= 8; matrix maps an OUTPUT pixel to the source position (X, Y) it is read
+ *       from; inside (B,1,H,W) or NULL.  Where the position is valid and 0 <= X <= W-1 and 0 <= Y <= H-1 (false for NaN): x0 = floor(X)
+ *       in double, tx = (float)(X - x0), x1 = min(x0 + 1, W-1), likewise in y, and out_c = (1-ty) * ((1-tx) * g00 + tx * g01) + ty *
+ *       ((1-tx) * g10 + tx * g11) in fp32, ofd_flow_chain's read; inside = 1.  Elsewhere out = +0.0 and inside = 0.  A position becomes
+ *       an index only after that test; a pixel outside reads offset 0 of its plane and drops it.  One launch in ofd_layer_composite's
+ *       tile and thread layout; no LDS, no atomics.
+ * ofd_motion_fit enqueues 2 * (iterations + 1) launches and makes no host synchronisation; ws is ofd_motion_fit_ws_doubles(B, H, W)
+ * doubles of device scratch, B * min(ceil(H*W / 256), 128) * 47: it grows with B, so the workspace of a call serves any call of
+ * fewer samples.  H, W <= 32768; every array < 2^40 elements; model 0..3; 0 <= iterations <= 64; sigma finite and > 0;
+ * outputs must not alias inputs or each other.  Argument errors return OFD_ERR_ARG and set ofd_last_error before any GPU work.  The fit
+ * follows the majority: it breaks down as the outliers near half the weight, and a degenerate status is the only failure it reports.
+ * Compulsory traffic: the fit 4 * B * H * W * 2 (3 with conf) bytes per solve; the field 4 * B * H * W * (2 .. 8); the warp
+ * 4 * B * H * W * (2 C + 1).  Measured (tools/motion_bench.py), no model's pass is bound by HBM: 1.8 TB/s (translation) to 0.5 TB/s
+ * (homography) over these bytes at 16 x 440 x 1024. */
+size_t ofd_motion_fit_ws_doubles(int B, int H, int W);
+int ofd_motion_fit(const float* flow, const float* conf, int B, int H, int W, int model, int iterations, float sigma, double* params,
+                   double* matrix, double* stats, double* ws, void* stream);
+int ofd_motion_field(const double* matrix, const float* flow, const float* conf, float sigma, float* model_flow, float* residual,
+                     float* weight, int B, int H, int W, void* stream);
+int ofd_homography_warp(const float* img, const double* matrix, float* out, float* inside, int B, int C, int H, int W, void* stream);
 
 /* ------------------------------------------------------------ grid_sample warp (WP:95-119) -
  * second: (B,C,H,W), flow: (B,2,H,W) exactly as handed to the reference's warp(mode='backward'):

@@ -21,8 +21,9 @@ import torch
 
 from .denoising_diffusion import UNSET, PhotoGuide, Unet, ConditionalDiffusion, loss_by_timestep
 from .ema import EMA_DEFAULTS, EmaMixin, ema_optimizer_kwargs
-from .warp import (box_reduce, chain_flows, chain_flows_to, composite_layer, consistency_params, flow_consistency, interpolate_frames,
-                   loop_frames, loop_params, median_filter_flow, median_params, upsample_flow, upsample_params, warp)
+from .warp import (STATE_HELD, box_reduce, chain_flows, chain_flows_to, composite_layer, consistency_params, fit_motion, flow_consistency,
+                   interpolate_frames, loop_frames, loop_params, median_filter_flow, median_params, motion_params, path_params,
+                   stabilize_clip, upsample_flow, upsample_params, warp)
 from . import _lib as L
 
 try:                                                   # pragma: no cover - not installed in this image
@@ -781,6 +782,42 @@ class FlowDiffuser(EmaMixin, _Base):
             fwd, bwd = self.estimate_flow_clip(clip, **sample_kw)
         disp, _state = chain_flows_to(fwd, bwd, anchor=anchor, check=check, a1=par["a1"], a2=par["a2"])
         return composite_layer(clip, layer, disp, premultiplied=premultiplied), fwd, bwd
+
+    def camera_motion(self, frame1, frame2, flow=None, model="affine", conf=None, iterations=6, sigma=1.0, **sample_kw):
+        """The camera's motion between two frames, and what moves relative to it (not in the reference): the `warp.MotionFit` of
+        `warp.fit_motion(flow, model, conf, iterations, sigma)`, which has the method.  frame1, frame2: (B, 3, H, W) in cond's range.
+        flow: (B, 2, H, W) IN PIXELS as `estimate_flow` returns it, or None: it then comes from `estimate_flow(frame1, frame2,
+        **sample_kw)`.  With the flow given no UNet call is made, the frames are not looked at and sample_kw is an error.  The fit's
+        defaults are untuned on real footage.  Forward only."""
+        par = motion_params(model, iterations, sigma, name="camera_motion")
+        if flow is not None and sample_kw:
+            raise ValueError(f"camera_motion: {sorted(sample_kw)} are sampling arguments; with the flow given nothing is sampled")
+        if flow is None:
+            if not self.is_diffusion:
+                raise ValueError("camera_motion: estimating the flow needs a diffusion model (estimate_flow); pass flow")
+            flow = self.estimate_flow(frame1, frame2, **sample_kw)
+        return fit_motion(flow, model=model, conf=conf, iterations=par["iterations"], sigma=par["sigma"])
+
+    def stabilize(self, clip, fwd=None, bwd=None, refine=0, model="similarity", mode="smooth", sigma_t=4.0, anchor=0, iterations=6, sigma=1.0,
+                  a1=0.01, a2=0.5, **sample_kw):
+        """A clip held still, or its camera path smoothed (not in the reference): (video, inside, fwd, bwd), video and inside those of
+        `warp.stabilize_clip(clip, fwd, conf, model, mode, sigma_t, anchor, iterations, sigma)`, which has the method.  clip:
+        (B, T + 1, 3, H, W) in cond's range.  fwd, bwd: (B, T, 2, H, W) IN PIXELS as `estimate_flow_clip` returns them, both or
+        neither.  Neither: they come from `estimate_flow_clip(clip, refine=refine, **sample_kw)`.  Both: no UNet call is made, and
+        sample_kw is an error.  conf is 1 on the pixels of fwd that `warp.flow_consistency(fwd, bwd, a1, a2)` holds and 0 elsewhere:
+        occluded pixels do not vote for the camera.  The defaults are untuned on real footage.  Forward only."""
+        T = self._clip_flows("stabilize", clip, fwd, bwd, sample_kw)
+        if isinstance(refine, bool) or not isinstance(refine, int) or not 0 <= refine <= 16:
+            raise ValueError(f"stabilize: refine must be an integer in 0..16, got {refine!r}")
+        par, path = motion_params(model, iterations, sigma, name="stabilize"), path_params(T, mode, sigma_t, anchor, "stabilize")
+        check = consistency_params(a1, a2, name="stabilize")
+        if fwd is None:
+            fwd, bwd = self.estimate_flow_clip(clip, refine=refine, **sample_kw)
+        B, _, _, H, W = fwd.shape
+        held = flow_consistency(fwd.reshape(B * T, 2, H, W), bwd.reshape(B * T, 2, H, W), a1=check["a1"], a2=check["a2"]).state12
+        conf = (held == STATE_HELD).float().reshape(B, T, 1, H, W)
+        video, inside, _matrices, _path = stabilize_clip(clip, fwd, conf, model=model, iterations=par["iterations"], sigma=par["sigma"], **path)
+        return video, inside, fwd, bwd
 
     @staticmethod
     def _batch_stats(x):

@@ -7,6 +7,7 @@ rep='filter' (FlowLearner / MatrixFlow only) is outside the FlowDiffuser path an
 """
 import collections
 import ctypes
+import math
 
 import torch
 
@@ -527,11 +528,11 @@ def _chain_flows(name, fwd, bwd, need_bwd=True):
     return B, T, H, W
 
 
-def _chain_ready(name, *tensors):
+def _chain_ready(name, *tensors, what="the walk has"):
     """forward only, GPU only, one device: the rules that come after the host-only ones"""
     given = [t for t in tensors if t is not None]
     if any(t.requires_grad for t in given):
-        raise L.OfdError(f"{name}: forward only (the walk has no backward pass): detach the inputs")
+        raise L.OfdError(f"{name}: forward only ({what} no backward pass): detach the inputs")
     L.require_gpu(*given)
     if any(t.device != given[0].device for t in given):
         raise ValueError(f"{name}: all tensors must be on one device, got {[str(t.device) for t in given]}")
@@ -654,6 +655,236 @@ def composite_layer(frames, layer, disp, premultiplied=True):
         out = torch.empty_like(frames)
         L.check(L.lib().ofd_layer_composite(L.ptr(frames), L.ptr(layer), L.ptr(disp), L.ptr(out), B, n, C, H, W, L.stream()))
     return out
+
+
+# ---- global motion of a flow: robust fit, split, render, camera path (not in the reference; semantics: include/ofd.h, `ofd_motion_fit`) ----
+MOTION_MODELS = ("translation", "similarity", "affine", "homography")
+
+
+class MotionFit(collections.namedtuple("MotionFit", "matrix params stats model_flow residual weight")):
+    """what `fit_motion` returns; `degenerate` is a (B,) bool tensor, True where the fit had no solution and the matrix is what the
+    last good solve left (the identity if none)"""
+    __slots__ = ()
+
+    @property
+    def degenerate(self):
+        return self.stats[:, 3] != 0
+
+
+def motion_params(model="affine", iterations=6, sigma=1.0, name="fit_motion"):
+    """the rules of the fit's model, rounds and scale (ValueError); host logic, no engine call"""
+    if not isinstance(model, str) or model not in MOTION_MODELS:
+        raise ValueError(f"{name}: model must be one of {MOTION_MODELS}, got {model!r}")
+    if isinstance(sigma, bool) or not isinstance(sigma, (int, float)) or not 0.0 < sigma < float("inf"):      # false for NaN
+        raise ValueError(f"{name}: sigma must be a finite number > 0 (the residual, in pixels, at which a pixel's weight is 1/4), got {sigma!r}")
+    return dict(model=MOTION_MODELS.index(model), iterations=_loop_int(name, "iterations", iterations, 0, 64), sigma=float(sigma))
+
+
+def _motion_flow_conf(name, flow, conf):
+    """the shape and dtype rules of a flow and its confidence -> (B, H, W)"""
+    if not torch.is_tensor(flow) or flow.dim() != 4 or flow.shape[1] != 2 or flow.numel() == 0:
+        raise ValueError(f"{name}: flow must be a non-empty (B, 2, H, W) tensor, got {_shape_of(flow)}")
+    B, _, H, W = flow.shape
+    if max(H, W) > 32768:
+        raise ValueError(f"{name}: H and W must be at most 32768, got {tuple(flow.shape)}")
+    if conf is not None and (not torch.is_tensor(conf) or tuple(conf.shape) != (B, 1, H, W)):
+        raise ValueError(f"{name}: conf must be (B, 1, H, W) = {(B, 1, H, W)} or None, got {_shape_of(conf)}")
+    given = [t for t in (flow, conf) if t is not None]
+    if not all(t.is_floating_point() for t in given):
+        raise ValueError(f"{name}: flow and conf must be floating-point tensors, got {[t.dtype for t in given]}")
+    return B, H, W
+
+
+def _motion_matrix(name, matrix, B=None):
+    if not torch.is_tensor(matrix) or matrix.dim() != 3 or tuple(matrix.shape[1:]) != (3, 3) or matrix.numel() == 0 or \
+            (B is not None and matrix.shape[0] != B) or not matrix.is_floating_point():
+        want = "a non-empty (B, 3, 3) floating-point tensor" if B is None else f"a ({B}, 3, 3) floating-point tensor"
+        raise ValueError(f"{name}: matrix must be {want}, got {_shape_of(matrix)}")
+
+
+def _motion_ready(name, *tensors):
+    _chain_ready(name, *tensors, what="the fit, the field and the warp have")
+
+
+def _motion_fit(flow, conf, par, per_call=None):
+    """ofd_motion_fit on prepared fp32 tensors, at most per_call samples per call -> (matrix (B, 3, 3), params, stats), float64"""
+    B, _, H, W = flow.shape
+    dev, lib = flow.device, L.lib()
+    matrix = torch.empty(B, 3, 3, dtype=torch.float64, device=dev)
+    params = torch.empty(B, 8, dtype=torch.float64, device=dev)
+    stats = torch.empty(B, 4, dtype=torch.float64, device=dev)
+    nb = B if per_call is None else per_call
+    ws = torch.empty(lib.ofd_motion_fit_ws_doubles(min(nb, B), H, W), dtype=torch.float64, device=dev)
+    for b0 in range(0, B, nb):
+        cb = min(nb, B - b0)
+        L.check(lib.ofd_motion_fit(L.ptr(flow[b0:b0 + cb]), None if conf is None else L.ptr(conf[b0:b0 + cb]), cb, H, W, par["model"],
+                                   par["iterations"], par["sigma"], L.ptr(params[b0:b0 + cb]), L.ptr(matrix[b0:b0 + cb]),
+                                   L.ptr(stats[b0:b0 + cb]), L.ptr(ws), L.stream()))
+    return matrix, params, stats
+
+
+def fit_motion(flow, model="affine", conf=None, iterations=6, sigma=1.0):
+    """The motion most pixels of a flow share -- the camera's -- by a robust parametric fit (Odobez & Bouthemy 1995, Black & Anandan
+    1996; not in the reference): a `MotionFit` (matrix, params, stats, model_flow, residual, weight).  flow: (B, 2, H, W) IN PIXELS,
+    channel 0 = x, what `FlowDiffuser.estimate_flow` returns; conf: (B, 1, H, W), a confidence per vector, or None; a pixel whose
+    flow or conf is not finite, or whose conf is <= 0, does not vote.  model: "translation", "similarity", "affine" or "homography"
+    (2, 4, 6, 8 parameters).  The fit is iteratively reweighted least squares: `iterations` + 1 solves, the first weighted by conf
+    alone, every later one by conf times the Geman-McClure weight 1 / (1 + r^2 / sigma^2)^2 of the pixel's residual r against the
+    model of the solve before.  matrix (B, 3, 3) float64 maps [x, y, 1] to ~[x + u, y + v, 1] in pixels; params (B, 8) float64 are
+    the model's parameters in frame-normalised coordinates; stats (B, 4) float64 are sum w, sum w r^2, the voting pixels and the
+    status (`.degenerate`: no solution, e.g. no voting pixel; the matrix is then the identity).  model_flow (B, 2, H, W) is the
+    matrix's flow, residual = flow - model_flow -- what moves relative to the background -- and weight (B, 1, H, W) = conf times the
+    weight of that residual, near 1 on the background and near 0 on what moves by itself.  The fit follows the majority: it breaks
+    down as the outliers near half the weight.  The defaults come from a synthetic block scene and are untuned on real footage.
+    No host synchronisation; forward only; inputs are not modified; the same input gives the same bits.  Semantics: include/ofd.h."""
+    B, H, W = _motion_flow_conf("fit_motion", flow, conf)
+    par = motion_params(model, iterations, sigma)
+    _motion_ready("fit_motion", flow, conf)
+    with torch.no_grad():
+        flow, conf = L.f32c(flow), None if conf is None else L.f32c(conf)
+        matrix, params, stats = _motion_fit(flow, conf, par)
+        model_flow, residual = torch.empty_like(flow), torch.empty_like(flow)
+        weight = torch.empty(B, 1, H, W, dtype=torch.float32, device=flow.device)
+        L.check(L.lib().ofd_motion_field(L.ptr(matrix), L.ptr(flow), L.ptr(conf), par["sigma"], L.ptr(model_flow), L.ptr(residual),
+                                         L.ptr(weight), B, H, W, L.stream()))
+    return MotionFit(matrix, params, stats, model_flow, residual, weight)
+
+
+def motion_flow(matrix, H, W):
+    """The flow of a matrix (not in the reference): (B, 2, H, W) fp32 in pixels, M [x, y, 1] - [x, y], computed in double and rounded
+    once; NaN where the projective denominator is not > 0.  matrix: (B, 3, 3), e.g. `fit_motion`'s.  One launch; forward only."""
+    _motion_matrix("motion_flow", matrix)
+    H, W = _loop_int("motion_flow", "H", H, 1, 32768), _loop_int("motion_flow", "W", W, 1, 32768)
+    _motion_ready("motion_flow", matrix)
+    with torch.no_grad():
+        matrix = matrix.double().contiguous()
+        out = torch.empty(matrix.shape[0], 2, H, W, dtype=torch.float32, device=matrix.device)
+        L.check(L.lib().ofd_motion_field(L.ptr(matrix), None, None, 1.0, L.ptr(out), None, None, matrix.shape[0], H, W, L.stream()))
+    return out
+
+
+def warp_homography(img, matrix):
+    """An image read through a homography (not in the reference): (out (B, C, H, W) fp32, inside (B, 1, H, W) fp32).  img: (B, C, H, W),
+    C <= 8; matrix: (B, 3, 3), which sends every OUTPUT pixel to the place in img it is read from (bilinear, positions in double).
+    Where that place is outside the frame out is 0 and inside 0; elsewhere inside is 1.  A gather: no holes.  One launch; forward
+    only; inputs are not modified; the same input gives the same bits.  Semantics: include/ofd.h (`ofd_homography_warp`)."""
+    if not torch.is_tensor(img) or img.dim() != 4 or img.numel() == 0 or not 1 <= img.shape[1] <= 8 or not img.is_floating_point():
+        raise ValueError(f"warp_homography: img must be a non-empty floating-point (B, C, H, W) tensor with 1 <= C <= 8, got {_shape_of(img)}")
+    B, C, H, W = img.shape
+    if max(H, W) > 32768:
+        raise ValueError(f"warp_homography: H and W must be at most 32768, got {tuple(img.shape)}")
+    _motion_matrix("warp_homography", matrix, B)
+    _motion_ready("warp_homography", img, matrix)
+    with torch.no_grad():
+        img, matrix = L.f32c(img), matrix.double().contiguous()
+        out, inside = torch.empty_like(img), torch.empty(B, 1, H, W, dtype=torch.float32, device=img.device)
+        L.check(L.lib().ofd_homography_warp(L.ptr(img), L.ptr(matrix), L.ptr(out), L.ptr(inside), B, C, H, W, L.stream()))
+    return out, inside
+
+
+def _mm3(a, b):
+    """(..., 3, 3) @ (..., 3, 3), written out: rows of a times columns of b, k ascending"""
+    return a[..., :, 0, None] * b[..., None, 0, :] + a[..., :, 1, None] * b[..., None, 1, :] + a[..., :, 2, None] * b[..., None, 2, :]
+
+
+def _inv3(m):
+    """the inverse of (..., 3, 3) matrices by the adjugate; exact for integer translations"""
+    a, b, c, d, e, f, g, h, i = (m[..., r, k] for r in range(3) for k in range(3))
+    A, B_, C = e * i - f * h, c * h - b * i, b * f - c * e
+    det = a * A + d * B_ + g * C
+    adj = torch.stack((A, B_, C, f * g - d * i, a * i - c * g, c * d - a * f, d * h - e * g, b * g - a * h, a * e - b * d), -1)
+    return (adj / det[..., None]).reshape(m.shape)
+
+
+def _unit3(m):
+    return m / m[..., 2:, 2:]
+
+
+def path_params(T, mode="smooth", sigma_t=4.0, anchor=0, name="camera_path"):
+    """the rules of a camera path over T matrices (ValueError); host logic, no engine call"""
+    if mode not in ("smooth", "lock"):
+        raise ValueError(f"{name}: mode must be 'smooth' or 'lock', got {mode!r}")
+    if T > 4096:
+        raise ValueError(f"{name}: at most 4096 matrices (4097 frames), got {T}")
+    if isinstance(sigma_t, bool) or not isinstance(sigma_t, (int, float)) or not 0.0 < sigma_t <= 1024.0:   # false for NaN
+        raise ValueError(f"{name}: sigma_t must be a number in (0, 1024] (frames), got {sigma_t!r}")
+    return dict(mode=mode, sigma_t=float(sigma_t), anchor=_loop_int(name, "anchor", anchor, 0, T))
+
+
+def camera_path(matrices, mode="smooth", sigma_t=4.0, anchor=0):
+    """The stabilising transform of every frame of a clip from its frame-to-frame camera motion (Matsushita et al., "Full-frame video
+    stabilization", 2006; not in the reference): (B, T + 1, 3, 3) float64, for every frame t the matrix that sends a pixel of the
+    STABILISED frame to the place in the original frame it is read from -- what `warp_homography` takes.  matrices: (B, T, 3, 3),
+    M_j carries frame j to frame j + 1, e.g. `fit_motion`'s of a clip's forward flows.  With T_t^j the transform from frame t's
+    coordinates to frame j's (the ordered product of the M for j > t, the inverse of that product for j < t, each scaled to
+    [2][2] = 1) and S_t the transform from frame t to its stabilised place, the result is S_t^-1, scaled likewise.
+    mode="lock": S_t = T_t^anchor: the camera of frame `anchor` (0..T) for the whole clip.  mode="smooth": S_t = sum_j g(j - t) T_t^j
+    / sum_j g(j - t) over the frames |j - t| <= ceil(3 sigma_t) that exist, g a Gaussian of width sigma_t frames: the entrywise average
+    of the paper, which removes jitter and keeps a pan.  float64 torch operations on the matrices' device with 3 x 3 products and
+    adjugate inverses written out; no host synchronisation.  sigma_t is untuned on real footage."""
+    if not torch.is_tensor(matrices) or matrices.dim() != 4 or tuple(matrices.shape[2:]) != (3, 3) or matrices.numel() == 0 or \
+            not matrices.is_floating_point():
+        raise ValueError(f"camera_path: matrices must be a non-empty floating-point (B, T, 3, 3) tensor, got {_shape_of(matrices)}")
+    B, T = matrices.shape[:2]
+    par = path_params(T, mode, sigma_t, anchor)
+    if matrices.requires_grad:
+        raise L.OfdError("camera_path: forward only: detach the matrices")
+    with torch.no_grad():
+        M = matrices.double()
+        cum = [torch.eye(3, dtype=torch.float64, device=M.device).expand(B, 3, 3)]         # cum[t]: frame 0 -> frame t
+        for j in range(T):
+            cum.append(_unit3(_mm3(M[:, j], cum[-1])))
+        cum = torch.stack(cum, 1)
+        back = _inv3(cum)                                                                 # frame t -> frame 0
+        if par["mode"] == "lock":
+            S = _unit3(_mm3(cum[:, par["anchor"]:par["anchor"] + 1], back))
+        else:
+            R = min(math.ceil(3.0 * par["sigma_t"]), T)
+            S = torch.zeros_like(cum)
+            for k in range(-R, R + 1):                                                    # j = t + k, over the t for which frame j exists
+                t0, t1 = max(0, -k), min(T, T - k) + 1
+                S[:, t0:t1] += math.exp(-0.5 * (k / par["sigma_t"]) ** 2) * _unit3(_mm3(cum[:, t0 + k:t1 + k], back[:, t0:t1]))
+            S = _unit3(S)                                                                 # every T has [2][2] = 1: S[2][2] is sum_j g(j - t)
+        return _unit3(_inv3(S))
+
+
+def stabilize_clip(clip, fwd, conf=None, model="similarity", mode="smooth", sigma_t=4.0, anchor=0, iterations=6, sigma=1.0):
+    """A clip held still, or its camera path smoothed (Matsushita et al. 2006; not in the reference): (video (B, T + 1, C, H, W) fp32,
+    inside (B, T + 1, 1, H, W) fp32, matrices (B, T, 3, 3) float64, path (B, T + 1, 3, 3) float64).  clip: (B, T + 1, C, H, W),
+    C <= 8; fwd: (B, T, 2, H, W) IN PIXELS, fwd[:, j] carries frame j to frame j + 1 (`FlowDiffuser.estimate_flow_clip`'s); conf:
+    (B, T, 1, H, W) or None.  matrices = `fit_motion(fwd, model, conf, iterations, sigma).matrix` of the B * T flows, path =
+    `camera_path(matrices, mode, sigma_t, anchor)`, video, inside = `warp_homography` of every frame through its path matrix; inside
+    is 0 where a stabilised pixel falls outside its original frame (video is 0 there: nothing is inpainted).  One
+    `ofd_motion_fit` and one `ofd_homography_warp` call per at most flow_diffuser.ANIMATE_MAX_PIXELS pixels; chunked or not, the
+    bits are the same.  The defaults are untuned on real footage.  Forward only; inputs are not modified."""
+    from .flow_diffuser import ANIMATE_MAX_PIXELS
+    if not torch.is_tensor(clip) or clip.dim() != 5 or clip.numel() == 0 or clip.shape[1] < 2 or not 1 <= clip.shape[2] <= 8 or \
+            not clip.is_floating_point():
+        raise ValueError(f"stabilize_clip: clip must be a non-empty floating-point (B, T + 1, C, H, W) tensor with at least two frames and "
+                         f"1 <= C <= 8, got {_shape_of(clip)}")
+    B, N, C, H, W = clip.shape
+    T = N - 1
+    if not torch.is_tensor(fwd) or tuple(fwd.shape) != (B, T, 2, H, W):
+        raise ValueError(f"stabilize_clip: fwd must be (B, T, 2, H, W) = {(B, T, 2, H, W)}, got {_shape_of(fwd)}")
+    if conf is not None and (not torch.is_tensor(conf) or tuple(conf.shape) != (B, T, 1, H, W)):
+        raise ValueError(f"stabilize_clip: conf must be (B, T, 1, H, W) = {(B, T, 1, H, W)} or None, got {_shape_of(conf)}")
+    _motion_flow_conf("stabilize_clip", fwd.reshape(B * T, 2, H, W), None if conf is None else conf.reshape(B * T, 1, H, W))
+    par, path_par = motion_params(model, iterations, sigma, name="stabilize_clip"), path_params(T, mode, sigma_t, anchor, "stabilize_clip")
+    _motion_ready("stabilize_clip", clip, fwd, conf)
+    with torch.no_grad():
+        per = max(1, ANIMATE_MAX_PIXELS // (H * W))                          # flows, frames per call
+        flows = L.f32c(fwd).reshape(B * T, 2, H, W)
+        confs = None if conf is None else L.f32c(conf).reshape(B * T, 1, H, W)
+        matrices = _motion_fit(flows, confs, par, per)[0].reshape(B, T, 3, 3)
+        path = camera_path(matrices, **path_par).contiguous()
+        frames, mats = L.f32c(clip).reshape(B * N, C, H, W), path.reshape(B * N, 9)
+        video = torch.empty_like(frames)
+        inside = torch.empty(B * N, 1, H, W, dtype=torch.float32, device=frames.device)
+        for f0 in range(0, B * N, per):
+            cf = min(per, B * N - f0)
+            L.check(L.lib().ofd_homography_warp(L.ptr(frames[f0:f0 + cf]), L.ptr(mats[f0:f0 + cf]), L.ptr(video[f0:f0 + cf]),
+                                                L.ptr(inside[f0:f0 + cf]), cf, C, H, W, L.stream()))
+    return video.reshape(B, N, C, H, W), inside.reshape(B, N, 1, H, W), matrices, path
 
 
 # ---- guided weighted median of a flow (not in the reference; semantics: include/ofd.h, `ofd_flow_median`) ----------------------------
