@@ -1020,6 +1020,33 @@ int ofd_time_mlp(const int64_t* t, const float* w1, const float* b1, const float
 int ofd_gn_finalize(const float* partial, int B, int H, int W, int C, const float* gamma, const float* beta,
                     const float* ss, int ss_stride, int ss_offset, float* a_out, float* s_out, float* stats_out, void* stream);
 
+/* --------------------------------------------------- the small kernels between them, one launch each (single-op tests) ----
+ * The executor's own launchers behind argument checks; nothing here is a different kernel.
+ * ofd_block_mlp (DD:193-196, 205-208): ss[b][offsets[i] + j] = weights[i][j][:] . temb_silu[b][:] + biases[i][j] for j < n_out[i], every
+ *   ResnetBlock's Linear in ONE launch (grid.y = n_desc).  weights / biases / n_out / offsets are HOST arrays of n_desc entries (device
+ *   pointers in the first two; weights[i] is [n_out[i]][tdim], 16-byte aligned when tdim % 4 == 0); the call uploads them as the kernel's
+ *   descriptor rows and waits for the stream before it returns.  temb_silu [B][tdim], ss [B][ss_stride]; tdim <= 1024; columns of ss
+ *   outside every [offsets[i], offsets[i] + n_out[i]) are not written.
+ * ofd_block_mlp_backward: one ResnetBlock's Linear.  dss [B][ss_stride] (columns [offset, offset + n_out) are read), weight [n_out][tdim];
+ *   dweight [n_out][tdim], dbias [n_out] and dts [B][tdim] are ADDED to (dts by float atomics: every block adds into it).
+ * ofd_time_mlp_backward: t, temb [B][4 dim] as ofd_time_mlp took / wrote them, dts [B][4 dim] = dL/d SiLU(temb); dw1 [4 dim][dim],
+ *   db1 [4 dim], dw2 [4 dim][4 dim], db2 [4 dim] are ADDED to; scratch: ofd_time_mlp_backward_scratch_floats(B, dim) floats.  dim <= 256.
+ * ofd_resblock_out (DD:214, identity res_conv): out = SiLU(h * a[b][c] + s[b][c]) + x, NHWC bf16, a / s [B][C] fp32, C % 8 == 0.
+ * ofd_grad_add: dst = src (accumulate == 0) or dst + src in fp32, rounded once; bf16, elems % 8 == 0.
+ * ofd_pack_input (DD:368): cat(x [B][Cx][H][W], cond [B][Cc][H][W]) fp32 -> NHWC bf16 padded with zeros to cpad = 8, 16, 32 or 48
+ *   channels; ax / ac != 0: the x / cond planes enter as 2 v - 1.  cond may be NULL when Cc == 0. */
+int ofd_block_mlp(const float* temb_silu, const float* const* weights, const float* const* biases, const int* n_out, const int* offsets,
+                  int n_desc, float* ss, int B, int tdim, int ss_stride, void* stream);
+int ofd_block_mlp_backward(const float* dss, const float* temb_silu, const float* weight, int n_out, int offset, float* dweight,
+                           float* dbias, float* dts, int B, int tdim, int ss_stride, void* stream);
+size_t ofd_time_mlp_backward_scratch_floats(int B, int dim);
+int ofd_time_mlp_backward(const int64_t* t, const float* temb, const float* dts, const float* w1, const float* b1, const float* w2,
+                          float* dw1, float* db1, float* dw2, float* db2, float* scratch, int B, int dim, void* stream);
+int ofd_resblock_out(const void* h, const float* a, const float* s, const void* x, void* out, int B, int H, int W, int C, void* stream);
+int ofd_grad_add(void* dst, const void* src, size_t elems, int accumulate, void* stream);
+int ofd_pack_input(const float* x, int Cx, const float* cond, int Cc, void* out, int B, int H, int W, int cpad, int ax, int ac,
+                   void* stream);
+
 /* Batched training augmentation in one pass (replaces the per-sample torchvision pipeline of augmentation.py:6-76 behind
  * FlowDiffuser.preprocess(aug=True), flow_diffuser.py:137-138).  img / tgt (B,3,H,W), flow (B,2,H,W) fp32 NCHW; params (B,16) fp32:
  * 0 jitter on, 1 brightness, 2 contrast, 3 saturation, 4 grayscale on, 5 blur on, 6 sigma, 7 h-flip, 8 v-flip, 9 crop on,

@@ -180,6 +180,13 @@ SIGNATURES = {
     "ofd_layernorm_c": (c_int, [c_void_p] * 4 + [c_size_t, c_int, c_float, c_void_p]),
     "ofd_time_mlp": (c_int, [c_void_p] * 7 + [c_int, c_int, c_void_p]),
     "ofd_gn_finalize": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ofd_block_mlp": (c_int, [c_void_p] * 5 + [c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "ofd_block_mlp_backward": (c_int, [c_void_p] * 3 + [c_int, c_int] + [c_void_p] * 3 + [c_int] * 3 + [c_void_p]),
+    "ofd_time_mlp_backward_scratch_floats": (c_size_t, [c_int, c_int]),
+    "ofd_time_mlp_backward": (c_int, [c_void_p] * 11 + [c_int, c_int, c_void_p]),
+    "ofd_resblock_out": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p]),
+    "ofd_grad_add": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    "ofd_pack_input": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p] + [c_int] * 6 + [c_void_p]),
     "ofd_conv_upsample_phase_weight_prep": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "ofd_conv_weight_prep": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_float, c_int, c_void_p]),
     "ofd_sparse_flow_ws_bytes": (c_size_t, [c_int] * 3),

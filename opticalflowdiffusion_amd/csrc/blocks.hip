@@ -3,6 +3,7 @@
 // channel LayerNorm, LinearAttention (context pass + output pass), flash attention for the mid
 // block and the final 1x1 convolution.
 #include <cstdlib>
+#include <vector>
 #include "blocks.h"
 #include "conv_common.h"      // silu_f
 
@@ -482,3 +483,48 @@ int k_nchw_to_nhwc(const float* x, bf16_t* out, int B, int H, int W, int C, hipS
 }
 
 }  // namespace ofd
+using namespace ofd;
+
+// single launches of the small forward kernels (single-op tests; the backward ones: train_ops.hip)
+extern "C" int ofd_block_mlp(const float* temb_silu, const float* const* weights, const float* const* biases, const int* n_out, const int* offsets,
+                             int n_desc, float* ss, int B, int tdim, int ss_stride, void* stream) {
+    OFD_CHECK_ARG(temb_silu && weights && biases && n_out && offsets && ss, "block_mlp: null argument");
+    OFD_CHECK_ARG(B > 0 && n_desc > 0 && n_desc <= 65535, "block_mlp: B=%d n_desc=%d", B, n_desc);
+    OFD_CHECK_ARG(tdim > 0 && tdim <= 1024, "block_mlp: tdim %d outside 1..1024", tdim);           // block_mlp_kernel's e[1024]
+    std::vector<MlpDesc> descs((size_t)n_desc);
+    for (int i = 0; i < n_desc; ++i) {
+        OFD_CHECK_ARG(weights[i] && biases[i], "block_mlp: null weight or bias in descriptor %d", i);
+        OFD_CHECK_ARG(n_out[i] > 0 && offsets[i] >= 0 && (long)offsets[i] + n_out[i] <= (long)ss_stride,
+                      "block_mlp: descriptor %d writes columns [%d, %d + %d) of a row of %d", i, offsets[i], offsets[i], n_out[i], ss_stride);
+        OFD_CHECK_ARG((tdim & 3) != 0 || ((uintptr_t)weights[i] & 15) == 0, "block_mlp: weight of descriptor %d is not 16-byte aligned", i);
+        descs[i].weight = weights[i];
+        descs[i].bias = biases[i];
+        descs[i].n_out = n_out[i];
+        descs[i].offset = offsets[i];
+    }
+    MlpDesc* d_descs = nullptr;
+    OFD_HIP(hipMalloc(&d_descs, descs.size() * sizeof(MlpDesc)));
+    int rc = OFD_OK;
+    if (hipMemcpy(d_descs, descs.data(), descs.size() * sizeof(MlpDesc), hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("block_mlp: uploading the descriptors failed");
+        rc = OFD_ERR_HIP;
+    }
+    if (rc == OFD_OK) rc = k_block_mlp(temb_silu, d_descs, n_desc, ss, B, tdim, ss_stride, (hipStream_t)stream);
+    if (rc == OFD_OK && hipStreamSynchronize((hipStream_t)stream) != hipSuccess) {       // the table is freed below
+        set_error("block_mlp: the launch failed");
+        rc = OFD_ERR_HIP;
+    }
+    (void)hipFree(d_descs);
+    return rc;
+}
+extern "C" int ofd_resblock_out(const void* h, const float* a, const float* s, const void* x, void* out, int B, int H, int W, int C, void* stream) {
+    OFD_CHECK_ARG(h && a && s && x && out, "resblock_out: null argument");
+    OFD_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, "resblock_out: B=%d H=%d W=%d C=%d", B, H, W, C);
+    return k_resblock_out((const bf16_t*)h, a, s, (const bf16_t*)x, (bf16_t*)out, B, H, W, C, (hipStream_t)stream);
+}
+extern "C" int ofd_pack_input(const float* x, int Cx, const float* cond, int Cc, void* out, int B, int H, int W, int cpad, int ax, int ac,
+                              void* stream) {
+    OFD_CHECK_ARG(x && out && (cond || Cc == 0), "pack_input: null argument");
+    OFD_CHECK_ARG(B > 0 && H > 0 && W > 0 && Cc >= 0, "pack_input: B=%d H=%d W=%d Cc=%d", B, H, W, Cc);
+    return k_pack_input(x, Cx, cond, Cc, (bf16_t*)out, B, H, W, (hipStream_t)stream, cpad, ax, ac);
+}

@@ -620,3 +620,27 @@ extern "C" int ofd_gn_finalize(const float* partial, int B, int H, int W, int C,
     OFD_CHECK_ARG(partial && gamma && beta && a_out && s_out, "gn_finalize: null argument");
     return k_gn_finalize(partial, B, H, W, C, gamma, beta, ss, ss_stride, ss_offset, a_out, s_out, (hipStream_t)stream, stats_out);
 }
+
+// single launches of the time-conditioning backward and the gradient fan-in (single-op tests; the forward ones: blocks.hip)
+extern "C" int ofd_block_mlp_backward(const float* dss, const float* temb_silu, const float* weight, int n_out, int offset, float* dweight,
+                                      float* dbias, float* dts, int B, int tdim, int ss_stride, void* stream) {
+    OFD_CHECK_ARG(dss && temb_silu && weight && dweight && dbias && dts, "block_mlp_backward: null argument");
+    OFD_CHECK_ARG(B > 0 && tdim > 0, "block_mlp_backward: B=%d tdim=%d", B, tdim);
+    OFD_CHECK_ARG(n_out > 0 && offset >= 0 && (long)offset + n_out <= (long)ss_stride,
+                  "block_mlp_backward: columns [%d, %d + %d) of a row of %d", offset, offset, n_out, ss_stride);
+    return k_block_mlp_bwd(dss, temb_silu, weight, n_out, offset, dweight, dbias, dts, B, tdim, ss_stride, (hipStream_t)stream);
+}
+extern "C" size_t ofd_time_mlp_backward_scratch_floats(int B, int dim) {
+    return B > 0 && dim > 0 ? (size_t)B * ((size_t)dim + 3 * 4 * (size_t)dim) : 0;      // per sample { emb[dim] | g1 | dtemb | dz1 } of 4 dim each
+}
+extern "C" int ofd_time_mlp_backward(const int64_t* t, const float* temb, const float* dts, const float* w1, const float* b1, const float* w2,
+                                     float* dw1, float* db1, float* dw2, float* db2, float* scratch, int B, int dim, void* stream) {
+    OFD_CHECK_ARG(t && temb && dts && w1 && b1 && w2 && dw1 && db1 && dw2 && db2 && scratch, "time_mlp_backward: null argument");
+    OFD_CHECK_ARG(B > 0 && dim > 0, "time_mlp_backward: B=%d dim=%d", B, dim);
+    return k_time_mlp_bwd(t, temb, dts, w1, b1, w2, dw1, db1, dw2, db2, scratch, B, dim, (hipStream_t)stream);
+}
+extern "C" int ofd_grad_add(void* dst, const void* src, size_t elems, int accumulate, void* stream) {
+    OFD_CHECK_ARG(dst && src, "grad_add: null argument");
+    OFD_CHECK_ARG(elems > 0 && elems % 8 == 0, "grad_add: %zu elements (units of 8)", elems);
+    return k_grad_add((bf16_t*)dst, (const bf16_t*)src, elems, accumulate, (hipStream_t)stream);
+}
