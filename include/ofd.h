@@ -33,6 +33,7 @@
  *   (not in the reference)            tracks through a clip's flows, layer propagation -> ofd_flow_chain, ofd_flow_chain_to, ofd_layer_composite
  *   (not in the reference)            guided weighted median of a flow  -> ofd_flow_median
  *   (not in the reference)            global motion of a flow: robust fit, split, render -> ofd_motion_fit, ofd_motion_field, ofd_homography_warp
+ *   (not in the reference)            motion layers: K motions of a flow, labels, label vote -> ofd_motion_layers, ofd_motion_assign, ofd_label_vote
  *   denoising_diffusion.py:806-812    q_sample                          -> ofd_q_sample
  *   denoising_diffusion.py:844-879,985-993  p_losses noise / target     -> ofd_diffusion_prep
  *   denoising_diffusion.py:73-77      (un)normalize                     -> ofd_range_map
@@ -423,7 +424,8 @@ int ofd_layer_composite(const float* frames, const float* layer, const float* di
  * doubles of device scratch, B * min(ceil(H*W / 256), 128) * 47: it grows with B, so the workspace of a call serves any call of
  * fewer samples.  H, W <= 32768; every array < 2^40 elements; model 0..3; 0 <= iterations <= 64; sigma finite and > 0;
  * outputs must not alias inputs or each other.  Argument errors return OFD_ERR_ARG and set ofd_last_error before any GPU work.  The fit
- * follows the majority: it breaks down as the outliers near half the weight, and a degenerate status is the only failure it reports.
+ * follows the majority: it breaks down as the outliers near half the weight, and a degenerate status is the only failure it reports
+ * (several motions with no majority: ofd_motion_layers, below).
  * Compulsory traffic: the fit 4 * B * H * W * 2 (3 with conf) bytes per solve; the field 4 * B * H * W * (2 .. 8); the warp
  * 4 * B * H * W * (2 C + 1).  Measured (tools/motion_bench.py), no model's pass is bound by HBM: 1.8 TB/s (translation) to 0.5 TB/s
  * (homography) over these bytes at 16 x 440 x 1024. */
@@ -433,6 +435,67 @@ int ofd_motion_fit(const float* flow, const float* conf, int B, int H, int W, in
 int ofd_motion_field(const double* matrix, const float* flow, const float* conf, float sigma, float* model_flow, float* residual,
                      float* weight, int B, int H, int W, void* stream);
 int ofd_homography_warp(const float* img, const double* matrix, float* out, float* inside, int B, int C, int H, int W, void* stream);
+
+/* Motion layers: the split of a flow into K parametric motions and the pixels that follow each (Wang & Adelson 1994; the multiple-
+ * motions half of Black & Anandan 1996).  An addition: ofd_motion_fit describes ONE motion and follows the majority; a frame with a
+ * camera and two objects, or a parallax scene with no majority, holds several.  flow, conf, the models, coordinates, design rows, a
+ * pixel's weight and the arithmetic (double, every operation rounded on its own, in the order written) are M1 ... M4, unchanged.
+ * Labels are uint8: 0 .. K-1 a layer, OFD_LABEL_OUTLIER = 254 (usable, no layer explains it), OFD_LABEL_INVALID = 255 (not usable).
+ *   L1. Parameters.  1 <= K <= 8 layers; model 0..3; solves T, 0..64; sigma and tau (pixels) finite and > 0; min_support >= 1, raised
+ *       to the model's parameter count P where it is below.  tau2 = tau*tau, sig2 = sigma*sigma, claim2 = (1.5*tau)*(1.5*tau), the
+ *       floats taken in double first.  A pixel is usable as in M4; any other pixel is INVALID everywhere and is not read further.
+ *   L2. Seeds, by peeling translations (in pixels, not normalised).  For k = 0 .. K-1 in turn: the candidates of layer k are the usable
+ *       pixels with (u - tx_j)*(u - tx_j) + (v - ty_j)*(v - ty_j) > claim2 for every live j < k.  Eleven means follow; mean m sums, over
+ *       the candidates, w*u, w*v, w and 1.0 with w = c in mean 0 and w = c * rho in mean 1 .. 10, rho of M4 from r2 = (u - tx_k)*(u - tx_k)
+ *       + (v - ty_k)*(v - ty_k) and tau2 in sigma's place; then tx_k = (sum w*u) / (sum w), ty_k likewise.  The layer is DEAD if the
+ *       count is < min_support, sum w is not finite and > 0, or a mean is not finite; it then stays dead, with zero parameters.  After
+ *       mean 10: params = (tx_k / s, ty_k / s, 0, ...), exact for every model's parameterisation; matrix by M8; stats = (sum w, 0,
+ *       count, status) of mean 10.  The sums are M5's: a thread adds its pixels' terms in ascending address from +0.0, the
+ *       workgroup's values go through the waves-then-four-slots order, the partials are added in ascending order; units, workgroups
+ *       per sample and the alignment rule are M5's.  The candidate test is evaluated from the earlier seeds on the fly.
+ *   L3. T joint solves.  In each, every usable pixel evaluates r2_j and D_j (M2, M4) against every live layer's current parameters.  A
+ *       layer whose D is not > 0 there, or whose r2 is not finite, cannot win the pixel; the pixel's label is the layer of least r2,
+ *       the lowest index among equals; OUTLIER if no layer can win or the least r2 > tau2.  A pixel with label k adds 1.0 to layer
+ *       k's count and, where w = (c * rho(r2_k)) / (D_k * D_k) is finite, M5's terms with that w to layer k's sums, in L2's order
+ *       (the pixels of other labels add nothing).  Each live layer then gets M6's solve.  A layer whose count is < min_support, or
+ *       whose solve is degenerate, keeps its parameters, is dead for every later solve and for ofd_motion_layers' status: 1.  stats
+ *       (B,K,4): sum w, sum w*r2 and the count of the layer's LAST solve (zeros for a layer that was dead before it; with T = 0
+ *       L2's), and the status, 0 live / 1 dead.  params (B,K,8) and matrix (B,K,9) as M7, M8, of every layer, dead ones too (the
+ *       parameters it kept); a matrix that M8 cannot form is the identity and its layer dead.
+ *   L4. Order.  ofd_motion_layers leaves the layers in seed order.  warp.segment_motion orders them by the last solve's count,
+ *       descending, the lower index first among equals, dead layers last (a stable device sort and gathers: no kernel).
+ *   L5. ofd_motion_assign, against pixel matrices (M9), one elementwise launch: for each layer j with alive[j] != 0 (all, if alive is
+ *       NULL), (mx, my) = ((float)(X - x), (float)(Y - y)), (rx, ry) = (u - mx, v - my) in fp32, r2 = rx*rx + ry*ry with the fp32
+ *       residual taken in double.  A layer whose position is not valid or whose r2 is not finite cannot win.  The label is the layer
+ *       of least r2, the lowest index among equals; OUTLIER if none can win or the least r2 > tau2; INVALID where the pixel is not
+ *       usable.  dist = (float)sqrt(r2) of the winner, model_flow and residual its (mx, my) and (rx, ry); all NaN where the label is
+ *       OUTLIER or INVALID.  counts (B, K+2) int64: pixels per layer, then outliers, then invalid; zeroed by the call, integer atomics
+ *       (a wave counts with ballots into its workgroup's table in LDS; one atomic per workgroup, sample and label).  With labels_in (B,1,H,W) the winner is not searched: a usable pixel takes the layer
+ *       labels_in names if that layer is alive and can win there (no tau test), OUTLIER otherwise (also where labels_in is >= K); this
+ *       recomputes dist, model_flow and residual for labels that ofd_label_vote changed.  Every output but labels may be NULL.
+ *       The matrices may come from anywhere.  This assignment works from the rounded pixel matrices and the fp32 residual, L3 from
+ *       the normalised parameters in double: at a pixel on a decision boundary (two layers equally near, or the winner at tau) the
+ *       two may differ.
+ *   L6. ofd_label_vote, radius 1..3, integer arithmetic only: a pixel takes the label 0 .. K-1 that is most frequent in its
+ *       (2 radius + 1)^2 window, clipped to the frame; neighbours with any other label do not vote.  Among equally frequent labels
+ *       the pixel's own wins if it is one of them, otherwise the lowest.  An OUTLIER pixel (any label >= K but INVALID) is filled
+ *       where a neighbour votes; an INVALID pixel stays INVALID; a window without votes keeps the pixel's label.  A 64 x 16 tile per
+ *       workgroup, the labels of the tile and its ring staged once in LDS.
+ *   L7. ofd_motion_layers enqueues 2 * (11 K + T) launches and makes no host synchronisation; ws is ofd_motion_layers_ws_doubles(B, K,
+ *       H, W) doubles of device scratch, B * K * (min(ceil(H*W / 256), 128) * 47 + 4).  In a joint solve a workgroup serves one (sample,
+ *       share, layer): every pixel is read K times, and evaluated against the other layers only where its own is within tau.  A sample's bits do not depend on B or on what shares its call.
+ * H, W <= 32768; every array < 2^40 elements; outputs must not alias inputs or each other.  Argument errors return OFD_ERR_ARG and set
+ * ofd_last_error before any GPU work.  The seeds are translations: two motions that differ by less than 1.5 tau everywhere in the
+ * frame share a seed.  tau, sigma, T, the claim radius 1.5 tau and the ten means come from synthetic band scenes; untuned on footage. */
+#define OFD_LABEL_OUTLIER 254
+#define OFD_LABEL_INVALID 255
+size_t ofd_motion_layers_ws_doubles(int B, int K, int H, int W);
+int ofd_motion_layers(const float* flow, const float* conf, int B, int H, int W, int model, int K, int solves, float sigma, float tau,
+                      int min_support, double* params, double* matrix, double* stats, double* ws, void* stream);
+int ofd_motion_assign(const double* matrix, const uint8_t* alive, const float* flow, const float* conf, float tau, const uint8_t* labels_in,
+                      uint8_t* labels, float* dist, float* model_flow, float* residual, int64_t* counts, int B, int K, int H, int W,
+                      void* stream);
+int ofd_label_vote(const uint8_t* labels, uint8_t* out, int B, int H, int W, int K, int radius, void* stream);
 
 /* ------------------------------------------------------------ grid_sample warp (WP:95-119) -
  * second: (B,C,H,W), flow: (B,2,H,W) exactly as handed to the reference's warp(mode='backward'):

@@ -6,6 +6,7 @@ from .warp import (flow_consistency, FlowConsistency, STATE_HELD, STATE_RELEASED
 from .warp import median_filter_flow, median_params  # noqa: F401
 from .warp import chain_flows, chain_flows_to, composite_layer, FlowChain  # noqa: F401
 from .warp import fit_motion, motion_flow, warp_homography, camera_path, stabilize_clip, motion_params, MotionFit  # noqa: F401
+from .warp import segment_motion, assign_motion, vote_labels, layers_params, MotionLayers, LABEL_OUTLIER, LABEL_INVALID  # noqa: F401
 from .softsplat import softsplat  # noqa: F401
 from .denoising_diffusion import Unet, ConditionalDiffusion, PhotoGuide  # noqa: F401,E402
 from .flow_diffuser import FlowDiffuser, UnetWithWarp  # noqa: F401,E402

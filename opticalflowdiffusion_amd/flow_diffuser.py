@@ -22,8 +22,8 @@ import torch
 from .denoising_diffusion import UNSET, PhotoGuide, Unet, ConditionalDiffusion, loss_by_timestep
 from .ema import EMA_DEFAULTS, EmaMixin, ema_optimizer_kwargs
 from .warp import (STATE_HELD, box_reduce, chain_flows, chain_flows_to, composite_layer, consistency_params, fit_motion, flow_consistency,
-                   interpolate_frames, loop_frames, loop_params, median_filter_flow, median_params, motion_params, path_params,
-                   stabilize_clip, upsample_flow, upsample_params, warp)
+                   interpolate_frames, layers_params, loop_frames, loop_params, median_filter_flow, median_params, motion_params, path_params,
+                   segment_motion, stabilize_clip, upsample_flow, upsample_params, warp)
 from . import _lib as L
 
 try:                                                   # pragma: no cover - not installed in this image
@@ -797,6 +797,23 @@ class FlowDiffuser(EmaMixin, _Base):
                 raise ValueError("camera_motion: estimating the flow needs a diffusion model (estimate_flow); pass flow")
             flow = self.estimate_flow(frame1, frame2, **sample_kw)
         return fit_motion(flow, model=model, conf=conf, iterations=par["iterations"], sigma=par["sigma"])
+
+    def motion_layers(self, frame1, frame2, flow=None, layers=3, model="affine", conf=None, solves=8, sigma=1.0, tau=2.0, min_support=8,
+                      vote_radius=0, **sample_kw):
+        """The motions between two frames and the pixels of each (not in the reference): the `warp.MotionLayers` of
+        `warp.segment_motion(flow, layers, model, conf, solves, sigma, tau, min_support, vote_radius)`, which has the method.  frame1,
+        frame2: (B, 3, H, W) in cond's range.  flow: (B, 2, H, W) IN PIXELS as `estimate_flow` returns it, or None: it then comes from
+        `estimate_flow(frame1, frame2, **sample_kw)`.  With the flow given no UNet call is made, the frames are not looked at and
+        sample_kw is an error.  The defaults are untuned on real footage.  Forward only."""
+        par = layers_params(layers, model, solves, sigma, tau, min_support, vote_radius, name="motion_layers")
+        if flow is not None and sample_kw:
+            raise ValueError(f"motion_layers: {sorted(sample_kw)} are sampling arguments; with the flow given nothing is sampled")
+        if flow is None:
+            if not self.is_diffusion:
+                raise ValueError("motion_layers: estimating the flow needs a diffusion model (estimate_flow); pass flow")
+            flow = self.estimate_flow(frame1, frame2, **sample_kw)
+        return segment_motion(flow, layers=par["layers"], model=model, conf=conf, solves=par["solves"], sigma=par["sigma"], tau=par["tau"],
+                              min_support=par["min_support"], vote_radius=par["vote_radius"])
 
     def stabilize(self, clip, fwd=None, bwd=None, refine=0, model="similarity", mode="smooth", sigma_t=4.0, anchor=0, iterations=6, sigma=1.0,
                   a1=0.01, a2=0.5, **sample_kw):

@@ -735,7 +735,8 @@ def fit_motion(flow, model="affine", conf=None, iterations=6, sigma=1.0):
     status (`.degenerate`: no solution, e.g. no voting pixel; the matrix is then the identity).  model_flow (B, 2, H, W) is the
     matrix's flow, residual = flow - model_flow -- what moves relative to the background -- and weight (B, 1, H, W) = conf times the
     weight of that residual, near 1 on the background and near 0 on what moves by itself.  The fit follows the majority: it breaks
-    down as the outliers near half the weight.  The defaults come from a synthetic block scene and are untuned on real footage.
+    down as the outliers near half the weight (`segment_motion` describes several motions with no majority).  The defaults come
+    from a synthetic block scene and are untuned on real footage.
     No host synchronisation; forward only; inputs are not modified; the same input gives the same bits.  Semantics: include/ofd.h."""
     B, H, W = _motion_flow_conf("fit_motion", flow, conf)
     par = motion_params(model, iterations, sigma)
@@ -780,6 +781,141 @@ def warp_homography(img, matrix):
         out, inside = torch.empty_like(img), torch.empty(B, 1, H, W, dtype=torch.float32, device=img.device)
         L.check(L.lib().ofd_homography_warp(L.ptr(img), L.ptr(matrix), L.ptr(out), L.ptr(inside), B, C, H, W, L.stream()))
     return out, inside
+
+
+# ---- motion layers: K parametric motions and the pixels of each (not in the reference; semantics: include/ofd.h, `ofd_motion_layers`) ----
+LABEL_OUTLIER, LABEL_INVALID = 254, 255
+MAX_LAYERS = 8
+
+
+class MotionLayers(collections.namedtuple("MotionLayers", "matrix params stats labels dist model_flow residual counts")):
+    """what `segment_motion` returns; `alive` is a (B, K) bool tensor, False for a layer that found no support (its matrix is what
+    its last good solve left, the identity if none, and no pixel carries its label)"""
+    __slots__ = ()
+
+    @property
+    def alive(self):
+        return self.stats[:, :, 3] == 0
+
+
+def layers_params(layers=3, model="affine", solves=8, sigma=1.0, tau=2.0, min_support=8, vote_radius=0, name="segment_motion"):
+    """the rules of the layer count, the model, the solves, the two scales, the support and the vote (ValueError); host logic, no
+    engine call"""
+    par = motion_params(model, 0, sigma, name=name)
+    if isinstance(tau, bool) or not isinstance(tau, (int, float)) or not 0.0 < tau < float("inf"):             # false for NaN
+        raise ValueError(f"{name}: tau must be a finite number > 0 (the residual, in pixels, beyond which no layer claims a pixel), got {tau!r}")
+    return dict(model=par["model"], sigma=par["sigma"], tau=float(tau), layers=_loop_int(name, "layers", layers, 1, MAX_LAYERS),
+                solves=_loop_int(name, "solves", solves, 0, 64), min_support=_loop_int(name, "min_support", min_support, 1, 2 ** 31 - 1),
+                vote_radius=_loop_int(name, "vote_radius", vote_radius, 0, 3))
+
+
+def _layer_labels(name, labels, B=None, H=None, W=None):
+    ok = torch.is_tensor(labels) and labels.dim() == 4 and labels.shape[1] == 1 and labels.numel() > 0 and labels.dtype == torch.uint8
+    if ok and B is not None:
+        ok = tuple(labels.shape) == (B, 1, H, W)
+    if not ok:
+        raise ValueError(f"{name}: labels must be a non-empty (B, 1, H, W) uint8 tensor, got {_shape_of(labels)}")
+    if max(labels.shape[2:]) > 32768:
+        raise ValueError(f"{name}: H and W must be at most 32768, got {tuple(labels.shape)}")
+
+
+def _layer_matrices(name, matrices, B):
+    if not torch.is_tensor(matrices) or matrices.dim() != 4 or tuple(matrices.shape[2:]) != (3, 3) or matrices.shape[0] != B or \
+            not 1 <= matrices.shape[1] <= MAX_LAYERS or not matrices.is_floating_point():
+        raise ValueError(f"{name}: matrices must be a floating-point ({B}, K, 3, 3) tensor with 1 <= K <= {MAX_LAYERS}, got {_shape_of(matrices)}")
+    return matrices.shape[1]
+
+
+def _motion_assign(flow, conf, matrix, alive, tau, labels_in=None):
+    """ofd_motion_assign on prepared tensors -> (labels, dist, model_flow, residual, counts)"""
+    B, _, H, W = flow.shape
+    K, dev = matrix.shape[1], flow.device
+    labels = torch.empty(B, 1, H, W, dtype=torch.uint8, device=dev)
+    dist = torch.empty(B, 1, H, W, dtype=torch.float32, device=dev)
+    model_flow, residual = torch.empty_like(flow), torch.empty_like(flow)
+    counts = torch.empty(B, K + 2, dtype=torch.int64, device=dev)
+    L.check(L.lib().ofd_motion_assign(L.ptr(matrix), L.ptr(alive), L.ptr(flow), L.ptr(conf), tau, L.ptr(labels_in), L.ptr(labels), L.ptr(dist),
+                                      L.ptr(model_flow), L.ptr(residual), L.ptr(counts), B, K, H, W, L.stream()))
+    return labels, dist, model_flow, residual, counts
+
+
+def _label_vote(labels, K, radius):
+    B, _, H, W = labels.shape
+    out = torch.empty_like(labels)
+    L.check(L.lib().ofd_label_vote(L.ptr(labels), L.ptr(out), B, H, W, K, radius, L.stream()))
+    return out
+
+
+def segment_motion(flow, layers=3, model="affine", conf=None, solves=8, sigma=1.0, tau=2.0, min_support=8, vote_radius=0):
+    """The motions a flow holds and the pixels of each (the layers of Wang & Adelson 1994, the multiple motions of Black & Anandan
+    1996; not in the reference): a `MotionLayers` (matrix, params, stats, labels, dist, model_flow, residual, counts).  Where
+    `fit_motion` describes the one motion of the majority, this describes up to `layers` (K <= 8) motions with no majority needed:
+    the camera and two objects, or the planes of a parallax scene.  flow, conf, model as `fit_motion`.  The layers are seeded by
+    peeling translations: the robust mean of the flow is a seed, the pixels within 1.5 tau of it are set aside, and so on K times.
+    Then `solves` joint solves: every pixel votes for the layer of least residual (none, if that exceeds tau pixels), and every layer
+    is refitted to its voters with the Geman-McClure weight at scale sigma.  A layer with fewer than max(min_support, parameters)
+    voters, or without a solution, is dead (`.alive` (B, K) is False) and takes no further part.  The layers are ordered by their
+    voters, most first, dead ones last.  matrix (B, K, 3, 3) float64, each as `fit_motion`'s and good for `motion_flow`,
+    `warp_homography`, `composite_layer` and `stabilize_clip`; params (B, K, 8), stats (B, K, 4) float64: sum w, sum w r^2, voters
+    and status of the last solve.  labels (B, 1, H, W) uint8: the layer 0 .. K-1 of each pixel, LABEL_OUTLIER (254) where no layer
+    is within tau, LABEL_INVALID (255) where the flow or conf is not usable; dist (B, 1, H, W): the residual's length to the pixel's
+    layer; model_flow, residual (B, 2, H, W): that layer's flow and what is left; all three NaN without a layer.  counts (B, K + 2)
+    int64: pixels per layer, outliers, invalid.  vote_radius 1..3 cleans the labels by a majority vote over the (2 r + 1)^2 window
+    (`vote_labels`), which also fills outliers; dist, model_flow, residual and counts are then those of the voted labels.  The
+    seeds are translations: motions nowhere 1.5 tau apart share a layer.  The defaults (tau, sigma, solves, the 1.5 tau claim
+    radius, the ten means of a seed) come from synthetic band scenes and are untuned on real footage.  No host synchronisation;
+    forward only; inputs are not modified; the same input gives the same bits.  Semantics: include/ofd.h (L1 ... L7)."""
+    B, H, W = _motion_flow_conf("segment_motion", flow, conf)
+    par = layers_params(layers, model, solves, sigma, tau, min_support, vote_radius)
+    _motion_ready("segment_motion", flow, conf)
+    K, lib, dev = par["layers"], L.lib(), flow.device
+    with torch.no_grad():
+        flow, conf = L.f32c(flow), None if conf is None else L.f32c(conf)
+        params = torch.empty(B, K, 8, dtype=torch.float64, device=dev)
+        matrix = torch.empty(B, K, 9, dtype=torch.float64, device=dev)
+        stats = torch.empty(B, K, 4, dtype=torch.float64, device=dev)
+        ws = torch.empty(lib.ofd_motion_layers_ws_doubles(B, K, H, W), dtype=torch.float64, device=dev)
+        L.check(lib.ofd_motion_layers(L.ptr(flow), L.ptr(conf), B, H, W, par["model"], K, par["solves"], par["sigma"], par["tau"],
+                                      par["min_support"], L.ptr(params), L.ptr(matrix), L.ptr(stats), L.ptr(ws), L.stream()))
+        key = torch.where(stats[:, :, 3] == 0, stats[:, :, 2], torch.full_like(stats[:, :, 2], -1.0))
+        order = torch.sort(key, dim=1, descending=True, stable=True).indices
+        pick = lambda t: torch.gather(t, 1, order[:, :, None].expand(-1, -1, t.shape[2])).contiguous()
+        params, matrix, stats = pick(params), pick(matrix), pick(stats)
+        alive = (stats[:, :, 3] == 0).to(torch.uint8).contiguous()
+        labels, dist, model_flow, residual, counts = _motion_assign(flow, conf, matrix, alive, par["tau"])
+        if par["vote_radius"]:
+            labels = _label_vote(labels, K, par["vote_radius"])
+            labels, dist, model_flow, residual, counts = _motion_assign(flow, conf, matrix, alive, par["tau"], labels)
+    return MotionLayers(matrix.view(B, K, 3, 3), params, stats, labels, dist, model_flow, residual, counts)
+
+
+def assign_motion(flow, matrices, conf=None, tau=2.0, alive=None):
+    """Every pixel's motion among given ones (not in the reference): (labels, dist, model_flow, residual, counts) as in
+    `segment_motion`.  matrices: (B, K, 3, 3), K <= 8, from anywhere; alive: (B, K) bool or None, a False layer is skipped.  The label
+    is the layer whose flow is nearest the pixel's, the lowest index among equals; LABEL_OUTLIER beyond tau pixels, LABEL_INVALID
+    where flow or conf is not usable.  One launch; forward only; inputs are not modified.  Semantics: include/ofd.h (L5)."""
+    B, H, W = _motion_flow_conf("assign_motion", flow, conf)
+    K = _layer_matrices("assign_motion", matrices, B)
+    tau = layers_params(tau=tau, name="assign_motion")["tau"]
+    if alive is not None and (not torch.is_tensor(alive) or tuple(alive.shape) != (B, K) or alive.dtype != torch.bool):
+        raise ValueError(f"assign_motion: alive must be a ({B}, {K}) bool tensor or None, got {_shape_of(alive)}")
+    _motion_ready("assign_motion", flow, conf, matrices, alive)
+    with torch.no_grad():
+        flow, conf = L.f32c(flow), None if conf is None else L.f32c(conf)
+        matrix = matrices.double().reshape(B, K, 9).contiguous()
+        return _motion_assign(flow, conf, matrix, None if alive is None else alive.to(torch.uint8).contiguous(), tau)
+
+
+def vote_labels(labels, layers, radius=1):
+    """A majority vote over a label plane (not in the reference): a new (B, 1, H, W) uint8 tensor in which every pixel has the label
+    0 .. layers-1 most frequent in its (2 radius + 1)^2 window, clipped to the frame; its own among equally frequent ones, else the
+    lowest.  Other labels do not vote; LABEL_OUTLIER pixels are filled where a neighbour votes, LABEL_INVALID pixels stay.  radius
+    1..3.  One launch, integer arithmetic; forward only.  Semantics: include/ofd.h (L6)."""
+    _layer_labels("vote_labels", labels)
+    K = _loop_int("vote_labels", "layers", layers, 1, MAX_LAYERS)
+    radius = _loop_int("vote_labels", "radius", radius, 1, 3)
+    L.require_gpu(labels)
+    return _label_vote(labels.contiguous(), K, radius)
 
 
 def _mm3(a, b):
