@@ -34,6 +34,7 @@
  *   (not in the reference)            guided weighted median of a flow  -> ofd_flow_median
  *   (not in the reference)            global motion of a flow: robust fit, split, render -> ofd_motion_fit, ofd_motion_field, ofd_homography_warp
  *   (not in the reference)            motion layers: K motions of a flow, labels, label vote -> ofd_motion_layers, ofd_motion_assign, ofd_label_vote
+ *   (not in the reference)            background plate of a clip: temporal median mosaic, projection -> ofd_plate_reduce, ofd_plate_project
  *   denoising_diffusion.py:806-812    q_sample                          -> ofd_q_sample
  *   denoising_diffusion.py:844-879,985-993  p_losses noise / target     -> ofd_diffusion_prep
  *   denoising_diffusion.py:73-77      (un)normalize                     -> ofd_range_map
@@ -496,6 +497,57 @@ int ofd_motion_assign(const double* matrix, const uint8_t* alive, const float* f
                       uint8_t* labels, float* dist, float* model_flow, float* residual, int64_t* counts, int B, int K, int H, int W,
                       void* stream);
 int ofd_label_vote(const uint8_t* labels, uint8_t* out, int B, int H, int W, int K, int radius, void* stream);
+
+/* Background plate of a clip: the frames gathered through their camera path into one coordinate system and reduced over time, and the
+ * plate read back into every frame (Wang & Adelson 1994: a layer's intensity map is the temporal median of the warped frames; Irani,
+ * Anandan & Hsu 1995: mosaics of a pan).  An addition: ofd_homography_warp renders one frame at its own size and keeps what moves.
+ * Every operation is rounded on its own (no contraction), in the order written; a chain without brackets runs left to right.
+ *   P1. ofd_plate_reduce, arguments.  clip (B,N,C,H,W) fp32, 1 <= C <= 8, 1 <= N <= OFD_PLATE_MAX_FRAMES; weight (B,N,1,H,W) fp32 or NULL
+ *       (every weight 1); path (B,N,9) double, path[b][t] sends an anchor position to the place in frame t it is read from (what
+ *       warp.camera_path(mode="lock") returns); plate (B,C,Hc,Wc) fp32; votes (B,1,Hc,Wc) fp32 or NULL; count (B,1,Hc,Wc) uint8 or NULL.
+ *       The canvas pixel (i, j) (column, row) stands at the anchor position (x, y) = ((double)(x0 + i), (double)(y0 + j)); x0, y0 ints
+ *       with |x0|, |y0| <= 32768.  mode 0 median, 1 mean; 1 <= min_count <= N.
+ *   P2. The sample of frame t at a canvas pixel.  (X, Y) = path[b][t] at (x, y) by M9.  Valid and inside are tested as in
+ *       ofd_homography_warp (D finite and > 0, 0 <= X <= W-1, 0 <= Y <= H-1 in double, false for NaN); the cell (x0 = floor(X) in double,
+ *       tx = (float)(X - x0), x1 = min(x0 + 1, W-1), likewise in y) and the fp32 blend (1-ty) * ((1-tx) * g00 + tx * g01) + ty *
+ *       ((1-tx) * g10 + tx * g11) are as written there.  v[t][c] is the blend of plane c of frame t; w[t] the blend of the weight
+ *       plane, or 1.0f when weight is NULL.  The sample is usable when the position is valid and inside, w[t] is finite and > 0, and
+ *       all C values v[t][c] are finite.  A position becomes an index only after the inside test; a sample outside reads offset 0 of
+ *       its planes and drops it.
+ *   P3. Quantised weight, fp32 left to right: q[t] = (uint32) floorf(fminf(w[t], 1.0f) * 65535.0f + 0.5f); a sample with q[t] = 0 is
+ *       not usable.  Q = sum of q[t] and n = the number of usable samples (integer sums: no order).  votes = (float)Q / 65535.0f;
+ *       count = n.
+ *   P4. When n < min_count or Q = 0: plate = +0.0 in every plane.
+ *   P5. mode 0, the lower weighted median, for each plane c by itself.  Order the usable samples by (v[t][c] ascending, t ascending)
+ *       under the float `<` (-0.0 and +0.0 tie, and t decides); below_k = the sum of q over the samples before k; plate_c = the bits of
+ *       v[k][c] at the one sample with 2 * below_k < Q <= 2 * (below_k + q[k]).  It is always one of the N samples.  Found by counting,
+ *       not by sorting.
+ *   P6. mode 1, the weighted mean: plate_c = (float)(S / (double)Q), S = the sum over the usable t, ascending from +0.0, of
+ *       (double)q[t] * (double)v[t][c] in double.
+ *   P7. ofd_plate_project, arguments and read.  plate (B,C,Hc,Wc); votes (B,1,Hc,Wc) or NULL; inv (B,N,9) double, inv[b][t] sends the
+ *       pixel (x, y) of frame t to its anchor position (X, Y) by M9; any N >= 1.  The canvas position is (X - x0, Y - y0), double
+ *       subtractions.  A pixel is covered when the position is valid, 0 <= X - x0 <= Wc-1 and 0 <= Y - y0 <= Hc-1 (false for NaN), and,
+ *       where votes is given, the votes at all four corner texels of the cell are > 0.  proj_c is the fp32 blend of P2 on plane c of
+ *       the plate.  covered (B,N,1,H,W) fp32 or NULL holds 1 or 0.  A pixel whose position fails the test reads offset 0 and drops it.
+ *   P8. Output, out (B,N,C,H,W).  frames NULL (then alpha and fg must be NULL): out_c = proj_c where the pixel is covered, +0.0
+ *       elsewhere.  frames (B,N,C,H,W) given: d = (|frame_0 - proj_0| + |frame_1 - proj_1| + ...) / (float)C in fp32, c ascending.
+ *       With alpha (B,N,1,H,W): a = fminf(fmaxf(alpha, 0), 1), and 0 where alpha is not finite.  Otherwise a = fminf(fmaxf((d - lo) /
+ *       (hi - lo), 0), 1) with 0 <= lo < hi finite, and 0 where d is NaN.  Where the pixel is not covered a = 0.  out_c = the bits of
+ *       frame_c where a == 0, the bits of proj_c where a == 1, frame_c + a * (proj_c - frame_c) elsewhere: because of the two selects a
+ *       non-finite value on the side that is not chosen never leaks.  fg (B,N,1,H,W) or NULL holds a.
+ * Each entry point is one launch, makes no host synchronisation and uses no atomics; no float becomes an index before it passed the
+ * inside test; the same input gives the same bits; a sample's bits do not depend on B or on what shares its call.  H, W, Hc, Wc <= 32768;
+ * every array < 2^40 elements; outputs must not overlap inputs or each other.  Argument errors return OFD_ERR_ARG and set
+ * ofd_last_error before any GPU work.  Nothing is inpainted: where no frame saw the background, votes is 0 and the plate +0.0.
+ * Compulsory traffic: the reduce 4 * B * (N * (C + 1) * H * W + (C + 1) * Hc * Wc) + B * Hc * Wc bytes (the weight and votes planes
+ * included); the projection 4 * B * N * H * W * (2 C + 2) bytes plus the plate.  Measured (tools/plate_bench.py) at 16 x 3 x 440 x 1024:
+ * the median 1.7 TB/s (N = 8) and 0.66 TB/s (N = 32) over these bytes, the projection 2.4 TB/s. */
+#define OFD_PLATE_MAX_FRAMES 32
+int ofd_plate_reduce(const float* clip, const float* weight, const double* path, float* plate, float* votes, uint8_t* count, int B, int N,
+                     int C, int H, int W, int x0, int y0, int Hc, int Wc, int mode, int min_count, void* stream);
+int ofd_plate_project(const float* plate, const float* votes, const double* inv, const float* frames, const float* alpha, float* out,
+                      float* covered, float* fg, int B, int N, int C, int H, int W, int x0, int y0, int Hc, int Wc, float lo, float hi,
+                      void* stream);
 
 /* ------------------------------------------------------------ grid_sample warp (WP:95-119) -
  * second: (B,C,H,W), flow: (B,2,H,W) exactly as handed to the reference's warp(mode='backward'):

@@ -75,6 +75,8 @@ SIGNATURES = {
     "ofd_motion_layers": (c_int, [c_void_p] * 2 + [c_int] * 6 + [c_float] * 2 + [c_int] + [c_void_p] * 5),
     "ofd_motion_assign": (c_int, [c_void_p] * 4 + [c_float] + [c_void_p] * 6 + [c_int] * 4 + [c_void_p]),
     "ofd_label_vote": (c_int, [c_void_p] * 2 + [c_int] * 5 + [c_void_p]),
+    "ofd_plate_reduce": (c_int, [c_void_p] * 6 + [c_int] * 11 + [c_void_p]),
+    "ofd_plate_project": (c_int, [c_void_p] * 8 + [c_int] * 9 + [c_float] * 2 + [c_void_p]),
     "ofd_grid_warp_fwd": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p]),
     "ofd_splat_pyramid_workspace_bytes": (c_size_t, [c_int] * 4),
     "ofd_splat_pyramid_fwd": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_void_p, c_size_t, c_void_p]),

@@ -24,6 +24,7 @@ from .ema import EMA_DEFAULTS, EmaMixin, ema_optimizer_kwargs
 from .warp import (STATE_HELD, box_reduce, chain_flows, chain_flows_to, composite_layer, consistency_params, fit_motion, flow_consistency,
                    interpolate_frames, layers_params, loop_frames, loop_params, median_filter_flow, median_params, motion_params, path_params,
                    segment_motion, stabilize_clip, upsample_flow, upsample_params, warp)
+from .warp import background_plate, plate_params, plate_voters, remove_moving
 from . import _lib as L
 
 try:                                                   # pragma: no cover - not installed in this image
@@ -835,6 +836,52 @@ class FlowDiffuser(EmaMixin, _Base):
         conf = (held == STATE_HELD).float().reshape(B, T, 1, H, W)
         video, inside, _matrices, _path = stabilize_clip(clip, fwd, conf, model=model, iterations=par["iterations"], sigma=par["sigma"], **path)
         return video, inside, fwd, bwd
+
+    def _plate_flows(self, name, clip, fwd, bwd, refine, plate_kw, a1, a2, sample_kw):
+        """what `background_plate` and `remove_moving` share: every host rule before any model or engine call, the flows (estimated
+        where they are not given) and the two confidences of the forward-backward check -> (fwd, bwd, conf, conf_bwd)"""
+        T = self._clip_flows(name, clip, fwd, bwd, sample_kw)
+        if isinstance(refine, bool) or not isinstance(refine, int) or not 0 <= refine <= 16:
+            raise ValueError(f"{name}: refine must be an integer in 0..16, got {refine!r}")
+        motion_params(plate_kw["model"], plate_kw["iterations"], plate_kw["sigma"], name=name)
+        voters = plate_voters(T, plate_kw["anchor"], plate_kw["every"], name)
+        plate_params(len(voters), clip.shape[3], clip.shape[4], plate_kw["canvas"], plate_kw["mode"], plate_kw["min_count"],
+                     plate_kw.get("lo", 0.05), plate_kw.get("hi", 0.15), name=name)
+        check = consistency_params(a1, a2, name=name)
+        if fwd is None:
+            fwd, bwd = self.estimate_flow_clip(clip, refine=refine, **sample_kw)
+        B, _, _, H, W = fwd.shape
+        fc = flow_consistency(fwd.reshape(B * T, 2, H, W), bwd.reshape(B * T, 2, H, W), a1=check["a1"], a2=check["a2"])
+        conf = (fc.state12 == STATE_HELD).float().reshape(B, T, 1, H, W)
+        conf_bwd = (fc.state21 == STATE_HELD).float().reshape(B, T, 1, H, W)
+        return fwd, bwd, conf, conf_bwd
+
+    def background_plate(self, clip, fwd=None, bwd=None, refine=0, model="homography", anchor=0, canvas="frame", mode="median", every=1,
+                         min_count=1, iterations=6, sigma=1.0, a1=0.01, a2=0.5, **sample_kw):
+        """The background of a clip without what moves by itself, on the anchor frame's rectangle or as a panorama (not in the
+        reference): (plate, fwd, bwd), plate the `warp.Plate` of `warp.background_plate(clip, fwd, bwd, conf, conf_bwd, model, anchor,
+        canvas, mode, every, min_count, iterations, sigma)`, which has the method and its limits.  clip: (B, T + 1, 3, H, W) in cond's
+        range.  fwd, bwd: (B, T, 2, H, W) IN PIXELS as `estimate_flow_clip` returns them, both or neither.  Neither: they come from
+        `estimate_flow_clip(clip, refine=refine, **sample_kw)`.  Both: no UNet call is made, and sample_kw is an error.  conf is 1 on
+        the pixels of fwd that `warp.flow_consistency(fwd, bwd, a1, a2)` holds (state12) and 0 elsewhere, conf_bwd the same for bwd
+        (state21): occluded pixels vote neither for the camera nor for the plate.  The defaults are untuned on real footage.
+        Forward only."""
+        kw = dict(model=model, anchor=anchor, canvas=canvas, mode=mode, every=every, min_count=min_count, iterations=iterations, sigma=sigma)
+        fwd, bwd, conf, conf_bwd = self._plate_flows("background_plate", clip, fwd, bwd, refine, kw, a1, a2, sample_kw)
+        plate, _matrices, _path, _weight = background_plate(clip, fwd, bwd, conf, conf_bwd, **kw)
+        return plate, fwd, bwd
+
+    def remove_moving(self, clip, fwd=None, bwd=None, refine=0, model="homography", anchor=0, canvas="frame", mode="median", every=1,
+                      min_count=1, iterations=6, sigma=1.0, lo=0.05, hi=0.15, alpha=None, a1=0.01, a2=0.5, **sample_kw):
+        """A clip with what moves by itself replaced by the background behind it (not in the reference): (video, fg, plate, fwd, bwd),
+        the first three those of `warp.remove_moving(clip, fwd, bwd, conf, conf_bwd, model, anchor, canvas, mode, every, min_count,
+        iterations, sigma, lo, hi, alpha)`, which has the method and its limits (a thin rim stays around what a derived matte removes;
+        nothing is inpainted where no frame saw the background).  clip, fwd, bwd, refine, conf, conf_bwd and sample_kw as for
+        `background_plate`.  The defaults are untuned on real footage.  Forward only."""
+        kw = dict(model=model, anchor=anchor, canvas=canvas, mode=mode, every=every, min_count=min_count, iterations=iterations, sigma=sigma)
+        fwd, bwd, conf, conf_bwd = self._plate_flows("remove_moving", clip, fwd, bwd, refine, dict(kw, lo=lo, hi=hi), a1, a2, sample_kw)
+        video, fg, plate, _path = remove_moving(clip, fwd, bwd, conf, conf_bwd, lo=lo, hi=hi, alpha=alpha, **kw)
+        return video, fg, plate, fwd, bwd
 
     @staticmethod
     def _batch_stats(x):

@@ -1023,6 +1023,255 @@ def stabilize_clip(clip, fwd, conf=None, model="similarity", mode="smooth", sigm
     return video.reshape(B, N, C, H, W), inside.reshape(B, N, 1, H, W), matrices, path
 
 
+# ---- background plate of a clip: temporal median mosaic, projection, object removal (not in the reference; semantics: include/ofd.h,
+# `ofd_plate_reduce`) -------------------------------------------------------------------------------------------------------------------
+PLATE_MAX_FRAMES = 32
+PLATE_MODES = ("median", "mean")
+Plate = collections.namedtuple("Plate", "plate votes count canvas")
+
+
+def plate_voters(T, anchor=0, every=1, name="background_plate"):
+    """the frames of a clip of T + 1 frames that vote for its plate: anchor +- k * every, ascending (ValueError); host logic"""
+    anchor = _loop_int(name, "anchor", anchor, 0, T)
+    every = _loop_int(name, "every", every, 1, max(T, 1))
+    idx = list(range(anchor % every, T + 1, every))
+    if len(idx) > PLATE_MAX_FRAMES:
+        raise ValueError(f"{name}: at most {PLATE_MAX_FRAMES} frames vote for a plate, got {len(idx)} of {T + 1}: raise every= (now {every})")
+    return idx
+
+
+def plate_params(N, H, W, canvas="frame", mode="median", min_count=1, lo=0.05, hi=0.15, name="build_plate"):
+    """the rules of a plate's frames, canvas, reduction and thresholds (ValueError); host logic, no engine call.  canvas comes back as
+    (x0, y0, Wc, Hc), or as "union" where it has to be measured from the path (`plate_canvas`)"""
+    from .flow_diffuser import ANIMATE_MAX_PIXELS
+    if isinstance(N, bool) or not isinstance(N, int) or N < 1:
+        raise ValueError(f"{name}: a plate needs at least one frame, got {N!r}")
+    if N > PLATE_MAX_FRAMES:
+        raise ValueError(f"{name}: at most {PLATE_MAX_FRAMES} frames vote for a plate, got {N}: take a subset of the clip "
+                         f"(`background_plate(..., every=)`)")
+    H, W = _loop_int(name, "H", H, 1, 32768), _loop_int(name, "W", W, 1, 32768)
+    if isinstance(canvas, str):
+        if canvas not in ("frame", "union"):
+            raise ValueError(f"{name}: canvas must be 'frame', 'union' or (x0, y0, Wc, Hc), got {canvas!r}")
+        canvas = (0, 0, W, H) if canvas == "frame" else canvas
+    else:
+        if not isinstance(canvas, (tuple, list)) or len(canvas) != 4:
+            raise ValueError(f"{name}: canvas must be 'frame', 'union' or (x0, y0, Wc, Hc), got {canvas!r}")
+        x0, y0 = (_loop_int(name, f"canvas {k}", v, -32768, 32768) for k, v in zip(("x0", "y0"), canvas[:2]))
+        Wc, Hc = (_loop_int(name, f"canvas {k}", v, 1, 32768) for k, v in zip(("Wc", "Hc"), canvas[2:]))
+        if Wc * Hc > ANIMATE_MAX_PIXELS:
+            raise ValueError(f"{name}: a canvas of {Wc} x {Hc} is over {ANIMATE_MAX_PIXELS} pixels")
+        canvas = (x0, y0, Wc, Hc)
+    if not isinstance(mode, str) or mode not in PLATE_MODES:
+        raise ValueError(f"{name}: mode must be one of {PLATE_MODES}, got {mode!r}")
+    min_count = _loop_int(name, "min_count", min_count, 1, N)
+    lo, hi = _loop_real(name, "lo", lo), _loop_real(name, "hi", hi)
+    if not 0.0 <= lo < hi:
+        raise ValueError(f"{name}: lo and hi must satisfy 0 <= lo < hi, got {lo!r} and {hi!r}")
+    return dict(canvas=canvas, mode=PLATE_MODES.index(mode), min_count=min_count, lo=lo, hi=hi)
+
+
+def plate_canvas(path, H, W, name="build_plate"):
+    """The "union" canvas (x0, y0, Wc, Hc) of a path (B, N, 3, 3): the bounding box, over the whole batch, of the four corner pixels of
+    every frame carried to the anchor through the inverse path (M9's arithmetic in float64 torch operations), floor of the least and
+    ceil of the greatest coordinate.  ONE HOST SYNCHRONISATION, to read four integers.  ValueError where a corner is not finite (or
+    its projective denominator not > 0) or the box exceeds 32768 a side or flow_diffuser.ANIMATE_MAX_PIXELS."""
+    from .flow_diffuser import ANIMATE_MAX_PIXELS
+    with torch.no_grad():
+        m = _unit3(_inv3(path.double())).reshape(-1, 9, 1)
+        x = torch.tensor([0.0, W - 1.0, 0.0, W - 1.0], dtype=torch.float64, device=path.device)
+        y = torch.tensor([0.0, 0.0, H - 1.0, H - 1.0], dtype=torch.float64, device=path.device)
+        D = (m[:, 6] * x + m[:, 7] * y) + m[:, 8]
+        X, Y = ((m[:, 0] * x + m[:, 1] * y) + m[:, 2]) / D, ((m[:, 3] * x + m[:, 4] * y) + m[:, 5]) / D
+        good = ((D > 0) & torch.isfinite(D) & torch.isfinite(X) & torch.isfinite(Y)).all()
+        X, Y = torch.where(good, X, torch.zeros_like(X)), torch.where(good, Y, torch.zeros_like(Y))
+        box = torch.stack((torch.floor(X.min()), torch.floor(Y.min()), torch.ceil(X.max()), torch.ceil(Y.max()), good.double()))
+        xa, ya, xb, yb, ok = box.clamp(-1e9, 1e9).tolist()                   # the host synchronisation
+    if not ok:
+        raise ValueError(f"{name}: canvas='union': a frame corner has no finite anchor position under this path")
+    x0, y0, Wc, Hc = int(xa), int(ya), int(xb) - int(xa) + 1, int(yb) - int(ya) + 1
+    if max(abs(x0), abs(y0), Wc, Hc) > 32768 or Wc * Hc > ANIMATE_MAX_PIXELS:
+        raise ValueError(f"{name}: canvas='union' is {Wc} x {Hc} at ({x0}, {y0}): over 32768 a side or {ANIMATE_MAX_PIXELS} pixels; "
+                         f"give an explicit canvas")
+    return x0, y0, Wc, Hc
+
+
+def _plate_clip(name, clip, what="clip"):
+    if not torch.is_tensor(clip) or clip.dim() != 5 or clip.numel() == 0 or not 1 <= clip.shape[2] <= 8 or not clip.is_floating_point():
+        raise ValueError(f"{name}: {what} must be a non-empty floating-point (B, N, C, H, W) tensor with 1 <= C <= 8, got {_shape_of(clip)}")
+    return tuple(clip.shape)
+
+
+def _plate_path(name, path, B, N=None):
+    if not torch.is_tensor(path) or path.dim() != 4 or tuple(path.shape[2:]) != (3, 3) or path.shape[0] != B or path.numel() == 0 or \
+            (N is not None and path.shape[1] != N) or not path.is_floating_point():
+        raise ValueError(f"{name}: path must be a floating-point ({B}, {'N' if N is None else N}, 3, 3) tensor, got {_shape_of(path)}")
+
+
+def build_plate(clip, path, weight=None, canvas="frame", mode="median", min_count=1):
+    """The background plate of a clip (Wang & Adelson 1994; Irani et al. 1995; not in the reference): a `Plate` (plate (B, C, Hc, Wc)
+    fp32, votes (B, 1, Hc, Wc) fp32, count (B, 1, Hc, Wc) uint8, canvas (x0, y0, Wc, Hc)).  clip: (B, N, C, H, W), C <= 8, N <= 32;
+    path: (B, N, 3, 3), for every frame the matrix that sends a position of the anchor frame to the place in that frame it is read
+    from, e.g. `camera_path(matrices, "lock", anchor)`; weight: (B, N, 1, H, W) or None, near 1 on the background and near 0 on what
+    moves by itself (`MotionFit.weight`).  Every canvas pixel gathers its N samples (bilinear, positions in double) and takes their
+    weighted median, plane by plane (mode="median": always one of the samples, so a passer-by seen in fewer than half of the voting
+    weight leaves no trace), or their weighted mean (mode="mean", for comparison: it keeps a ghost).  votes is the voting weight that
+    reached the pixel, count the number of frames; where count < min_count the plate is 0.  canvas: "frame" = (0, 0, W, H), the anchor
+    frame's rectangle, no host synchronisation; an explicit (x0, y0, Wc, Hc) in anchor coordinates; or "union", the bounding box of
+    all frames (`plate_canvas`), a panorama of a pan, which costs ONE HOST SYNCHRONISATION to read four integers.
+    Limits: the plate is the background only where the background is visible for more than half of the voting weight; nothing is
+    inpainted where no frame saw it (votes = 0; `fill_holes(plate, votes > 0)` is the caller's choice).  One launch; forward only;
+    inputs are not modified; the same input gives the same bits.  Semantics: include/ofd.h (`ofd_plate_reduce`)."""
+    B, N, C, H, W = _plate_clip("build_plate", clip)
+    par = plate_params(N, H, W, canvas, mode, min_count)
+    _plate_path("build_plate", path, B, N)
+    if weight is not None and (not torch.is_tensor(weight) or tuple(weight.shape) != (B, N, 1, H, W) or not weight.is_floating_point()):
+        raise ValueError(f"build_plate: weight must be a floating-point (B, N, 1, H, W) = {(B, N, 1, H, W)} tensor or None, got {_shape_of(weight)}")
+    _chain_ready("build_plate", clip, path, weight, what="the plate has")
+    with torch.no_grad():
+        clip, path = L.f32c(clip), path.double().contiguous()
+        weight = None if weight is None else L.f32c(weight)
+        x0, y0, Wc, Hc = plate_canvas(path, H, W) if par["canvas"] == "union" else par["canvas"]
+        plate = torch.empty(B, C, Hc, Wc, dtype=torch.float32, device=clip.device)
+        votes = torch.empty(B, 1, Hc, Wc, dtype=torch.float32, device=clip.device)
+        count = torch.empty(B, 1, Hc, Wc, dtype=torch.uint8, device=clip.device)
+        L.check(L.lib().ofd_plate_reduce(L.ptr(clip), L.ptr(weight), L.ptr(path), L.ptr(plate), L.ptr(votes), L.ptr(count), B, N, C, H, W,
+                                         x0, y0, Hc, Wc, par["mode"], par["min_count"], L.stream()))
+    return Plate(plate, votes, count, (x0, y0, Wc, Hc))
+
+
+def project_plate(plate, path, H, W, frames=None, alpha=None, lo=0.05, hi=0.15):
+    """A plate read back into the frames of its clip, and, given the frames, what does not belong to the background replaced by it
+    (not in the reference): (out (B, N, C, H, W) fp32, covered (B, N, 1, H, W) fp32, fg (B, N, 1, H, W) fp32 or None).  plate: a
+    `Plate`; path: (B, N, 3, 3) as for `build_plate`, of any number of frames -- those that voted or others; its inverse
+    (float64 torch operations, as in `camera_path`) carries every pixel of frame t to the plate.  covered is 1 where the plate has
+    something to say: the pixel falls on the canvas and all four texels of its bilinear cell have votes > 0.  frames None: out is the
+    projection, 0 where not covered; fg is None.  frames (B, N, C, H, W): out = frame + a * (projection - frame) with the matte a =
+    fg: `alpha` (B, N, 1, H, W), clamped to 0..1, where it is given; otherwise derived from the mean absolute difference d of frame
+    and projection over the planes, a = clamp((d - lo) / (hi - lo), 0, 1); 0 where the pixel is not covered.  Where a is 0 the frame's
+    own bits come back, where it is 1 the plate's.
+    Limits: a derived matte leaves a thin rim around what it removes, since nothing is dilated; nothing is inpainted where no frame saw
+    the background (covered = 0: the frame stays); lo and hi are untuned on real footage.  One launch per at most
+    flow_diffuser.ANIMATE_MAX_PIXELS pixels of whole frames (a single frame above that is a ValueError), the same bits chunked or
+    not; forward only; inputs are not modified."""
+    from .flow_diffuser import ANIMATE_MAX_PIXELS
+    name = "project_plate"
+    if not isinstance(plate, Plate) or not torch.is_tensor(plate.plate) or plate.plate.dim() != 4:
+        raise ValueError(f"{name}: plate must be a Plate, what build_plate returns, got {type(plate).__name__}")
+    B, C, Hc, Wc = plate.plate.shape
+    par = plate_params(1, H, W, "frame", "median", 1, lo, hi, name=name)
+    if H * W > ANIMATE_MAX_PIXELS:                                          # a call takes whole frames: the same rule as for a canvas
+        raise ValueError(f"{name}: a frame of {W} x {H} is over {ANIMATE_MAX_PIXELS} pixels")
+    x0, y0 = (_loop_int(name, f"canvas {k}", v, -32768, 32768) for k, v in zip(("x0", "y0"), tuple(plate.canvas)[:2]))
+    if tuple(plate.canvas)[2:] != (Wc, Hc) or not 1 <= C <= 8 or (plate.votes is not None and tuple(plate.votes.shape) != (B, 1, Hc, Wc)):
+        raise ValueError(f"{name}: the plate {_shape_of(plate.plate)}, its votes {_shape_of(plate.votes)} and its canvas {plate.canvas} disagree")
+    _plate_path(name, path, B)
+    N = path.shape[1]
+    if frames is not None and _plate_clip(name, frames, "frames") != (B, N, C, H, W):
+        raise ValueError(f"{name}: frames must be (B, N, C, H, W) = {(B, N, C, H, W)}, got {_shape_of(frames)}")
+    if alpha is not None and (frames is None or not torch.is_tensor(alpha) or tuple(alpha.shape) != (B, N, 1, H, W) or not alpha.is_floating_point()):
+        raise ValueError(f"{name}: alpha needs frames and must be a floating-point (B, N, 1, H, W) = {(B, N, 1, H, W)} tensor, got {_shape_of(alpha)}")
+    _chain_ready(name, plate.plate, plate.votes, path, frames, alpha, what="the projection has")
+    with torch.no_grad():
+        pl, votes = L.f32c(plate.plate), None if plate.votes is None else L.f32c(plate.votes)
+        inv = _unit3(_inv3(path.double())).contiguous().reshape(B, N, 9)
+        frames, alpha = (None if t is None else L.f32c(t) for t in (frames, alpha))
+        dev = pl.device
+        out = torch.empty(B, N, C, H, W, dtype=torch.float32, device=dev)
+        covered = torch.empty(B, N, 1, H, W, dtype=torch.float32, device=dev)
+        fg = None if frames is None else torch.empty(B, N, 1, H, W, dtype=torch.float32, device=dev)
+        per = max(1, ANIMATE_MAX_PIXELS // (H * W))                          # frames per call
+        if per >= N:                                                        # whole samples
+            calls = [(slice(b0, min(b0 + per // N, B)), slice(0, N)) for b0 in range(0, B, per // N)]
+        else:                                                               # a sample in pieces
+            calls = [(slice(b, b + 1), slice(t0, min(t0 + per, N))) for b in range(B) for t0 in range(0, N, per)]
+        for sb, st in calls:                                                # all frames of some samples, or some frames of one: contiguous
+            part = [None if t is None else t[sb, st] for t in (inv, frames, alpha, out, covered, fg)]
+            assert all(t is None or t.is_contiguous() for t in part)
+            L.check(L.lib().ofd_plate_project(L.ptr(pl[sb]), L.ptr(None if votes is None else votes[sb]), *(L.ptr(t) for t in part),
+                                              sb.stop - sb.start, st.stop - st.start, C, H, W, x0, y0, Hc, Wc, par["lo"], par["hi"], L.stream()))
+    return out, covered, fg
+
+
+def _plate_weights(flows, confs, matrix, sigma, per):
+    """`fit_motion`'s weight of prepared (n, 2, H, W) flows against their fitted matrices (n, 3, 3) -> (n, 1, H, W)"""
+    n, _, H, W = flows.shape
+    scratch = torch.empty(min(per, n), 2, H, W, dtype=torch.float32, device=flows.device)
+    weight = torch.empty(n, 1, H, W, dtype=torch.float32, device=flows.device)
+    for f0 in range(0, n, per):
+        cf = min(per, n - f0)
+        L.check(L.lib().ofd_motion_field(L.ptr(matrix[f0:f0 + cf]), L.ptr(flows[f0:f0 + cf]), None if confs is None else L.ptr(confs[f0:f0 + cf]),
+                                         sigma, L.ptr(scratch), None, L.ptr(weight[f0:f0 + cf]), cf, H, W, L.stream()))
+    return weight
+
+
+def background_plate(clip, fwd, bwd=None, conf=None, conf_bwd=None, model="homography", anchor=0, canvas="frame", mode="median", every=1,
+                     min_count=1, iterations=6, sigma=1.0):
+    """The background plate of a clip from its flows (Wang & Adelson 1994; Irani et al. 1995; not in the reference): (`Plate`, matrices
+    (B, T, 3, 3) float64, path (B, T + 1, 3, 3) float64, weight (B, T + 1, 1, H, W) fp32).  clip: (B, T + 1, C, H, W), C <= 8; fwd:
+    (B, T, 2, H, W) IN PIXELS, fwd[:, j] carries frame j to frame j + 1; bwd: the same for frame j + 1 to frame j, or None; conf,
+    conf_bwd: (B, T, 1, H, W) or None.  matrices = the robust fit of `fit_motion(fwd, model, conf, iterations, sigma)` to the B * T
+    forward flows (one `ofd_motion_fit`), path = `camera_path(matrices, "lock", anchor)`, and the voting weight of frame t < T is that
+    fit's `weight` for fwd[:, t]: near 1 on the background, near 0 on what moves by itself.  Frame T has no forward flow: its weight is
+    that of the fit to bwd[:, T - 1] where bwd is given, and 1 everywhere otherwise -- THE LAST FRAME THEN VOTES UNWEIGHTED.  The frames
+    anchor +- k * every vote, at most 32 of them; the plate is `build_plate` of those frames, which has canvas ("union" costs one
+    host synchronisation), mode and min_count.  path and weight cover every frame, voting or not.
+    Limits: as `build_plate`; the homography default and the fit's defaults are untuned on real footage.  Forward only; inputs are
+    not modified."""
+    from .flow_diffuser import ANIMATE_MAX_PIXELS
+    name = "background_plate"
+    B, N, C, H, W = _plate_clip(name, clip)
+    T = N - 1
+    if T < 1:
+        raise ValueError(f"{name}: clip must have at least two frames, got {_shape_of(clip)}")
+    for key, fl, ch in (("fwd", fwd, 2), ("bwd", bwd, 2), ("conf", conf, 1), ("conf_bwd", conf_bwd, 1)):
+        if (fl is not None or key == "fwd") and (not torch.is_tensor(fl) or tuple(fl.shape) != (B, T, ch, H, W) or not fl.is_floating_point()):
+            raise ValueError(f"{name}: {key} must be a floating-point (B, T, {ch}, H, W) = {(B, T, ch, H, W)} tensor, got {_shape_of(fl)}")
+    if conf_bwd is not None and bwd is None:
+        raise ValueError(f"{name}: conf_bwd needs bwd")
+    par = motion_params(model, iterations, sigma, name=name)
+    idx = plate_voters(T, anchor, every, name)
+    plate_params(len(idx), H, W, canvas, mode, min_count, name=name)
+    _chain_ready(name, clip, fwd, bwd, conf, conf_bwd, what="the plate has")
+    with torch.no_grad():
+        per = max(1, ANIMATE_MAX_PIXELS // (H * W))
+        flows = L.f32c(fwd).reshape(B * T, 2, H, W)
+        confs = None if conf is None else L.f32c(conf).reshape(B * T, 1, H, W)
+        mats = _motion_fit(flows, confs, par, per)[0]
+        matrices = mats.reshape(B, T, 3, 3)
+        path = camera_path(matrices, "lock", anchor=anchor).contiguous()
+        weight = torch.empty(B, N, 1, H, W, dtype=torch.float32, device=flows.device)
+        weight[:, :T] = _plate_weights(flows, confs, mats, par["sigma"], per).reshape(B, T, 1, H, W)
+        if bwd is None:
+            weight[:, T] = 1.0
+        else:
+            last = L.f32c(bwd[:, T - 1])
+            clast = None if conf_bwd is None else L.f32c(conf_bwd[:, T - 1])
+            weight[:, T] = _plate_weights(last, clast, _motion_fit(last, clast, par, per)[0], par["sigma"], per)
+        pick = torch.tensor(idx, device=flows.device)
+        plate = build_plate(L.f32c(clip).index_select(1, pick), path.index_select(1, pick), weight.index_select(1, pick), canvas, mode, min_count)
+    return plate, matrices, path, weight
+
+
+def remove_moving(clip, fwd, bwd=None, conf=None, conf_bwd=None, model="homography", anchor=0, canvas="frame", mode="median", every=1,
+                  min_count=1, iterations=6, sigma=1.0, lo=0.05, hi=0.15, alpha=None):
+    """A clip with what moves by itself removed (a "clean plate" shown through every frame; not in the reference): (video
+    (B, T + 1, C, H, W) fp32, fg (B, T + 1, 1, H, W) fp32, `Plate`, path (B, T + 1, 3, 3) float64).  It is `background_plate(clip, fwd,
+    bwd, conf, conf_bwd, model, anchor, canvas, mode, every, min_count, iterations, sigma)` followed by `project_plate(plate, path, H, W,
+    frames=clip, alpha=alpha, lo=lo, hi=hi)` on EVERY frame, voting or not; those two have the method.  fg is the matte that was used.
+    Limits: the plate is the background only where it is visible for more than half of the voting weight; a derived matte leaves a
+    thin rim, since nothing is dilated; nothing is inpainted where no frame saw the background; lo, hi and the homography default are
+    untuned on real footage.  Forward only; inputs are not modified."""
+    B, N, C, H, W = _plate_clip("remove_moving", clip)
+    plate_params(1, H, W, "frame", "median", 1, lo, hi, name="remove_moving")
+    if alpha is not None and (not torch.is_tensor(alpha) or tuple(alpha.shape) != (B, N, 1, H, W) or not alpha.is_floating_point()):
+        raise ValueError(f"remove_moving: alpha must be a floating-point (B, T + 1, 1, H, W) = {(B, N, 1, H, W)} tensor or None, got {_shape_of(alpha)}")
+    plate, _matrices, path, _weight = background_plate(clip, fwd, bwd, conf, conf_bwd, model, anchor, canvas, mode, every, min_count, iterations,
+                                                       sigma)
+    video, _covered, fg = project_plate(plate, path, H, W, frames=clip, alpha=alpha, lo=lo, hi=hi)
+    return video, fg, plate, path
+
+
 # ---- guided weighted median of a flow (not in the reference; semantics: include/ofd.h, `ofd_flow_median`) ----------------------------
 def median_params(radius=2, sigma_s=2.0, sigma_r=0.1, iterations=1, fill=False, name="median_filter_flow"):
     """the rules of the median's window, widths and passes (ValueError); host logic, no engine call"""
