@@ -21,12 +21,12 @@
 //
 // No float atomics, no host synchronisation; a thread writes only its own pixels: the same input gives the same bits.  Built with
 // -ffp-contract=off like the other warp units, so that the operation order the header states is the one that runs.  A float becomes a
-// gather index only after it passed the `inside` test, which a non-finite or huge value fails: every read is inside its plane.
-#include "warp_common.h"
+// gather index only after it passed cell_inside (gather.h), which a non-finite or huge value fails: every read is inside its plane.
+#include "gather.h"
 
 namespace ofd {
 
-constexpr int FC_TILE_W = 64, FC_TILE_H = 16, FC_THREADS = 256, FC_MAX_DILATE = 4, FC_MAX_SIDE = 32768;
+constexpr int FC_TILE_W = 64, FC_TILE_H = 16, FC_THREADS = 256, FC_MAX_DILATE = 4;      // gather.h's tile, its own thread layout (below)
 constexpr int FC_ROW_WORDS = 20;                                            // LDS row: 80 bytes >= 64 + 2 * 4, a row pass reads 3 words
 constexpr int FC_ROWS = FC_TILE_H + 2 * FC_MAX_DILATE;
 enum { FC_HELD = 0, FC_RELEASED = 1, FC_INCONSISTENT = 2, FC_LEAVES = 3, FC_UNMATCHED = 4, FC_INVALID = 5, FC_STATES = 6 };
@@ -41,23 +41,13 @@ struct FcArgs {
     float a1, a2, hmax, wmax;
 };
 
-__device__ __forceinline__ bool fc_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-
-// the corners and weights of the bilinear read at q, or those of (0, 0) where q is not inside
-struct FcCell {
-    int o00, o01, o10, o11;
-    float tx, ty;
+// the cell of the bilinear read at q, or that of (0, 0) where q is not inside (gather.h says why not bilinear_cell)
+struct FcCell : BilinearCell {
     bool inside;
 };
 __device__ __forceinline__ FcCell fc_cell(float qx, float qy, const FcArgs& a) {
-    const bool inside = qx >= 0.0f && qx <= a.wmax && qy >= 0.0f && qy <= a.hmax;     // false for NaN and Inf
-    const float sx = inside ? qx : 0.0f, sy = inside ? qy : 0.0f;
-    const int x0 = (int)sx, y0 = (int)sy;                                    // 0 <= s <= size - 1: truncation is floor
-    const int x1 = min(x0 + 1, a.W - 1), y1 = min(y0 + 1, a.H - 1);
-    return FcCell{y0 * a.W + x0, y0 * a.W + x1, y1 * a.W + x0, y1 * a.W + x1, sx - (float)x0, sy - (float)y0, inside};
-}
-__device__ __forceinline__ float fc_bilerp(const float* __restrict__ p, const FcCell& c) {
-    return (1.0f - c.ty) * ((1.0f - c.tx) * p[c.o00] + c.tx * p[c.o01]) + c.ty * ((1.0f - c.tx) * p[c.o10] + c.tx * p[c.o11]);
+    const bool inside = cell_inside(qx, qy, a.wmax, a.hmax);
+    return FcCell{cell_at(inside ? qx : 0.0f, inside ? qy : 0.0f, a.H, a.W), inside};
 }
 
 // the state of the pixel (x, y) with flow (fx, fy) before dilation -- FC_HELD stands for "consistent" -- and e2 (where it has one);
@@ -65,14 +55,14 @@ __device__ __forceinline__ float fc_bilerp(const float* __restrict__ p, const Fc
 __device__ __forceinline__ int fc_classify(const FcArgs& a, const float* __restrict__ gx, const float* __restrict__ gy, int x, int y,
                                            float fx, float fy, float& e2) {
     const FcCell c = fc_cell((float)x + fx, (float)y + fy, a);
-    const float vx = fc_bilerp(gx, c), vy = fc_bilerp(gy, c);
+    const float vx = bilerp(gx, c), vy = bilerp(gy, c);
     const float rx = fx + vx, ry = fy + vy;
     e2 = rx * rx + ry * ry;
     const float m = (fx * fx + fy * fy) + (vx * vx + vy * vy);
     const float bound = a.a1 * m + a.a2;
-    if (!(fc_finite(fx) && fc_finite(fy))) return FC_INVALID;
+    if (!(is_finite(fx) && is_finite(fy))) return FC_INVALID;
     if (!c.inside) return FC_LEAVES;
-    if (!(fc_finite(vx) && fc_finite(vy))) return FC_UNMATCHED;
+    if (!(is_finite(vx) && is_finite(vy))) return FC_UNMATCHED;
     return e2 <= bound ? FC_HELD : FC_INCONSISTENT;
 }
 
@@ -205,8 +195,8 @@ using namespace ofd;
 extern "C" int ofd_flow_consistency(const float* flow12, const float* flow21, float a1, float a2, int dilate, float* known, float* err,
                                     uint8_t* state, int32_t* counts, int B, int H, int W, void* stream) {
     OFD_CHECK_ARG(flow12 && flow21 && known && err && state && counts, "flow_consistency: null pointer");
-    OFD_CHECK_ARG(B > 0 && H > 0 && W > 0 && H <= FC_MAX_SIDE && W <= FC_MAX_SIDE,
-                  "flow_consistency: bad shape B=%d H=%d W=%d, H and W must be in 1..%d", B, H, W, FC_MAX_SIDE);
+    OFD_CHECK_ARG(B > 0 && H > 0 && W > 0 && H <= MAX_SIDE && W <= MAX_SIDE,
+                  "flow_consistency: bad shape B=%d H=%d W=%d, H and W must be in 1..%d", B, H, W, MAX_SIDE);
     OFD_CHECK_ARG(2 * (size_t)B * cdiv(H, FC_TILE_H) * cdiv(W, FC_TILE_W) < (1u << 30),
                   "flow_consistency: bad shape, 2 * B * ceil(H / %d) * ceil(W / %d) must be < 2^30", FC_TILE_H, FC_TILE_W);
     OFD_CHECK_ARG(4 * (size_t)B * (size_t)H * W < (1ull << 40), "flow_consistency: bad shape, 4*B*H*W must be < 2^40");

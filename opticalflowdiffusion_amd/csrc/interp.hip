@@ -12,14 +12,12 @@
 // -ffp-contract=off like the other warp units, so that the operation order the header states is the one that runs.  Every gather
 // index is formed from a coordinate that passed the `inside` test as a float first: a huge or non-finite flow never reaches an integer
 // conversion.
-#include "warp_common.h"
+#include "gather.h"
 
 namespace ofd {
 
 constexpr int INTERP_MAX_N = 64;
 constexpr int INTERP_MAX_C = 8;
-
-__device__ __forceinline__ bool interp_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
 template <int VEC> __device__ __forceinline__ void interp_load(const float* __restrict__ p, float (&v)[VEC]) {
     if constexpr (VEC == 4) {
@@ -35,10 +33,6 @@ template <int VEC> __device__ __forceinline__ void interp_store(float* __restric
     } else {
         p[0] = v[0];
     }
-}
-
-__device__ __forceinline__ float interp_bilerp(const float* __restrict__ p, size_t o00, size_t o01, size_t o10, size_t o11, float tx, float ty) {
-    return (1.0f - ty) * ((1.0f - tx) * p[o00] + tx * p[o01]) + ty * ((1.0f - tx) * p[o10] + tx * p[o11]);
 }
 
 struct InterpPrep {
@@ -71,23 +65,24 @@ template <int C, int VEC> __global__ void __launch_bounds__(256) interp_prep_ker
         float e[VEC], v[VEC];                                              // exp(Z) and the validity of every pixel
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
-            bool ok = interp_finite(fx[j]) && interp_finite(fy[j]);
+            bool ok = is_finite(fx[j]) && is_finite(fy[j]);
 #pragma unroll
-            for (int c = 0; c < C; ++c) ok = ok && interp_finite(av[c][j]);
+            for (int c = 0; c < C; ++c) ok = ok && is_finite(av[c][j]);
             v[j] = ok ? 1.0f : 0.0f;
             const float qx = (float)(x + j) + fx[j], qy = (float)y + fy[j];
             float z;
-            if (qx >= 0.0f && qx <= wmax && qy >= 0.0f && qy <= hmax) {    // false for NaN and Inf
+            if (cell_inside(qx, qy, wmax, hmax)) {
+                // bilinear_cell's rule with size_t offsets: ofd_interp_prep does not bound H * W below 2^31, as a BilinearCell needs
                 const int x0 = (int)qx, y0 = (int)qy;                      // 0 <= q <= size - 1: truncation is floor
                 const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
                 const float tx = qx - (float)x0, ty = qy - (float)y0;
-                const size_t o00 = (size_t)y0 * W + x0, o01 = (size_t)y0 * W + x1, o10 = (size_t)y1 * W + x0, o11 = (size_t)y1 * W + x1;
+                const BilinearCellOf<size_t> cell{(size_t)y0 * W + x0, (size_t)y0 * W + x1, (size_t)y1 * W + x0, (size_t)y1 * W + x1, tx, ty};
                 float d = 0.0f;
 #pragma unroll
-                for (int c = 0; c < C; ++c) d += fabsf(av[c][j] - interp_bilerp(fb + (size_t)c * plane, o00, o01, o10, o11, tx, ty));
+                for (int c = 0; c < C; ++c) d += fabsf(av[c][j] - bilerp(fb + (size_t)c * plane, cell));
                 d = d / (float)C;
-                const float rx = fx[j] + interp_bilerp(wba, o00, o01, o10, o11, tx, ty);
-                const float ry = fy[j] + interp_bilerp(wba + plane, o00, o01, o10, o11, tx, ty);
+                const float rx = fx[j] + bilerp(wba, cell);
+                const float ry = fy[j] + bilerp(wba + plane, cell);
                 z = -a.alpha * d - a.beta * sqrtf(rx * rx + ry * ry);
             } else {
                 z = -a.alpha * a.oob;

@@ -382,10 +382,10 @@ extern "C" int ofd_motion_layers(const float* flow, const float* conf, int B, in
     const size_t obytes[4] = {BK * 8 * sizeof(double), BK * 9 * sizeof(double), BK * 4 * sizeof(double),
                               ofd_motion_layers_ws_doubles(B, K, H, W) * sizeof(double)};
     for (int k = 0; k < 4; ++k) {
-        OFD_CHECK_ARG(!ch_overlap(outs[k], obytes[k], flow, 2 * px) && !ch_overlap(outs[k], obytes[k], conf, px),
+        OFD_CHECK_ARG(!ranges_overlap(outs[k], obytes[k], flow, 2 * px) && !ranges_overlap(outs[k], obytes[k], conf, px),
                       "motion_layers: an output (params, matrix, stats, ws: %d) must not alias flow or conf", k);
         for (int j = 0; j < k; ++j)
-            OFD_CHECK_ARG(!ch_overlap(outs[k], obytes[k], outs[j], obytes[j]), "motion_layers: the outputs %d and %d alias each other", j, k);
+            OFD_CHECK_ARG(!ranges_overlap(outs[k], obytes[k], outs[j], obytes[j]), "motion_layers: the outputs %d and %d alias each other", j, k);
     }
     hipStream_t s = (hipStream_t)stream;
     const bool vec = plane % 4 == 0 && mo_aligned16(flow) && (!conf || mo_aligned16(conf));
@@ -435,10 +435,10 @@ extern "C" int ofd_motion_assign(const double* matrix, const uint8_t* alive, con
     for (int k = 0; k < 5; ++k) {
         if (!outs[k]) continue;
         for (int j = 0; j < 5; ++j)
-            OFD_CHECK_ARG(!ch_overlap(outs[k], obytes[k], ins[j], ibytes[j]),
+            OFD_CHECK_ARG(!ranges_overlap(outs[k], obytes[k], ins[j], ibytes[j]),
                           "motion_assign: an output (labels, dist, model_flow, residual, counts: %d) must not alias an input (%d)", k, j);
         for (int j = 0; j < k; ++j)
-            OFD_CHECK_ARG(!ch_overlap(outs[k], obytes[k], outs[j], obytes[j]), "motion_assign: the outputs %d and %d alias each other", j, k);
+            OFD_CHECK_ARG(!ranges_overlap(outs[k], obytes[k], outs[j], obytes[j]), "motion_assign: the outputs %d and %d alias each other", j, k);
     }
     hipStream_t s = (hipStream_t)stream;
     if (counts) OFD_HIP(hipMemsetAsync(counts, 0, obytes[4], s));
@@ -460,7 +460,7 @@ extern "C" int ofd_label_vote(const uint8_t* labels, uint8_t* out, int B, int H,
     OFD_CHECK_ARG((size_t)B * tiles_y * tiles_x < (1u << 30), "label_vote: bad shape, B * ceil(H / %d) * ceil(W / %d) must be < 2^30",
                   LY_TILE_H, LY_TILE_W);
     const size_t bytes = (size_t)B * H * W;
-    OFD_CHECK_ARG(!ch_overlap(out, bytes, labels, bytes), "label_vote: out must not alias labels");
+    OFD_CHECK_ARG(!ranges_overlap(out, bytes, labels, bytes), "label_vote: out must not alias labels");
     const int tiles = B * tiles_y * tiles_x;
     label_vote_kernel<<<tiles < (1 << 20) ? tiles : (1 << 20), 256, 0, (hipStream_t)stream>>>(labels, out, B, H, W, K, radius, tiles_x, tiles_y,
                                                                                              tiles);

@@ -20,11 +20,11 @@
 // All sums are integer sums: the result does not depend on their order.  No branch depends on data, no float becomes an index, no
 // atomics, no host synchronisation, one launch; a thread writes only its own pixels: the same input gives the same bits.  Built with
 // -ffp-contract=off like the other warp units, so that the operation order the header states is the one that runs.
-#include "warp_common.h"
+#include "gather.h"
 
 namespace ofd {
 
-constexpr int FM_TILE_W = 64, FM_TILE_H = 16, FM_THREADS = 256, FM_MAX_C = 4, FM_MAX_CG = 4, FM_MAX_RADIUS = 3, FM_MAX_SIDE = 32768;
+constexpr int FM_TILE_W = 64, FM_TILE_H = 16, FM_THREADS = 256, FM_MAX_C = 4, FM_MAX_CG = 4, FM_MAX_RADIUS = 3;
 
 struct FmArgs {
     const float* flow;              // (B, C, H, W)
@@ -35,8 +35,6 @@ struct FmArgs {
     float k_r;                      // 1 / (Cg * 2 sigma_r^2); 0 for sigma_r = +inf and for Cg = 0
     float zs[2 * FM_MAX_RADIUS * FM_MAX_RADIUS + 1];      // -d / (2 sigma_s^2) for d = dx^2 + dy^2 = 0 .. 2 radius^2
 };
-
-__device__ __forceinline__ bool fm_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
 // the lower weighted median of one plane: v, w: the values and weights of the N taps, j ascending; T: the sum of w, > 0
 template <int N> __device__ __forceinline__ float fm_select(const float (&v)[N], const uint32_t (&w)[N], uint32_t T) {
@@ -82,7 +80,7 @@ template <int R> __global__ void __launch_bounds__(FM_THREADS) flow_median_kerne
             bool ok = inside;
             for (int c = 0; c < C; ++c) {
                 const float v = flow_b[c * plane + off];
-                ok = ok && fm_finite(v);
+                ok = ok && is_finite(v);
                 fm_lds[c * PLANE + q] = inside ? v : 0.0f;
             }
             for (int c = 0; c < Cg; ++c) fm_lds[(C + c) * PLANE + q] = inside ? guide_b[c * plane + off] : 0.0f;
@@ -124,7 +122,7 @@ template <int R> __global__ void __launch_bounds__(FM_THREADS) flow_median_kerne
                 T += w[j];
             }
             bool own = true;                                                // the pixel's own flow is finite in every plane
-            for (int c = 0; c < C; ++c) own = own && fm_finite(win[c * PLANE + R * STRIDE + R]);
+            for (int c = 0; c < C; ++c) own = own && is_finite(win[c * PLANE + R * STRIDE + R]);
             const bool some = T > 0 && (own || a.fill != 0);
 #pragma unroll 1
             for (int c = 0; c < C; ++c) {                                   // rolled: one copy of the pair network in the code
@@ -154,11 +152,6 @@ template <int R> __global__ void __launch_bounds__(FM_THREADS) flow_median_kerne
     }
 }
 
-// [p, p + n) and [q, q + m) share a byte
-static bool fm_overlap(const void* p, size_t n, const void* q, size_t m) {
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return q != nullptr && a < b + m && b < a + n;
-}
 
 }  // namespace ofd
 using namespace ofd;
@@ -169,8 +162,8 @@ extern "C" int ofd_flow_median(const float* flow, const float* guide, const floa
     OFD_CHECK_ARG(Cg >= 0 && Cg <= FM_MAX_CG, "flow_median: bad shape Cg=%d, Cg must be in 0..%d", Cg, FM_MAX_CG);
     OFD_CHECK_ARG((guide != nullptr) == (Cg > 0), "flow_median: guide must be null exactly when Cg == 0, got Cg=%d", Cg);
     OFD_CHECK_ARG(C >= 1 && C <= FM_MAX_C, "flow_median: bad shape C=%d, C must be in 1..%d", C, FM_MAX_C);
-    OFD_CHECK_ARG(B > 0 && H > 0 && W > 0 && H <= FM_MAX_SIDE && W <= FM_MAX_SIDE,
-                  "flow_median: bad shape B=%d H=%d W=%d, H and W must be in 1..%d", B, H, W, FM_MAX_SIDE);
+    OFD_CHECK_ARG(B > 0 && H > 0 && W > 0 && H <= MAX_SIDE && W <= MAX_SIDE,
+                  "flow_median: bad shape B=%d H=%d W=%d, H and W must be in 1..%d", B, H, W, MAX_SIDE);
     OFD_CHECK_ARG((size_t)B * cdiv(H, FM_TILE_H) * cdiv(W, FM_TILE_W) < (1u << 30),
                   "flow_median: bad shape, B * ceil(H / %d) * ceil(W / %d) must be < 2^30", FM_TILE_H, FM_TILE_W);
     OFD_CHECK_ARG((size_t)B * (C + Cg + 1) * (size_t)H * W < (1ull << 40), "flow_median: bad shape, B*(C+Cg+1)*H*W must be < 2^40");
@@ -179,7 +172,8 @@ extern "C" int ofd_flow_median(const float* flow, const float* guide, const floa
                   (double)sigma_s, (double)sigma_r);
     OFD_CHECK_ARG(fill == 0 || fill == 1, "flow_median: fill=%d, fill must be 0 or 1", fill);
     const size_t pix = (size_t)B * H * W * sizeof(float);
-    OFD_CHECK_ARG(!fm_overlap(out, C * pix, flow, C * pix) && !fm_overlap(out, C * pix, guide, Cg * pix) && !fm_overlap(out, C * pix, conf, pix),
+    OFD_CHECK_ARG(!ranges_overlap(out, C * pix, flow, C * pix) && !ranges_overlap(out, C * pix, guide, Cg * pix) &&
+                      !ranges_overlap(out, C * pix, conf, pix),
                   "flow_median: out must not overlap flow, guide or conf (the filter is not in place)");
     FmArgs a;
     a.flow = flow; a.guide = guide; a.conf = conf; a.out = out;

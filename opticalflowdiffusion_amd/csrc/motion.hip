@@ -15,8 +15,9 @@
 //           and after the last solve writes the pixel-coordinate matrix.  No atomics, no float accumulation: the same input gives
 //           the same bits.
 //   field   one elementwise launch, all arithmetic in double and rounded once.
-//   warp    the tile, thread layout and XCD-aware order of chain.hip (chain_common.h); the source position and its floor in double, the
-//           blend in fp32 in ch_bilerp's order; no LDS, no atomics.  A position becomes an index only after it passed the inside test.
+//   warp    the tile, thread layout and XCD-aware order of gather.h; the source position and its floor in double (so the cell is formed
+//           here, by bilinear_cell's rule on doubles), the blend in fp32 in bilerp's order; no LDS, no atomics.  A position becomes an
+//           index only after it passed the inside test.
 //
 // Built with -ffp-contract=off like the other warp units, so that the operation order the header states is the one that runs.
 // Measured (tools/motion_bench.py): no model's pass is bound by HBM; what bounds it -- the double divisions and the
@@ -52,7 +53,7 @@ __global__ void __launch_bounds__(256) motion_accumulate_kernel(const float* __r
 #pragma unroll
             for (int j = 0; j < VEC; ++j) {
                 const float cj = fc ? c.v[j] : 1.0f;
-                if (!(ch_finite(u.v[j]) && ch_finite(v.v[j]) && ch_finite(cj) && cj > 0.0f)) continue;      // weight 0: not read further
+                if (!(is_finite(u.v[j]) && is_finite(v.v[j]) && is_finite(cj) && cj > 0.0f)) continue;      // weight 0: not read further
                 const unsigned pix = (unsigned)(i * VEC + j), y = pix / (unsigned)f.W;
                 mo_pixel<MODEL>(u.v[j], v.v[j], (double)cj, (int)(pix - y * (unsigned)f.W), (int)y, f, p, first != 0, sig2, acc);
             }
@@ -120,7 +121,7 @@ __global__ void __launch_bounds__(256) motion_field_kernel(const double* __restr
             const double r2 = (double)rx * (double)rx + (double)ry * (double)ry;
             const double g = 1.0 + r2 / sig2;
             const double rho = 1.0 / (g * g);
-            const bool fin = ch_finite(rx) && ch_finite(ry) && ch_finite(c) && c > 0.0f;
+            const bool fin = is_finite(rx) && is_finite(ry) && is_finite(c) && c > 0.0f;
             weight[q.n * plane + q.pix] = fin ? (float)((double)c * rho) : 0.0f;
         }
     }
@@ -131,24 +132,24 @@ struct MoWarp {
     const double* matrix;           // (B, 9): output pixel -> source position
     float* out;                     // (B, C, H, W)
     float* inside;                  // (B, 1, H, W) or null
-    ChGeom g;
+    TileGeom g;
 };
 
-template <int C> __global__ void __launch_bounds__(CH_THREADS) homography_warp_kernel(MoWarp a) {
-    const ChGeom g = a.g;
+template <int C> __global__ void __launch_bounds__(TILE_THREADS) homography_warp_kernel(MoWarp a) {
+    const TileGeom g = a.g;
     const size_t plane = (size_t)g.H * g.W;
     const double wmax = (double)(g.W - 1), hmax = (double)(g.H - 1);
     for (int t = blockIdx.x; t < g.tiles; t += gridDim.x) {
         int walk, y, x;
         size_t b;
-        if (!ch_decode(t, g, walk, b, y, x)) continue;                      // no barrier in this loop, and such a thread owns no pixel
-        const int rows = min(CH_ROWS, g.H - y);
+        if (!tile_decode(t, g, walk, b, y, x)) continue;                    // no barrier in this loop, and such a thread owns no pixel
+        const int rows = min(TILE_ROWS, g.H - y);
         const size_t pix = (size_t)y * g.W + x;
         const double* M = a.matrix + b * 9;                                 // uniform in the workgroup
         const float* src = a.img + b * C * plane;
-        float o[C][CH_ROWS], in[CH_ROWS];
+        float o[C][TILE_ROWS], in[TILE_ROWS];
 #pragma unroll
-        for (int k = 0; k < CH_ROWS; ++k) {
+        for (int k = 0; k < TILE_ROWS; ++k) {
             double X, Y;
             const bool ok = mo_project(M, x, y + min(k, rows - 1), X, Y) && X >= 0.0 && X <= wmax && Y >= 0.0 && Y <= hmax;      // false for NaN
             const double sx = ok ? X : 0.0, sy = ok ? Y : 0.0;
@@ -156,10 +157,10 @@ template <int C> __global__ void __launch_bounds__(CH_THREADS) homography_warp_k
             const int x0 = (int)fx, y0 = (int)fy;                           // 0 <= s <= size - 1
             const int dx = ok && x0 < g.W - 1 ? 1 : 0, dy = ok && y0 < g.H - 1 ? g.W : 0;
             const int o00 = y0 * g.W + x0;
-            const ChCell c{o00, o00 + dx, o00 + dy, o00 + dy + dx, (float)(sx - fx), (float)(sy - fy)};
+            const BilinearCell c{o00, o00 + dx, o00 + dy, o00 + dy + dx, (float)(sx - fx), (float)(sy - fy)};
 #pragma unroll
             for (int ch = 0; ch < C; ++ch) {
-                const float v = ch_bilerp(src + (size_t)ch * plane, c);     // a pixel outside reads offset 0 and drops it
+                const float v = bilerp(src + (size_t)ch * plane, c);        // a pixel outside reads offset 0 and drops it
                 o[ch][k] = ok ? v : 0.0f;
             }
             in[k] = ok ? 1.0f : 0.0f;
@@ -168,25 +169,25 @@ template <int C> __global__ void __launch_bounds__(CH_THREADS) homography_warp_k
 #pragma unroll
         for (int ch = 0; ch < C; ++ch)
 #pragma unroll
-            for (int k = 0; k < CH_ROWS; ++k)
+            for (int k = 0; k < TILE_ROWS; ++k)
                 if (k < rows) dst[(size_t)ch * plane + (size_t)k * g.W] = o[ch][k];
         if (a.inside)
 #pragma unroll
-            for (int k = 0; k < CH_ROWS; ++k)
+            for (int k = 0; k < TILE_ROWS; ++k)
                 if (k < rows) a.inside[b * plane + pix + (size_t)k * g.W] = in[k];
     }
 }
 
 static void homography_warp_launch(int C, int grid, hipStream_t s, const MoWarp& a) {
     switch (C) {
-        case 1: homography_warp_kernel<1><<<grid, CH_THREADS, 0, s>>>(a); break;
-        case 2: homography_warp_kernel<2><<<grid, CH_THREADS, 0, s>>>(a); break;
-        case 3: homography_warp_kernel<3><<<grid, CH_THREADS, 0, s>>>(a); break;
-        case 4: homography_warp_kernel<4><<<grid, CH_THREADS, 0, s>>>(a); break;
-        case 5: homography_warp_kernel<5><<<grid, CH_THREADS, 0, s>>>(a); break;
-        case 6: homography_warp_kernel<6><<<grid, CH_THREADS, 0, s>>>(a); break;
-        case 7: homography_warp_kernel<7><<<grid, CH_THREADS, 0, s>>>(a); break;
-        default: homography_warp_kernel<8><<<grid, CH_THREADS, 0, s>>>(a); break;
+        case 1: homography_warp_kernel<1><<<grid, TILE_THREADS, 0, s>>>(a); break;
+        case 2: homography_warp_kernel<2><<<grid, TILE_THREADS, 0, s>>>(a); break;
+        case 3: homography_warp_kernel<3><<<grid, TILE_THREADS, 0, s>>>(a); break;
+        case 4: homography_warp_kernel<4><<<grid, TILE_THREADS, 0, s>>>(a); break;
+        case 5: homography_warp_kernel<5><<<grid, TILE_THREADS, 0, s>>>(a); break;
+        case 6: homography_warp_kernel<6><<<grid, TILE_THREADS, 0, s>>>(a); break;
+        case 7: homography_warp_kernel<7><<<grid, TILE_THREADS, 0, s>>>(a); break;
+        default: homography_warp_kernel<8><<<grid, TILE_THREADS, 0, s>>>(a); break;
     }
 }
 
@@ -212,10 +213,10 @@ extern "C" int ofd_motion_fit(const float* flow, const float* conf, int B, int H
     const size_t obytes[4] = {(size_t)B * 8 * sizeof(double), (size_t)B * 9 * sizeof(double), (size_t)B * 4 * sizeof(double),
                               ofd_motion_fit_ws_doubles(B, H, W) * sizeof(double)};
     for (int k = 0; k < 4; ++k) {
-        OFD_CHECK_ARG(!ch_overlap(outs[k], obytes[k], flow, 2 * px) && !ch_overlap(outs[k], obytes[k], conf, px),
+        OFD_CHECK_ARG(!ranges_overlap(outs[k], obytes[k], flow, 2 * px) && !ranges_overlap(outs[k], obytes[k], conf, px),
                       "motion_fit: an output (params, matrix, stats, ws: %d) must not alias flow or conf", k);
         for (int j = 0; j < k; ++j)
-            OFD_CHECK_ARG(!ch_overlap(outs[k], obytes[k], outs[j], obytes[j]), "motion_fit: the outputs %d and %d alias each other", j, k);
+            OFD_CHECK_ARG(!ranges_overlap(outs[k], obytes[k], outs[j], obytes[j]), "motion_fit: the outputs %d and %d alias each other", j, k);
     }
     hipStream_t s = (hipStream_t)stream;
     const bool vec = plane % 4 == 0 && mo_aligned16(flow) && (!conf || mo_aligned16(conf));
@@ -248,11 +249,11 @@ extern "C" int ofd_motion_field(const double* matrix, const float* flow, const f
     const size_t obytes[3] = {2 * px, 2 * px, px};
     for (int k = 0; k < 3; ++k) {
         if (!outs[k]) continue;
-        OFD_CHECK_ARG(!ch_overlap(outs[k], obytes[k], flow, 2 * px) && !ch_overlap(outs[k], obytes[k], conf, px) &&
-                          !ch_overlap(outs[k], obytes[k], matrix, mbytes),
+        OFD_CHECK_ARG(!ranges_overlap(outs[k], obytes[k], flow, 2 * px) && !ranges_overlap(outs[k], obytes[k], conf, px) &&
+                          !ranges_overlap(outs[k], obytes[k], matrix, mbytes),
                       "motion_field: an output (model_flow, residual, weight: %d) must not alias matrix, flow or conf", k);
         for (int j = 0; j < k; ++j)
-            OFD_CHECK_ARG(!ch_overlap(outs[k], obytes[k], outs[j], obytes[j]), "motion_field: the outputs %d and %d alias each other", j, k);
+            OFD_CHECK_ARG(!ranges_overlap(outs[k], obytes[k], outs[j], obytes[j]), "motion_field: the outputs %d and %d alias each other", j, k);
     }
     const size_t total = (size_t)B * H * W;
     motion_field_kernel<<<stream_grid(total, 256), 256, 0, (hipStream_t)stream>>>(matrix, flow, conf, (double)sigma * (double)sigma, model_flow,
@@ -264,16 +265,16 @@ extern "C" int ofd_motion_field(const double* matrix, const float* flow, const f
 extern "C" int ofd_homography_warp(const float* img, const double* matrix, float* out, float* inside, int B, int C, int H, int W,
                                    void* stream) {
     OFD_CHECK_ARG(img && matrix && out, "homography_warp: null pointer (img, matrix, out)");
-    OFD_CHECK_ARG(C >= 1 && C <= CH_MAX_C, "homography_warp: bad shape C=%d, C must be in 1..%d", C, CH_MAX_C);
+    OFD_CHECK_ARG(C >= 1 && C <= MO_MAX_C, "homography_warp: bad shape C=%d, C must be in 1..%d", C, MO_MAX_C);
     MO_CHECK_SHAPE("homography_warp", B, H, W, C);
-    OFD_CHECK_ARG((size_t)B * cdiv(H, CH_TILE_H) * cdiv(W, CH_TILE_W) < (1u << 30),
-                  "homography_warp: bad shape, B * ceil(H / %d) * ceil(W / %d) must be < 2^30", CH_TILE_H, CH_TILE_W);
+    OFD_CHECK_ARG((size_t)B * cdiv(H, TILE_H) * cdiv(W, TILE_W) < (1u << 30),
+                  "homography_warp: bad shape, B * ceil(H / %d) * ceil(W / %d) must be < 2^30", TILE_H, TILE_W);
     const size_t px = (size_t)B * H * W * sizeof(float), mbytes = (size_t)B * 9 * sizeof(double);
-    OFD_CHECK_ARG(!ch_overlap(out, px * C, img, px * C) && !ch_overlap(out, px * C, matrix, mbytes) && !ch_overlap(inside, px, img, px * C) &&
-                      !ch_overlap(inside, px, matrix, mbytes) && !ch_overlap(inside, px, out, px * C),
+    OFD_CHECK_ARG(!ranges_overlap(out, px * C, img, px * C) && !ranges_overlap(out, px * C, matrix, mbytes) && !ranges_overlap(inside, px, img, px * C) &&
+                      !ranges_overlap(inside, px, matrix, mbytes) && !ranges_overlap(inside, px, out, px * C),
                   "homography_warp: out and inside must not alias img, matrix or each other");
-    const MoWarp a{img, matrix, out, inside, ch_geom(B, H, W, (size_t)B)};
-    homography_warp_launch(C, ch_grid(a.g), (hipStream_t)stream, a);
+    const MoWarp a{img, matrix, out, inside, tile_geom(B, H, W, (size_t)B)};
+    homography_warp_launch(C, tile_grid(a.g), (hipStream_t)stream, a);
     OFD_LAUNCH_CHECK();
     return OFD_OK;
 }

@@ -4,12 +4,13 @@
 // the order the header states; both units are built with -ffp-contract=off so that this order is the one that runs.
 #pragma once
 #include <cmath>
-#include "chain_common.h"
 #include "diffusion_common.h"
+#include "gather.h"
 #include "reduce.h"
 
 namespace ofd {
 
+constexpr int MO_MAX_C = 8;           // the most planes of an image read through a matrix (the homography warp, the plate)
 constexpr int MO_BLOCKS = 2048;       // the largest grid of one accumulate launch, as ROWS_BLOCKS
 constexpr int MO_WPS = 128;           // the most workgroups a sample's pixels are spread over
 constexpr int MO_MAX_ITER = 64, MO_MAX_P = 8;
@@ -44,7 +45,7 @@ static MoPlan mo_plan(size_t B, size_t units) {
 __device__ __forceinline__ bool mo_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }      // false for NaN
 
 // a usable pixel: u, v and the confidence finite, the confidence > 0 (M4)
-__device__ __forceinline__ bool mo_usable(float u, float v, float c) { return ch_finite(u) && ch_finite(v) && ch_finite(c) && c > 0.0f; }
+__device__ __forceinline__ bool mo_usable(float u, float v, float c) { return is_finite(u) && is_finite(v) && is_finite(c) && c > 0.0f; }
 
 // which entries of the two design rows of a pixel are not statically zero (M3): Jx = [1, 0, xn, +-yn, 0, 0, -xn x', -yn x'],
 // Jy = [0, 1, ...]; the similarity's Jy = [0, 1, yn, xn], the others' Jy = [0, 1, 0, 0, xn, yn, -xn y', -yn y']
@@ -240,6 +241,6 @@ static bool mo_aligned16(const void* p) { return ((uintptr_t)p % 16) == 0; }
 }  // namespace ofd
 
 #define MO_CHECK_SHAPE(what, B, H, W, planes)                                                                                              \
-    OFD_CHECK_ARG(B > 0 && H > 0 && W > 0 && H <= CH_MAX_SIDE && W <= CH_MAX_SIDE,                                                           \
-                  what ": bad shape B=%d H=%d W=%d, H and W must be in 1..%d", B, H, W, CH_MAX_SIDE);                                        \
+    OFD_CHECK_ARG(B > 0 && H > 0 && W > 0 && H <= MAX_SIDE && W <= MAX_SIDE,                                                               \
+                  what ": bad shape B=%d H=%d W=%d, H and W must be in 1..%d", B, H, W, MAX_SIDE);                                         \
     OFD_CHECK_ARG((size_t)B * (size_t)(planes) * (size_t)H * W < (1ull << 40), what ": bad shape, B*%d*H*W must be < 2^40", (int)(planes))

@@ -62,7 +62,8 @@ __global__ void __launch_bounds__(256) photo_pyramid_kernel(const float* __restr
 }
 
 // the bilinear cell of a coordinate c that lies in [0, n - 1]: i0 = floor(c), except that the far edge belongs to the last cell; n == 1 is
-// a single sample (i0 == i1, t == 0).  Both indices are in [0, n - 1].
+// a single sample (i0 == i1, t == 0).  Both indices are in [0, n - 1].  Not gather.h's bilinear_cell, a different rule: there the far edge
+// starts a cell of its own with t == 0, here it belongs to the last cell and t reaches 1.
 __device__ __forceinline__ void photo_cell(float c, int n, int& i0, int& i1, float& t) {
     int i = (int)c;                       // 0 <= c <= n - 1 < 2^31: no overflow, truncation is floor
     i = min(i, max(n - 2, 0));

@@ -5,15 +5,15 @@
 // median or a weighted mean; ofd_plate_project reads the plate back into every frame and, given the frames, replaces what does not
 // belong to the background.  Semantics: include/ofd.h (P1 ... P8).  Built with -ffp-contract=off: every operation is rounded on its own.
 //
-// Layout of the reduction.  One workgroup of 256 threads per 64 x 16 canvas tile in the XCD-aware order; a thread owns one column of
-// four rows and finishes one pixel before it starts the next: the N samples of a pixel, not four rows of them, are what the register
-// file holds.  The kernel is a template of N rounded up to 4, 8, 16 or 32 and every loop over the samples is unrolled, so that each
-// sample's cell, weight and value is a register of its own (an array indexed at run time would live in scratch).  Per pixel the N
-// CELLS are kept across the planes -- the corner offset with its two border flags in one word, and the two fp32 weights: 3 registers
-// a sample -- rather than the positions recomputed per plane: a position costs two double divisions, about the instructions of a
-// whole 32-sample count, and C + 1 planes would pay it C + 1 times.  The median is counted, not sorted (as in median.hip): for each
-// candidate the weights of the samples not after it are added, N (N - 1) compare-and-add pairs with no data-dependent branch and no
-// movement of values, all at compile-time register positions; a sorting network would have to carry the weight and the index along.
+// Layout of the reduction.  The tile and thread layout of gather.h over the canvas, except that a thread finishes one pixel of its column
+// of four rows before it starts the next: the N samples of a pixel, not four rows of them, are what the register file holds.  The kernel
+// is a template of N rounded up to 4, 8, 16 or 32 and every loop over the samples is unrolled, so that each sample's cell, weight and
+// value is a register of its own (an array indexed at run time would live in scratch).  Per pixel the N CELLS are kept across the planes
+// -- the corner offset with its two border flags in one word, and the two fp32 weights: 3 registers a sample -- rather than the positions
+// recomputed per plane: a position costs two double divisions, about the instructions of a whole 32-sample count, and C + 1 planes would
+// pay it C + 1 times.  The median is counted, not sorted (as in median.hip): for each candidate the weights of the samples not after it
+// are added, N (N - 1) compare-and-add pairs with no data-dependent branch and no movement of values, all at compile-time register
+// positions; a sorting network would have to carry the weight and the index along.
 #include "motion_common.h"
 
 namespace ofd {
@@ -22,9 +22,10 @@ constexpr int PL_MAX_N = OFD_PLATE_MAX_FRAMES;
 constexpr int PL_GRID = 2048;                  // the largest grid: a workgroup walks the tiles beyond it
 constexpr int PL_GROUP = 4;                    // samples whose gathers are in flight together
 
-// the bilinear cell of a read in an h x w plane: the north-west corner's offset (< 2^30) with bit 30 set where the east corners are one
-// pixel on and bit 31 where the south corners are one row on (clear at the last column and row, and wherever `ok` is false: such a
-// read is offset 0 four times), and the fp32 weights.  `ok`: the position is valid and inside, so that 0 <= X <= w - 1, 0 <= Y <= h - 1.
+// the bilinear cell of a read in an h x w plane, packed into three registers a sample where gather.h's BilinearCell is six, and formed
+// from a position in double: the north-west corner's offset (< 2^30) with bit 30 set where the east corners are one pixel on and bit 31
+// where the south corners are one row on (clear at the last column and row, and wherever `ok` is false: such a read is offset 0 four
+// times), and the fp32 weights.  `ok`: the position is valid and inside, so that 0 <= X <= w - 1, 0 <= Y <= h - 1.
 struct PlCell {
     unsigned o;
     float tx, ty;
@@ -36,11 +37,11 @@ __device__ __forceinline__ PlCell pl_cell(bool ok, double X, double Y, int h, in
     const unsigned o = (unsigned)(y0 * w + x0) | (ok && x0 < w - 1 ? 1u << 30 : 0u) | (ok && y0 < h - 1 ? 1u << 31 : 0u);
     return PlCell{o, (float)(sx - fx), (float)(sy - fy)};
 }
-__device__ __forceinline__ ChCell pl_corners(const PlCell& c, int w) {
+__device__ __forceinline__ BilinearCell pl_corners(const PlCell& c, int w) {
     const int o00 = (int)(c.o & 0x3fffffffu), dx = (int)((c.o >> 30) & 1u), dy = (c.o >> 31) ? w : 0;
-    return ChCell{o00, o00 + dx, o00 + dy, o00 + dy + dx, c.tx, c.ty};
+    return BilinearCell{o00, o00 + dx, o00 + dy, o00 + dy + dx, c.tx, c.ty};
 }
-__device__ __forceinline__ float pl_read(const float* __restrict__ p, const PlCell& c, int w) { return ch_bilerp(p, pl_corners(c, w)); }
+__device__ __forceinline__ float pl_read(const float* __restrict__ p, const PlCell& c, int w) { return bilerp(p, pl_corners(c, w)); }
 
 struct PlReduce {
     const float* clip;              // (B, N, C, H, W)
@@ -50,21 +51,21 @@ struct PlReduce {
     float* votes;                   // (B, 1, Hc, Wc) or null
     uint8_t* count;                 // (B, 1, Hc, Wc) or null
     int N, C, H, W, x0, y0, min_count;
-    ChGeom g;                       // the canvas
+    TileGeom g;                     // the canvas
 };
 
 // two workgroups a CU for the median: at NB = 32 that holds it to 256 registers (248 used, none spilled) and two waves a SIMD hide each
 // other's gathers; the mean at NB = 32 would spill under that bound and keeps the whole file
-template <int NB, int MODE> __global__ void __launch_bounds__(CH_THREADS, MODE == 0 ? 2 : 1) plate_reduce_kernel(PlReduce a) {
-    const ChGeom g = a.g;
+template <int NB, int MODE> __global__ void __launch_bounds__(TILE_THREADS, MODE == 0 ? 2 : 1) plate_reduce_kernel(PlReduce a) {
+    const TileGeom g = a.g;
     const int N = a.N, C = a.C, W = a.W, H = a.H;
     const size_t plane = (size_t)H * W, cplane = (size_t)g.H * g.W;
     const double wmax = (double)(W - 1), hmax = (double)(H - 1);
     for (int t = blockIdx.x; t < g.tiles; t += gridDim.x) {
         int walk, y, x;
         size_t b;
-        if (!ch_decode(t, g, walk, b, y, x)) continue;                      // no barrier in this loop, and such a thread owns no pixel
-        const int rows = min(CH_ROWS, g.H - y);
+        if (!tile_decode(t, g, walk, b, y, x)) continue;                    // no barrier in this loop, and such a thread owns no pixel
+        const int rows = min(TILE_ROWS, g.H - y);
         const double* M = a.path + b * N * 9;                               // uniform in the workgroup
         const float* src = a.clip + b * N * C * plane;
         const float* wsrc = a.weight ? a.weight + b * N * plane : nullptr;
@@ -91,7 +92,7 @@ template <int NB, int MODE> __global__ void __launch_bounds__(CH_THREADS, MODE =
                                     f < N;
                     cell[f] = pl_cell(ok, X, Y, H, W);
                     const float w = wsrc ? pl_read(wsrc + (size_t)fs * plane, cell[f], W) : 1.0f;
-                    const float ws = ok && ch_finite(w) && w > 0.0f ? w : 0.0f;
+                    const float ws = ok && is_finite(w) && w > 0.0f ? w : 0.0f;
                     q[f] = (uint32_t)floorf(fminf(ws, 1.0f) * 65535.0f + 0.5f);
                 }
             }
@@ -125,7 +126,7 @@ template <int NB, int MODE> __global__ void __launch_bounds__(CH_THREADS, MODE =
                             PlCell cc = cell[f];
                             asm volatile("" : "+v"(cc.o), "+v"(cc.tx), "+v"(cc.ty));            // three registers a sample cross the planes, not
                             v[f] = pl_read(src + ((size_t)fs * C + c) * plane, cc, W);          // the addresses and weights derived from them
-                            bad |= q[f] != 0u && !ch_finite(v[f]) ? 1u << f : 0u;
+                            bad |= q[f] != 0u && !is_finite(v[f]) ? 1u << f : 0u;
                         }
                     }
                     float res = 0.0f;
@@ -167,8 +168,8 @@ template <int NB, int MODE> __global__ void __launch_bounds__(CH_THREADS, MODE =
 }
 
 template <int NB> static void plate_reduce_launch(int mode, int grid, hipStream_t s, const PlReduce& a) {
-    if (mode == 0) plate_reduce_kernel<NB, 0><<<grid, CH_THREADS, 0, s>>>(a);
-    else plate_reduce_kernel<NB, 1><<<grid, CH_THREADS, 0, s>>>(a);
+    if (mode == 0) plate_reduce_kernel<NB, 0><<<grid, TILE_THREADS, 0, s>>>(a);
+    else plate_reduce_kernel<NB, 1><<<grid, TILE_THREADS, 0, s>>>(a);
 }
 
 struct PlProject {
@@ -182,22 +183,22 @@ struct PlProject {
     float* fg;                      // (B, N, 1, H, W) or null
     int N, Hc, Wc, x0, y0;
     float lo, hi;
-    ChGeom g;                       // the frames: B * N units
+    TileGeom g;                     // the frames: B * N units
 };
 
 // FRAMES: the frames are given.  Inside the four rows there is no branch: votes and alpha are read through pointers that are always
 // valid (the plate's first plane, the frames' first planes stand in for a missing one) and a uniform flag drops what was read, so the
 // rows are one block and all their loads are in flight together.
-template <int C, bool FRAMES> __global__ void __launch_bounds__(CH_THREADS) plate_project_kernel(PlProject a) {
-    const ChGeom g = a.g;
+template <int C, bool FRAMES> __global__ void __launch_bounds__(TILE_THREADS) plate_project_kernel(PlProject a) {
+    const TileGeom g = a.g;
     const size_t plane = (size_t)g.H * g.W, cplane = (size_t)a.Hc * a.Wc;
     const double wmax = (double)(a.Wc - 1), hmax = (double)(a.Hc - 1), ox = (double)a.x0, oy = (double)a.y0;
     const bool has_votes = a.votes != nullptr, has_alpha = a.alpha != nullptr;
     for (int t = blockIdx.x; t < g.tiles; t += gridDim.x) {
         int walk, y, x;
         size_t u;                                                           // the frame: b * N + t
-        if (!ch_decode(t, g, walk, u, y, x)) continue;                      // no barrier in this loop
-        const int rows = min(CH_ROWS, g.H - y);
+        if (!tile_decode(t, g, walk, u, y, x)) continue;                    // no barrier in this loop
+        const int rows = min(TILE_ROWS, g.H - y);
         const size_t b = u / (size_t)a.N;
         const double* M = a.inv + u * 9;                                    // uniform in the workgroup
         const float* src = a.plate + b * C * cplane;
@@ -205,21 +206,21 @@ template <int C, bool FRAMES> __global__ void __launch_bounds__(CH_THREADS) plat
         const float* asrc = has_alpha ? a.alpha : a.frames;                 // at least (B, N, 1, H, W) either way; used with FRAMES only
         const size_t pix = (size_t)y * g.W + x;
         // the four rows' reads first, their stores after: no load waits behind a store it might alias (a missing row repeats the last)
-        float o[C][CH_ROWS], cv[CH_ROWS], av[CH_ROWS];
+        float o[C][TILE_ROWS], cv[TILE_ROWS], av[TILE_ROWS];
 #pragma unroll
-        for (int k = 0; k < CH_ROWS; ++k) {
+        for (int k = 0; k < TILE_ROWS; ++k) {
             const int kk = min(k, rows - 1);
             double X, Y;
             bool ok = mo_project(M, x, y + kk, X, Y);
             const double px = X - ox, py = Y - oy;
             ok = ok && px >= 0.0 && px <= wmax && py >= 0.0 && py <= hmax;      // false for NaN
             const PlCell cell = pl_cell(ok, px, py, a.Hc, a.Wc);
-            const ChCell cc = pl_corners(cell, a.Wc);
+            const BilinearCell cc = pl_corners(cell, a.Wc);
             const bool voted = vsrc[cc.o00] > 0.0f && vsrc[cc.o01] > 0.0f && vsrc[cc.o10] > 0.0f && vsrc[cc.o11] > 0.0f;
             ok = ok && (voted || !has_votes);
             float proj[C];
 #pragma unroll
-            for (int c = 0; c < C; ++c) proj[c] = ch_bilerp(src + (size_t)c * cplane, cc);
+            for (int c = 0; c < C; ++c) proj[c] = bilerp(src + (size_t)c * cplane, cc);
             cv[k] = ok ? 1.0f : 0.0f;
             av[k] = 0.0f;
             if constexpr (!FRAMES) {
@@ -237,7 +238,7 @@ template <int C, bool FRAMES> __global__ void __launch_bounds__(CH_THREADS) plat
                 }
                 d = d / (float)C;
                 const float al = asrc[fpix];
-                const float given = ch_finite(al) ? fminf(fmaxf(al, 0.0f), 1.0f) : 0.0f;
+                const float given = is_finite(al) ? fminf(fmaxf(al, 0.0f), 1.0f) : 0.0f;
                 const float derived = d != d ? 0.0f : fminf(fmaxf((d - a.lo) / (a.hi - a.lo), 0.0f), 1.0f);
                 const float m = ok ? (has_alpha ? given : derived) : 0.0f;
 #pragma unroll
@@ -252,10 +253,10 @@ template <int C, bool FRAMES> __global__ void __launch_bounds__(CH_THREADS) plat
 #pragma unroll
         for (int c = 0; c < C; ++c)
 #pragma unroll
-            for (int k = 0; k < CH_ROWS; ++k)
+            for (int k = 0; k < TILE_ROWS; ++k)
                 if (k < rows) dst[(size_t)c * plane + (size_t)k * g.W] = o[c][k];
 #pragma unroll
-        for (int k = 0; k < CH_ROWS; ++k) {
+        for (int k = 0; k < TILE_ROWS; ++k) {
             if (k >= rows) break;
             if (a.covered) a.covered[u * plane + pix + (size_t)k * g.W] = cv[k];
             if (FRAMES && a.fg) a.fg[u * plane + pix + (size_t)k * g.W] = av[k];
@@ -264,8 +265,8 @@ template <int C, bool FRAMES> __global__ void __launch_bounds__(CH_THREADS) plat
 }
 
 template <int C> static void plate_project_launch_c(int grid, hipStream_t s, const PlProject& a) {
-    if (a.frames) plate_project_kernel<C, true><<<grid, CH_THREADS, 0, s>>>(a);
-    else plate_project_kernel<C, false><<<grid, CH_THREADS, 0, s>>>(a);
+    if (a.frames) plate_project_kernel<C, true><<<grid, TILE_THREADS, 0, s>>>(a);
+    else plate_project_kernel<C, false><<<grid, TILE_THREADS, 0, s>>>(a);
 }
 
 static void plate_project_launch(int C, int grid, hipStream_t s, const PlProject& a) {
@@ -281,19 +282,19 @@ static void plate_project_launch(int C, int grid, hipStream_t s, const PlProject
     }
 }
 
-static bool pl_side_ok(int v) { return v >= 1 && v <= CH_MAX_SIDE; }
-static bool pl_origin_ok(int v) { return v >= -CH_MAX_SIDE && v <= CH_MAX_SIDE; }
-static int pl_grid(const ChGeom& g) { return g.tiles < PL_GRID ? g.tiles : PL_GRID; }
+static bool pl_side_ok(int v) { return v >= 1 && v <= MAX_SIDE; }
+static bool pl_origin_ok(int v) { return v >= -MAX_SIDE && v <= MAX_SIDE; }
+static int pl_grid(const TileGeom& g) { return g.tiles < PL_GRID ? g.tiles : PL_GRID; }
 
 }  // namespace ofd
 using namespace ofd;
 
 #define PL_CHECK_COMMON(what)                                                                                                              \
-    OFD_CHECK_ARG(B > 0 && pl_side_ok(H) && pl_side_ok(W) && pl_side_ok(Hc) && pl_side_ok(Wc),                                               \
-                  what ": bad shape B=%d H=%d W=%d Hc=%d Wc=%d, the sides must be in 1..%d", B, H, W, Hc, Wc, CH_MAX_SIDE);                  \
-    OFD_CHECK_ARG(C >= 1 && C <= CH_MAX_C, what ": bad shape C=%d, C must be in 1..%d", C, CH_MAX_C);                                        \
-    OFD_CHECK_ARG(pl_origin_ok(x0) && pl_origin_ok(y0), what ": canvas origin x0=%d y0=%d, |x0| and |y0| must be at most %d", x0, y0,        \
-                  CH_MAX_SIDE)
+    OFD_CHECK_ARG(B > 0 && pl_side_ok(H) && pl_side_ok(W) && pl_side_ok(Hc) && pl_side_ok(Wc),                                             \
+                  what ": bad shape B=%d H=%d W=%d Hc=%d Wc=%d, the sides must be in 1..%d", B, H, W, Hc, Wc, MAX_SIDE);                   \
+    OFD_CHECK_ARG(C >= 1 && C <= MO_MAX_C, what ": bad shape C=%d, C must be in 1..%d", C, MO_MAX_C);                                      \
+    OFD_CHECK_ARG(pl_origin_ok(x0) && pl_origin_ok(y0), what ": canvas origin x0=%d y0=%d, |x0| and |y0| must be at most %d", x0, y0,      \
+                  MAX_SIDE)
 
 extern "C" int ofd_plate_reduce(const float* clip, const float* weight, const double* path, float* plate, float* votes, uint8_t* count, int B,
                                 int N, int C, int H, int W, int x0, int y0, int Hc, int Wc, int mode, int min_count, void* stream) {
@@ -304,19 +305,19 @@ extern "C" int ofd_plate_reduce(const float* clip, const float* weight, const do
     OFD_CHECK_ARG(min_count >= 1 && min_count <= N, "plate_reduce: min_count=%d must be in 1..N=%d", min_count, N);
     const size_t fpx = (size_t)B * N * H * W, cpx = (size_t)B * Hc * Wc;
     OFD_CHECK_ARG(fpx * C < (1ull << 40) && cpx * C < (1ull << 40), "plate_reduce: bad shape, B*N*C*H*W and B*C*Hc*Wc must be < 2^40");
-    OFD_CHECK_ARG((size_t)B * cdiv(Hc, CH_TILE_H) * cdiv(Wc, CH_TILE_W) < (1u << 30),
-                  "plate_reduce: bad shape, B * ceil(Hc / %d) * ceil(Wc / %d) must be < 2^30", CH_TILE_H, CH_TILE_W);
+    OFD_CHECK_ARG((size_t)B * cdiv(Hc, TILE_H) * cdiv(Wc, TILE_W) < (1u << 30),
+                  "plate_reduce: bad shape, B * ceil(Hc / %d) * ceil(Wc / %d) must be < 2^30", TILE_H, TILE_W);
     const void* outs[3] = {plate, votes, count};
     const size_t obytes[3] = {cpx * C * sizeof(float), cpx * sizeof(float), cpx};
     for (int k = 0; k < 3; ++k) {
         if (!outs[k]) continue;
-        OFD_CHECK_ARG(!ch_overlap(outs[k], obytes[k], clip, fpx * C * sizeof(float)) && !ch_overlap(outs[k], obytes[k], weight, fpx * sizeof(float)) &&
-                          !ch_overlap(outs[k], obytes[k], path, (size_t)B * N * 9 * sizeof(double)),
+        OFD_CHECK_ARG(!ranges_overlap(outs[k], obytes[k], clip, fpx * C * sizeof(float)) && !ranges_overlap(outs[k], obytes[k], weight, fpx * sizeof(float)) &&
+                          !ranges_overlap(outs[k], obytes[k], path, (size_t)B * N * 9 * sizeof(double)),
                       "plate_reduce: an output (plate, votes, count: %d) must not overlap clip, weight or path", k);
         for (int j = 0; j < k; ++j)
-            OFD_CHECK_ARG(!ch_overlap(outs[k], obytes[k], outs[j], obytes[j]), "plate_reduce: the outputs %d and %d overlap", j, k);
+            OFD_CHECK_ARG(!ranges_overlap(outs[k], obytes[k], outs[j], obytes[j]), "plate_reduce: the outputs %d and %d overlap", j, k);
     }
-    const PlReduce a{clip, weight, path, plate, votes, count, N, C, H, W, x0, y0, min_count, ch_geom(B, Hc, Wc, (size_t)B)};
+    const PlReduce a{clip, weight, path, plate, votes, count, N, C, H, W, x0, y0, min_count, tile_geom(B, Hc, Wc, (size_t)B)};
     const int grid = pl_grid(a.g);
     hipStream_t s = (hipStream_t)stream;
     if (N <= 4) plate_reduce_launch<4>(mode, grid, s, a);
@@ -339,8 +340,8 @@ extern "C" int ofd_plate_project(const float* plate, const float* votes, const d
                       (double)lo, (double)hi);                              // false for NaN
     const size_t fpx = (size_t)B * N * H * W, cpx = (size_t)B * Hc * Wc;
     OFD_CHECK_ARG(fpx * C < (1ull << 40) && cpx * C < (1ull << 40), "plate_project: bad shape, B*N*C*H*W and B*C*Hc*Wc must be < 2^40");
-    OFD_CHECK_ARG((size_t)B * N * cdiv(H, CH_TILE_H) * cdiv(W, CH_TILE_W) < (1u << 30),
-                  "plate_project: bad shape, B * N * ceil(H / %d) * ceil(W / %d) must be < 2^30", CH_TILE_H, CH_TILE_W);
+    OFD_CHECK_ARG((size_t)B * N * cdiv(H, TILE_H) * cdiv(W, TILE_W) < (1u << 30),
+                  "plate_project: bad shape, B * N * ceil(H / %d) * ceil(W / %d) must be < 2^30", TILE_H, TILE_W);
     const void* outs[3] = {out, covered, fg};
     const size_t obytes[3] = {fpx * C * sizeof(float), fpx * sizeof(float), fpx * sizeof(float)};
     const void* ins[5] = {plate, votes, inv, frames, alpha};
@@ -349,13 +350,13 @@ extern "C" int ofd_plate_project(const float* plate, const float* votes, const d
     for (int k = 0; k < 3; ++k) {
         if (!outs[k]) continue;
         for (int j = 0; j < 5; ++j)
-            OFD_CHECK_ARG(!ch_overlap(outs[k], obytes[k], ins[j], ibytes[j]),
+            OFD_CHECK_ARG(!ranges_overlap(outs[k], obytes[k], ins[j], ibytes[j]),
                           "plate_project: an output (out, covered, fg: %d) must not overlap an input (plate, votes, inv, frames, alpha: %d)", k, j);
         for (int j = 0; j < k; ++j)
-            OFD_CHECK_ARG(!ch_overlap(outs[k], obytes[k], outs[j], obytes[j]), "plate_project: the outputs %d and %d overlap", j, k);
+            OFD_CHECK_ARG(!ranges_overlap(outs[k], obytes[k], outs[j], obytes[j]), "plate_project: the outputs %d and %d overlap", j, k);
     }
     const PlProject a{plate, votes, inv, frames, alpha, out, covered, fg, N, Hc, Wc, x0, y0, lo, hi,
-                      ch_geom(B * N, H, W, (size_t)B * N)};
+                      tile_geom(B * N, H, W, (size_t)B * N)};
     plate_project_launch(C, pl_grid(a.g), (hipStream_t)stream, a);
     OFD_LAUNCH_CHECK();
     return OFD_OK;

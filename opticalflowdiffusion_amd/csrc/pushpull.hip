@@ -68,6 +68,7 @@ static void pp_levels(PPLevels& lv, int B, int C, int H, int W) {
     lv.total = off;
 }
 
+// pp_finite and pp_bilerp stay copies of gather.h's: this unit is built with fp contraction on, and gather.h is for units built without
 __device__ __forceinline__ bool pp_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
 // four pixels x .. x+3 of row y of one plane; `fill` outside the image

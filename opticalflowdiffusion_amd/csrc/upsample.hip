@@ -21,7 +21,7 @@
 // One launch, no atomics, no host synchronisation; a thread writes only its own pixels: the same input gives the same bits.  Built with
 // -ffp-contract=off like the other warp units, so that the operation order the header states is the one that runs.  Tap indices are
 // formed in integers; no float ever becomes an index.
-#include "warp_common.h"
+#include "gather.h"
 
 namespace ofd {
 
@@ -39,8 +39,6 @@ struct JuArgs {
     int win_rows, stride;           // ... then the window: rows allocated per plane, floats per row (odd)
     float den_s, k_r, gain;         // 2 sigma_s^2, 1 / (Cg * 2 sigma_r^2)
 };
-
-__device__ __forceinline__ bool ju_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
 // i0 = floor((2 x + 1 - s) / (2 s)) and the numerator of the offset inside the cell, nx - 2 s i0 in [0, 2 s): 2 x + 1 - s > -2 s, so
 // the only negative quotient is -1.  rem has the parity of s + 1 for every x: rem >> 1 numbers the s places of a pixel in its cell.
@@ -142,7 +140,7 @@ template <int C, int CG, bool VEC> __global__ void __launch_bounds__(JU_THREADS)
 #pragma unroll
             for (int c = 0; c < C; ++c) {
                 v[c] = lo_b[c * lo_plane + off];
-                ok = ok && ju_finite(v[c]);
+                ok = ok && is_finite(v[c]);
             }
 #pragma unroll
             for (int c = 0; c < C; ++c) dst[c * plane_floats] = ok ? v[c] : 0.0f;

@@ -16,6 +16,7 @@ from collections import namedtuple
 import torch
 from torch import nn
 
+from . import _args as A
 from . import _lib as L
 from .warp import nan_mse
 
@@ -925,7 +926,7 @@ class ConditionalDiffusion(nn.Module):
                              "model output, not part of the diffused tensor")
         if not torch.is_tensor(known) or tuple(known.shape) != tuple(shape):
             raise ValueError(f"known must be a tensor shaped like the diffused tensor {tuple(shape)}, got "
-                             f"{tuple(known.shape) if torch.is_tensor(known) else type(known).__name__}")
+                             f"{A.shape_of(known)}")
         L.require_gpu(known)
         return L.f32c(known)
 
@@ -994,7 +995,7 @@ class ConditionalDiffusion(nn.Module):
         for name, f in (("first", photo.first), ("second", photo.second)):
             if not torch.is_tensor(f) or f.dim() != 4 or f.shape[0] != B or not 1 <= f.shape[1] <= 4 or tuple(f.shape[2:]) != (H, W):
                 raise ValueError(f"photo.{name} must be a (B, Ci, H, W) = ({B}, 1..4, {H}, {W}) tensor, got "
-                                 f"{tuple(f.shape) if torch.is_tensor(f) else type(f).__name__}")
+                                 f"{A.shape_of(f)}")
         if tuple(photo.first.shape) != tuple(photo.second.shape):
             raise ValueError(f"photo.first and photo.second must have one shape, got {tuple(photo.first.shape)} and {tuple(photo.second.shape)}")
         if not _positive_finite(photo.flow_max):

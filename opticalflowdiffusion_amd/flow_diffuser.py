@@ -25,6 +25,7 @@ from .warp import (STATE_HELD, box_reduce, chain_flows, chain_flows_to, composit
                    interpolate_frames, layers_params, loop_frames, loop_params, median_filter_flow, median_params, motion_params, path_params,
                    segment_motion, stabilize_clip, upsample_flow, upsample_params, warp)
 from .warp import background_plate, plate_params, plate_voters, remove_moving
+from . import _args as A
 from . import _lib as L
 
 try:                                                   # pragma: no cover - not installed in this image
@@ -302,7 +303,7 @@ class FlowDiffuser(EmaMixin, _Base):
                              "of the diffused tensor")
         if not torch.is_tensor(known_flow) or known_flow.dim() != 4 or known_flow.shape[1] != 2:
             raise ValueError(f"known_flow must be a (B, 2, H, W) tensor of pixel displacements (NaN = free), got "
-                             f"{tuple(known_flow.shape) if torch.is_tensor(known_flow) else type(known_flow).__name__}")
+                             f"{A.shape_of(known_flow)}")
         known = torch.clamp(known_flow.float() / self.flow_max, -1.0, 1.0)
         if self.target == "joint":
             b, _, h, w = known.shape
@@ -323,11 +324,11 @@ class FlowDiffuser(EmaMixin, _Base):
             raise ValueError(f"target_frame is not supported for target={self.target!r}: there the flow is an extra model output, not "
                              "part of the diffused tensor")
         if not torch.is_tensor(cond) or cond.dim() != 4 or cond.shape[1] < 3:
-            raise ValueError(f"cond must be (B, 3, H, W), got {tuple(cond.shape) if torch.is_tensor(cond) else type(cond).__name__}")
+            raise ValueError(f"cond must be (B, 3, H, W), got {A.shape_of(cond)}")
         want = (cond.shape[0], 3) + tuple(cond.shape[2:])
         if not torch.is_tensor(target_frame) or tuple(target_frame.shape) != want:
             raise ValueError(f"target_frame must be a (B, 3, H, W) = {want} tensor in cond's range, got "
-                             f"{tuple(target_frame.shape) if torch.is_tensor(target_frame) else type(target_frame).__name__}")
+                             f"{A.shape_of(target_frame)}")
         pick = lambda v, key: getattr(self.cfg, key) if v is UNSET else v
         return PhotoGuide(cond[:, :3], target_frame, float(self.flow_max), 0 if self.target == "flow" else self.dim,
                           scale=pick(photo_scale, "photo_scale"), levels=tuple(pick(photo_levels, "photo_levels")),
@@ -358,7 +359,7 @@ class FlowDiffuser(EmaMixin, _Base):
         if known_flow is not None:
             raise ValueError("sample_scale > 1 cannot be combined with known_flow: the constraints would need a NaN-aware reduction")
         if not torch.is_tensor(cond) or cond.dim() != 4 or cond.shape[1] < 3:
-            raise ValueError(f"cond must be (B, 3, H, W), got {tuple(cond.shape) if torch.is_tensor(cond) else type(cond).__name__}")
+            raise ValueError(f"cond must be (B, 3, H, W), got {A.shape_of(cond)}")
         H, W = cond.shape[-2:]
         if H % s or W % s:
             raise ValueError(f"sample_scale={s} must divide H={H} and W={W}")
@@ -497,7 +498,7 @@ class FlowDiffuser(EmaMixin, _Base):
         and are untuned on real footage.  median_radius = 0 or unset is the call without them, launch for launch."""
         if not torch.is_tensor(frame1) or frame1.dim() != 4:
             raise ValueError(f"estimate_flow: frame1 must be (B, 3, H, W), got "
-                             f"{tuple(frame1.shape) if torch.is_tensor(frame1) else type(frame1).__name__}")
+                             f"{A.shape_of(frame1)}")
         if frame2 is None:
             raise ValueError("estimate_flow: frame2 is needed (the target_frame of sample)")
         sample_kw, median = self.median_filtering(sample_kw)
@@ -525,13 +526,12 @@ class FlowDiffuser(EmaMixin, _Base):
         The `median_*` keys of `estimate_flow` (sample_kw or cfg; checked before any model call) clean round 0 inside that call,
         each direction guided by its own first frame, and in every refine round the freshly sampled flow the same way BEFORE it is
         merged: held pixels keep their bits, and the keys never reach the round's `sample`."""
-        if isinstance(refine, bool) or not isinstance(refine, int) or not 0 <= refine <= 16:
-            raise ValueError(f"estimate_flow_pair: refine must be an integer in 0..16, got {refine!r}")
+        A.integer("estimate_flow_pair", "refine", refine, 0, 16)
         par = consistency_params(a1, a2, dilate, name="estimate_flow_pair")
         for name, fr in (("frame1", frame1), ("frame2", frame2)):
             if not torch.is_tensor(fr) or fr.dim() != 4 or fr.shape[1] != 3:
                 raise ValueError(f"estimate_flow_pair: {name} must be (B, 3, H, W), got "
-                                 f"{tuple(fr.shape) if torch.is_tensor(fr) else type(fr).__name__}")
+                                 f"{A.shape_of(fr)}")
         if frame1.shape != frame2.shape:
             raise ValueError(f"estimate_flow_pair: frame2 must have frame1's shape {tuple(frame1.shape)}, got {tuple(frame2.shape)}")
         if "known_flow" in sample_kw or "target_frame" in sample_kw:
@@ -583,7 +583,7 @@ class FlowDiffuser(EmaMixin, _Base):
             raise ValueError("animate: latent=True is not supported (every frame would have to be decoded by the Autoencoder)")
         times = animation_times(frames, times)
         if not torch.is_tensor(cond) or cond.dim() != 4 or cond.shape[1] < 3:
-            raise ValueError(f"animate: cond must be (B, 3, H, W), got {tuple(cond.shape) if torch.is_tensor(cond) else type(cond).__name__}")
+            raise ValueError(f"animate: cond must be (B, 3, H, W), got {A.shape_of(cond)}")
         B, _, H, W = cond.shape
         L.require_gpu(cond, flow)
         with torch.no_grad():
@@ -619,18 +619,17 @@ class FlowDiffuser(EmaMixin, _Base):
         last is frame 0 again; no NaN, no holes: a trace that leaves the frame repeats the border's colour.  Forward only."""
         if self.latent:
             raise ValueError("animate_loop: latent=True is not supported (every frame would have to be decoded by the Autoencoder)")
-        if isinstance(frames, bool) or not isinstance(frames, int) or not 1 <= frames <= 4096:
-            raise ValueError(f"animate_loop: frames must be an integer in 1..4096, got {frames!r}")
+        A.integer("animate_loop", "frames", frames, 1, 4096)
         par = loop_params(substeps, order, speed, name="animate_loop")
         if not torch.is_tensor(cond) or cond.dim() != 4 or cond.shape[1] < 3:
-            raise ValueError(f"animate_loop: cond must be (B, 3, H, W), got {tuple(cond.shape) if torch.is_tensor(cond) else type(cond).__name__}")
+            raise ValueError(f"animate_loop: cond must be (B, 3, H, W), got {A.shape_of(cond)}")
         B, _, H, W = cond.shape
         if flow is not None:
             if sample_kw:
                 raise ValueError(f"animate_loop: {sorted(sample_kw)} are sampling arguments; with a flow given nothing is sampled")
             if not torch.is_tensor(flow) or tuple(flow.shape) != (B, 2, H, W):
                 raise ValueError(f"animate_loop: flow must be (B, 2, H, W) = {(B, 2, H, W)}, got "
-                                 f"{tuple(flow.shape) if torch.is_tensor(flow) else type(flow).__name__}")
+                                 f"{A.shape_of(flow)}")
         L.require_gpu(cond, flow)
         with torch.no_grad():
             if flow is None:
@@ -662,15 +661,14 @@ class FlowDiffuser(EmaMixin, _Base):
             times = [k / (frames + 1) for k in range(1, frames + 1)]
         for name, fr in (("frame1", frame1), ("frame2", frame2)):
             if not torch.is_tensor(fr) or fr.dim() != 4 or fr.shape[1] != 3:
-                raise ValueError(f"interpolate: {name} must be (B, 3, H, W), got {tuple(fr.shape) if torch.is_tensor(fr) else type(fr).__name__}")
+                raise ValueError(f"interpolate: {name} must be (B, 3, H, W), got {A.shape_of(fr)}")
         if frame1.shape != frame2.shape:
             raise ValueError(f"interpolate: frame2 must have frame1's shape {tuple(frame1.shape)}, got {tuple(frame2.shape)}")
         if (flow12 is None) != (flow21 is None):
             raise ValueError("interpolate: flow12 and flow21 come together: give both, or neither to have both estimated")
         if flow12 is not None and sample_kw:
             raise ValueError(f"interpolate: {sorted(sample_kw)} are sampling arguments; with the flows given nothing is sampled")
-        if isinstance(refine, bool) or not isinstance(refine, int) or not 0 <= refine <= 16:
-            raise ValueError(f"interpolate: refine must be an integer in 0..16, got {refine!r}")
+        A.integer("interpolate", "refine", refine, 0, 16)
         if refine > 0 and flow12 is not None:
             raise ValueError("interpolate: refine > 0 refines estimated flows; with the flows given nothing is estimated")
         B = frame1.shape[0]
@@ -700,7 +698,7 @@ class FlowDiffuser(EmaMixin, _Base):
             raise ValueError("estimate_flow_clip: latent=True is not supported (the photometric estimate compares frames in pixel space)")
         if not torch.is_tensor(clip) or clip.dim() != 5 or clip.shape[2] != 3 or clip.shape[1] < 2 or clip.numel() == 0:
             raise ValueError(f"estimate_flow_clip: clip must be (B, T + 1, 3, H, W) with at least two frames, got "
-                             f"{tuple(clip.shape) if torch.is_tensor(clip) else type(clip).__name__}")
+                             f"{A.shape_of(clip)}")
         B, N, _, H, W = clip.shape
         T = N - 1
         if T > 4096:
@@ -722,7 +720,7 @@ class FlowDiffuser(EmaMixin, _Base):
             raise ValueError(f"{name}: latent=True is not supported (the flows are estimated and chained in pixel space)")
         if not torch.is_tensor(clip) or clip.dim() != 5 or clip.shape[2] != 3 or clip.shape[1] < 2 or clip.numel() == 0:
             raise ValueError(f"{name}: clip must be (B, T + 1, 3, H, W) with at least two frames, got "
-                             f"{tuple(clip.shape) if torch.is_tensor(clip) else type(clip).__name__}")
+                             f"{A.shape_of(clip)}")
         B, N, _, H, W = clip.shape
         if (fwd is None) != (bwd is None):
             raise ValueError(f"{name}: fwd and bwd come together: give both, or neither to have both estimated")
@@ -732,7 +730,7 @@ class FlowDiffuser(EmaMixin, _Base):
             for key, fl in (("fwd", fwd), ("bwd", bwd)):
                 if not torch.is_tensor(fl) or tuple(fl.shape) != (B, N - 1, 2, H, W):
                     raise ValueError(f"{name}: {key} must be (B, T, 2, H, W) = {(B, N - 1, 2, H, W)}, got "
-                                     f"{tuple(fl.shape) if torch.is_tensor(fl) else type(fl).__name__}")
+                                     f"{A.shape_of(fl)}")
         elif not self.is_diffusion:
             raise ValueError(f"{name}: estimating the flows needs a diffusion model (estimate_flow_clip); pass fwd and bwd")
         if any(t is not None and t.requires_grad for t in (clip, fwd, bwd)):
@@ -749,8 +747,7 @@ class FlowDiffuser(EmaMixin, _Base):
         estimated flows is unmeasured.  Forward only."""
         T = self._clip_flows("track", clip, fwd, bwd, sample_kw)
         for key, v in (("start", start), ("stop", T if stop is None else stop)):
-            if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= T:
-                raise ValueError(f"track: {key} must be an integer in 0..{T}, got {v!r}")
+            A.integer("track", key, v, 0, T)
         if not isinstance(check, bool):
             raise ValueError(f"track: check must be True or False, got {check!r}")
         par = consistency_params(a1, a2, name="track")
@@ -771,9 +768,8 @@ class FlowDiffuser(EmaMixin, _Base):
         B, _, _, H, W = clip.shape
         if not torch.is_tensor(layer) or tuple(layer.shape) != (B, 4, H, W):
             raise ValueError(f"propagate: layer must be (B, 4, H, W) = {(B, 4, H, W)}, got "
-                             f"{tuple(layer.shape) if torch.is_tensor(layer) else type(layer).__name__}")
-        if isinstance(anchor, bool) or not isinstance(anchor, int) or not 0 <= anchor <= T:
-            raise ValueError(f"propagate: anchor must be an integer in 0..{T}, got {anchor!r}")
+                             f"{A.shape_of(layer)}")
+        A.integer("propagate", "anchor", anchor, 0, T)
         if not isinstance(check, bool) or not isinstance(premultiplied, bool):
             raise ValueError(f"propagate: check and premultiplied must be True or False, got {check!r} and {premultiplied!r}")
         if layer.requires_grad:
@@ -825,8 +821,7 @@ class FlowDiffuser(EmaMixin, _Base):
         sample_kw is an error.  conf is 1 on the pixels of fwd that `warp.flow_consistency(fwd, bwd, a1, a2)` holds and 0 elsewhere:
         occluded pixels do not vote for the camera.  The defaults are untuned on real footage.  Forward only."""
         T = self._clip_flows("stabilize", clip, fwd, bwd, sample_kw)
-        if isinstance(refine, bool) or not isinstance(refine, int) or not 0 <= refine <= 16:
-            raise ValueError(f"stabilize: refine must be an integer in 0..16, got {refine!r}")
+        A.integer("stabilize", "refine", refine, 0, 16)
         par, path = motion_params(model, iterations, sigma, name="stabilize"), path_params(T, mode, sigma_t, anchor, "stabilize")
         check = consistency_params(a1, a2, name="stabilize")
         if fwd is None:
@@ -841,8 +836,7 @@ class FlowDiffuser(EmaMixin, _Base):
         """what `background_plate` and `remove_moving` share: every host rule before any model or engine call, the flows (estimated
         where they are not given) and the two confidences of the forward-backward check -> (fwd, bwd, conf, conf_bwd)"""
         T = self._clip_flows(name, clip, fwd, bwd, sample_kw)
-        if isinstance(refine, bool) or not isinstance(refine, int) or not 0 <= refine <= 16:
-            raise ValueError(f"{name}: refine must be an integer in 0..16, got {refine!r}")
+        A.integer(name, "refine", refine, 0, 16)
         motion_params(plate_kw["model"], plate_kw["iterations"], plate_kw["sigma"], name=name)
         voters = plate_voters(T, plate_kw["anchor"], plate_kw["every"], name)
         plate_params(len(voters), clip.shape[3], clip.shape[4], plate_kw["canvas"], plate_kw["mode"], plate_kw["min_count"],

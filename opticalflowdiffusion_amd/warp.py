@@ -11,6 +11,7 @@ import math
 
 import torch
 
+from . import _args as A
 from . import _lib as L
 from .softsplat import softsplat_func, splat_forward
 
@@ -237,9 +238,8 @@ def interpolate_frames(frame1, frame2, flow12, flow21, times, alpha=10.0, beta=0
     params = _interp_params(alpha, beta, oob, zmax)
     if fill_holes and (not fill_gain >= 1.0 or fill_gain == float("inf")):
         raise ValueError(f"interpolate: fill_gain must be finite and >= 1, got {fill_gain}")
-    if any(t.requires_grad for t in (frame1, frame2, flow12, flow21)):
-        raise L.OfdError("interpolate: forward only (neither the merge nor the push-pull fill has a backward pass): detach the inputs")
-    L.require_gpu(frame1, frame2, flow12, flow21)
+    A.forward_only("interpolate", frame1, frame2, flow12, flow21, why="neither the merge nor the push-pull fill has a backward pass",
+                   who=None)
     n = len(ts)
     with torch.no_grad():
         frame1, frame2, flow12, flow21 = (L.f32c(t) for t in (frame1, frame2, flow12, flow21))
@@ -271,10 +271,6 @@ def interpolate_frames(frame1, frame2, flow12, flow21, times, alpha=10.0, beta=0
 
 
 # ---- joint bilateral upsampling (not in the reference; semantics: include/ofd.h, `ofd_joint_upsample`) --------------------------------
-def _shape_of(t):
-    return tuple(t.shape) if torch.is_tensor(t) else type(t).__name__
-
-
 def box_reduce(img, scale):
     """the scale x scale box average of a (B, Ci, H, W) GPU tensor, Ci <= 4, scale dividing H and W: one `ofd_photo_pyramid` launch"""
     B, Ci, H, W = img.shape
@@ -290,12 +286,10 @@ def box_reduce(img, scale):
 
 def upsample_params(radius=2, sigma_s=1.0, sigma_r=0.1):
     """the rules of `upsample_flow`'s window and widths (ValueError); host logic, no engine call"""
-    if isinstance(radius, bool) or not isinstance(radius, int) or not 1 <= radius <= 3:
-        raise ValueError(f"upsample_flow: radius must be an integer in 1..3, got {radius!r}")
-    real = lambda v: not isinstance(v, bool) and isinstance(v, (int, float))
-    if not real(sigma_s) or not 0.0 < sigma_s < float("inf"):               # false for NaN
+    A.integer("upsample_flow", "radius", radius, 1, 3)
+    if not A.is_number(sigma_s) or not 0.0 < sigma_s < float("inf"):        # false for NaN
         raise ValueError(f"upsample_flow: sigma_s must be finite and > 0, got {sigma_s!r}")
-    if not real(sigma_r) or not sigma_r > 0.0:
+    if not A.is_number(sigma_r) or not sigma_r > 0.0:
         raise ValueError(f"upsample_flow: sigma_r must be > 0 (inf switches the guide off), got {sigma_r!r}")
     return dict(radius=radius, sigma_s=float(sigma_s), sigma_r=float(sigma_r))
 
@@ -311,27 +305,21 @@ def upsample_flow(lo, guide, scale, radius=2, sigma_s=1.0, sigma_r=0.1, gain=Non
     without an engine call.  radius 1..3, scale 1..8.  The defaults suit frames in [-1, 1]; they come from a synthetic edge and are
     untuned on real footage.  Forward only; inputs are not modified; the same input gives the same bits.  Semantics: include/ofd.h."""
     if not torch.is_tensor(lo) or lo.dim() != 4 or lo.numel() == 0 or not 1 <= lo.shape[1] <= 8:
-        raise ValueError(f"upsample_flow: lo must be a non-empty (B, C, h, w) tensor with 1 <= C <= 8, got {_shape_of(lo)}")
-    if isinstance(scale, bool) or not isinstance(scale, int) or not 1 <= scale <= 8:
-        raise ValueError(f"upsample_flow: scale must be an integer in 1..8, got {scale!r}")
+        raise ValueError(f"upsample_flow: lo must be a non-empty (B, C, h, w) tensor with 1 <= C <= 8, got {A.shape_of(lo)}")
+    A.integer("upsample_flow", "scale", scale, 1, 8)
     upsample_params(radius, sigma_s, sigma_r)
     B, C, h, w = lo.shape
     if not torch.is_tensor(guide) or guide.dim() != 4 or not 1 <= guide.shape[1] <= 4 or \
             (guide.shape[0], guide.shape[2], guide.shape[3]) != (B, h * scale, w * scale):
         raise ValueError(f"upsample_flow: guide must be (B, 1..4, h * scale, w * scale) = ({B}, 1..4, {h * scale}, {w * scale}), "
-                         f"got {_shape_of(guide)}")
+                         f"got {A.shape_of(guide)}")
     Cg = guide.shape[1]
     if guide_lo is not None and (not torch.is_tensor(guide_lo) or tuple(guide_lo.shape) != (B, Cg, h, w)):
-        raise ValueError(f"upsample_flow: guide_lo must be (B, Cg, h, w) = {(B, Cg, h, w)}, got {_shape_of(guide_lo)}")
+        raise ValueError(f"upsample_flow: guide_lo must be (B, Cg, h, w) = {(B, Cg, h, w)}, got {A.shape_of(guide_lo)}")
     gain = float(scale if gain is None else gain)
     if not abs(gain) < float("inf"):
         raise ValueError(f"upsample_flow: gain must be finite, got {gain!r}")
-    given = [t for t in (lo, guide, guide_lo) if t is not None]
-    if any(t.requires_grad for t in given):
-        raise L.OfdError("upsample_flow: forward only (the upsampling has no backward pass): detach the inputs")
-    L.require_gpu(*given)
-    if any(t.device != lo.device for t in given):
-        raise ValueError(f"upsample_flow: lo, guide and guide_lo must be on one device, got {[str(t.device) for t in given]}")
+    A.forward_only("upsample_flow", lo, guide, guide_lo, why="the upsampling has no backward pass", who="lo, guide and guide_lo")
     with torch.no_grad():
         if scale == 1:
             return L.f32c(lo) * gain
@@ -347,33 +335,21 @@ def upsample_flow(lo, guide, scale, radius=2, sigma_s=1.0, sigma_r=0.1, gain=Non
 _loop_ws = {}                                          # device index -> the forward displacements of a call (grown on demand)
 
 
-def _loop_int(name, what, v, lo, hi):
-    if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
-        raise ValueError(f"{name}: {what} must be an integer in {lo}..{hi}, got {v!r}")
-    return v
-
-
-def _loop_real(name, what, v):
-    if isinstance(v, bool) or not isinstance(v, (int, float)) or not abs(v) < float("inf"):       # false for NaN
-        raise ValueError(f"{name}: {what} must be a finite number, got {v!r}")
-    return float(v)
-
-
 def _loop_motion(name, motion, B=None, H=None, W=None):
     ok = torch.is_tensor(motion) and motion.dim() == 4 and motion.shape[1] == 2 and motion.numel() > 0
     if ok and B is not None:
         ok = tuple(motion.shape) == (B, 2, H, W)
     if not ok:
         want = "a non-empty (B, 2, H, W) tensor" if B is None else f"(B, 2, H, W) = {(B, 2, H, W)}"
-        raise ValueError(f"{name}: motion must be {want}, got {_shape_of(motion)}")
+        raise ValueError(f"{name}: motion must be {want}, got {A.shape_of(motion)}")
     if max(motion.shape[2:]) > 32768:
         raise ValueError(f"{name}: H and W must be at most 32768, got {tuple(motion.shape)}")
 
 
 def loop_params(substeps=1, order=2, speed=1.0, name="loop_frames"):
     """the rules of the traces' integrator and step (ValueError); host logic, no engine call"""
-    return dict(substeps=_loop_int(name, "substeps", substeps, 1, 16), order=_loop_int(name, "order", order, 1, 2),
-                speed=_loop_real(name, "speed", speed))
+    return dict(substeps=A.integer(name, "substeps", substeps, 1, 16), order=A.integer(name, "order", order, 1, 2),
+                speed=A.real(name, "speed", speed))
 
 
 def integrate_flow(motion, steps, substeps=1, order=2, dt=1.0):
@@ -384,13 +360,11 @@ def integrate_flow(motion, steps, substeps=1, order=2, dt=1.0):
     negative (a trace back).  The field is read bilinearly with the coordinates clamped to the frame.  steps 0..4096.  Forward only;
     inputs are not modified; the same input gives the same bits.  Semantics: include/ofd.h (`ofd_flow_integrate`)."""
     _loop_motion("integrate_flow", motion)
-    steps = _loop_int("integrate_flow", "steps", steps, 0, 4096)
-    substeps = _loop_int("integrate_flow", "substeps", substeps, 1, 16)
-    order = _loop_int("integrate_flow", "order", order, 1, 2)
-    dt = _loop_real("integrate_flow", "dt", dt)
-    if motion.requires_grad:
-        raise L.OfdError("integrate_flow: forward only (the trace has no backward pass): detach the input")
-    L.require_gpu(motion)
+    steps = A.integer("integrate_flow", "steps", steps, 0, 4096)
+    substeps = A.integer("integrate_flow", "substeps", substeps, 1, 16)
+    order = A.integer("integrate_flow", "order", order, 1, 2)
+    dt = A.real("integrate_flow", "dt", dt)
+    A.forward_only("integrate_flow", motion, why="the trace has no backward pass", detach="the input")
     B, _, H, W = motion.shape
     with torch.no_grad():
         motion = L.f32c(motion)
@@ -425,16 +399,14 @@ def loop_frames(img, motion, frames, substeps=1, order=2, speed=1.0):
     chunked or not, the bits are the same.  Forward only; inputs are not modified.  Semantics: include/ofd.h."""
     from .flow_diffuser import ANIMATE_MAX_PIXELS
     if not torch.is_tensor(img) or img.dim() != 4 or img.numel() == 0:
-        raise ValueError(f"loop_frames: img must be a non-empty (B, C, H, W) tensor, got {_shape_of(img)}")
+        raise ValueError(f"loop_frames: img must be a non-empty (B, C, H, W) tensor, got {A.shape_of(img)}")
     B, C, H, W = img.shape
     if not 1 <= C <= 8:
         raise ValueError(f"loop_frames: 1 to 8 channels, got {C}")
     _loop_motion("loop_frames", motion, B, H, W)
-    N = _loop_int("loop_frames", "frames", frames, 1, 4096)
+    N = A.integer("loop_frames", "frames", frames, 1, 4096)
     par = loop_params(substeps, order, speed)
-    if img.requires_grad or motion.requires_grad:
-        raise L.OfdError("loop_frames: forward only (neither the trace nor the gather has a backward pass): detach the inputs")
-    L.require_gpu(img, motion)
+    A.forward_only("loop_frames", img, motion, why="neither the trace nor the gather has a backward pass", who=None)
     if img.device != motion.device:
         raise ValueError(f"loop_frames: img and motion must be on one device, got {img.device} and {motion.device}")
     with torch.no_grad():
@@ -461,10 +433,9 @@ FlowConsistency = collections.namedtuple("FlowConsistency", "known12 known21 err
 
 def consistency_params(a1=0.01, a2=0.5, dilate=0, name="flow_consistency"):
     """the rules of the check's bound and dilation (ValueError); host logic, no engine call"""
-    real = lambda v: not isinstance(v, bool) and isinstance(v, (int, float)) and 0.0 <= v < float("inf")      # false for NaN
-    if not real(a1) or not real(a2):
+    if not all(A.is_number(v) and 0.0 <= v < float("inf") for v in (a1, a2)):                  # false for NaN
         raise ValueError(f"{name}: a1 and a2 must be finite numbers >= 0, got {a1!r} and {a2!r}")
-    return dict(a1=float(a1), a2=float(a2), dilate=_loop_int(name, "dilate", dilate, 0, 4))
+    return dict(a1=float(a1), a2=float(a2), dilate=A.integer(name, "dilate", dilate, 0, 4))
 
 
 def flow_consistency(flow12, flow21, a1=0.01, a2=0.5, dilate=0):
@@ -481,17 +452,15 @@ def flow_consistency(flow12, flow21, a1=0.01, a2=0.5, dilate=0):
     trained weights.  One launch; forward only; inputs are not modified; the same input gives the same bits.  Semantics:
     include/ofd.h."""
     if not torch.is_tensor(flow12) or flow12.dim() != 4 or flow12.shape[1] != 2 or flow12.numel() == 0:
-        raise ValueError(f"flow_consistency: flow12 must be a non-empty (B, 2, H, W) tensor, got {_shape_of(flow12)}")
+        raise ValueError(f"flow_consistency: flow12 must be a non-empty (B, 2, H, W) tensor, got {A.shape_of(flow12)}")
     if not torch.is_tensor(flow21) or flow21.shape != flow12.shape:
-        raise ValueError(f"flow_consistency: flow21 must have flow12's shape {tuple(flow12.shape)}, got {_shape_of(flow21)}")
+        raise ValueError(f"flow_consistency: flow21 must have flow12's shape {tuple(flow12.shape)}, got {A.shape_of(flow21)}")
     if max(flow12.shape[2:]) > 32768:
         raise ValueError(f"flow_consistency: H and W must be at most 32768, got {tuple(flow12.shape)}")
     if not flow12.is_floating_point() or not flow21.is_floating_point():
         raise ValueError(f"flow_consistency: the flows must be floating-point tensors, got {flow12.dtype} and {flow21.dtype}")
     par = consistency_params(a1, a2, dilate)
-    if flow12.requires_grad or flow21.requires_grad:
-        raise L.OfdError("flow_consistency: forward only (the check has no backward pass): detach the inputs")
-    L.require_gpu(flow12, flow21)
+    A.forward_only("flow_consistency", flow12, flow21, why="the check has no backward pass", who=None)
     if flow12.device != flow21.device:
         raise ValueError(f"flow_consistency: flow12 and flow21 must be on one device, got {flow12.device} and {flow21.device}")
     B, _, H, W = flow12.shape
@@ -514,11 +483,11 @@ FlowChain = collections.namedtuple("FlowChain", "disp state life")
 def _chain_flows(name, fwd, bwd, need_bwd=True):
     """the shape, dtype, grad and device rules of a clip's flows -> (B, T, H, W); bwd may be None unless need_bwd"""
     if not torch.is_tensor(fwd) or fwd.dim() != 5 or fwd.shape[2] != 2 or fwd.numel() == 0:
-        raise ValueError(f"{name}: fwd must be a non-empty (B, T, 2, H, W) tensor, got {_shape_of(fwd)}")
+        raise ValueError(f"{name}: fwd must be a non-empty (B, T, 2, H, W) tensor, got {A.shape_of(fwd)}")
     if bwd is None and need_bwd:
         raise ValueError(f"{name}: bwd is needed (the flows from every frame to the one before it)")
     if bwd is not None and (not torch.is_tensor(bwd) or bwd.shape != fwd.shape):
-        raise ValueError(f"{name}: bwd must have fwd's shape {tuple(fwd.shape)}, got {_shape_of(bwd)}")
+        raise ValueError(f"{name}: bwd must have fwd's shape {tuple(fwd.shape)}, got {A.shape_of(bwd)}")
     B, T, _, H, W = fwd.shape
     if max(H, W) > 32768 or T > 4096:
         raise ValueError(f"{name}: H and W must be at most 32768 and T at most 4096, got {tuple(fwd.shape)}")
@@ -526,16 +495,6 @@ def _chain_flows(name, fwd, bwd, need_bwd=True):
     if not all(t.is_floating_point() for t in given):
         raise ValueError(f"{name}: the flows must be floating-point tensors, got {[t.dtype for t in given]}")
     return B, T, H, W
-
-
-def _chain_ready(name, *tensors, what="the walk has"):
-    """forward only, GPU only, one device: the rules that come after the host-only ones"""
-    given = [t for t in tensors if t is not None]
-    if any(t.requires_grad for t in given):
-        raise L.OfdError(f"{name}: forward only ({what} no backward pass): detach the inputs")
-    L.require_gpu(*given)
-    if any(t.device != given[0].device for t in given):
-        raise ValueError(f"{name}: all tensors must be on one device, got {[str(t.device) for t in given]}")
 
 
 def _chain_check(name, check, default):
@@ -563,8 +522,8 @@ def chain_flows(fwd, bwd=None, start=0, stop=None, check=None, a1=0.01, a2=0.5, 
     long clips with real estimated flows is unmeasured.  One launch; forward only; inputs are not modified; the same input gives the
     same bits.  Semantics: include/ofd.h."""
     B, T, H, W = _chain_flows("chain_flows", fwd, bwd, need_bwd=False)
-    start = _loop_int("chain_flows", "start", start, 0, T)
-    stop = T if stop is None else _loop_int("chain_flows", "stop", stop, 0, T)
+    start = A.integer("chain_flows", "start", start, 0, T)
+    stop = T if stop is None else A.integer("chain_flows", "stop", stop, 0, T)
     ahead = stop >= start
     other = bwd if ahead else fwd
     check = _chain_check("chain_flows", check, bwd is not None)
@@ -575,7 +534,7 @@ def chain_flows(fwd, bwd=None, start=0, stop=None, check=None, a1=0.01, a2=0.5, 
     if check and other is None:
         raise ValueError("chain_flows: check=True needs the flows of the other direction (bwd)")
     par = consistency_params(a1, a2, name="chain_flows")
-    _chain_ready("chain_flows", fwd, bwd)
+    A.forward_only("chain_flows", fwd, bwd)
     n = abs(stop - start)
     slots = n + 1 if all_steps else 1
     with torch.no_grad():
@@ -600,11 +559,11 @@ def chain_flows_to(fwd, bwd, anchor=0, check=True, a1=0.01, a2=0.5):
     with real estimated flows is unmeasured.  Forward only; inputs are not modified.  Semantics: include/ofd.h."""
     from .flow_diffuser import ANIMATE_MAX_PIXELS
     B, T, H, W = _chain_flows("chain_flows_to", fwd, bwd)
-    anchor = _loop_int("chain_flows_to", "anchor", anchor, 0, T)
+    anchor = A.integer("chain_flows_to", "anchor", anchor, 0, T)
     if not isinstance(check, bool):
         raise ValueError(f"chain_flows_to: check must be True or False, got {check!r}")
     par = consistency_params(a1, a2, name="chain_flows_to")
-    _chain_ready("chain_flows_to", fwd, bwd)
+    A.forward_only("chain_flows_to", fwd, bwd)
     N = T + 1
     with torch.no_grad():
         fwd, bwd = L.f32c(fwd), L.f32c(bwd)
@@ -634,20 +593,20 @@ def composite_layer(frames, layer, disp, premultiplied=True):
     first, in torch.  One launch; forward only; inputs are not modified; the same input gives the same bits.  Semantics:
     include/ofd.h (`ofd_layer_composite`)."""
     if not torch.is_tensor(frames) or frames.dim() != 5 or frames.numel() == 0 or not 1 <= frames.shape[2] <= 8:
-        raise ValueError(f"composite_layer: frames must be a non-empty (B, n, C, H, W) tensor with 1 <= C <= 8, got {_shape_of(frames)}")
+        raise ValueError(f"composite_layer: frames must be a non-empty (B, n, C, H, W) tensor with 1 <= C <= 8, got {A.shape_of(frames)}")
     B, n, C, H, W = frames.shape
     if max(H, W) > 32768 or n > 4097:
         raise ValueError(f"composite_layer: H and W must be at most 32768 and n at most 4097, got {tuple(frames.shape)}")
     if not torch.is_tensor(layer) or tuple(layer.shape) != (B, C + 1, H, W):
-        raise ValueError(f"composite_layer: layer must be (B, C + 1, H, W) = {(B, C + 1, H, W)}, got {_shape_of(layer)}")
+        raise ValueError(f"composite_layer: layer must be (B, C + 1, H, W) = {(B, C + 1, H, W)}, got {A.shape_of(layer)}")
     if not torch.is_tensor(disp) or tuple(disp.shape) != (B, n, 2, H, W):
-        raise ValueError(f"composite_layer: disp must be (B, n, 2, H, W) = {(B, n, 2, H, W)}, got {_shape_of(disp)}")
+        raise ValueError(f"composite_layer: disp must be (B, n, 2, H, W) = {(B, n, 2, H, W)}, got {A.shape_of(disp)}")
     if not all(t.is_floating_point() for t in (frames, layer, disp)):
         raise ValueError(f"composite_layer: frames, layer and disp must be floating-point tensors, got "
                          f"{[t.dtype for t in (frames, layer, disp)]}")
     if not isinstance(premultiplied, bool):
         raise ValueError(f"composite_layer: premultiplied must be True or False, got {premultiplied!r}")
-    _chain_ready("composite_layer", frames, layer, disp)
+    A.forward_only("composite_layer", frames, layer, disp)
     with torch.no_grad():
         frames, layer, disp = L.f32c(frames), L.f32c(layer), L.f32c(disp)
         if not premultiplied:
@@ -659,6 +618,7 @@ def composite_layer(frames, layer, disp, premultiplied=True):
 
 # ---- global motion of a flow: robust fit, split, render, camera path (not in the reference; semantics: include/ofd.h, `ofd_motion_fit`) ----
 MOTION_MODELS = ("translation", "similarity", "affine", "homography")
+_MOTION_WHY = "the fit, the field and the warp have no backward pass"
 
 
 class MotionFit(collections.namedtuple("MotionFit", "matrix params stats model_flow residual weight")):
@@ -675,20 +635,20 @@ def motion_params(model="affine", iterations=6, sigma=1.0, name="fit_motion"):
     """the rules of the fit's model, rounds and scale (ValueError); host logic, no engine call"""
     if not isinstance(model, str) or model not in MOTION_MODELS:
         raise ValueError(f"{name}: model must be one of {MOTION_MODELS}, got {model!r}")
-    if isinstance(sigma, bool) or not isinstance(sigma, (int, float)) or not 0.0 < sigma < float("inf"):      # false for NaN
+    if not A.is_number(sigma) or not 0.0 < sigma < float("inf"):            # false for NaN
         raise ValueError(f"{name}: sigma must be a finite number > 0 (the residual, in pixels, at which a pixel's weight is 1/4), got {sigma!r}")
-    return dict(model=MOTION_MODELS.index(model), iterations=_loop_int(name, "iterations", iterations, 0, 64), sigma=float(sigma))
+    return dict(model=MOTION_MODELS.index(model), iterations=A.integer(name, "iterations", iterations, 0, 64), sigma=float(sigma))
 
 
 def _motion_flow_conf(name, flow, conf):
     """the shape and dtype rules of a flow and its confidence -> (B, H, W)"""
     if not torch.is_tensor(flow) or flow.dim() != 4 or flow.shape[1] != 2 or flow.numel() == 0:
-        raise ValueError(f"{name}: flow must be a non-empty (B, 2, H, W) tensor, got {_shape_of(flow)}")
+        raise ValueError(f"{name}: flow must be a non-empty (B, 2, H, W) tensor, got {A.shape_of(flow)}")
     B, _, H, W = flow.shape
     if max(H, W) > 32768:
         raise ValueError(f"{name}: H and W must be at most 32768, got {tuple(flow.shape)}")
     if conf is not None and (not torch.is_tensor(conf) or tuple(conf.shape) != (B, 1, H, W)):
-        raise ValueError(f"{name}: conf must be (B, 1, H, W) = {(B, 1, H, W)} or None, got {_shape_of(conf)}")
+        raise ValueError(f"{name}: conf must be (B, 1, H, W) = {(B, 1, H, W)} or None, got {A.shape_of(conf)}")
     given = [t for t in (flow, conf) if t is not None]
     if not all(t.is_floating_point() for t in given):
         raise ValueError(f"{name}: flow and conf must be floating-point tensors, got {[t.dtype for t in given]}")
@@ -699,11 +659,7 @@ def _motion_matrix(name, matrix, B=None):
     if not torch.is_tensor(matrix) or matrix.dim() != 3 or tuple(matrix.shape[1:]) != (3, 3) or matrix.numel() == 0 or \
             (B is not None and matrix.shape[0] != B) or not matrix.is_floating_point():
         want = "a non-empty (B, 3, 3) floating-point tensor" if B is None else f"a ({B}, 3, 3) floating-point tensor"
-        raise ValueError(f"{name}: matrix must be {want}, got {_shape_of(matrix)}")
-
-
-def _motion_ready(name, *tensors):
-    _chain_ready(name, *tensors, what="the fit, the field and the warp have")
+        raise ValueError(f"{name}: matrix must be {want}, got {A.shape_of(matrix)}")
 
 
 def _motion_fit(flow, conf, par, per_call=None):
@@ -740,7 +696,7 @@ def fit_motion(flow, model="affine", conf=None, iterations=6, sigma=1.0):
     No host synchronisation; forward only; inputs are not modified; the same input gives the same bits.  Semantics: include/ofd.h."""
     B, H, W = _motion_flow_conf("fit_motion", flow, conf)
     par = motion_params(model, iterations, sigma)
-    _motion_ready("fit_motion", flow, conf)
+    A.forward_only("fit_motion", flow, conf, why=_MOTION_WHY)
     with torch.no_grad():
         flow, conf = L.f32c(flow), None if conf is None else L.f32c(conf)
         matrix, params, stats = _motion_fit(flow, conf, par)
@@ -755,8 +711,8 @@ def motion_flow(matrix, H, W):
     """The flow of a matrix (not in the reference): (B, 2, H, W) fp32 in pixels, M [x, y, 1] - [x, y], computed in double and rounded
     once; NaN where the projective denominator is not > 0.  matrix: (B, 3, 3), e.g. `fit_motion`'s.  One launch; forward only."""
     _motion_matrix("motion_flow", matrix)
-    H, W = _loop_int("motion_flow", "H", H, 1, 32768), _loop_int("motion_flow", "W", W, 1, 32768)
-    _motion_ready("motion_flow", matrix)
+    H, W = A.integer("motion_flow", "H", H, 1, 32768), A.integer("motion_flow", "W", W, 1, 32768)
+    A.forward_only("motion_flow", matrix, why=_MOTION_WHY)
     with torch.no_grad():
         matrix = matrix.double().contiguous()
         out = torch.empty(matrix.shape[0], 2, H, W, dtype=torch.float32, device=matrix.device)
@@ -770,12 +726,12 @@ def warp_homography(img, matrix):
     Where that place is outside the frame out is 0 and inside 0; elsewhere inside is 1.  A gather: no holes.  One launch; forward
     only; inputs are not modified; the same input gives the same bits.  Semantics: include/ofd.h (`ofd_homography_warp`)."""
     if not torch.is_tensor(img) or img.dim() != 4 or img.numel() == 0 or not 1 <= img.shape[1] <= 8 or not img.is_floating_point():
-        raise ValueError(f"warp_homography: img must be a non-empty floating-point (B, C, H, W) tensor with 1 <= C <= 8, got {_shape_of(img)}")
+        raise ValueError(f"warp_homography: img must be a non-empty floating-point (B, C, H, W) tensor with 1 <= C <= 8, got {A.shape_of(img)}")
     B, C, H, W = img.shape
     if max(H, W) > 32768:
         raise ValueError(f"warp_homography: H and W must be at most 32768, got {tuple(img.shape)}")
     _motion_matrix("warp_homography", matrix, B)
-    _motion_ready("warp_homography", img, matrix)
+    A.forward_only("warp_homography", img, matrix, why=_MOTION_WHY)
     with torch.no_grad():
         img, matrix = L.f32c(img), matrix.double().contiguous()
         out, inside = torch.empty_like(img), torch.empty(B, 1, H, W, dtype=torch.float32, device=img.device)
@@ -802,11 +758,11 @@ def layers_params(layers=3, model="affine", solves=8, sigma=1.0, tau=2.0, min_su
     """the rules of the layer count, the model, the solves, the two scales, the support and the vote (ValueError); host logic, no
     engine call"""
     par = motion_params(model, 0, sigma, name=name)
-    if isinstance(tau, bool) or not isinstance(tau, (int, float)) or not 0.0 < tau < float("inf"):             # false for NaN
+    if not A.is_number(tau) or not 0.0 < tau < float("inf"):                # false for NaN
         raise ValueError(f"{name}: tau must be a finite number > 0 (the residual, in pixels, beyond which no layer claims a pixel), got {tau!r}")
-    return dict(model=par["model"], sigma=par["sigma"], tau=float(tau), layers=_loop_int(name, "layers", layers, 1, MAX_LAYERS),
-                solves=_loop_int(name, "solves", solves, 0, 64), min_support=_loop_int(name, "min_support", min_support, 1, 2 ** 31 - 1),
-                vote_radius=_loop_int(name, "vote_radius", vote_radius, 0, 3))
+    return dict(model=par["model"], sigma=par["sigma"], tau=float(tau), layers=A.integer(name, "layers", layers, 1, MAX_LAYERS),
+                solves=A.integer(name, "solves", solves, 0, 64), min_support=A.integer(name, "min_support", min_support, 1, 2 ** 31 - 1),
+                vote_radius=A.integer(name, "vote_radius", vote_radius, 0, 3))
 
 
 def _layer_labels(name, labels, B=None, H=None, W=None):
@@ -814,7 +770,7 @@ def _layer_labels(name, labels, B=None, H=None, W=None):
     if ok and B is not None:
         ok = tuple(labels.shape) == (B, 1, H, W)
     if not ok:
-        raise ValueError(f"{name}: labels must be a non-empty (B, 1, H, W) uint8 tensor, got {_shape_of(labels)}")
+        raise ValueError(f"{name}: labels must be a non-empty (B, 1, H, W) uint8 tensor, got {A.shape_of(labels)}")
     if max(labels.shape[2:]) > 32768:
         raise ValueError(f"{name}: H and W must be at most 32768, got {tuple(labels.shape)}")
 
@@ -822,7 +778,7 @@ def _layer_labels(name, labels, B=None, H=None, W=None):
 def _layer_matrices(name, matrices, B):
     if not torch.is_tensor(matrices) or matrices.dim() != 4 or tuple(matrices.shape[2:]) != (3, 3) or matrices.shape[0] != B or \
             not 1 <= matrices.shape[1] <= MAX_LAYERS or not matrices.is_floating_point():
-        raise ValueError(f"{name}: matrices must be a floating-point ({B}, K, 3, 3) tensor with 1 <= K <= {MAX_LAYERS}, got {_shape_of(matrices)}")
+        raise ValueError(f"{name}: matrices must be a floating-point ({B}, K, 3, 3) tensor with 1 <= K <= {MAX_LAYERS}, got {A.shape_of(matrices)}")
     return matrices.shape[1]
 
 
@@ -867,7 +823,7 @@ def segment_motion(flow, layers=3, model="affine", conf=None, solves=8, sigma=1.
     forward only; inputs are not modified; the same input gives the same bits.  Semantics: include/ofd.h (L1 ... L7)."""
     B, H, W = _motion_flow_conf("segment_motion", flow, conf)
     par = layers_params(layers, model, solves, sigma, tau, min_support, vote_radius)
-    _motion_ready("segment_motion", flow, conf)
+    A.forward_only("segment_motion", flow, conf, why=_MOTION_WHY)
     K, lib, dev = par["layers"], L.lib(), flow.device
     with torch.no_grad():
         flow, conf = L.f32c(flow), None if conf is None else L.f32c(conf)
@@ -898,8 +854,8 @@ def assign_motion(flow, matrices, conf=None, tau=2.0, alive=None):
     K = _layer_matrices("assign_motion", matrices, B)
     tau = layers_params(tau=tau, name="assign_motion")["tau"]
     if alive is not None and (not torch.is_tensor(alive) or tuple(alive.shape) != (B, K) or alive.dtype != torch.bool):
-        raise ValueError(f"assign_motion: alive must be a ({B}, {K}) bool tensor or None, got {_shape_of(alive)}")
-    _motion_ready("assign_motion", flow, conf, matrices, alive)
+        raise ValueError(f"assign_motion: alive must be a ({B}, {K}) bool tensor or None, got {A.shape_of(alive)}")
+    A.forward_only("assign_motion", flow, conf, matrices, alive, why=_MOTION_WHY)
     with torch.no_grad():
         flow, conf = L.f32c(flow), None if conf is None else L.f32c(conf)
         matrix = matrices.double().reshape(B, K, 9).contiguous()
@@ -912,8 +868,8 @@ def vote_labels(labels, layers, radius=1):
     lowest.  Other labels do not vote; LABEL_OUTLIER pixels are filled where a neighbour votes, LABEL_INVALID pixels stay.  radius
     1..3.  One launch, integer arithmetic; forward only.  Semantics: include/ofd.h (L6)."""
     _layer_labels("vote_labels", labels)
-    K = _loop_int("vote_labels", "layers", layers, 1, MAX_LAYERS)
-    radius = _loop_int("vote_labels", "radius", radius, 1, 3)
+    K = A.integer("vote_labels", "layers", layers, 1, MAX_LAYERS)
+    radius = A.integer("vote_labels", "radius", radius, 1, 3)
     L.require_gpu(labels)
     return _label_vote(labels.contiguous(), K, radius)
 
@@ -942,9 +898,9 @@ def path_params(T, mode="smooth", sigma_t=4.0, anchor=0, name="camera_path"):
         raise ValueError(f"{name}: mode must be 'smooth' or 'lock', got {mode!r}")
     if T > 4096:
         raise ValueError(f"{name}: at most 4096 matrices (4097 frames), got {T}")
-    if isinstance(sigma_t, bool) or not isinstance(sigma_t, (int, float)) or not 0.0 < sigma_t <= 1024.0:   # false for NaN
+    if not A.is_number(sigma_t) or not 0.0 < sigma_t <= 1024.0:             # false for NaN
         raise ValueError(f"{name}: sigma_t must be a number in (0, 1024] (frames), got {sigma_t!r}")
-    return dict(mode=mode, sigma_t=float(sigma_t), anchor=_loop_int(name, "anchor", anchor, 0, T))
+    return dict(mode=mode, sigma_t=float(sigma_t), anchor=A.integer(name, "anchor", anchor, 0, T))
 
 
 def camera_path(matrices, mode="smooth", sigma_t=4.0, anchor=0):
@@ -960,7 +916,7 @@ def camera_path(matrices, mode="smooth", sigma_t=4.0, anchor=0):
     adjugate inverses written out; no host synchronisation.  sigma_t is untuned on real footage."""
     if not torch.is_tensor(matrices) or matrices.dim() != 4 or tuple(matrices.shape[2:]) != (3, 3) or matrices.numel() == 0 or \
             not matrices.is_floating_point():
-        raise ValueError(f"camera_path: matrices must be a non-empty floating-point (B, T, 3, 3) tensor, got {_shape_of(matrices)}")
+        raise ValueError(f"camera_path: matrices must be a non-empty floating-point (B, T, 3, 3) tensor, got {A.shape_of(matrices)}")
     B, T = matrices.shape[:2]
     par = path_params(T, mode, sigma_t, anchor)
     if matrices.requires_grad:
@@ -997,16 +953,16 @@ def stabilize_clip(clip, fwd, conf=None, model="similarity", mode="smooth", sigm
     if not torch.is_tensor(clip) or clip.dim() != 5 or clip.numel() == 0 or clip.shape[1] < 2 or not 1 <= clip.shape[2] <= 8 or \
             not clip.is_floating_point():
         raise ValueError(f"stabilize_clip: clip must be a non-empty floating-point (B, T + 1, C, H, W) tensor with at least two frames and "
-                         f"1 <= C <= 8, got {_shape_of(clip)}")
+                         f"1 <= C <= 8, got {A.shape_of(clip)}")
     B, N, C, H, W = clip.shape
     T = N - 1
     if not torch.is_tensor(fwd) or tuple(fwd.shape) != (B, T, 2, H, W):
-        raise ValueError(f"stabilize_clip: fwd must be (B, T, 2, H, W) = {(B, T, 2, H, W)}, got {_shape_of(fwd)}")
+        raise ValueError(f"stabilize_clip: fwd must be (B, T, 2, H, W) = {(B, T, 2, H, W)}, got {A.shape_of(fwd)}")
     if conf is not None and (not torch.is_tensor(conf) or tuple(conf.shape) != (B, T, 1, H, W)):
-        raise ValueError(f"stabilize_clip: conf must be (B, T, 1, H, W) = {(B, T, 1, H, W)} or None, got {_shape_of(conf)}")
+        raise ValueError(f"stabilize_clip: conf must be (B, T, 1, H, W) = {(B, T, 1, H, W)} or None, got {A.shape_of(conf)}")
     _motion_flow_conf("stabilize_clip", fwd.reshape(B * T, 2, H, W), None if conf is None else conf.reshape(B * T, 1, H, W))
     par, path_par = motion_params(model, iterations, sigma, name="stabilize_clip"), path_params(T, mode, sigma_t, anchor, "stabilize_clip")
-    _motion_ready("stabilize_clip", clip, fwd, conf)
+    A.forward_only("stabilize_clip", clip, fwd, conf, why=_MOTION_WHY)
     with torch.no_grad():
         per = max(1, ANIMATE_MAX_PIXELS // (H * W))                          # flows, frames per call
         flows = L.f32c(fwd).reshape(B * T, 2, H, W)
@@ -1032,8 +988,8 @@ Plate = collections.namedtuple("Plate", "plate votes count canvas")
 
 def plate_voters(T, anchor=0, every=1, name="background_plate"):
     """the frames of a clip of T + 1 frames that vote for its plate: anchor +- k * every, ascending (ValueError); host logic"""
-    anchor = _loop_int(name, "anchor", anchor, 0, T)
-    every = _loop_int(name, "every", every, 1, max(T, 1))
+    anchor = A.integer(name, "anchor", anchor, 0, T)
+    every = A.integer(name, "every", every, 1, max(T, 1))
     idx = list(range(anchor % every, T + 1, every))
     if len(idx) > PLATE_MAX_FRAMES:
         raise ValueError(f"{name}: at most {PLATE_MAX_FRAMES} frames vote for a plate, got {len(idx)} of {T + 1}: raise every= (now {every})")
@@ -1049,7 +1005,7 @@ def plate_params(N, H, W, canvas="frame", mode="median", min_count=1, lo=0.05, h
     if N > PLATE_MAX_FRAMES:
         raise ValueError(f"{name}: at most {PLATE_MAX_FRAMES} frames vote for a plate, got {N}: take a subset of the clip "
                          f"(`background_plate(..., every=)`)")
-    H, W = _loop_int(name, "H", H, 1, 32768), _loop_int(name, "W", W, 1, 32768)
+    H, W = A.integer(name, "H", H, 1, 32768), A.integer(name, "W", W, 1, 32768)
     if isinstance(canvas, str):
         if canvas not in ("frame", "union"):
             raise ValueError(f"{name}: canvas must be 'frame', 'union' or (x0, y0, Wc, Hc), got {canvas!r}")
@@ -1057,15 +1013,15 @@ def plate_params(N, H, W, canvas="frame", mode="median", min_count=1, lo=0.05, h
     else:
         if not isinstance(canvas, (tuple, list)) or len(canvas) != 4:
             raise ValueError(f"{name}: canvas must be 'frame', 'union' or (x0, y0, Wc, Hc), got {canvas!r}")
-        x0, y0 = (_loop_int(name, f"canvas {k}", v, -32768, 32768) for k, v in zip(("x0", "y0"), canvas[:2]))
-        Wc, Hc = (_loop_int(name, f"canvas {k}", v, 1, 32768) for k, v in zip(("Wc", "Hc"), canvas[2:]))
+        x0, y0 = (A.integer(name, f"canvas {k}", v, -32768, 32768) for k, v in zip(("x0", "y0"), canvas[:2]))
+        Wc, Hc = (A.integer(name, f"canvas {k}", v, 1, 32768) for k, v in zip(("Wc", "Hc"), canvas[2:]))
         if Wc * Hc > ANIMATE_MAX_PIXELS:
             raise ValueError(f"{name}: a canvas of {Wc} x {Hc} is over {ANIMATE_MAX_PIXELS} pixels")
         canvas = (x0, y0, Wc, Hc)
     if not isinstance(mode, str) or mode not in PLATE_MODES:
         raise ValueError(f"{name}: mode must be one of {PLATE_MODES}, got {mode!r}")
-    min_count = _loop_int(name, "min_count", min_count, 1, N)
-    lo, hi = _loop_real(name, "lo", lo), _loop_real(name, "hi", hi)
+    min_count = A.integer(name, "min_count", min_count, 1, N)
+    lo, hi = A.real(name, "lo", lo), A.real(name, "hi", hi)
     if not 0.0 <= lo < hi:
         raise ValueError(f"{name}: lo and hi must satisfy 0 <= lo < hi, got {lo!r} and {hi!r}")
     return dict(canvas=canvas, mode=PLATE_MODES.index(mode), min_count=min_count, lo=lo, hi=hi)
@@ -1098,14 +1054,14 @@ def plate_canvas(path, H, W, name="build_plate"):
 
 def _plate_clip(name, clip, what="clip"):
     if not torch.is_tensor(clip) or clip.dim() != 5 or clip.numel() == 0 or not 1 <= clip.shape[2] <= 8 or not clip.is_floating_point():
-        raise ValueError(f"{name}: {what} must be a non-empty floating-point (B, N, C, H, W) tensor with 1 <= C <= 8, got {_shape_of(clip)}")
+        raise ValueError(f"{name}: {what} must be a non-empty floating-point (B, N, C, H, W) tensor with 1 <= C <= 8, got {A.shape_of(clip)}")
     return tuple(clip.shape)
 
 
 def _plate_path(name, path, B, N=None):
     if not torch.is_tensor(path) or path.dim() != 4 or tuple(path.shape[2:]) != (3, 3) or path.shape[0] != B or path.numel() == 0 or \
             (N is not None and path.shape[1] != N) or not path.is_floating_point():
-        raise ValueError(f"{name}: path must be a floating-point ({B}, {'N' if N is None else N}, 3, 3) tensor, got {_shape_of(path)}")
+        raise ValueError(f"{name}: path must be a floating-point ({B}, {'N' if N is None else N}, 3, 3) tensor, got {A.shape_of(path)}")
 
 
 def build_plate(clip, path, weight=None, canvas="frame", mode="median", min_count=1):
@@ -1126,8 +1082,8 @@ def build_plate(clip, path, weight=None, canvas="frame", mode="median", min_coun
     par = plate_params(N, H, W, canvas, mode, min_count)
     _plate_path("build_plate", path, B, N)
     if weight is not None and (not torch.is_tensor(weight) or tuple(weight.shape) != (B, N, 1, H, W) or not weight.is_floating_point()):
-        raise ValueError(f"build_plate: weight must be a floating-point (B, N, 1, H, W) = {(B, N, 1, H, W)} tensor or None, got {_shape_of(weight)}")
-    _chain_ready("build_plate", clip, path, weight, what="the plate has")
+        raise ValueError(f"build_plate: weight must be a floating-point (B, N, 1, H, W) = {(B, N, 1, H, W)} tensor or None, got {A.shape_of(weight)}")
+    A.forward_only("build_plate", clip, path, weight, why="the plate has no backward pass")
     with torch.no_grad():
         clip, path = L.f32c(clip), path.double().contiguous()
         weight = None if weight is None else L.f32c(weight)
@@ -1162,16 +1118,16 @@ def project_plate(plate, path, H, W, frames=None, alpha=None, lo=0.05, hi=0.15):
     par = plate_params(1, H, W, "frame", "median", 1, lo, hi, name=name)
     if H * W > ANIMATE_MAX_PIXELS:                                          # a call takes whole frames: the same rule as for a canvas
         raise ValueError(f"{name}: a frame of {W} x {H} is over {ANIMATE_MAX_PIXELS} pixels")
-    x0, y0 = (_loop_int(name, f"canvas {k}", v, -32768, 32768) for k, v in zip(("x0", "y0"), tuple(plate.canvas)[:2]))
+    x0, y0 = (A.integer(name, f"canvas {k}", v, -32768, 32768) for k, v in zip(("x0", "y0"), tuple(plate.canvas)[:2]))
     if tuple(plate.canvas)[2:] != (Wc, Hc) or not 1 <= C <= 8 or (plate.votes is not None and tuple(plate.votes.shape) != (B, 1, Hc, Wc)):
-        raise ValueError(f"{name}: the plate {_shape_of(plate.plate)}, its votes {_shape_of(plate.votes)} and its canvas {plate.canvas} disagree")
+        raise ValueError(f"{name}: the plate {A.shape_of(plate.plate)}, its votes {A.shape_of(plate.votes)} and its canvas {plate.canvas} disagree")
     _plate_path(name, path, B)
     N = path.shape[1]
     if frames is not None and _plate_clip(name, frames, "frames") != (B, N, C, H, W):
-        raise ValueError(f"{name}: frames must be (B, N, C, H, W) = {(B, N, C, H, W)}, got {_shape_of(frames)}")
+        raise ValueError(f"{name}: frames must be (B, N, C, H, W) = {(B, N, C, H, W)}, got {A.shape_of(frames)}")
     if alpha is not None and (frames is None or not torch.is_tensor(alpha) or tuple(alpha.shape) != (B, N, 1, H, W) or not alpha.is_floating_point()):
-        raise ValueError(f"{name}: alpha needs frames and must be a floating-point (B, N, 1, H, W) = {(B, N, 1, H, W)} tensor, got {_shape_of(alpha)}")
-    _chain_ready(name, plate.plate, plate.votes, path, frames, alpha, what="the projection has")
+        raise ValueError(f"{name}: alpha needs frames and must be a floating-point (B, N, 1, H, W) = {(B, N, 1, H, W)} tensor, got {A.shape_of(alpha)}")
+    A.forward_only(name, plate.plate, plate.votes, path, frames, alpha, why="the projection has no backward pass")
     with torch.no_grad():
         pl, votes = L.f32c(plate.plate), None if plate.votes is None else L.f32c(plate.votes)
         inv = _unit3(_inv3(path.double())).contiguous().reshape(B, N, 9)
@@ -1223,16 +1179,16 @@ def background_plate(clip, fwd, bwd=None, conf=None, conf_bwd=None, model="homog
     B, N, C, H, W = _plate_clip(name, clip)
     T = N - 1
     if T < 1:
-        raise ValueError(f"{name}: clip must have at least two frames, got {_shape_of(clip)}")
+        raise ValueError(f"{name}: clip must have at least two frames, got {A.shape_of(clip)}")
     for key, fl, ch in (("fwd", fwd, 2), ("bwd", bwd, 2), ("conf", conf, 1), ("conf_bwd", conf_bwd, 1)):
         if (fl is not None or key == "fwd") and (not torch.is_tensor(fl) or tuple(fl.shape) != (B, T, ch, H, W) or not fl.is_floating_point()):
-            raise ValueError(f"{name}: {key} must be a floating-point (B, T, {ch}, H, W) = {(B, T, ch, H, W)} tensor, got {_shape_of(fl)}")
+            raise ValueError(f"{name}: {key} must be a floating-point (B, T, {ch}, H, W) = {(B, T, ch, H, W)} tensor, got {A.shape_of(fl)}")
     if conf_bwd is not None and bwd is None:
         raise ValueError(f"{name}: conf_bwd needs bwd")
     par = motion_params(model, iterations, sigma, name=name)
     idx = plate_voters(T, anchor, every, name)
     plate_params(len(idx), H, W, canvas, mode, min_count, name=name)
-    _chain_ready(name, clip, fwd, bwd, conf, conf_bwd, what="the plate has")
+    A.forward_only(name, clip, fwd, bwd, conf, conf_bwd, why="the plate has no backward pass")
     with torch.no_grad():
         per = max(1, ANIMATE_MAX_PIXELS // (H * W))
         flows = L.f32c(fwd).reshape(B * T, 2, H, W)
@@ -1265,7 +1221,7 @@ def remove_moving(clip, fwd, bwd=None, conf=None, conf_bwd=None, model="homograp
     B, N, C, H, W = _plate_clip("remove_moving", clip)
     plate_params(1, H, W, "frame", "median", 1, lo, hi, name="remove_moving")
     if alpha is not None and (not torch.is_tensor(alpha) or tuple(alpha.shape) != (B, N, 1, H, W) or not alpha.is_floating_point()):
-        raise ValueError(f"remove_moving: alpha must be a floating-point (B, T + 1, 1, H, W) = {(B, N, 1, H, W)} tensor or None, got {_shape_of(alpha)}")
+        raise ValueError(f"remove_moving: alpha must be a floating-point (B, T + 1, 1, H, W) = {(B, N, 1, H, W)} tensor or None, got {A.shape_of(alpha)}")
     plate, _matrices, path, _weight = background_plate(clip, fwd, bwd, conf, conf_bwd, model, anchor, canvas, mode, every, min_count, iterations,
                                                        sigma)
     video, _covered, fg = project_plate(plate, path, H, W, frames=clip, alpha=alpha, lo=lo, hi=hi)
@@ -1275,13 +1231,12 @@ def remove_moving(clip, fwd, bwd=None, conf=None, conf_bwd=None, model="homograp
 # ---- guided weighted median of a flow (not in the reference; semantics: include/ofd.h, `ofd_flow_median`) ----------------------------
 def median_params(radius=2, sigma_s=2.0, sigma_r=0.1, iterations=1, fill=False, name="median_filter_flow"):
     """the rules of the median's window, widths and passes (ValueError); host logic, no engine call"""
-    real = lambda v: not isinstance(v, bool) and isinstance(v, (int, float)) and v > 0.0                      # false for NaN
-    if not real(sigma_s) or not real(sigma_r):
+    if not all(A.is_number(v) and v > 0.0 for v in (sigma_s, sigma_r)):                         # false for NaN
         raise ValueError(f"{name}: sigma_s and sigma_r must be numbers > 0 (inf switches a term off), got {sigma_s!r} and {sigma_r!r}")
     if not isinstance(fill, bool):
         raise ValueError(f"{name}: fill must be True or False, got {fill!r}")
-    return dict(radius=_loop_int(name, "radius", radius, 1, 3), sigma_s=float(sigma_s), sigma_r=float(sigma_r),
-                iterations=_loop_int(name, "iterations", iterations, 1, 8), fill=fill)
+    return dict(radius=A.integer(name, "radius", radius, 1, 3), sigma_s=float(sigma_s), sigma_r=float(sigma_r),
+                iterations=A.integer(name, "iterations", iterations, 1, 8), fill=fill)
 
 
 def median_filter_flow(flow, guide=None, radius=2, sigma_s=2.0, sigma_r=0.1, conf=None, iterations=1, fill=False):
@@ -1298,24 +1253,20 @@ def median_filter_flow(flow, guide=None, radius=2, sigma_s=2.0, sigma_r=0.1, con
     untuned on real footage.  One launch per pass; forward only; inputs are not modified; the same input gives the same bits.
     Semantics: include/ofd.h."""
     if not torch.is_tensor(flow) or flow.dim() != 4 or flow.numel() == 0 or not 1 <= flow.shape[1] <= 4:
-        raise ValueError(f"median_filter_flow: flow must be a non-empty (B, C, H, W) tensor with 1 <= C <= 4, got {_shape_of(flow)}")
+        raise ValueError(f"median_filter_flow: flow must be a non-empty (B, C, H, W) tensor with 1 <= C <= 4, got {A.shape_of(flow)}")
     B, C, H, W = flow.shape
     if max(H, W) > 32768:
         raise ValueError(f"median_filter_flow: H and W must be at most 32768, got {tuple(flow.shape)}")
     if guide is not None and (not torch.is_tensor(guide) or guide.dim() != 4 or not 1 <= guide.shape[1] <= 4 or
                               (guide.shape[0], guide.shape[2], guide.shape[3]) != (B, H, W)):
-        raise ValueError(f"median_filter_flow: guide must be (B, 1..4, H, W) = ({B}, 1..4, {H}, {W}) or None, got {_shape_of(guide)}")
+        raise ValueError(f"median_filter_flow: guide must be (B, 1..4, H, W) = ({B}, 1..4, {H}, {W}) or None, got {A.shape_of(guide)}")
     if conf is not None and (not torch.is_tensor(conf) or tuple(conf.shape) != (B, 1, H, W)):
-        raise ValueError(f"median_filter_flow: conf must be (B, 1, H, W) = {(B, 1, H, W)} or None, got {_shape_of(conf)}")
+        raise ValueError(f"median_filter_flow: conf must be (B, 1, H, W) = {(B, 1, H, W)} or None, got {A.shape_of(conf)}")
     given = [t for t in (flow, guide, conf) if t is not None]
     if not all(t.is_floating_point() for t in given):
         raise ValueError(f"median_filter_flow: flow, guide and conf must be floating-point tensors, got {[t.dtype for t in given]}")
     par = median_params(radius, sigma_s, sigma_r, iterations, fill)
-    if any(t.requires_grad for t in given):
-        raise L.OfdError("median_filter_flow: forward only (the selection has no backward pass): detach the inputs")
-    L.require_gpu(*given)
-    if any(t.device != flow.device for t in given):
-        raise ValueError(f"median_filter_flow: flow, guide and conf must be on one device, got {[str(t.device) for t in given]}")
+    A.forward_only("median_filter_flow", *given, why="the selection has no backward pass", who="flow, guide and conf")
     Cg = 0 if guide is None else guide.shape[1]
     with torch.no_grad():
         src, guide, conf = L.f32c(flow), None if guide is None else L.f32c(guide), None if conf is None else L.f32c(conf)

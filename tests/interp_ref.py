@@ -176,6 +176,37 @@ def make_case(shape, amplitude=None, nans=False):
     return frame1, frame2, flow12, flow21
 
 
+EDGE_SHAPES = ((5, 7), (17, 65))           # the smallest frame with an interior, and one pixel past a 64 x 16 tile both ways
+EDGE_PARAMS = dict(alpha=1.0, beta=0.0, oob=0.5, zmax=20.0)
+
+
+@functools.lru_cache(maxsize=None)
+def edge_case(H, W, B=2, C=2):
+    """(frame1, frame2, flow12, flow21) whose sample points q = p + flow(p) lie exactly on the last column and row, half a pixel before
+    them, past every side of the frame and at +-1e30, NaN and +-Inf, in both directions.  The frames are multiples of 1/8 in [-1, 1],
+    every other flow a multiple of 1/2 px: with EDGE_PARAMS every weight is 0, 1/2 or 1 and Z is exact in fp32, so that the fp32
+    restatement and the kernel differ only by exp and the two products behind it.  Computed once, shared, never modified."""
+    gen = torch.Generator().manual_seed(100 * H + W)
+    frames = [torch.randint(-8, 9, (B, C, H, W), generator=gen).float() / 8.0 for _ in range(2)]
+    flows = [torch.randint(-4, 5, (B, 2, H, W), generator=gen).float() * 0.5 for _ in range(2)]
+    xs, ys = torch.arange(W, dtype=torch.float32), torch.arange(H, dtype=torch.float32)
+    for k, fl in enumerate(flows):
+        a, b = k, 1 - k                                                      # the two directions use the two samples the other way round
+        fl[a, 0, 0, :] = W - 1 - xs                                          # q.x = W - 1 exactly
+        fl[a, 1, :, 0] = H - 1 - ys                                          # q.y = H - 1 exactly
+        fl[b, 0, H - 1, :] = W - 1.5 - xs                                    # half a pixel before the last column, on the last row
+        fl[b, 1, :, W - 1] = H - 1.5 - ys                                    # half a pixel before the last row, on the last column
+        fl[b, 0, 0, :] = float(W)                                            # past the right side
+        fl[b, 1, 1, :W // 2] = -float(H) - 0.5                               # past the top
+        fl[a, 0, 2, 1:3] = -float(W)                                         # past the left side
+        fl[a, 1, 3, 1:3] = float(H)                                          # past the bottom
+        for i, v in enumerate((float("nan"), float("inf"), float("-inf"), 1e30, -1e30)):
+            fl[(i + k) % B, i % 2, (2 + i) % H, (3 + i + k) % W] = v
+    frames[0][0, 0, H // 2, W // 2] = float("nan")
+    frames[1][1, 1, 1, 1] = float("inf")
+    return frames[0], frames[1], flows[0], flows[1]
+
+
 BIG = SHAPES[:2] + SHAPES[3:4]              # the shapes whose default inputs leave M >= 0.05 on most of what they cover
 # (shape, beta, amplitude [None: by shape], oob, NaN pixels, compare colour): both betas at every shape; one case with NaN in frames and
 # flows; the two small many-channel / few-row shapes again with a small motion and a mild out-of-frame score, so that their colour is

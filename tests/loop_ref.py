@@ -127,6 +127,33 @@ def smooth_image(B, C, H, W, seed=0):
     return smooth(gen, (B, C, H, W), 8)
 
 
+EDGE_SHAPES = ((5, 7), (17, 65))               # the smallest frame with an interior, and one pixel past a 64 x 16 tile both ways
+
+
+@functools.lru_cache(maxsize=None)
+def edge_case(H, W, B=2, C=3):
+    """(img, motion) whose first Euler step of width 1 sends pixels exactly onto the last column and row, half a pixel before them,
+    past every side of the frame and to +-1e30, beside NaN and +-Inf entries (which count as 0).  Everything else is a multiple of
+    1/2 px (motion) or 1/8 (img): with order=1, substeps=1 and |speed| = 1 every coordinate is a multiple of 1/2, every weight is 0, 1/2
+    or 1, and every product and sum is exact in fp32 -- or, next to 1e30, rounded once from an exact value -- so the fp32 kernels must
+    give the float64 restatement rounded to fp32, bit for bit.  Computed once, shared, never modified."""
+    gen = torch.Generator().manual_seed(100 * H + W)
+    motion = torch.randint(-4, 5, (B, 2, H, W), generator=gen).float() * 0.5
+    img = torch.randint(-32, 33, (B, C, H, W), generator=gen).float() / 8.0
+    xs, ys = torch.arange(W, dtype=torch.float32), torch.arange(H, dtype=torch.float32)
+    motion[0, 0, 0, :] = W - 1 - xs                                          # q.x = W - 1 exactly, from every column of row 0
+    motion[0, 1, :, 0] = H - 1 - ys                                          # q.y = H - 1 exactly, from every row of column 0
+    motion[1, 0, H - 1, :] = W - 1.5 - xs                                    # half a pixel before the last column, on the last row
+    motion[1, 1, :, W - 1] = H - 1.5 - ys                                    # half a pixel before the last row, on the last column
+    motion[1, 0, 0, :] = float(W)                                            # past the right side
+    motion[1, 1, 1, :W // 2] = -float(H) - 0.5                               # past the top
+    motion[0, 0, 2, 1:3] = -float(W)                                         # past the left side
+    motion[0, 1, 3, 1:3] = float(H)                                          # past the bottom
+    for i, v in enumerate((float("nan"), float("inf"), float("-inf"), 1e30, -1e30)):
+        motion[i % B, i % 2, (2 + i) % H, (3 + i) % W] = v
+    return img, motion
+
+
 FIELDS = dict(const=lambda B, H, W: constant_field(B, H, W), rot=lambda B, H, W: rotation_field(B, H, W),
               smooth=lambda B, H, W: smooth_field(B, H, W), nan=lambda B, H, W: smooth_field(B, H, W, nans=True))
 

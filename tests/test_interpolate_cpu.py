@@ -78,6 +78,20 @@ def test_restatement_handles_nan_and_the_frame_border():
 
 
 # ---------------------------------------------------------------------------------------------------- conditioning of the GPU cases
+@pytest.mark.parametrize("H, W", R.EDGE_SHAPES)
+def test_edge_case_scores_are_exact(H, W):
+    """interp_ref.edge_case: Z of the fp32 run is Z of the float64 run, bit for bit, except where a 1e30 under q overflows the fp32
+    square (NaN, the worst match) and not the float64 one; all three kinds of score occur (-alpha * oob outside, -zmax under a NaN, an
+    exact -d inside), and ten_in is finite whatever the flows hold"""
+    case = R.edge_case(H, W)
+    (t32, _f32, Z32), (_t64, _f64, Z64) = (R.prep_ref(*case, R.TIMES, **R.EDGE_PARAMS, dtype=dtype) for dtype in (torch.float32, torch.float64))
+    worst = Z32 == -R.EDGE_PARAMS["zmax"]
+    assert torch.equal(Z32[~worst], Z64.float()[~worst]) and torch.isfinite(t32).all()
+    outside = Z32 == -R.EDGE_PARAMS["alpha"] * R.EDGE_PARAMS["oob"]
+    assert worst.any() and outside.any() and (~worst & ~outside).any()
+    assert (Z64[worst] != Z32[worst]).sum() <= 16                           # the neighbours of the four +-1e30 entries
+
+
 def test_case_inputs_stay_off_the_border_lines():
     for case in R.CASES:
         _f1, _f2, flow12, flow21 = R.make_case(case[0], case[2], False)

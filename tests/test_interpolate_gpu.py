@@ -52,6 +52,26 @@ def test_prep_matches_the_restatement(case):
     assert torch.equal(again[0], ten_in) and _nan_equal(again[1], flows)     # the same bits
 
 
+@pytest.mark.parametrize("H, W", R.EDGE_SHAPES)
+def test_prep_edge_case(H, W):
+    """interp_ref.edge_case (q exactly on the last column and row, half a pixel before them, outside on every side, at +-1e30, NaN and
+    +-Inf, in both directions) against the fp32 run of the restatement, whose Z is exact (test_interpolate_cpu): ten_in is
+    v * a * (s * exp(Z)) with |a|, s, exp(Z) <= 1; on either side, the restatement's torch ops and the kernel, exp is within 1 ulp and the
+    two products round by 1/2 ulp each, 2 ulp a side of a value below 1 (ulp 2^-24): 4 * 2^-24.  flows are the one fp32 product, bit for bit.  5 x 7 and 17 x 65 take
+    the scalar path; 17 x 65 is one pixel past a 64 x 16 tile both ways."""
+    from opticalflowdiffusion_amd.warp import interp_prep
+    case = R.edge_case(H, W)
+    want, _flows, _Z = R.prep_ref(*case, R.TIMES, **R.EDGE_PARAMS, dtype=torch.float32)
+    dev = [t.cuda() for t in case]
+    ten_in, flows = interp_prep(*dev, R.TIMES, **R.EDGE_PARAMS)
+    assert torch.isfinite(ten_in).all()
+    err, tol = float((ten_in.cpu() - want).abs().max()), 4 * 2.0 ** -24
+    print(f"prep edge {H}x{W}: ten_in max abs err {err:.3e} (tolerance {tol:.3e})")
+    assert err <= tol
+    t = torch.tensor(R.TIMES, dtype=torch.float32).view(1, -1, 1, 1, 1)
+    assert _nan_equal(flows[0].cpu(), t * case[2][:, None]) and _nan_equal(flows[1].cpu(), (1.0 - t) * case[3][:, None])
+
+
 # ------------------------------------------------------------------------------------------------------------------- stage 2: merge
 def _ulp32(x):
     """the spacing of fp32 at |x| (x: float64), 2^-149 at and below the smallest normal"""

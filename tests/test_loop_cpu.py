@@ -73,6 +73,25 @@ def test_non_finite_motion_counts_as_zero():
     assert float(err) <= 4 * 2.0 ** -53 * float(img.abs().max())
 
 
+@pytest.mark.parametrize("H, W", R.EDGE_SHAPES)
+def test_edge_case_is_exact(H, W):
+    """loop_ref.edge_case: the fp32 run of the restatement is its float64 run rounded to fp32, in the displacements both ways and in
+    the frames, and every pixel the case is about is where its docstring says: on the last column and row, half a pixel before them,
+    outside on every side and at +-1e30, with NaN and +-Inf counting as 0"""
+    img, m = R.edge_case(H, W)
+    for dt in (1.0, -1.0):
+        d32, d64 = (R.integrate_ref(m, 2, 1, 1, dt, dtype) for dtype in (torch.float32, torch.float64))
+        assert torch.isfinite(d32).all() and torch.equal(d32, d64.float())
+    v32, v64 = (R.loop_ref(img, m, 2, 1, 1, 1.0, dtype) for dtype in (torch.float32, torch.float64))
+    assert torch.isfinite(v32).all() and torch.equal(v32, v64.float())
+    D1 = R.integrate_ref(m, 1, 1, 1, 1.0)[:, 1]
+    xs, ys = torch.arange(W, dtype=torch.float64), torch.arange(H, dtype=torch.float64)[:, None]
+    qx, qy = xs + D1[:, 0], ys + D1[:, 1]
+    assert (qx[0, 0, :W - 1] == W - 1).all() and (qy[0, 1:H - 1, 0] == H - 1).any() and (qx[1, H - 1, :W - 1] == W - 1.5).all()
+    assert (qx > W - 1).any() and (qx < 0).any() and (qy > H - 1).any() and (qy < 0).any() and (D1.abs() >= 1e30).sum() == 2
+    assert not torch.isfinite(m).all() and (D1[~torch.isfinite(m)] == 0).all()
+
+
 def test_chunks_of_the_restatement_agree():
     img, motion = R.make_case("13x18-c3-n8-smooth")
     whole = R.case_ref("13x18-c3-n8-smooth")[2]

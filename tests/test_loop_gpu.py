@@ -187,6 +187,22 @@ def test_non_finite_motion_never_reaches_the_output():
         assert torch.equal(loop_frames(img, dirty, 6, order=order), loop_frames(img, clean, 6, order=order))
 
 
+@pytest.mark.parametrize("H, W", R.EDGE_SHAPES)
+def test_edge_case_bit_for_bit(H, W):
+    """loop_ref.edge_case (q exactly on the last column and row, half a pixel before them, outside on every side, at +-1e30; NaN and
+    +-Inf entries): with Euler steps of width 1 every operation is exact or rounded once from an exact value (test_loop_cpu holds the
+    restatement to that), so integrate_flow both ways and loop_frames give the float64 restatement rounded to fp32, bit for bit.  5 x 7
+    is the smallest frame with an interior, 17 x 65 is one pixel past a 64 x 16 tile both ways: four tiles a sample, three of them one column
+    wide or one row high."""
+    from opticalflowdiffusion_amd import integrate_flow, loop_frames
+    img, motion = (t.cuda() for t in R.edge_case(H, W))
+    for dt in (1.0, -1.0):
+        want = R.integrate_ref(motion.cpu(), 2, 1, 1, dt).float()
+        assert torch.equal(integrate_flow(motion, 2, substeps=1, order=1, dt=dt).cpu(), want), dt
+    want = R.loop_ref(img.cpu(), motion.cpu(), 2, 1, 1, 1.0).float()
+    assert torch.equal(loop_frames(img, motion, 2, substeps=1, order=1).cpu(), want)
+
+
 # ----------------------------------------------------------------------------------------------------------------------- the method
 @pytest.fixture(scope="module")
 def fd():
