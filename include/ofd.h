@@ -31,6 +31,7 @@
  *   (not in the reference)            looping clips from a steady motion field -> ofd_flow_integrate, ofd_loop_render
  *   (not in the reference)            forward-backward check of a flow pair -> ofd_flow_consistency
  *   (not in the reference)            tracks through a clip's flows, layer propagation -> ofd_flow_chain, ofd_flow_chain_to, ofd_layer_composite
+ *   (not in the reference)            motion-compensated temporal filter of a clip, along its tracks -> ofd_temporal_filter
  *   (not in the reference)            guided weighted median of a flow  -> ofd_flow_median
  *   (not in the reference)            global motion of a flow: robust fit, split, render -> ofd_motion_fit, ofd_motion_field, ofd_homography_warp
  *   (not in the reference)            motion layers: K motions of a flow, labels, label vote -> ofd_motion_layers, ofd_motion_assign, ofd_label_vote
@@ -358,6 +359,51 @@ int ofd_flow_chain_to(const float* fwd, const float* bwd, float* disp, uint8_t* 
                       int use_check, float a1, float a2, void* stream);
 int ofd_layer_composite(const float* frames, const float* layer, const float* disp, float* out, int B, int n, int C, int H, int W,
                         void* stream);
+
+/* Motion-compensated temporal filtering: every pixel of a frame averaged with itself in the neighbouring frames, found by walking the
+ * clip's flows from it (Liu & Freeman, "A high-quality video denoising algorithm based on reliable motion estimation", ECCV 2010; with
+ * a guide that is not the filtered clip, the joint form of Lang et al., "Practical temporal consistency for image-based graphics
+ * applications", SIGGRAPH 2012).  An addition: nothing in the reference looks at more than two frames.  One launch; the walks and the
+ * sums stay in registers, no displacement and no gathered frame is stored.  All arithmetic fp32, every operation rounded on its own (no
+ * contraction), in the order written; a chain without brackets runs left to right.
+ * clip (B,T+1,C,H,W), 1 <= C <= 8: the values.  guide (B,T+1,Cg,H,W), 1 <= Cg <= 4, or NULL with Cg = 0: the clip guides itself, over its C
+ * planes, and is read once.  fwd, bwd (B,T,2,H,W) in pixels with ofd_flow_chain's conventions, both non-null.  wt: HOST array of
+ * radius + 1 floats, copied into the launch: wt[0] the centre's weight, wt[k] the weight of a tap k frames away; every one finite and
+ * >= 0, not all zero (there is no exp on the device: warp.temporal_params makes them).  1 <= radius <= 8.  out (B,nt,C,H,W);
+ * support (B,nt,1,H,W) fp32, the sum of the weights used; taps (B,nt,1,H,W) uint8, the neighbour taps that were used, 0..2*radius.  Slot
+ * t - t0 holds frame t of [t0, t0 + nt).  For frame t and pixel p = (x, y):
+ *   T1. Centre.  v0_c = clip[t]_c(p), g0_c = guide[t]_c(p) (the guide's planes; v0 itself without a guide).  If any of them is not
+ *       finite: out = the centre's bits, support = +0.0, taps = 0, and both walks of the pixel are dead from the start (a dead walk
+ *       reads offset 0 of a plane and drops what it reads).
+ *   T2. Walks.  Two walks start at p with D = 0 and state 0: ahead over fwd[t], fwd[t+1], ..., step k arriving at frame t + k, for
+ *       k = 1 .. min(radius, T - t); back over bwd[t-1], bwd[t-2], ..., step k arriving at frame t - k, for k = 1 .. min(radius, t).  A
+ *       step is exactly ofd_flow_chain's: the same read of S at q, D' = D + v, the same states in the same order, and with use_check = 1
+ *       the same read of K at q' and the same bound a1 * m + a2.  A dead walk stays dead and adds nothing further; no thread leaves the
+ *       loop for it.
+ *   T3. Tap.  After step k of a walk that is alive, q = ((float)x + D.x, (float)y + D.y) is inside the frame (the step would have left
+ *       otherwise; the kernel tests it again before it forms an index).  One cell is formed at q, and the C value planes and the guide's
+ *       planes of the frame arrived at are read with it by ofd_flow_chain's bilinear formula: val_c, gq_c (without a guide gq = val).
+ *       If any of these is not finite -- a non-finite corner makes it so even under weight 0 -- the tap is dropped; the walk goes on.
+ *   T4. Weight.  d2 = the sum over the guide's planes, in plane order from +0.0, of (gq_c - g0_c) * (gq_c - g0_c); with use_range = 0,
+ *       d2 = +0.0 instead.  r = range_scale / (range_scale + d2), one correctly rounded division; the tap's weight is
+ *       w = wt[k] * (r * r): ofd_motion_fit's Geman-McClure weight, and wt[k] exactly with use_range = 0.  range_scale is Cg * sigma_r^2
+ *       (C * sigma_r^2 without a guide), finite and > 0.  (A finite gq so large that d2 overflows gives r = 0: the tap counts, with w = 0.)
+ *   T5. Sums.  num_c = wt[0] * v0_c and den = wt[0]; then for every tap that was not dropped, the walk ahead k = 1, 2, ... first and
+ *       the walk back k = 1, 2, ... after it: num_c = num_c + w * val_c, den = den + w, taps + 1.  out_c = num_c / den, support = den.
+ *       Where den == 0 (wt[0] = 0 and no tap with w > 0), out = the centre's bits.
+ *   T6. Aliasing and limits.  out, support and taps must not share a byte with clip, guide, fwd or bwd: a thread gathers other pixels'
+ *       inputs.  H, W <= 32768; 1 <= T <= 4096; 0 <= t0, 1 <= nt, t0 + nt <= T + 1; a1, a2 finite and >= 0; use_range and use_check 0
+ *       or 1; nt * B * ceil(H / 16) * ceil(W / 64) < 2^30; B * (T+1) * max(C, 2) * H * W < 2^40.  Every float becomes a gather index only
+ *       after the inside test, which a non-finite or huge value fails: whatever the arrays hold, every read is inside its plane.
+ * No atomics, no LDS, no host sync; a thread writes only its own pixels; the same input gives the same bits.  A workgroup owns a 64 x 16
+ * tile of one frame and sample, so a frame's bits depend neither on how [t0, t0 + nt) is split over calls nor on what shares the
+ * batch.  Argument errors return OFD_ERR_ARG and set ofd_last_error before any GPU work.  Per step and pixel a walk makes the chain's
+ * 8 (16 with the check) corner loads and 4 * (C + Cg) more for the tap, each step's behind the one before: it is taken to be bound by
+ * the latency of these gathers, like ofd_flow_chain.  Compulsory traffic: 4 * B * nt * H * W * (2 C + Cg + 1) + B * nt * H * W bytes plus the
+ * flows of the frames it walks. */
+int ofd_temporal_filter(const float* clip, const float* guide, const float* fwd, const float* bwd, const float* wt, float* out,
+                        float* support, uint8_t* taps, int B, int T, int C, int Cg, int H, int W, int radius, int use_range,
+                        float range_scale, int use_check, float a1, float a2, int t0, int nt, void* stream);
 
 /* Global motion of a flow: a robust parametric fit of the motion most pixels share (the camera's), the split of a flow into that motion
  * and the rest, and the render of a frame through a homography (Odobez & Bouthemy 1995; Black & Anandan 1996).  An addition: the

@@ -20,7 +20,8 @@ COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-fp-a
 # per-file extra flags: the warp kernels need the reference's exact fp32 operation order
 EXTRA = {f: ["-ffp-contract=off"] for f in ("splat.hip", "grid_warp.hip", "splat_pyramid.hip", "diffusion.hip", "x0_quantile.hip",
                                                 "loss_rows.hip", "photo_guide.hip", "interp.hip", "upsample.hip", "loop.hip",
-                                                "consistency.hip", "median.hip", "chain.hip", "motion.hip", "layers.hip", "plate.hip")}
+                                                "consistency.hip", "median.hip", "chain.hip", "motion.hip", "layers.hip", "plate.hip",
+                                                "temporal.hip")}
 
 
 def sources():

@@ -10,21 +10,21 @@
 //           length and direction, which are uniform in a workgroup.  Both are chain_walk_kernel: the lookup form has the bits of the
 //           tracks form because it is the same code.  The four tracks of a thread are independent.
 //   walk    D, the state and the number of steps lived stay in registers for the whole walk; a slot is stored per step (all_steps) or
-//           once at the end.  A step is 8 corner loads (the stepping field at q) and, with the check on, 8 more (the checking field
-//           at q'), the second behind the first.  What bounds the kernel is taken to be the latency of these gathers, as in
-//           ofd_flow_integrate, whose time it matches; no counter run has shown it.
+//           once at the end.  The step itself is chain_step.h's, which temporal.hip takes too.  A step is 8 corner loads (the stepping
+//           field at q) and, with the check on, 8 more (the checking field at q'), the second behind the first.  What bounds the
+//           kernel is taken to be the latency of these gathers, as in ofd_flow_integrate, whose time it matches; no counter run has
+//           shown it.
 //   dead    a dead track goes on through the loop with D = NaN: its reads go to offset 0 of the plane and are dropped, its stores are
 //           NaN and its state.  No thread leaves the loop early, so no store is skipped.
 //
 // No atomics, no LDS, no host synchronisation; a thread writes only its own pixels: the same input gives the same bits.  Built with
 // -ffp-contract=off like the other warp units, so that the operation order the header states is the one that runs.  A float becomes a
 // gather index only after it passed cell_inside (gather.h): whatever the fields hold, every read is inside its plane.
-#include "gather.h"
+#include "chain_step.h"
 
 namespace ofd {
 
-constexpr int CH_MAX_C = 8, CH_MAX_T = 4096;
-enum { CH_TRACKED = 0, CH_INCONSISTENT = 2, CH_LEAVES = 3, CH_UNMATCHED = 4, CH_INVALID = 5 };
+constexpr int CH_MAX_C = 8;
 
 struct ChWalk {
     const float* fwd;               // (B, T, 2, H, W): fwd[:, j] carries frame j to frame j + 1
@@ -42,7 +42,6 @@ struct ChWalk {
 __global__ void __launch_bounds__(TILE_THREADS) chain_walk_kernel(ChWalk a) {
     const TileGeom g = a.g;
     const size_t plane = (size_t)g.H * g.W;
-    const float nan = __uint_as_float(0x7fc00000u);
     for (int t = blockIdx.x; t < g.tiles; t += gridDim.x) {
         int walk, y, x;
         size_t b;
@@ -70,43 +69,17 @@ __global__ void __launch_bounds__(TILE_THREADS) chain_walk_kernel(ChWalk a) {
                 const size_t j = (size_t)(ahead ? start + i - 1 : start - i);                 // the flow between the two frames
                 const float* sx = step + j * 2 * plane;
                 const float* sy = sx + plane;
+                const float* kx = a.use_check ? back + j * 2 * plane : nullptr;     // uniform; the only place the checking field is touched
+                const float* ky = a.use_check ? kx + plane : nullptr;
                 float vx[TILE_ROWS], vy[TILE_ROWS], nx[TILE_ROWS], ny[TILE_ROWS];
                 int ns[TILE_ROWS];
 #pragma unroll
-                for (int k = 0; k < TILE_ROWS; ++k) {
-                    const float qx = px + Dx[k], qy = py[k] + Dy[k];
-                    const BilinearCell c = bilinear_cell(qx, qy, st[k] == CH_TRACKED && cell_inside(qx, qy, g.wmax, g.hmax), g.H, g.W);
-                    vx[k] = bilerp(sx, c);
-                    vy[k] = bilerp(sy, c);
-                }
+                for (int k = 0; k < TILE_ROWS; ++k) chain_step_read(sx, sy, px, py[k], Dx[k], Dy[k], st[k], g, vx[k], vy[k]);
 #pragma unroll
-                for (int k = 0; k < TILE_ROWS; ++k) {
-                    nx[k] = Dx[k] + vx[k];
-                    ny[k] = Dy[k] + vy[k];
-                    const float qx = px + nx[k], qy = py[k] + ny[k];
-                    const bool vfin = is_finite(vx[k]) && is_finite(vy[k]), in = cell_inside(qx, qy, g.wmax, g.hmax);
-                    ns[k] = !vfin ? CH_INVALID : !in ? CH_LEAVES : CH_TRACKED;
-                    if (a.use_check) {                                      // uniform; the only place the checking field is touched
-                        const float* kx = back + j * 2 * plane;
-                        const float* ky = kx + plane;
-                        const BilinearCell c = bilinear_cell(qx, qy, st[k] == CH_TRACKED && vfin && in, g.H, g.W);
-                        const float gx = bilerp(kx, c), gy = bilerp(ky, c);
-                        const float rx = vx[k] + gx, ry = vy[k] + gy;
-                        const float e2 = rx * rx + ry * ry;
-                        const float m = (vx[k] * vx[k] + vy[k] * vy[k]) + (gx * gx + gy * gy);
-                        const float bound = a.a1 * m + a.a2;
-                        const int checked = !(is_finite(gx) && is_finite(gy)) ? CH_UNMATCHED : e2 <= bound ? CH_TRACKED : CH_INCONSISTENT;
-                        ns[k] = ns[k] == CH_TRACKED ? checked : ns[k];
-                    }
-                }
+                for (int k = 0; k < TILE_ROWS; ++k)
+                    ns[k] = chain_step_judge(kx, ky, a.use_check, a.a1, a.a2, px, py[k], Dx[k], Dy[k], st[k], vx[k], vy[k], g, nx[k], ny[k]);
 #pragma unroll
-                for (int k = 0; k < TILE_ROWS; ++k) {
-                    st[k] = st[k] == CH_TRACKED ? ns[k] : st[k];            // a dead track keeps its state
-                    const bool alive = st[k] == CH_TRACKED;
-                    Dx[k] = alive ? nx[k] : nan;
-                    Dy[k] = alive ? ny[k] : nan;
-                    lived[k] += alive ? 1 : 0;
-                }
+                for (int k = 0; k < TILE_ROWS; ++k) lived[k] += chain_step_commit(st[k], ns[k], Dx[k], Dy[k], nx[k], ny[k]) ? 1 : 0;
             }
             if (a.all_steps || i == n) {                                    // uniform
                 const size_t slot = a.all_steps ? (size_t)i : (size_t)walk;
@@ -187,8 +160,6 @@ static void layer_composite_launch(int C, int grid, hipStream_t s, const ChCompo
         default: layer_composite_kernel<8><<<grid, TILE_THREADS, 0, s>>>(a); break;
     }
 }
-
-static bool ch_real(float v) { return v >= 0.0f && v <= 3.402823466e+38f; }          // finite and >= 0; false for NaN
 
 }  // namespace ofd
 using namespace ofd;

@@ -25,6 +25,7 @@ from .warp import (STATE_HELD, box_reduce, chain_flows, chain_flows_to, composit
                    interpolate_frames, layers_params, loop_frames, loop_params, median_filter_flow, median_params, motion_params, path_params,
                    segment_motion, stabilize_clip, upsample_flow, upsample_params, warp)
 from .warp import background_plate, plate_params, plate_voters, remove_moving
+from .warp import temporal_filter, temporal_params
 from . import _args as A
 from . import _lib as L
 
@@ -831,6 +832,39 @@ class FlowDiffuser(EmaMixin, _Base):
         conf = (held == STATE_HELD).float().reshape(B, T, 1, H, W)
         video, inside, _matrices, _path = stabilize_clip(clip, fwd, conf, model=model, iterations=par["iterations"], sigma=par["sigma"], **path)
         return video, inside, fwd, bwd
+
+    def temporal_filter(self, clip, values=None, fwd=None, bwd=None, refine=0, radius=2, sigma_t=1.5, sigma_r=0.1, mode="robust", check=True,
+                        a1=0.01, a2=0.5, center=True, frames=None, **sample_kw):
+        """A clip, or a per-frame result on it, averaged along its motion (not in the reference): (video, support, taps, fwd, bwd), the
+        first three those of `warp.temporal_filter(values or clip, fwd, bwd, guide, radius, sigma_t, sigma_r, mode, check, a1, a2, center,
+        frames)`, which has the method.  clip: (B, T + 1, 3, H, W) in cond's range.  values: None -- the clip is filtered and guides
+        itself (denoising) -- or (B, T + 1, C, H, W), C <= 8: that is filtered while the clip guides it (the joint form: a grade, a
+        matte, a stylisation made stable in time).  fwd, bwd: (B, T, 2, H, W) IN PIXELS as `estimate_flow_clip` returns them, both or
+        neither.  Neither: they come from `estimate_flow_clip(clip, refine=refine, **sample_kw)`.  Both: no UNet call is made, and
+        sample_kw is an error.  radius, sigma_t and sigma_r were chosen on synthetic scenes; untuned on real footage.  Forward only."""
+        T = self._clip_flows("temporal_filter", clip, fwd, bwd, sample_kw)
+        A.integer("temporal_filter", "refine", refine, 0, 16)
+        B, N, _, H, W = clip.shape
+        if values is not None:
+            if not torch.is_tensor(values) or values.dim() != 5 or tuple(values.shape[:2]) != (B, N) or tuple(values.shape[3:]) != (H, W) \
+                    or not 1 <= values.shape[2] <= 8:
+                raise ValueError(f"temporal_filter: values must be None or (B, T + 1, C, H, W) = {(B, N, 'C', H, W)} with 1 <= C <= 8, got "
+                                 f"{A.shape_of(values)}")
+            if values.requires_grad:
+                raise L.OfdError("temporal_filter: forward only (the filter has no backward pass): detach the values")
+        temporal_params(radius, sigma_t, sigma_r, mode, center, name="temporal_filter")
+        if not isinstance(check, bool):
+            raise ValueError(f"temporal_filter: check must be True or False, got {check!r}")
+        par = consistency_params(a1, a2, name="temporal_filter")
+        if frames is not None:
+            if not isinstance(frames, (tuple, list)) or len(frames) != 2:
+                raise ValueError(f"temporal_filter: frames must be None or (first, stop), got {frames!r}")
+            A.integer("temporal_filter", "frames[1]", frames[1], A.integer("temporal_filter", "frames[0]", frames[0], 0, T) + 1, N)
+        if fwd is None:
+            fwd, bwd = self.estimate_flow_clip(clip, refine=refine, **sample_kw)
+        res = temporal_filter(clip if values is None else values, fwd, bwd, guide=None if values is None else clip, radius=radius,
+                              sigma_t=sigma_t, sigma_r=sigma_r, mode=mode, check=check, a1=par["a1"], a2=par["a2"], center=center, frames=frames)
+        return res.video, res.support, res.taps, fwd, bwd
 
     def _plate_flows(self, name, clip, fwd, bwd, refine, plate_kw, a1, a2, sample_kw):
         """what `background_plate` and `remove_moving` share: every host rule before any model or engine call, the flows (estimated

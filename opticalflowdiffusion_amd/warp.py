@@ -616,6 +616,111 @@ def composite_layer(frames, layer, disp, premultiplied=True):
     return out
 
 
+# ---- motion-compensated temporal filtering along a clip's tracks (not in the reference; semantics: include/ofd.h, `ofd_temporal_filter`) ----
+TemporalFilter = collections.namedtuple("TemporalFilter", "video support taps")
+TEMPORAL_MODES = ("robust", "mean")
+
+
+def temporal_params(radius=2, sigma_t=1.5, sigma_r=0.1, mode="robust", center=True, name="temporal_filter"):
+    """the rules of the temporal filter's window and weights (ValueError) -> dict(radius, wt, use_range, sigma_r); host logic, no
+    engine call.  wt[k] = exp(-k^2 / (2 sigma_t^2)) computed in double and rounded to fp32, k = 0..radius; sigma_t=None: all ones;
+    center=False: wt[0] = 0.  mode "robust" weighs a tap by the guide's difference (sigma_r, per plane), "mean" does not."""
+    radius = A.integer(name, "radius", radius, 1, 8)
+    if mode not in TEMPORAL_MODES:
+        raise ValueError(f"{name}: mode must be one of {TEMPORAL_MODES}, got {mode!r}")
+    if not isinstance(center, bool):
+        raise ValueError(f"{name}: center must be True or False, got {center!r}")
+    if sigma_t is not None and (not A.is_number(sigma_t) or not 0.0 < sigma_t <= 1024.0):      # false for NaN
+        raise ValueError(f"{name}: sigma_t must be None or a number in (0, 1024] (frames), got {sigma_t!r}")
+    if not A.is_number(sigma_r) or not 0.0 < sigma_r < float("inf"):
+        raise ValueError(f"{name}: sigma_r must be a finite number > 0, got {sigma_r!r}")
+    wt = [1.0 if sigma_t is None else math.exp(-k * k / (2.0 * float(sigma_t) ** 2)) for k in range(radius + 1)]
+    wt = [float(torch.tensor(w, dtype=torch.float64).float()) for w in wt]                     # what the kernel is handed
+    if not center:
+        wt[0] = 0.0
+    if not any(w > 0.0 for w in wt):
+        raise ValueError(f"{name}: every weight is zero in fp32 (sigma_t={sigma_t!r}, center={center!r})")
+    return dict(radius=radius, wt=wt, use_range=mode == "robust", sigma_r=float(sigma_r))
+
+
+def _temporal_range_scale(name, par, planes):
+    """Cg * sigma_r^2 as the kernel's fp32, > 0 and finite (ValueError otherwise); 1 where the range weight is off"""
+    if not par["use_range"]:
+        return 1.0
+    scale = float(torch.tensor(planes * par["sigma_r"] ** 2, dtype=torch.float64).float())
+    if not 0.0 < scale < float("inf"):
+        raise ValueError(f"{name}: planes * sigma_r^2 = {scale!r} is not a positive fp32 number (sigma_r={par['sigma_r']!r})")
+    return scale
+
+
+def temporal_filter(clip, fwd, bwd, guide=None, radius=2, sigma_t=1.5, sigma_r=0.1, mode="robust", check=True, a1=0.01, a2=0.5, center=True,
+                    frames=None):
+    """Motion-compensated temporal filtering of a clip (Liu & Freeman 2010; with a guide, the joint form of Lang et al. 2012; not in the
+    reference): a `TemporalFilter` (video, support, taps).  clip: (B, T + 1, C, H, W), C <= 8: the values, a video or any per-frame
+    result (a matte, a grade).  fwd, bwd: (B, T, 2, H, W) IN PIXELS as for `chain_flows`.  Every pixel of a frame is followed up to
+    `radius` (1..8) frames ahead and back by `chain_flows`' step -- with check=True a walk stops where a step's round trip fails, so
+    nothing is averaged across an occlusion -- and averaged with what the clip holds where the walks arrive, read bilinearly.  A tap k
+    frames away weighs exp(-k^2 / (2 sigma_t^2)) (sigma_t=None: 1) times, in mode "robust", the Geman-McClure weight
+    (s / (s + d2))^2 of the squared difference d2 between the guide there and the guide at the pixel, s = planes * sigma_r^2; mode
+    "mean" leaves that factor out.  guide: (B, T + 1, Cg, H, W), Cg <= 4, or None: the clip guides itself.  center=False leaves the
+    pixel itself out of its average.  frames: None for all, or (first, stop) for frames first..stop-1.  video (B, n, C, H, W);
+    support (B, n, 1, H, W): the sum of the weights used; taps (B, n, 1, H, W) uint8: the neighbour taps used, 0..2 * radius.  A pixel
+    whose own value or guide is not finite is returned as it is with support 0.  One `ofd_temporal_filter` call per at most
+    flow_diffuser.ANIMATE_MAX_PIXELS pixels of output, over samples first and then over frames; chunked or not, the bits are the
+    same.  radius, sigma_t and sigma_r were chosen on synthetic scenes and a1, a2 are UnFlow's: all untuned on real footage.  Forward
+    only; inputs are not modified; the same input gives the same bits.  Semantics: include/ofd.h."""
+    from .flow_diffuser import ANIMATE_MAX_PIXELS
+    name = "temporal_filter"
+    if not torch.is_tensor(clip) or clip.dim() != 5 or clip.numel() == 0 or not 1 <= clip.shape[2] <= 8 or clip.shape[1] < 2 or \
+            not clip.is_floating_point():
+        raise ValueError(f"{name}: clip must be a non-empty floating-point (B, T + 1, C, H, W) tensor with at least two frames and "
+                         f"1 <= C <= 8, got {A.shape_of(clip)}")
+    B, N, C, H, W = clip.shape
+    T = N - 1
+    if not torch.is_tensor(fwd) or tuple(fwd.shape) != (B, T, 2, H, W):
+        raise ValueError(f"{name}: fwd must be (B, T, 2, H, W) = {(B, T, 2, H, W)}, got {A.shape_of(fwd)}")
+    _chain_flows(name, fwd, bwd)
+    if guide is not None and (not torch.is_tensor(guide) or guide.dim() != 5 or tuple(guide.shape[:2]) != (B, N) or
+                              tuple(guide.shape[3:]) != (H, W) or not 1 <= guide.shape[2] <= 4 or not guide.is_floating_point()):
+        raise ValueError(f"{name}: guide must be None or a floating-point (B, T + 1, Cg, H, W) = {(B, N, 'Cg', H, W)} tensor with "
+                         f"1 <= Cg <= 4, got {A.shape_of(guide)}")
+    Cg = 0 if guide is None else guide.shape[2]
+    par = temporal_params(radius, sigma_t, sigma_r, mode, center, name=name)
+    scale = _temporal_range_scale(name, par, Cg or C)
+    if not isinstance(check, bool):
+        raise ValueError(f"{name}: check must be True or False, got {check!r}")
+    bound = consistency_params(a1, a2, name=name)
+    if frames is None:
+        first, stop = 0, N
+    else:
+        if not isinstance(frames, (tuple, list)) or len(frames) != 2:
+            raise ValueError(f"{name}: frames must be None or (first, stop), got {frames!r}")
+        first = A.integer(name, "frames[0]", frames[0], 0, T)
+        stop = A.integer(name, "frames[1]", frames[1], first + 1, N)
+    A.forward_only(name, clip, fwd, bwd, guide, why="the filter has no backward pass")
+    n = stop - first
+    with torch.no_grad():
+        clip, fwd, bwd, guide = L.f32c(clip), L.f32c(fwd), L.f32c(bwd), None if guide is None else L.f32c(guide)
+        wt = (ctypes.c_float * len(par["wt"]))(*par["wt"])
+        per = max(1, ANIMATE_MAX_PIXELS // (H * W))                          # frames per call
+        nt, nb = min(n, per), max(1, per // n)
+        video = torch.empty(B, n, C, H, W, dtype=torch.float32, device=clip.device)
+        support = torch.empty(B, n, 1, H, W, dtype=torch.float32, device=clip.device)
+        taps = torch.empty(B, n, 1, H, W, dtype=torch.uint8, device=clip.device)
+        lib = L.lib()
+        for b0 in range(0, B, nb):
+            cb = min(nb, B - b0)
+            for f0 in range(0, n, nt):
+                ct = min(nt, n - f0)                                         # ct == n: whole samples, contiguous in the result
+                sl = slice(b0, b0 + cb) if ct == n else slice(b0, b0 + 1)
+                v, s, k = (o[sl] if ct == n else o[sl, f0:f0 + ct] for o in (video, support, taps))
+                L.check(lib.ofd_temporal_filter(L.ptr(clip[sl]), L.ptr(None if guide is None else guide[sl]), L.ptr(fwd[sl]), L.ptr(bwd[sl]),
+                                                wt, L.ptr(v), L.ptr(s), L.ptr(k), cb if ct == n else 1, T, C, Cg, H, W, par["radius"],
+                                                int(par["use_range"]), scale, int(check), bound["a1"], bound["a2"], first + f0, ct,
+                                                L.stream()))
+    return TemporalFilter(video, support, taps)
+
+
 # ---- global motion of a flow: robust fit, split, render, camera path (not in the reference; semantics: include/ofd.h, `ofd_motion_fit`) ----
 MOTION_MODELS = ("translation", "similarity", "affine", "homography")
 _MOTION_WHY = "the fit, the field and the warp have no backward pass"
