@@ -860,7 +860,10 @@ int ofd_nan_mse_rows_grad(const float* pred, const float* target, const float* w
  * uint64 numel}; tasks: device arrays (tensor index, chunk index) with ofd_adam_chunk() elements
  * per chunk.  sqnorm_acc (n_tasks + 1 doubles: [0] the squared norm, then one partial sum per task, added in a
  * fixed order -- the same gradients give the same clip coefficient bit for bit), clip_coef (1 float) and optional
- * total_norm are device scratch/outputs.  step counts from 1.  max_norm <= 0 disables clipping. */
+ * total_norm are device scratch/outputs.  step counts from 1.  max_norm <= 0 disables clipping.  The clip coefficient is
+ * min(1, max_norm / (norm + 1e-6)) with a NaN kept (a NaN norm makes every element NaN, as clip_grad_norm_ does) and 0 for an
+ * infinite norm.  The bias corrections 1 - beta^step are formed in double from the float betas and rounded once.  Rows may be
+ * 4-byte aligned only. */
 int ofd_adam_chunk(void);
 int ofd_adam_step(const void* table, const unsigned* task_tensor, const unsigned* task_chunk, int n_tasks,
                   double* sqnorm_acc, float* clip_coef, float* total_norm, float max_norm, float lr,

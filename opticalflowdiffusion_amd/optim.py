@@ -54,22 +54,28 @@ class FusedAdam(torch.optim.Optimizer):
         self._ema_flat = {}             # index into _ema_unets -> the flat buffer its averages are views of
 
     def _table(self, gi, group, params, ema=False):
-        key = (gi, tuple((p.data_ptr(), p.grad.data_ptr()) for p in params))
-        if ema:                          # _ema_sync may have moved the averages (load_state_dict, .to(device))
-            key += (tuple(self.state[p]["ema"].data_ptr() for p in params),)
+        # The key is the table itself: every address and length the kernels dereference.  Gradients are re-allocated by
+        # zero_grad(set_to_none=True), the moments replaced by load_state_dict, the averages moved by _ema_sync: a table built for
+        # tensors that have since been replaced would step on freed memory.
+        state = self.state
+        names = ("exp_avg", "exp_avg_sq", "ema") if ema else ("exp_avg", "exp_avg_sq")
+        key = []
+        for p in params:
+            st = state[p]
+            key.append((p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel())
+                       + ((st["ema"].data_ptr(),) if ema else ()))
         tab = self._tables.get((gi, ema))
         if tab is not None and tab["key"] == key:
             return tab
         dev = params[0].device
         chunk = L.lib().ofd_adam_chunk()
         rows, tt, tc = [], [], []
-        for i, p in enumerate(params):
-            st = self.state[p]
-            row = (p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel())
-            if ema:
-                if st["ema"].shape != p.shape or st["ema"].dtype != torch.float32 or not st["ema"].is_contiguous() or st["ema"].device != dev:
-                    raise L.OfdError("FusedAdam: an EMA tensor does not match its parameter")
-                row += (st["ema"].data_ptr(),)
+        for i, (p, row) in enumerate(zip(params, key)):
+            for name in names:
+                t = state[p][name]
+                if t.shape != p.shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+                    raise L.OfdError("FusedAdam: an EMA tensor does not match its parameter" if name == "ema" else
+                                     f"FusedAdam: state[{name!r}] does not match its parameter")
             rows.append(struct.pack(f"<{len(row)}Q", *row))
             for c in range((p.numel() + chunk - 1) // chunk):
                 tt.append(i)
