@@ -32,6 +32,7 @@
  *   (not in the reference)            forward-backward check of a flow pair -> ofd_flow_consistency
  *   (not in the reference)            tracks through a clip's flows, layer propagation -> ofd_flow_chain, ofd_flow_chain_to, ofd_layer_composite
  *   (not in the reference)            motion-compensated temporal filter of a clip, along its tracks -> ofd_temporal_filter
+ *   (not in the reference)            flow-guided completion of a masked region of a clip, along its tracks -> ofd_clip_fill
  *   (not in the reference)            guided weighted median of a flow  -> ofd_flow_median
  *   (not in the reference)            global motion of a flow: robust fit, split, render -> ofd_motion_fit, ofd_motion_field, ofd_homography_warp
  *   (not in the reference)            motion layers: K motions of a flow, labels, label vote -> ofd_motion_layers, ofd_motion_assign, ofd_label_vote
@@ -404,6 +405,48 @@ int ofd_layer_composite(const float* frames, const float* layer, const float* di
 int ofd_temporal_filter(const float* clip, const float* guide, const float* fwd, const float* bwd, const float* wt, float* out,
                         float* support, uint8_t* taps, int B, int T, int C, int Cg, int H, int W, int radius, int use_range,
                         float range_scale, int use_check, float a1, float a2, int t0, int nt, void* stream);
+
+/* Flow-guided completion of a masked region of a clip: every hole pixel of a frame is followed through the clip's flows, ahead and back,
+ * until it lands where another frame really saw the scene, and takes the colour there (Huang et al., "Temporally coherent completion
+ * of dynamic video", SIGGRAPH Asia 2016; Xu et al., "Deep flow-guided video inpainting", CVPR 2019).  An addition: nothing in the
+ * reference looks at more than two frames.  One launch; the walks stay in registers, no displacement and no gathered frame is stored.
+ * All arithmetic fp32, every operation rounded on its own (no contraction), in the order written.
+ * clip (B,T+1,C,H,W), 1 <= C <= 8.  mask (B,T+1,1,H,W) uint8: nonzero = hole, the pixels to be filled and never to be copied from.
+ * fwd, bwd (B,T,2,H,W) in pixels with ofd_flow_chain's conventions, both non-null and already completed inside the holes (the flow
+ * under a hole is the flow of what the hole hides: warp.complete_flows).  out (B,nt,C,H,W); steps (B,nt,2,H,W) uint8.  Slot t - t0
+ * holds frame t of [t0, t0 + nt).  For frame t and pixel p = (x, y):
+ *   F1. Non-hole pixel (mask[t](p) == 0).  out = the clip's bits, whatever they are; steps = (0, 0).
+ *   F2. Walks.  For a hole pixel two walks start at p with D = 0 and state 0, exactly as in T2 of ofd_temporal_filter: ahead over
+ *       fwd[t], fwd[t+1], ..., step k arriving at frame t + k, for k = 1 .. min(reach, T - t); back over bwd[t-1], bwd[t-2], ..., step k
+ *       arriving at frame t - k, for k = 1 .. min(reach, t).  A step is exactly ofd_flow_chain's: the same read of S at q, D' = D + v,
+ *       the same states in the same order, and with use_check = 1 the same read of K at q' and the same bound a1 * m + a2.  A dead walk
+ *       stays dead.
+ *   F3. Source.  After step k of a walk that is alive, q = ((float)x + D.x, (float)y + D.y) is inside the frame (the kernel tests it
+ *       again before it forms an index).  One cell is formed at q: x0 = floor(q.x), x1 = min(x0 + 1, W-1), likewise in y.  The arrival is
+ *       SEEN iff the four bytes of mask[t +- k] at (y0,x0), (y0,x1), (y1,x0), (y1,x1) are all 0 -- all four whatever their weights, so
+ *       that a hole's colour can never enter a read; seen depends on the mask alone, not on what the clip holds.  The first seen arrival
+ *       of a walk fixes its source: its k and its D.  From there on the walk is finished and adds nothing.
+ *   F4. Colour.  For a walk with a source, val_c = the bilinear read of plane c of the frame arrived at, at that q, by ofd_flow_chain's
+ *       formula.  A non-finite corner makes val_c non-finite even under weight 0: the caller can mask such pixels.  The colours are read
+ *       once, after both walks, from the two stored D.
+ *   F5. Result.  With k_f, k_b the steps of the sources ahead and back and vf, vb their colours: both found and blend = 1:
+ *       a = (float)k_b, b = (float)k_f, out_c = (a * vf_c + b * vb_c) / (a + b) -- two products, their sum, the sum a + b, one division: the
+ *       nearer source weighs more; both found and blend = 0: the walk with the smaller k wins, a tie goes to the walk ahead.  One found:
+ *       its colour's bits.  Neither: the clip's own bits.  steps = (k_f, k_b), 0 = no source: the pixels still unfilled are those with
+ *       mask != 0 and steps == (0, 0).
+ *   F6. Aliasing and limits.  out and steps must not share a byte with clip, mask, fwd or bwd: a thread gathers other pixels' inputs.
+ *       1 <= reach <= 255; H, W <= 32768; 1 <= T <= 4096; 0 <= t0, 1 <= nt, t0 + nt <= T + 1; a1, a2 finite and >= 0; use_check and blend
+ *       0 or 1; nt * B * ceil(H / 16) * ceil(W / 64) < 2^30; B * (T+1) * max(C, 2) * H * W < 2^40.  Every float becomes a gather index only
+ *       after the inside test, which a non-finite or huge value fails: whatever the arrays hold, every read is inside its plane.
+ * No atomics, no LDS, no host sync; a thread writes only its own pixels; the same input gives the same bits.  A workgroup owns a 64 x 16
+ * tile of one frame and sample, so a frame's bits depend neither on how [t0, t0 + nt) is split over calls nor on what shares the
+ * batch.  The cost follows the hole, not the clip: a wave (64 columns of four rows) whose pixels hold no hole copies them and reads no
+ * flow, and a wave leaves the step loop once every walk of its lanes is finished or dead; neither changes a bit.  Argument errors
+ * return OFD_ERR_ARG and set ofd_last_error before any GPU work.  Per step and hole pixel a walk makes the chain's 8 (16 with the
+ * check) corner loads and 4 byte loads of the mask, each step's behind the one before: it is taken to be bound by the latency of these
+ * gathers, like ofd_flow_chain.  Compulsory traffic: B * nt * H * W * (8 C + 3) bytes plus the flows under the holes. */
+int ofd_clip_fill(const float* clip, const uint8_t* mask, const float* fwd, const float* bwd, float* out, uint8_t* steps, int B, int T,
+                  int C, int H, int W, int reach, int use_check, float a1, float a2, int blend, int t0, int nt, void* stream);
 
 /* Global motion of a flow: a robust parametric fit of the motion most pixels share (the camera's), the split of a flow into that motion
  * and the rest, and the render of a frame through a homography (Odobez & Bouthemy 1995; Black & Anandan 1996).  An addition: the

@@ -26,6 +26,7 @@ from .warp import (STATE_HELD, box_reduce, chain_flows, chain_flows_to, composit
                    segment_motion, stabilize_clip, upsample_flow, upsample_params, warp)
 from .warp import background_plate, plate_params, plate_voters, remove_moving
 from .warp import temporal_filter, temporal_params
+from .warp import _clip_mask, clipfill_params, complete_flows, fill_holes, inpaint_clip
 from . import _args as A
 from . import _lib as L
 
@@ -865,6 +866,71 @@ class FlowDiffuser(EmaMixin, _Base):
         res = temporal_filter(clip if values is None else values, fwd, bwd, guide=None if values is None else clip, radius=radius,
                               sigma_t=sigma_t, sigma_r=sigma_r, mode=mode, check=check, a1=par["a1"], a2=par["a2"], center=center, frames=frames)
         return res.video, res.support, res.taps, fwd, bwd
+
+    def inpaint_clip(self, clip, mask, fwd=None, bwd=None, refine=0, flow_fill="pushpull", reach=None, check=True, a1=0.01, a2=0.5,
+                     blend=True, flow_dilate=2, key_frame=None, spatial=True, **sample_kw):
+        """A marked object taken out of a clip by flow-guided completion (not in the reference): (video, left, fwd_c, bwd_c), video and
+        left those of `warp.inpaint_clip(clip, mask, fwd_c, bwd_c, reach, check, a1, a2, blend, None, key_frame, spatial)`, which has
+        the method, and fwd_c, bwd_c the flows completed under the mask.  clip: (B, T + 1, 3, H, W) in cond's range; mask:
+        (B, T + 1, 1, H, W) bool, uint8 or floating point (> 0.5), the holes.  fwd, bwd: (B, T, 2, H, W) IN PIXELS as
+        `estimate_flow_clip` returns them, both or neither.  Neither: they come from `estimate_flow_clip(clip, refine=refine,
+        **sample_kw)`, which sees the object and estimates ITS motion under the mask; that part is then replaced.
+        flow_fill="pushpull": `warp.complete_flows(fwd, bwd, mask, flow_dilate)`, a smooth fill; with both flows given no UNet call is
+        made, and sample_kw is an error.  flow_fill="prior": every flow is completed by one constrained chain of the model instead --
+        `sample(cond, ., known_flow=)` with the flow's held vectors as known_flow (NaN in the dilated hole, clamped to +-flow_max like
+        every known_flow) and cond the flow's own first frame with its hole push-pull filled, so that the model is not shown the
+        object; held vectors keep their bits, and what the chain returns under the hole is merged in.  sample_kw (without the median_*
+        and photo_* keys) goes to those chains too.  Everything known_flow rejects is a ValueError before any model call: a
+        non-diffusion model, target 'target', latent=True, sample_scale > 1.  A diffusion model over flow fields is the one tool here
+        that can propose a motion for what it cannot see, with no retraining; HOW WELL the prior completes a flow under a mask HAS NOT
+        BEEN MEASURED with trained weights.  The defaults are untuned on real footage.  Forward only."""
+        name = "inpaint_clip"
+        if flow_fill not in ("pushpull", "prior"):
+            raise ValueError(f"{name}: flow_fill must be 'pushpull' or 'prior', got {flow_fill!r}")
+        T = self._clip_flows(name, clip, fwd, bwd, {} if flow_fill == "prior" else sample_kw)
+        A.integer(name, "refine", refine, 0, 16)
+        B, N, _, H, W = clip.shape
+        _clip_mask(name, mask, B, N, H, W)
+        par = clipfill_params(T, reach, check, a1, a2, blend, flow_dilate, name=name)
+        if flow_dilate is None:
+            raise ValueError(f"{name}: flow_dilate must be an integer in 0..16, got None (the flows are completed here)")
+        if key_frame is not None:
+            A.integer(name, "key_frame", key_frame, 0, T)
+        if not isinstance(spatial, bool):
+            raise ValueError(f"{name}: spatial must be True or False, got {spatial!r}")
+        if mask.requires_grad:
+            raise L.OfdError(f"{name}: forward only (the propagation has no backward pass): detach the mask")
+        prior_kw = {}
+        if flow_fill == "prior":
+            if "known_flow" in sample_kw or "target_frame" in sample_kw:
+                raise ValueError(f"{name}: known_flow and target_frame are its own to set")
+            if not self.is_diffusion:
+                raise ValueError(f"{name}: flow_fill='prior' needs a diffusion model: is_diffusion=False is a plain regression, there is "
+                                 "no chain to constrain")
+            if self.target not in ("flow", "joint"):
+                raise ValueError(f"{name}: flow_fill='prior' is not supported for target={self.target!r}: there the flow is an extra "
+                                 "model output, not part of the diffused tensor")
+            reduced = {k: v for k, v in sample_kw.items() if k in ("sample_scale", "upsample_radius", "upsample_sigma_s", "upsample_sigma_r")}
+            if self.reduced_sampling(clip[:, 0], None, **reduced)[0] > 1:
+                raise ValueError(f"{name}: flow_fill='prior' cannot be combined with sample_scale > 1: known_flow has no reduced form")
+            prior_kw = {k: v for k, v in self.median_filtering(sample_kw, name=name)[0].items() if not k.startswith("photo_")}
+        if fwd is None:
+            fwd, bwd = self.estimate_flow_clip(clip, refine=refine, **sample_kw)
+        with torch.no_grad():
+            fwd_c, bwd_c, hole_f, hole_b = complete_flows(fwd, bwd, mask, dilate=par["dilate"])
+            if flow_fill == "prior":
+                done = []
+                for flow, hole, frames in ((fwd_c, hole_f, clip[:, :-1]), (bwd_c, hole_b, clip[:, 1:])):
+                    flat, hole = flow.reshape(B * T, 2, H, W), hole.reshape(B * T, 1, H, W)
+                    cond = fill_holes(frames.reshape(B * T, 3, H, W), weight=(~hole).float())
+                    known = torch.where(hole, torch.full_like(flat, float("nan")), flat)
+                    _samples, fl = self.sample(cond, cond.new_zeros(B * T, 2, H, W), known_flow=known, **prior_kw)
+                    fresh = fl[:, -1] * float(self.flow_max)
+                    done.append(torch.where(torch.isnan(known), fresh, flat).view(B, T, 2, H, W))    # held vectors keep their bits
+                fwd_c, bwd_c = done
+        res = inpaint_clip(clip, mask, fwd_c, bwd_c, reach=par["reach"], check=par["check"], a1=par["a1"], a2=par["a2"], blend=par["blend"],
+                           flow_dilate=None, key_frame=key_frame, spatial=spatial)
+        return res.video, res.left, fwd_c, bwd_c
 
     def _plate_flows(self, name, clip, fwd, bwd, refine, plate_kw, a1, a2, sample_kw):
         """what `background_plate` and `remove_moving` share: every host rule before any model or engine call, the flows (estimated

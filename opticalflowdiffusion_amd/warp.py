@@ -721,6 +721,170 @@ def temporal_filter(clip, fwd, bwd, guide=None, radius=2, sigma_t=1.5, sigma_r=0
     return TemporalFilter(video, support, taps)
 
 
+# ---- flow-guided completion of a masked region of a clip (not in the reference; semantics: include/ofd.h, `ofd_clip_fill`) ----
+ClipFill = collections.namedtuple("ClipFill", "video steps left")
+
+
+def clipfill_params(T, reach=None, check=True, a1=0.01, a2=0.5, blend=True, dilate=2, name="fill_along_tracks"):
+    """the rules of the completion's walks and of the flow holes' dilation (ValueError) -> dict(reach, check, a1, a2, blend, dilate);
+    host logic, no engine call.  T: the clip's flows per direction; reach None: min(T, 255), as far as a walk can go; dilate None: the
+    flows are already completed"""
+    reach = min(T, 255) if reach is None else A.integer(name, "reach", reach, 1, 255)
+    if not isinstance(check, bool) or not isinstance(blend, bool):
+        raise ValueError(f"{name}: check and blend must be True or False, got {check!r} and {blend!r}")
+    bound = consistency_params(a1, a2, name=name)
+    return dict(reach=reach, check=check, a1=bound["a1"], a2=bound["a2"], blend=blend,
+                dilate=None if dilate is None else A.integer(name, "dilate", dilate, 0, 16))
+
+
+def _clip_mask(name, mask, B, N, H, W):
+    """mask: a bool, uint8 or floating-point (B, N, 1, H, W) tensor (ValueError)"""
+    if not torch.is_tensor(mask) or tuple(mask.shape) != (B, N, 1, H, W) or \
+            not (mask.dtype in (torch.bool, torch.uint8) or mask.is_floating_point()):
+        raise ValueError(f"{name}: mask must be a bool, uint8 or floating-point (B, T + 1, 1, H, W) = {(B, N, 1, H, W)} tensor (True, "
+                         f"nonzero or > 0.5: a hole), got {A.shape_of(mask)} {getattr(mask, 'dtype', '')}")
+
+
+def _hole_bytes(mask):
+    """the mask as the kernel's contiguous uint8: nonzero = hole"""
+    if mask.dtype == torch.uint8:
+        return mask.contiguous()
+    return (mask if mask.dtype == torch.bool else mask > 0.5).to(torch.uint8).contiguous()
+
+
+def _clipfill_inputs(name, clip, mask, fwd, bwd):
+    """the shape and dtype rules of a clip, its mask and its flows (ValueError) -> (B, N, C, H, W)"""
+    if not torch.is_tensor(clip) or clip.dim() != 5 or clip.numel() == 0 or not 1 <= clip.shape[2] <= 8 or clip.shape[1] < 2 or \
+            not clip.is_floating_point():
+        raise ValueError(f"{name}: clip must be a non-empty floating-point (B, T + 1, C, H, W) tensor with at least two frames and "
+                         f"1 <= C <= 8, got {A.shape_of(clip)}")
+    B, N, C, H, W = clip.shape
+    if not torch.is_tensor(fwd) or tuple(fwd.shape) != (B, N - 1, 2, H, W):
+        raise ValueError(f"{name}: fwd must be (B, T, 2, H, W) = {(B, N - 1, 2, H, W)}, got {A.shape_of(fwd)}")
+    _chain_flows(name, fwd, bwd)
+    _clip_mask(name, mask, B, N, H, W)
+    return B, N, C, H, W
+
+
+def fill_along_tracks(clip, mask, fwd, bwd, reach=None, check=True, a1=0.01, a2=0.5, blend=True, frames=None):
+    """Flow-guided propagation into a masked region of a clip (Huang et al. 2016; Xu et al. 2019; not in the reference): a `ClipFill`
+    (video, steps, left).  clip: (B, T + 1, C, H, W), C <= 8.  mask: (B, T + 1, 1, H, W), bool, uint8 (nonzero) or floating point
+    (> 0.5): the holes -- the pixels to fill, which are never copied from.  fwd, bwd: (B, T, 2, H, W) IN PIXELS as for `chain_flows`,
+    already completed under the holes (`complete_flows`): the flow under a hole must be the flow of what the hole hides.  Every hole
+    pixel of a frame is followed up to `reach` (1..255; None: min(T, 255)) frames ahead and back by `chain_flows`' step -- with
+    check=True a walk stops where a step's round trip fails -- until all four pixels under its bilinear cell are outside the holes of
+    the frame it has arrived at; the colour is read there.  With a source on both sides blend=True mixes them, the nearer in time
+    weighing more, and blend=False takes the nearer (a tie: the one ahead).  frames: None for all, or (first, stop).  video
+    (B, n, C, H, W): the clip with the holes filled where a source was found, bit for bit the clip elsewhere; steps (B, n, 2, H, W)
+    uint8: the steps to the source ahead and back, 0 = none; left (B, n, 1, H, W) bool: the hole pixels still unfilled.  One
+    `ofd_clip_fill` call per at most flow_diffuser.ANIMATE_MAX_PIXELS pixels of output, over samples first and then over frames;
+    chunked or not, the bits are the same.  A wrong flow under a hole copies the wrong colour, changes of lighting along a track are
+    not compensated, and a1, a2 are UnFlow's: untuned on real footage.  Forward only; no host sync; inputs are not modified; the same
+    input gives the same bits.  Semantics: include/ofd.h."""
+    from .flow_diffuser import ANIMATE_MAX_PIXELS
+    name = "fill_along_tracks"
+    B, N, C, H, W = _clipfill_inputs(name, clip, mask, fwd, bwd)
+    T = N - 1
+    par = clipfill_params(T, reach, check, a1, a2, blend, name=name)
+    if frames is None:
+        first, stop = 0, N
+    else:
+        if not isinstance(frames, (tuple, list)) or len(frames) != 2:
+            raise ValueError(f"{name}: frames must be None or (first, stop), got {frames!r}")
+        first = A.integer(name, "frames[0]", frames[0], 0, T)
+        stop = A.integer(name, "frames[1]", frames[1], first + 1, N)
+    A.forward_only(name, clip, fwd, bwd, mask, why="the propagation has no backward pass")
+    n = stop - first
+    with torch.no_grad():
+        clip, fwd, bwd, holes = L.f32c(clip), L.f32c(fwd), L.f32c(bwd), _hole_bytes(mask)
+        per = max(1, ANIMATE_MAX_PIXELS // (H * W))                          # frames per call
+        nt, nb = min(n, per), max(1, per // n)
+        video = torch.empty(B, n, C, H, W, dtype=torch.float32, device=clip.device)
+        steps = torch.empty(B, n, 2, H, W, dtype=torch.uint8, device=clip.device)
+        lib = L.lib()
+        for b0 in range(0, B, nb):
+            cb = min(nb, B - b0)
+            for f0 in range(0, n, nt):
+                ct = min(nt, n - f0)                                         # ct == n: whole samples, contiguous in the result
+                sl = slice(b0, b0 + cb) if ct == n else slice(b0, b0 + 1)
+                v, s = (o[sl] if ct == n else o[sl, f0:f0 + ct] for o in (video, steps))
+                L.check(lib.ofd_clip_fill(L.ptr(clip[sl]), L.ptr(holes[sl]), L.ptr(fwd[sl]), L.ptr(bwd[sl]), L.ptr(v), L.ptr(s),
+                                          cb if ct == n else 1, T, C, H, W, par["reach"], int(par["check"]), par["a1"], par["a2"],
+                                          int(par["blend"]), first + f0, ct, L.stream()))
+        left = (holes[:, first:stop] != 0) & (steps == 0).all(2, keepdim=True)
+    return ClipFill(video, steps, left)
+
+
+def complete_flows(fwd, bwd, mask, dilate=2):
+    """A clip's flows completed under a mask, smoothly (the first step of flow-guided completion; not in the reference): (fwd_c, bwd_c,
+    hole_fwd, hole_bwd).  fwd, bwd: (B, T, 2, H, W) IN PIXELS; mask: (B, T + 1, 1, H, W) as for `fill_along_tracks`.  The hole of
+    fwd[:, j] is mask[:, j] and the hole of bwd[:, j] is mask[:, j + 1] -- each flow is defined on its own first frame -- grown by
+    `dilate` pixels (0..16; an estimated flow is unreliable along an object's outline) and extended by the flow's own non-finite
+    entries.  hole_fwd, hole_bwd: (B, T, 1, H, W) bool.  Inside its hole a flow is replaced by `fill_holes(flow, weight=valid)`, the
+    push-pull average of the valid vectors around it: right for a hole over one smoothly moving surface, wrong where the hidden
+    motion has an edge.  Outside, every vector keeps its bits.  No new kernel and no model call.  Forward only."""
+    name = "complete_flows"
+    B, T, H, W = _chain_flows(name, fwd, bwd)
+    _clip_mask(name, mask, B, T + 1, H, W)
+    dilate = A.integer(name, "dilate", dilate, 0, 16)
+    A.forward_only(name, fwd, bwd, mask, why="the completion has no backward pass")
+    with torch.no_grad():
+        holes = _hole_bytes(mask) != 0
+        done = []
+        for flow, hole in ((L.f32c(fwd), holes[:, :T]), (L.f32c(bwd), holes[:, 1:])):
+            flat = flow.reshape(B * T, 2, H, W)
+            hole = hole.reshape(B * T, 1, H, W).float()
+            if dilate:
+                hole = torch.nn.functional.max_pool2d(hole, 2 * dilate + 1, stride=1, padding=dilate)
+            hole = (hole > 0) | ~torch.isfinite(flat).all(1, keepdim=True)
+            filled = fill_holes(flat, weight=(~hole).float())
+            done.append((torch.where(hole, filled, flat).view(B, T, 2, H, W), hole.view(B, T, 1, H, W)))
+    return done[0][0], done[1][0], done[0][1], done[1][1]
+
+
+def _fill_left(video, left):
+    """`fill_holes` of every frame of video (B, n, C, H, W) under left (B, n, 1, H, W) bool; the other pixels keep their bits"""
+    B, n, C, H, W = video.shape
+    filled = fill_holes(video.reshape(B * n, C, H, W), weight=(~left).reshape(B * n, 1, H, W).float()).view(B, n, C, H, W)
+    return torch.where(left, filled, video)
+
+
+def inpaint_clip(clip, mask, fwd, bwd, reach=None, check=True, a1=0.01, a2=0.5, blend=True, flow_dilate=2, key_frame=None, spatial=True):
+    """A marked object taken out of a clip by flow-guided completion (Huang et al. 2016; one turn of the loop of Xu et al. 2019; not in
+    the reference): a `ClipFill` (video, steps, left) over all frames.  clip, mask, fwd, bwd, reach, check, a1, a2, blend: as for
+    `fill_along_tracks`, except that the flows are as estimated.  1. `complete_flows(fwd, bwd, mask, flow_dilate)` (flow_dilate None:
+    the flows are already completed and this step is skipped).  2. `fill_along_tracks`.  3. With key_frame = f (0..T): the pixels of
+    frame f that step 2 left are filled spatially with `fill_holes`, marked seen, and `fill_along_tracks` runs once more on the
+    result with mask = left, which carries that fill along the tracks into the other frames.  4. spatial=True: what is still left
+    in any frame is filled with `fill_holes`.  `left` reports what the last propagation left, before step 4; `steps` holds the last
+    propagation's steps where it filled a pixel and the first's elsewhere.  Unlike `remove_moving` this needs no rigid background
+    and takes the user's mask; like every copy along a flow it is as good as the flow under the hole, does not compensate changes
+    of lighting, and its defaults are untuned on real footage.  Forward only."""
+    name = "inpaint_clip"
+    B, N, C, H, W = _clipfill_inputs(name, clip, mask, fwd, bwd)
+    par = clipfill_params(N - 1, reach, check, a1, a2, blend, flow_dilate, name=name)
+    if key_frame is not None:
+        A.integer(name, "key_frame", key_frame, 0, N - 1)
+    if not isinstance(spatial, bool):
+        raise ValueError(f"{name}: spatial must be True or False, got {spatial!r}")
+    A.forward_only(name, clip, fwd, bwd, mask, why="the propagation has no backward pass")
+    walk = dict(reach=par["reach"], check=par["check"], a1=par["a1"], a2=par["a2"], blend=par["blend"])
+    with torch.no_grad():
+        if par["dilate"] is not None:
+            fwd, bwd = complete_flows(fwd, bwd, mask, par["dilate"])[:2]
+        video, steps, left = fill_along_tracks(clip, mask, fwd, bwd, **walk)
+        if key_frame is not None:
+            video = video.clone()
+            video[:, key_frame] = _fill_left(video[:, key_frame:key_frame + 1], left[:, key_frame:key_frame + 1])[:, 0]
+            todo = left.clone()
+            todo[:, key_frame] = False
+            video, again, left = fill_along_tracks(video, todo, fwd, bwd, **walk)
+            steps = torch.where(todo, again, steps)
+        if spatial:
+            video = _fill_left(video, left)
+    return ClipFill(video, steps, left)
+
+
 # ---- global motion of a flow: robust fit, split, render, camera path (not in the reference; semantics: include/ofd.h, `ofd_motion_fit`) ----
 MOTION_MODELS = ("translation", "similarity", "affine", "homography")
 _MOTION_WHY = "the fit, the field and the warp have no backward pass"
