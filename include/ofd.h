@@ -1260,7 +1260,9 @@ int ofd_pack_input(const float* x, int Cx, const float* cond, int Cc, void* out,
  * 10 oy, 11 ox, 12 ch, 13 cw (crop window origin / size as fractions of the image; 1, 1 without a crop).  means_ws: B*2 x 8 bytes of device scratch.
  * reference_semantics == 0 (default of the plugin): geometrically consistent flow -- a flip negates the component along the flipped
  * axis, a crop divides each component by its axis' window fraction.  != 0: the reference's own arithmetic on the flow channels --
- * flips negate the other channel (augmentation.py:37-45), the crop multiplies channel 0 by ch and channel 1 by cw (augmentation.py:47-48). */
+ * flips negate the other channel (augmentation.py:37-45), the crop multiplies channel 0 by ch and channel 1 by cw (augmentation.py:47-48).
+ * img and tgt must be finite.  flow may hold NaN (the holes of sparse ground truth): a flip moves a NaN with its pixel, a crop makes
+ * every output NaN whose bilinear cell holds one (a NaN corner of weight 0 included), and no image output depends on the flow. */
 int ofd_augment(const float* img, const float* tgt, const float* flow, const float* params, void* means_ws, float* out_img,
                 float* out_tgt, float* out_flow, int B, int H, int W, int reference_semantics, void* stream);
 /* the (B, 16) table above from (B, 14) uniform draws in [0, 1) (the caller's RNG: torch's device generator in the plugin), one launch:
@@ -1270,7 +1272,8 @@ int ofd_augment_table(const float* uniforms, float* params, int B, void* stream)
 
 /* the four statistics FlowDiffuser.training_step logs for cond and for flow (flow_diffuser.py:218-235: torch.min, torch.max, torch.mean,
  * torch.mean(torch.std(x, dim=0))) of x (B, n_per_sample) fp32 in one pass: out4 = {min, max, mean, mean over elements of the unbiased standard
- * deviation across the batch} (device); ws: ofd_batch_stats_ws_doubles() doubles of device scratch (partial sums, added in a fixed order). */
+ * deviation across the batch} (device); ws: ofd_batch_stats_ws_doubles() doubles of device scratch (partial sums, added in a fixed order).
+ * As in torch, one NaN in x makes min, max and mean NaN, and the deviation is NaN for B == 1. */
 size_t ofd_batch_stats_ws_doubles(void);
 int ofd_batch_stats(const float* x, int B, size_t n_per_sample, double* ws, float* out4, void* stream);
 

@@ -17,7 +17,13 @@ Deviations from the reference, all on purpose and all listed in INTEGRATION.md:
   * the crop divides each flow component by its axis' window fraction (a window of width fraction cw is zoomed by 1 / cw); the
     reference MULTIPLIES, and pairs channel -2 with the height and channel -1 with the width (augmentation.py:47-48);
   * hue jitter is dropped (above); the random factors are drawn per SAMPLE (the reference draws ColorJitter's factors once per call of
-    the transform and applies the transform sample by sample, 58-64 -- per sample as well, but from torchvision's own RNG stream).
+    the transform and applies the transform sample by sample, 58-64 -- per sample as well, but from torchvision's own RNG stream);
+  * torchvision's ColorJitter clamps to [0, 1] after each of brightness, contrast and saturation; here the three run on unclamped
+    values and ONE clamp follows the saturation;
+  * torchvision applies the three in a random order per call; here the order is fixed: brightness, contrast about the mean gray of
+    the brightened frame, saturation about the gray image.
+Images must be finite.  The flow may hold NaN (holes of sparse ground truth): a flip moves a NaN with its pixel, a crop makes every
+output NaN whose bilinear cell holds one, and no image output depends on the flow (tests/test_augment_gpu.py).
 `reference_semantics=True` reproduces the first two (the flow arithmetic); nothing reproduces torchvision's RNG stream.
 """
 import torch

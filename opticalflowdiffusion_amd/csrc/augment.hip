@@ -156,15 +156,19 @@ __global__ void __launch_bounds__(64) augment_table_kernel(const float* __restri
 // for cond and flow (flow_diffuser.py:218-235 of the reference: torch.min / max / mean / mean(std(x, dim = 0))) in one pass over x.
 // Per-workgroup partials (ws: 4 doubles per workgroup), added in a fixed order by the second kernel: both run reduce.h's 256-slot
 // tree over slots of their own, which carry the min and the max beside the two sums.
+// The min and the max keep a NaN once they have met one, as torch.min / torch.max do (fminf / fmaxf would drop it and log a finite
+// range beside a NaN mean): a NaN candidate always replaces the held value, and nothing compares below or above a held NaN.
 constexpr int BS_BLOCKS = 1024;
+template <typename T> __device__ __forceinline__ T nan_min(T a, T v) { return (v < a || v != v) ? v : a; }
+template <typename T> __device__ __forceinline__ T nan_max(T a, T v) { return (v > a || v != v) ? v : a; }
 __global__ void __launch_bounds__(256) batch_stats_kernel(const float* __restrict__ x, int B, size_t n, double* __restrict__ ws) {
-    float mn = 3.0e38f, mx = -3.0e38f;
+    float mn = __builtin_inff(), mx = -__builtin_inff();
     double sum = 0.0, sd = 0.0;
     for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (size_t)gridDim.x * 256) {
         float s1 = 0.0f;
         for (int b = 0; b < B; ++b) {
             const float v = x[(size_t)b * n + e];
-            mn = fminf(mn, v); mx = fmaxf(mx, v);
+            mn = nan_min(mn, v); mx = nan_max(mx, v);
             s1 += v;
         }
         const float m = s1 / (float)B;
@@ -178,7 +182,7 @@ __global__ void __launch_bounds__(256) batch_stats_kernel(const float* __restric
     r0[threadIdx.x] = sum; r1[threadIdx.x] = sd; r2[threadIdx.x] = mn; r3[threadIdx.x] = mx;
     block_tree([&](int i, int j) {
         r0[i] += r0[j]; r1[i] += r1[j];
-        r2[i] = fminf(r2[i], r2[j]); r3[i] = fmaxf(r3[i], r3[j]);
+        r2[i] = nan_min(r2[i], r2[j]); r3[i] = nan_max(r3[i], r3[j]);
     });
     if (threadIdx.x == 0) {
         double* o = ws + 4 * (size_t)blockIdx.x;
@@ -187,15 +191,15 @@ __global__ void __launch_bounds__(256) batch_stats_kernel(const float* __restric
 }
 __global__ void __launch_bounds__(256) batch_stats_total_kernel(const double* __restrict__ ws, int nblocks, int B, size_t n, float* __restrict__ out) {
     __shared__ double r0[256], r1[256], r2[256], r3[256];
-    double sum = 0.0, sd = 0.0, mn = 3.0e38, mx = -3.0e38;
+    double sum = 0.0, sd = 0.0, mn = __builtin_inf(), mx = -__builtin_inf();
     for (int i = threadIdx.x; i < nblocks; i += 256) {
         sum += ws[4 * i]; sd += ws[4 * i + 1];
-        mn = fmin(mn, ws[4 * i + 2]); mx = fmax(mx, ws[4 * i + 3]);
+        mn = nan_min(mn, ws[4 * i + 2]); mx = nan_max(mx, ws[4 * i + 3]);
     }
     r0[threadIdx.x] = sum; r1[threadIdx.x] = sd; r2[threadIdx.x] = mn; r3[threadIdx.x] = mx;
     block_tree([&](int i, int j) {
         r0[i] += r0[j]; r1[i] += r1[j];
-        r2[i] = fmin(r2[i], r2[j]); r3[i] = fmax(r3[i], r3[j]);
+        r2[i] = nan_min(r2[i], r2[j]); r3[i] = nan_max(r3[i], r3[j]);
     });
     if (threadIdx.x == 0) {
         out[0] = (float)r2[0];                                // min

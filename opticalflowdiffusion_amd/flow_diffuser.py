@@ -980,7 +980,7 @@ class FlowDiffuser(EmaMixin, _Base):
     @staticmethod
     def _batch_stats(x):
         """(min, max, mean, mean(std(x, dim=0))) of a (B, ...) tensor as 0-dim views of one 4-float result: what FD:218-235 logs, in one pass
-        over x (`ofd_batch_stats`) instead of five reductions"""
+        over x (`ofd_batch_stats`) instead of five reductions.  A NaN in x makes min, max and mean NaN, as torch.min / max / mean do."""
         L.require_gpu(x)
         x = L.f32c(x)
         ws = torch.empty(L.lib().ofd_batch_stats_ws_doubles(), dtype=torch.float64, device=x.device)
