@@ -33,6 +33,7 @@
  *   (not in the reference)            tracks through a clip's flows, layer propagation -> ofd_flow_chain, ofd_flow_chain_to, ofd_layer_composite
  *   (not in the reference)            motion-compensated temporal filter of a clip, along its tracks -> ofd_temporal_filter
  *   (not in the reference)            flow-guided completion of a masked region of a clip, along its tracks -> ofd_clip_fill
+ *   (not in the reference)            membrane of a masked region (multigrid Laplace solve), seamless fills -> ofd_membrane_solve
  *   (not in the reference)            guided weighted median of a flow  -> ofd_flow_median
  *   (not in the reference)            global motion of a flow: robust fit, split, render -> ofd_motion_fit, ofd_motion_field, ofd_homography_warp
  *   (not in the reference)            motion layers: K motions of a flow, labels, label vote -> ofd_motion_layers, ofd_motion_assign, ofd_label_vote
@@ -447,6 +448,54 @@ int ofd_temporal_filter(const float* clip, const float* guide, const float* fwd,
  * gathers, like ofd_flow_chain.  Compulsory traffic: B * nt * H * W * (8 C + 3) bytes plus the flows under the holes. */
 int ofd_clip_fill(const float* clip, const uint8_t* mask, const float* fwd, const float* bwd, float* out, uint8_t* steps, int B, int T,
                   int C, int H, int W, int reach, int use_check, float a1, float a2, int blend, int t0, int nt, void* stream);
+
+/* The membrane of a masked region: the solution of the discrete Laplace equation inside a hole, with the frame around the hole as
+ * boundary data (the smooth interpolant that ofd_pushpull_fill approximates; added to a copied patch it is the guided interpolation of
+ * Perez, Gangnet & Blake, "Poisson image editing", SIGGRAPH 2003).  An addition: nothing in the reference solves an equation.  A fixed
+ * number of multigrid cycles, fixed in advance by the arguments: no convergence test and no host sync.  All arithmetic fp32, every
+ * operation rounded on its own (no contraction), in the order written.
+ * data (B,C,H,W), 1 <= C <= 8.  hole (B,1,H,W) uint8: nonzero = unknown (ofd_clip_fill's byte convention).  init (B,C,H,W) or NULL
+ * (zeros): the start inside the hole.  out (B,C,H,W).  resid (B,) float.  cycles 1..32, nu 1..4, shape 1 (V) or 2 (W).
+ *   M1. Effective hole.  A pixel is UNKNOWN iff its hole byte is nonzero or data is non-finite in any plane there (as in
+ *       ofd_pushpull_fill); every other pixel is KNOWN.  At a known pixel out = data's bits.  data at an unknown pixel never reaches a
+ *       result.  At an unknown pixel the solve starts from c = init (0 without init).
+ *   M2. Levels.  Level 0 is the frame, H_0 x W_0 = H x W.  While H_l > 4 and W_l > 4 and l < 11 there is a level l + 1 of
+ *       ceil(H_l / 2) x ceil(W_l / 2) cells; cell (Y, X) of it has the children (2Y, 2X), (2Y, 2X+1), (2Y+1, 2X), (2Y+1, 2X+1) of level l and
+ *       is unknown iff all four are inside level l and unknown.  The number of levels follows from H and W alone -- a level without an
+ *       unknown cell changes nothing, so the bits are those of stopping above it, except that the level above then makes its nu + nu
+ *       sweeps and not M8's eight.  Per level and plane the state is c and b, read at unknown cells only.
+ *   M3. Equation.  n_p = the number of 4-neighbours of p inside the level, as a float (the level's edge is a Neumann wall).
+ *       S(t; p) = (t(x-1, y) + t(x+1, y)) + (t(x, y-1) + t(x, y+1)), a term outside the level being +0.0.  sum_p = S(c at unknown cells, +0.0
+ *       elsewhere).  Level 0: b_p = S(data at known pixels, +0.0 elsewhere): a known pixel is Dirichlet data.  The equation at an unknown p
+ *       is n_p * c_p - sum_p = b_p; on level l > 0, c is the error of level l - 1, b the restricted residual (M6), and a cell that is not
+ *       unknown is error 0.
+ *   M4. Sweep.  Red-black Gauss-Seidel: a sweep updates the unknown cells with ((x + y) & 1) == 0 in the level's own coordinates, then
+ *       those with 1, by c_p = (b_p + sum_p) / n_p.  A cell's update reads cells of the other colour only, so within a colour the order
+ *       of the cells does not matter, and sweeps fused in a tile with a halo have the bits of sweeps over the whole level.
+ *   M5. Residual.  r_p = b_p - (n_p * c_p - sum_p) at an unknown cell.
+ *   M6. Restriction.  At an unknown cell of level l + 1: b = (r(2Y, 2X) + r(2Y, 2X+1)) + (r(2Y+1, 2X) + r(2Y+1, 2X+1)), and c = 0.
+ *   M7. Prolongation.  At an unknown cell (x, y) of level l: c = c + e, e = (1 - ty) * ((1 - tx) * v00 + tx * v01) + ty * ((1 - tx) * v10 +
+ *       tx * v11): ofd_pushpull_fill's x2 bilinear read (half-pixel centres, weights 3/4 and 1/4, edge-clamped at the level's edge) of
+ *       level l + 1's c, a cell of level l + 1 that is not unknown reading +0.0.  Per axis, i even: lo = max(i/2 - 1, 0), hi = i/2, t = 0.75;
+ *       i odd: lo = i/2, hi = min(i/2 + 1, n - 1), t = 0.25; v00 = (y lo, x lo), v01 = (y lo, x hi), v10 = (y hi, x lo), v11 = (y hi, x hi).
+ *   M8. Cycle of level l.  The last level: eight sweeps.  Otherwise nu sweeps; M5 and M6 (level l + 1's c restarts at 0); `shape`
+ *       cycles of level l + 1, one after the other on the same c -- but level 0 descends once whatever `shape`; M7; nu sweeps.
+ *       `cycles` cycles of level 0 are run.
+ *   M9. Results.  out at unknown pixels = level 0's c.  resid[b] = the largest |r_p| (M5) over the unknown pixels and planes of sample
+ *       b after the last cycle, 0 without unknown pixels; the maximum is taken on the bits of the non-negative floats as integers.
+ *       A component of the hole that no known pixel touches solves a singular equation: it stays near its start.
+ *   M10. Aliasing and limits.  out and resid must not share a byte with data, hole, init, the workspace or each other.  2 <= H, W <=
+ *       32768; the last level has at most 4096 cells (a frame more than about a thousand times longer than wide is refused);
+ *       B * C * H * W < 2^36; B * ceil(H / 16) * ceil(W / 64) < 2^30.
+ * No float atomics.  The same input gives the same bits; a sample's bits depend neither on what shares its batch nor on how the level is
+ * cut into tiles.  A workgroup owns a 64 x 16 tile of one level and sample and fuses the nu sweeps of a leg in LDS; a tile without an
+ * unknown cell returns after reading its mask bytes: the cost follows the hole.  Every level of at most 4096 cells runs, with the
+ * recursion under it, in one launch.  Argument errors (null pointers, C, cycles, nu, shape out of range, a short or misaligned workspace,
+ * aliasing) return OFD_ERR_ARG and set ofd_last_error before any GPU work.
+ * workspace: ofd_membrane_workspace(B,C,H,W) bytes (0 for a bad shape), 16-byte aligned. */
+size_t ofd_membrane_workspace(int B, int C, int H, int W);
+int ofd_membrane_solve(const float* data, const uint8_t* hole, const float* init, float* out, float* resid, int B, int C, int H, int W,
+                       int cycles, int nu, int shape, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Global motion of a flow: a robust parametric fit of the motion most pixels share (the camera's), the split of a flow into that motion
  * and the rest, and the render of a frame through a homography (Odobez & Bouthemy 1995; Black & Anandan 1996).  An addition: the

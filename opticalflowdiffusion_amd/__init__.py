@@ -10,6 +10,7 @@ from .warp import segment_motion, assign_motion, vote_labels, layers_params, Mot
 from .warp import build_plate, project_plate, background_plate, remove_moving, plate_params, plate_canvas, plate_voters, Plate  # noqa: F401
 from .warp import temporal_filter, temporal_params, TemporalFilter  # noqa: F401
 from .warp import fill_along_tracks, complete_flows, inpaint_clip, clipfill_params, ClipFill  # noqa: F401
+from .warp import harmonic_fill, seamless_clone, membrane_params, HarmonicFill, SeamlessClone  # noqa: F401
 from .softsplat import softsplat  # noqa: F401
 from .denoising_diffusion import Unet, ConditionalDiffusion, PhotoGuide  # noqa: F401,E402
 from .flow_diffuser import FlowDiffuser, UnetWithWarp  # noqa: F401,E402

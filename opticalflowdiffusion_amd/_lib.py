@@ -69,6 +69,8 @@ SIGNATURES = {
     "ofd_layer_composite": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p]),
     "ofd_temporal_filter": (c_int, [c_void_p] * 8 + [c_int] * 8 + [c_float, c_int, c_float, c_float, c_int, c_int, c_void_p]),
     "ofd_clip_fill": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_float] * 2 + [c_int] * 3 + [c_void_p]),
+    "ofd_membrane_workspace": (c_size_t, [c_int] * 4),
+    "ofd_membrane_solve": (c_int, [c_void_p] * 5 + [c_int] * 7 + [c_void_p, c_size_t, c_void_p]),
     "ofd_motion_fit_ws_doubles": (c_size_t, [c_int] * 3),
     "ofd_motion_fit": (c_int, [c_void_p] * 2 + [c_int] * 5 + [c_float] + [c_void_p] * 5),
     "ofd_motion_field": (c_int, [c_void_p] * 3 + [c_float] + [c_void_p] * 3 + [c_int] * 3 + [c_void_p]),

@@ -21,7 +21,7 @@ COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-fp-a
 EXTRA = {f: ["-ffp-contract=off"] for f in ("splat.hip", "grid_warp.hip", "splat_pyramid.hip", "diffusion.hip", "x0_quantile.hip",
                                                 "loss_rows.hip", "photo_guide.hip", "interp.hip", "upsample.hip", "loop.hip",
                                                 "consistency.hip", "median.hip", "chain.hip", "motion.hip", "layers.hip", "plate.hip",
-                                                "temporal.hip", "clipfill.hip")}
+                                                "temporal.hip", "clipfill.hip", "membrane.hip")}
 
 
 def sources():

@@ -13,5 +13,5 @@ void set_error(const char* fmt, ...) {
 }
 }  // namespace ofd
 
-extern "C" int ofd_version(void) { return (0 << 16) | 18; }
+extern "C" int ofd_version(void) { return (0 << 16) | 19; }
 extern "C" const char* ofd_last_error(void) { return ofd::g_err; }

@@ -868,7 +868,7 @@ class FlowDiffuser(EmaMixin, _Base):
         return res.video, res.support, res.taps, fwd, bwd
 
     def inpaint_clip(self, clip, mask, fwd=None, bwd=None, refine=0, flow_fill="pushpull", reach=None, check=True, a1=0.01, a2=0.5,
-                     blend=True, flow_dilate=2, key_frame=None, spatial=True, **sample_kw):
+                     blend=True, flow_dilate=2, key_frame=None, spatial=True, seamless=False, seam_ring=1, **sample_kw):
         """A marked object taken out of a clip by flow-guided completion (not in the reference): (video, left, fwd_c, bwd_c), video and
         left those of `warp.inpaint_clip(clip, mask, fwd_c, bwd_c, reach, check, a1, a2, blend, None, key_frame, spatial)`, which has
         the method, and fwd_c, bwd_c the flows completed under the mask.  clip: (B, T + 1, 3, H, W) in cond's range; mask:
@@ -883,7 +883,8 @@ class FlowDiffuser(EmaMixin, _Base):
         and photo_* keys) goes to those chains too.  Everything known_flow rejects is a ValueError before any model call: a
         non-diffusion model, target 'target', latent=True, sample_scale > 1.  A diffusion model over flow fields is the one tool here
         that can propose a motion for what it cannot see, with no retraining; HOW WELL the prior completes a flow under a mask HAS NOT
-        BEEN MEASURED with trained weights.  The defaults are untuned on real footage.  Forward only."""
+        BEEN MEASURED with trained weights.  seamless, seam_ring: `warp.inpaint_clip`'s, passed on (the propagated colours are then
+        corrected by the membrane of their mismatch on the hole's rim).  The defaults are untuned on real footage.  Forward only."""
         name = "inpaint_clip"
         if flow_fill not in ("pushpull", "prior"):
             raise ValueError(f"{name}: flow_fill must be 'pushpull' or 'prior', got {flow_fill!r}")
@@ -898,6 +899,10 @@ class FlowDiffuser(EmaMixin, _Base):
             A.integer(name, "key_frame", key_frame, 0, T)
         if not isinstance(spatial, bool):
             raise ValueError(f"{name}: spatial must be True or False, got {spatial!r}")
+        if not isinstance(seamless, bool) or (seamless and not spatial):
+            raise ValueError(f"{name}: seamless must be True or False and needs spatial=True, got {seamless!r} with spatial={spatial!r}")
+        A.integer(name, "seam_ring", seam_ring, 1, 16)
+        seam = dict(seamless=True, seam_ring=seam_ring) if seamless else {}
         if mask.requires_grad:
             raise L.OfdError(f"{name}: forward only (the propagation has no backward pass): detach the mask")
         prior_kw = {}
@@ -929,7 +934,7 @@ class FlowDiffuser(EmaMixin, _Base):
                     done.append(torch.where(torch.isnan(known), fresh, flat).view(B, T, 2, H, W))    # held vectors keep their bits
                 fwd_c, bwd_c = done
         res = inpaint_clip(clip, mask, fwd_c, bwd_c, reach=par["reach"], check=par["check"], a1=par["a1"], a2=par["a2"], blend=par["blend"],
-                           flow_dilate=None, key_frame=key_frame, spatial=spatial)
+                           flow_dilate=None, key_frame=key_frame, spatial=spatial, **seam)
         return res.video, res.left, fwd_c, bwd_c
 
     def _plate_flows(self, name, clip, fwd, bwd, refine, plate_kw, a1, a2, sample_kw):

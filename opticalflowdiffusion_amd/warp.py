@@ -849,7 +849,8 @@ def _fill_left(video, left):
     return torch.where(left, filled, video)
 
 
-def inpaint_clip(clip, mask, fwd, bwd, reach=None, check=True, a1=0.01, a2=0.5, blend=True, flow_dilate=2, key_frame=None, spatial=True):
+def inpaint_clip(clip, mask, fwd, bwd, reach=None, check=True, a1=0.01, a2=0.5, blend=True, flow_dilate=2, key_frame=None, spatial=True,
+                 seamless=False, seam_ring=1):
     """A marked object taken out of a clip by flow-guided completion (Huang et al. 2016; one turn of the loop of Xu et al. 2019; not in
     the reference): a `ClipFill` (video, steps, left) over all frames.  clip, mask, fwd, bwd, reach, check, a1, a2, blend: as for
     `fill_along_tracks`, except that the flows are as estimated.  1. `complete_flows(fwd, bwd, mask, flow_dilate)` (flow_dilate None:
@@ -859,15 +860,36 @@ def inpaint_clip(clip, mask, fwd, bwd, reach=None, check=True, a1=0.01, a2=0.5, 
     in any frame is filled with `fill_holes`.  `left` reports what the last propagation left, before step 4; `steps` holds the last
     propagation's steps where it filled a pixel and the first's elsewhere.  Unlike `remove_moving` this needs no rigid background
     and takes the user's mask; like every copy along a flow it is as good as the flow under the hole, does not compensate changes
-    of lighting, and its defaults are untuned on real footage.  Forward only."""
+    of lighting, and its defaults are untuned on real footage.  seamless=True compensates them at the hole's rim: steps 1-4 run on
+    the mask grown by seam_ring (1..16) pixels with spatial=True, so that every pixel of the hole and of the ring around it has a
+    propagated colour s; on the ring the mismatch d = clip - s is formed (where the propagation found no source, d is
+    `fill_holes(d, weight=ring & found)`), and inside the mask video = s + `harmonic_fill(d, mask).out`: the propagated gradients with
+    the frame's own colours on the rim.  Outside the mask the clip's bits; steps and left report the propagation over the grown mask.
+    A mismatch that jumps INSIDE the hole (sources at different distances in time) is smoothed at the rim, not removed.  Forward only."""
     name = "inpaint_clip"
     B, N, C, H, W = _clipfill_inputs(name, clip, mask, fwd, bwd)
     par = clipfill_params(N - 1, reach, check, a1, a2, blend, flow_dilate, name=name)
     if key_frame is not None:
         A.integer(name, "key_frame", key_frame, 0, N - 1)
-    if not isinstance(spatial, bool):
-        raise ValueError(f"{name}: spatial must be True or False, got {spatial!r}")
+    if not isinstance(spatial, bool) or not isinstance(seamless, bool):
+        raise ValueError(f"{name}: spatial and seamless must be True or False, got {spatial!r} and {seamless!r}")
+    A.integer(name, "seam_ring", seam_ring, 1, 16)
+    if seamless and (not spatial or min(H, W) < 2):
+        raise ValueError(f"{name}: seamless=True needs spatial=True (every rim pixel needs a colour) and H, W >= 2, got spatial={spatial!r}, "
+                         f"H={H}, W={W}")
     A.forward_only(name, clip, fwd, bwd, mask, why="the propagation has no backward pass")
+    if seamless:
+        with torch.no_grad():
+            hole = (_hole_bytes(mask) != 0).reshape(B * N, 1, H, W)
+            grown = torch.nn.functional.max_pool2d(hole.float(), 2 * seam_ring + 1, stride=1, padding=seam_ring) > 0
+            res = inpaint_clip(clip, grown.view(B, N, 1, H, W), fwd, bwd, reach=par["reach"], check=par["check"], a1=par["a1"], a2=par["a2"],
+                               blend=par["blend"], flow_dilate=par["dilate"], key_frame=key_frame, spatial=True)
+            own, s = L.f32c(clip).reshape(B * N, C, H, W), res.video.reshape(B * N, C, H, W)
+            found = grown & ~hole & ~res.left.reshape(B * N, 1, H, W)
+            d = own - s
+            d = torch.where(found, d, fill_holes(d, weight=found.float()))
+            fix = _harmonic_fill(d.contiguous(), hole.to(torch.uint8), membrane_params(name=name), "pushpull")[0]
+            return ClipFill(torch.where(hole, s + fix, own).view(B, N, C, H, W), res.steps, res.left)
     walk = dict(reach=par["reach"], check=par["check"], a1=par["a1"], a2=par["a2"], blend=par["blend"])
     with torch.no_grad():
         if par["dilate"] is not None:
@@ -883,6 +905,116 @@ def inpaint_clip(clip, mask, fwd, bwd, reach=None, check=True, a1=0.01, a2=0.5, 
         if spatial:
             video = _fill_left(video, left)
     return ClipFill(video, steps, left)
+
+
+# ---- the membrane of a masked region and seamless fills (not in the reference; semantics: include/ofd.h, `ofd_membrane_solve`) ----
+HarmonicFill = collections.namedtuple("HarmonicFill", "out residual")
+SeamlessClone = collections.namedtuple("SeamlessClone", "out membrane residual")
+MEMBRANE_SHAPES = {"V": 1, "W": 2}
+MEMBRANE_CYCLES = 4                                    # the default: see README ("harmonic_fill") for the measurement behind it
+
+_membrane_ws = {}                                      # device index -> the solver's workspace (grown on demand)
+
+
+def membrane_params(cycles=None, nu=2, shape="W", name="harmonic_fill"):
+    """the rules of the membrane solver's arguments (ValueError) -> dict(cycles, nu, shape); host logic, no engine call.  cycles None:
+    MEMBRANE_CYCLES; cycles 1..32 multigrid cycles, fixed in advance; nu 1..4 sweeps before and after every coarse-grid correction;
+    shape "V" or "W" (-> 1 or 2, the cycles of the next level per cycle of a level)"""
+    cycles = MEMBRANE_CYCLES if cycles is None else A.integer(name, "cycles", cycles, 1, 32)
+    if not isinstance(shape, str) or shape not in MEMBRANE_SHAPES:
+        raise ValueError(f"{name}: shape must be 'V' or 'W', got {shape!r}")
+    return dict(cycles=cycles, nu=A.integer(name, "nu", nu, 1, 4), shape=MEMBRANE_SHAPES[shape])
+
+
+def _membrane_inputs(name, img, mask, what="img"):
+    """the shape and dtype rules of an image and its hole mask (ValueError) -> (B, C, H, W)"""
+    if not torch.is_tensor(img) or img.dim() != 4 or img.numel() == 0 or not 1 <= img.shape[1] <= 8 or min(img.shape[2:]) < 2 or \
+            not img.is_floating_point():
+        raise ValueError(f"{name}: {what} must be a non-empty floating-point (B, C, H, W) tensor with 1 <= C <= 8 and H, W >= 2, got "
+                         f"{A.shape_of(img)}")
+    B, C, H, W = img.shape
+    if not torch.is_tensor(mask) or tuple(mask.shape) != (B, 1, H, W) or not (mask.dtype in (torch.bool, torch.uint8) or mask.is_floating_point()):
+        raise ValueError(f"{name}: mask must be a bool, uint8 or floating-point (B, 1, H, W) = {(B, 1, H, W)} tensor (True, nonzero or "
+                         f"> 0.5: a hole), got {A.shape_of(mask)} {getattr(mask, 'dtype', '')}")
+    return B, C, H, W
+
+
+def _membrane(data, holes, init, par):
+    """ofd_membrane_solve on contiguous fp32 data (B, C, H, W), uint8 holes (B, 1, H, W) and init (the same shape as data, or None)"""
+    B, C, H, W = data.shape
+    lib = L.lib()
+    out = torch.empty_like(data)
+    resid = torch.empty(B, dtype=torch.float32, device=data.device)
+    nbytes = lib.ofd_membrane_workspace(B, C, H, W)
+    ws = _membrane_ws.get(data.device.index)
+    if ws is None or ws.numel() < nbytes:
+        ws = _membrane_ws[data.device.index] = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=data.device)
+    L.check(lib.ofd_membrane_solve(L.ptr(data), L.ptr(holes), L.ptr(init), L.ptr(out), L.ptr(resid), B, C, H, W, par["cycles"], par["nu"],
+                                   par["shape"], L.ptr(ws), ws.numel(), L.stream()))
+    return out, resid
+
+
+def _harmonic_fill(img, holes, par, init):
+    """`harmonic_fill` on contiguous fp32 img, uint8 holes and init "pushpull", "zero" or a contiguous fp32 tensor: one push-pull fill
+    and one solve per at most ANIMATE_MAX_PIXELS pixels"""
+    from .flow_diffuser import ANIMATE_MAX_PIXELS
+    B, C, H, W = img.shape
+    nb = max(1, ANIMATE_MAX_PIXELS // (H * W))
+    outs, resids = [], []
+    for b0 in range(0, B, nb):
+        sl = slice(b0, b0 + nb)
+        if isinstance(init, str):
+            start = _pushpull(img[sl], (holes[sl] == 0).float(), img[sl].shape[0], C, H, W, False, 1.0) if init == "pushpull" else None
+        else:
+            start = init[sl]
+        o, r = _membrane(img[sl], holes[sl], start, par)
+        outs.append(o), resids.append(r)
+    return (outs[0], resids[0]) if len(outs) == 1 else (torch.cat(outs), torch.cat(resids))
+
+
+def harmonic_fill(img, mask, cycles=None, nu=2, shape="W", init="pushpull"):
+    """The membrane of a masked region (not in the reference): a `HarmonicFill` (out, residual).  img: (B, C, H, W), C <= 8; mask:
+    (B, 1, H, W) bool, uint8 (nonzero) or floating point (> 0.5): the hole.  Inside the hole -- the mask plus every pixel where img is
+    non-finite in any channel -- out is the solution of the discrete Laplace equation with the pixels around the hole as boundary
+    data (only a hole's 4-neighbours count) and the frame's edge as a wall: the smoothest surface that meets its surroundings without
+    a seam, what `fill_holes` approximates.  Outside it out is img bit for bit.  `cycles` (None: 4) multigrid cycles of shape "W" or
+    "V" with nu sweeps before and after each correction are run, fixed in advance, from the start `init`: "pushpull" (`fill_holes(img,
+    weight=known)`, three more launches), "zero", or a (B, C, H, W) tensor read inside the hole.  residual (B,): the largest |b - A c|
+    left in each sample.  With W(2,2) cycles the error falls by about 0.3 a cycle from a push-pull start (README); a sample without
+    a known pixel comes back as its start.  One solve per at most flow_diffuser.ANIMATE_MAX_PIXELS pixels; chunked or not, the bits
+    are the same.  Forward only; no host sync; inputs are not modified; the same input gives the same bits.  Semantics: include/ofd.h."""
+    name = "harmonic_fill"
+    B, C, H, W = _membrane_inputs(name, img, mask)
+    par = membrane_params(cycles, nu, shape, name=name)
+    given = torch.is_tensor(init)
+    if not given and init not in ("pushpull", "zero"):
+        raise ValueError(f"{name}: init must be 'pushpull', 'zero' or a (B, C, H, W) tensor, got {init!r}")
+    if given and (tuple(init.shape) != (B, C, H, W) or not init.is_floating_point()):
+        raise ValueError(f"{name}: init must be a floating-point (B, C, H, W) = {(B, C, H, W)} tensor, got {A.shape_of(init)}")
+    A.forward_only(name, img, mask, init if given else None, why="the solve has no backward pass")
+    with torch.no_grad():
+        return HarmonicFill(*_harmonic_fill(L.f32c(img), _hole_bytes(mask), par, L.f32c(init) if given else init))
+
+
+def seamless_clone(source, target, mask, cycles=None, nu=2, shape="W", init="pushpull"):
+    """Seamless cloning (Perez, Gangnet & Blake 2003; not in the reference): a `SeamlessClone` (out, membrane, residual).  source,
+    target: (B, C, H, W), C <= 8; mask: (B, 1, H, W) as for `harmonic_fill`.  out is target outside the mask and source + membrane
+    inside, membrane = `harmonic_fill(target - source, mask, cycles, nu, shape, init).out`: the source's gradients with the target's
+    colours on the rim, Perez's guided interpolation with imported gradients through the membrane identity (no mixed gradients).
+    source must be finite on the mask and on its 4-neighbour rim: where target - source is non-finite the pixel joins the hole.
+    Forward only; the same input gives the same bits."""
+    name = "seamless_clone"
+    B, C, H, W = _membrane_inputs(name, target, mask, what="target")
+    if not torch.is_tensor(source) or tuple(source.shape) != (B, C, H, W) or not source.is_floating_point():
+        raise ValueError(f"{name}: source must be a floating-point (B, C, H, W) = {(B, C, H, W)} tensor like target, got {A.shape_of(source)}")
+    par = membrane_params(cycles, nu, shape, name=name)
+    if init not in ("pushpull", "zero"):
+        raise ValueError(f"{name}: init must be 'pushpull' or 'zero', got {init!r}")
+    A.forward_only(name, source, target, mask, why="the solve has no backward pass")
+    with torch.no_grad():
+        source, target, holes = L.f32c(source), L.f32c(target), _hole_bytes(mask)
+        membrane, resid = _harmonic_fill(target - source, holes, par, init)
+        return SeamlessClone(torch.where(holes != 0, source + membrane, target), membrane, resid)
 
 
 # ---- global motion of a flow: robust fit, split, render, camera path (not in the reference; semantics: include/ofd.h, `ofd_motion_fit`) ----
